@@ -23,8 +23,16 @@ one link to the root); --assemble rotate / fixed gather them onto rank k % N / r
 A ray = one traceRayEXT equivalent actually issued, counted per class by the counting build of the kernels in an untimed frame.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, algorithmic bytes / HIP-event
-time) and `cpu_baseline` (the C oracle's hierarchical traversal, a port -- the reference has no CPU ray traversal at all,
-SURVEY F2 -- on a bounded row sample of the same frame).
+time of the timed region's own launches). A plain run does only what that line's headline needs: set up, settle + warm up, time
+exactly --steps steps, write --dump-outputs if asked, print. --full adds what takes runs of its own: `cpu_baseline` (the C oracle's
+hierarchical traversal, a port -- the reference has no CPU ray traversal at all, SURVEY F2 -- on a bounded row sample of the same
+frame) and, on one GPU with the default workload, the extra curves (curves.one_frame_per_launch / moving / primary_ao_4k / gi_1080p /
+deep / ...).
+--dump-outputs DIR writes the planes the LAST timed step rendered as DIR/<plane>.npy (float32 / float64, at most 64 MB in all: a
+seeded pixel sample beyond that): illuminance, depth, voxel id and, filtered, the denoised plane -- not albedo, normal or motion, which
+the same frames also write. The timed frames of a primary + AO workload have fixed frame indices, whatever the number of settle
+frames the clock asked for, so that the same arguments give the same inputs from run to run (GI workloads carry the hash and
+accumulation history of their settle frames).
 """
 import argparse
 import ctypes
@@ -48,6 +56,7 @@ NAMES = ("primary", "sun_shadow", "ambient_occlusion", "final_gather", "surfel_s
 SETTLE_STEPS = 64
 SETTLE_SECONDS = 0.3   # ... and at least this long, back to back, so that the timed region starts on a GPU at its sustained clocks
 SETTLE_MAX_STEPS = 20000
+DUMP_MAX_BYTES = 63 * 1000 * 1000   # --dump-outputs: all files together (64 MB, less room for the .npy headers)
 
 
 def parse(argv=None):
@@ -104,20 +113,35 @@ def parse(argv=None):
     ap.add_argument("--props", type=int, default=0,
                     help="castle workloads: this many small extra instances scattered over the scene (curves.many_instances uses 4000: the packet "
                          "cull then goes through its 64-wide hierarchy, cull_instances in traverse.hpp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--camera", choices=["still", "orbit"], default="still",
                     help="orbit: the headline becomes the MOVING view (the eye swaying along its circle round the castle, the teapot of "
                          "examples/castle.rs:287-291 swinging, set_transform + commit every frame); the default line carries it as curves.moving")
     ap.add_argument("--no-extra-curves", action="store_true",
-                    help="one GPU, default workload: skip curves.moving / gi_1080p / primary_ao_4k / deep (short runs after the headline's timed region)")
+                    help="--full, one GPU, default workload: skip curves.moving / gi_1080p / primary_ao_4k / deep (short runs after the headline's timed region)")
     ap.add_argument("--extra-steps", type=int, default=40, help="timed steps of each extra curve (40: a 10-step region of 0.7 ms GI frames is 7 ms, of which the two synchronisations around it are percents)")
     ap.add_argument("--extra-timeout", type=float, default=150.0, help="seconds the extra curves may take before the line is printed without them")
     ap.add_argument("--assets", default=None,
                     help="directory with the reference's LFS assets (castle.vox, teapot.vox, stbn_scalar_*.png, stbn_unitvec3_cosine_*.png): a file "
                          "whose sha256 is the oid in /root/reference/assets/* replaces its stand-in, and config.workload says so (SURVEY 8d)")
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the frame the CPU baseline traces (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline and (one GPU, default workload) the extra curves; "
+                         "a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the planes the last timed step rendered (rank 0's rows) as DIR/<plane>.npy in "
+                         "float32 / float64, at most 64 MB in all (beyond that: the same seeded sample of pixels from every plane): illuminance, "
+                         "depth, voxel id and, with --denoise, the denoised plane; the albedo, normal and motion planes are not written. "
+                         "Reproducible for primary + AO frames; GI and denoised frames carry the history of a clock-driven number of settle frames")
     a = ap.parse_args(argv)
     a.shard = a.shard or a.gi_shard or "both"
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.workload == "teapot_cpu" or a.camera == "orbit"):
+        ap.error("--dump-outputs writes the frames of the GPU headline's timed region: not with --workload teapot_cpu or --camera orbit")
+    if a.dump_outputs and (a.workload in ("gi", "deep") or a.denoise):
+        sys.stderr.write("bench.py: --dump-outputs: GI and denoised frames carry the history of their settle frames, whose number follows the "
+                         "clock; the dumped planes differ from run to run\n")
     return a
 
 
@@ -633,9 +657,13 @@ def measure_curve(be, dist, args, lanes, shard):
     barrier()
     for lane in lanes:
         lane.pipe.mark_kernel_times()  # kernel durations: the HIP-event pairs the library records around its launches FROM HERE (no wait) ...
-    planned = plan_steps(1 + settle, args.steps) if batched else None   # (argument marshalling only: nothing is enqueued before t_start)
+    # The timed steps' numbers: a frame of primary + AO has no history, so its steps start at a fixed number past every settle frame's, and
+    # the same arguments render the same frames however many settle frames the clock asked for. GI frames read the previous frame's hash
+    # and accumulation, denoised ones the filter's history: they go on from the settle frames.
+    first = (1 + settle) if (gi_mode or denoise) else (1 + n_fixed + SETTLE_MAX_STEPS + D)
+    planned = plan_steps(first, args.steps) if batched else None   # (argument marshalling only: nothing is enqueued before t_start)
     t_start = time.perf_counter()
-    steps_from(1 + settle, args.steps, planned)   # (EXACTLY args.steps frames: a FIRST launch of fewer frames if D does not divide them)
+    steps_from(first, args.steps, planned)   # (EXACTLY args.steps frames: a FIRST launch of fewer frames if D does not divide them)
     barrier()
     elapsed = time.perf_counter() - t_start
     gc.enable()
@@ -679,7 +707,10 @@ def measure_curve(be, dist, args, lanes, shard):
             "launch_frames": launch_frames,
             "per_rows": per_rows, "assemble": assemble, "slices": slices, "settle": settle, "frames_in_flight": 1 if batched else D, "in_flight_slots": slots_mode if D > 1 else None, "band_cuts": band_cuts,
             "comm": "native" if native else "torch", "denoise": denoise, "band_balance": balance_log or None,
-            "band_steps_ms": [round(v, 4) for v in band_steps_ms] if band_steps_ms else None, "emulated_band": (f"{er}/{en}" if emulate else None)}
+            "band_steps_ms": [round(v, 4) for v in band_steps_ms] if band_steps_ms else None, "emulated_band": (f"{er}/{en}" if emulate else None),
+            # (--dump-outputs: the pipeline the last timed step rendered into, and this rank's rows of it)
+            "last_pipe": lanes[((first + args.steps - 1) % S) % D].pipe, "out_rows": rows if have_rows else (0, 0), "width": W,
+            "denoised": denoise and world == 1}
 
 
 def compact(curve, gi_mode):
@@ -951,6 +982,31 @@ def extra_curves(args, be, noise0, noise5, base):
     return out
 
 
+def dump_outputs(be, curve, path):
+    """--dump-outputs: the planes of the last timed step (this rank's rows) as path/<plane>.npy -- illuminance (RGBA16F -> float32), depth
+    (float32), voxel id (uint32 -> float64, exact) and, when the frames were filtered, the denoised plane. The albedo, normal and motion
+    planes the same frames write are left out (with them a 1080p frame would pass the 64 MB and be sampled). Beyond DUMP_MAX_BYTES every plane
+    keeps the same pixels, a sample drawn with a fixed seed, and pixel_index.npy says which (row-major in the rows written)."""
+    import numpy as np
+    L, pipe = be.L, curve["last_pipe"]
+    r0, r1 = curve["out_rows"]
+    planes = {"illuminance": pipe.read_plane(L.PLANE_ILLUMINANCE)[r0:r1].view(np.float16).astype(np.float32),
+              "depth": pipe.read_plane(L.PLANE_DEPTH)[r0:r1].astype(np.float32),
+              "voxel_id": pipe.read_plane(L.PLANE_VOXEL_ID)[r0:r1].astype(np.float64)}
+    if curve.get("denoised"):
+        planes["denoised"] = pipe.read_plane(L.PLANE_DENOISED)[r0:r1].view(np.float16).astype(np.float32)
+    n_px = (r1 - r0) * curve["width"]
+    px_bytes = sum(a.nbytes for a in planes.values()) // max(n_px, 1)
+    if n_px * px_bytes > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (px_bytes + 8)   # (+ 8: the pixel's index)
+        idx = np.sort(np.random.default_rng(0x5EED).choice(n_px, keep, replace=False))
+        planes = {k: a.reshape(n_px, -1)[idx] for k, a in planes.items()}
+        planes["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in planes.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def account(curve, gi_mode):
     """Algorithmic bytes per launch of every kernel of a measured curve, the dominant kernel and its achieved GB/s."""
     st, ms = curve["st"], curve["ms"]
@@ -1024,8 +1080,10 @@ def run_rank(args, be, dist):
             a_b = argparse.Namespace(**vars(args))
             a_b.frames_per_launch = len(batch_lanes)
             curves[shard] = measure_curve(be, dist, a_b, batch_lanes, shard)
-            continue
-        curves[shard] = measure_curve(be, dist, args, lanes_for(in_flight), shard)
+        else:
+            curves[shard] = measure_curve(be, dist, args, lanes_for(in_flight), shard)
+        if shard == wanted[0] and rank == 0 and getattr(args, "dump_outputs", None):   # (before a second curve renders into the same pipelines)
+            dump_outputs(be, curves[shard], args.dump_outputs)
     main_curve = curves[wanted[0]]
     if rank != 0:
         return None
@@ -1075,7 +1133,7 @@ def run_rank(args, be, dist):
                                   "ao_pass": round(bytes_ao / max(1, st[1].rays + st[2].rays), 1)}}
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if not args.no_cpu_baseline and args.full and world == 1:
         cpu = cpu_baseline(args, sc, noise5, be.synth)
     what = {"primary_ao": "1spp primary+shadow+AO", "gi": "1 GI frame: primary+shadow+AO+final gather+surfel",
             "deep": "1 GI frame: primary+shadow+AO+final gather+surfel"}[args.workload]
@@ -1140,7 +1198,7 @@ def run_rank(args, be, dist):
         threading.Thread(target=watchdog, daemon=True).start()
         if args.camera == "orbit":
             extras["moving"] = measure_moving(be, args, lanes[0], noise5, args.steps)
-        elif not args.no_extra_curves and (W, H) == (1920, 1080) and args.scale == 1.0:
+        elif args.full and not args.no_extra_curves and (W, H) == (1920, 1080) and args.scale == 1.0:
             extras = extra_curves(args, be, noise0, noise5, lanes[0])
         finished.set()
         if not said.acquire(blocking=False):   # the watchdog is printing: let it

@@ -36,8 +36,17 @@ class StubPipe:
         StubPipe.log.append(("frame", frame_index))
         self.launches_ms.append(0.25)
         self.px = W * H
+        self.drew(frame_index)
+
+    def drew(self, frame_index):
+        self.frame = frame_index
         if self.target is not None:
             self.target[:, :, 0] = float(frame_index % 1024)
+
+    def read_plane(self, plane):   # illuminance: the bound target's bits; every other plane: the frame index
+        if plane == L.PLANE_ILLUMINANCE:
+            return self.target.numpy().view(np.uint16).copy()
+        return np.full((H, W), self.frame, np.float32 if plane == L.PLANE_DEPTH else np.uint32)
 
     def pass_stats(self, i): return Stats(rays=getattr(self, "px", 0), hits=getattr(self, "px", 0) // 2)
     def mark_kernel_times(self): self.launches_ms = []
@@ -57,6 +66,8 @@ class StubStandardPipeline:
 
         def call():
             StubPipe.log.append(("frames", idx))
+            for p, i in zip(pipes, idx):
+                p.drew(i)
             pipes[0].launches_ms.append(0.21 * len(idx))   # the first pipeline's event pair brackets the launch of all frames
         return call
 
@@ -92,18 +103,20 @@ class StubBackend:
     def check_target(self, pipe, target, rows): pass
 
 
-def _run(steps, fpl=None):
+def _run(steps, fpl=None, extra=(), settle_seconds=0.0, settle_max=None):
     StubPipe.log = []
     argv = ["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--width", str(W), "--height", str(H), "--no-cpu-baseline", "--no-extra-curves"]
     if fpl is not None:
         argv += ["--frames-per-launch", str(fpl)]
-    args = bench.parse(argv)
-    old = bench.SETTLE_STEPS, bench.SETTLE_SECONDS
-    bench.SETTLE_STEPS, bench.SETTLE_SECONDS = 16, 0.0
+    args = bench.parse(argv + list(extra))
+    old = bench.SETTLE_STEPS, bench.SETTLE_SECONDS, bench.SETTLE_MAX_STEPS
+    bench.SETTLE_STEPS, bench.SETTLE_SECONDS = 16, settle_seconds
+    if settle_max is not None:
+        bench.SETTLE_MAX_STEPS = settle_max
     try:
         out = bench.run_rank(args, StubBackend(), None)
     finally:
-        bench.SETTLE_STEPS, bench.SETTLE_SECONDS = old
+        bench.SETTLE_STEPS, bench.SETTLE_SECONDS, bench.SETTLE_MAX_STEPS = old
     json.dumps(out)
     return out, list(StubPipe.log)
 
@@ -129,3 +142,53 @@ def test_a_launch_per_frame_and_other_counts():
     assert out["config"]["frames_per_launch"] == 1 and out["roofline"]["kernel"] == "k_primary_ao" and all(e[0] == "frame" for e in log)
     out, log = _run(12, fpl=3)
     assert out["config"]["frames_per_launch"] == 3 and [len(e[1]) for e in log[1:]] == [1, 3, 3, 3, 3, 3, 3, 3, 3, 3]   # (16 settle steps: a frame, then five launches; 12 timed: four)
+
+
+def test_dump_outputs_writes_the_last_timed_step_whatever_the_settle_count(tmp_path):
+    """--dump-outputs: the planes of the LAST timed step, in float32 / float64; the timed frames' indices do not depend on how many settle
+    frames the clock asked for, so two runs with the same arguments dump the same frame"""
+    dumps = []
+    for k, seconds in enumerate((0.0, 30.0)):   # no settle frames beyond the fixed 16, then as many more as allowed (24: whole launches)
+        d = tmp_path / str(k)
+        out, log = _run(20, extra=["--dump-outputs", str(d)], settle_seconds=seconds, settle_max=24)
+        assert out["steps"] == 20 and out["config"]["untimed_steps_before_timing"] == 16 + (24 if seconds else 0)
+        last = log[-1][1][-1]   # the last frame of the last launch
+        got = {f.name: np.load(f) for f in d.iterdir()}
+        assert sorted(got) == ["depth.npy", "illuminance.npy", "voxel_id.npy"]
+        assert got["illuminance.npy"].dtype == np.float32 and got["illuminance.npy"].shape == (H, W, 4)
+        assert got["depth.npy"].dtype == np.float32 and got["voxel_id.npy"].dtype == np.float64
+        assert (got["voxel_id.npy"] == last).all() and (got["illuminance.npy"][:, :, 0] == last % 1024).all()
+        dumps.append((last, got))
+    assert dumps[0][0] == dumps[1][0]
+    assert all(np.array_equal(dumps[0][1][n], dumps[1][1][n]) for n in dumps[0][1])
+
+
+def test_dump_outputs_samples_a_large_frame(tmp_path, monkeypatch):
+    """beyond the cap every plane keeps the same seeded sample of pixels, and pixel_index.npy names them"""
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20_000)
+    _run(8, extra=["--dump-outputs", str(tmp_path)])
+    got = {f.name: np.load(f) for f in tmp_path.iterdir()}
+    idx = got["pixel_index.npy"]
+    assert idx.dtype == np.float64 and 0 < len(idx) < W * H and sum(a.nbytes for a in got.values()) <= 20_000
+    assert got["illuminance.npy"].shape == (len(idx), 4) and got["depth.npy"].shape == (len(idx), 1)
+
+
+def test_a_plain_run_measures_the_headline_alone(monkeypatch):
+    """without --full: no CPU baseline and no extra curves, even where --no-cpu-baseline / --no-extra-curves are not given; with --full
+    both run. The stand-in backend has `assets` and the frame is the 1080p one, so only --full decides."""
+    called = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **kw: called.append("cpu_baseline") or {"value": 1.0})
+    monkeypatch.setattr(bench, "extra_curves", lambda *a, **kw: called.append("extra_curves") or {"one_frame_per_launch": {"value": 1.0}})
+    monkeypatch.setattr(bench, "SETTLE_STEPS", 16)
+    monkeypatch.setattr(bench, "SETTLE_SECONDS", 0.0)
+    be = StubBackend()
+    be.assets = types.SimpleNamespace(summary=lambda: {"used": []})
+    argv = ["--gpus", "1", "--steps", "8", "--warmup", "1", "--width", "1920", "--height", "1080"]
+    args = bench.parse(argv)
+    assert not args.full
+    out = bench.run_rank(args, be, None)
+    assert called == [] and out["cpu_baseline"] is None and set(out["curves"]) == {"strong"}
+    assert out["steps"] == 8 and out["ms_per_step"] > 0
+    out = bench.run_rank(bench.parse(argv + ["--full"]), be, None)
+    assert called == ["cpu_baseline", "extra_curves"] and out["cpu_baseline"] == {"value": 1.0}
+    assert set(out["curves"]) == {"strong", "one_frame_per_launch"}

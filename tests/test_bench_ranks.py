@@ -284,9 +284,9 @@ import pytest  # noqa: E402
 
 @pytest.mark.gpu
 def test_bench_line_on_the_gpu_keeps_the_contract():
-    """`python bench.py --gpus 1 --steps K --warmup W` as the driver runs it: one JSON line with the contract's keys, `roofline` and
-    `cpu_baseline`, and numbers that are consistent with each other."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--cpu-rows", "64"],
+    """`python bench.py --gpus 1 --steps K --warmup W --full`: one JSON line with the contract's keys, `roofline` and `cpu_baseline`, and
+    numbers that are consistent with each other."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--cpu-rows", "64", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600,
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -311,3 +311,31 @@ def test_bench_line_on_the_gpu_keeps_the_contract():
     assert abs(j["value"] - rays / (j["ms_per_step"] * 1e-3) / 1e6) / j["value"] < 2e-3
     cb = j["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` as the driver runs it: the headline alone (no CPU baseline, no
+    extra curves), exactly K timed steps, and the last step's planes -- the same ones from two runs with the same arguments."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "2", "--dump-outputs", str(d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 12 and j["ms_per_step"] > 0 and j["unit"] == "Mrays/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert j["cpu_baseline"] is None and set(j["curves"]) == {"strong"}
+        got = {f.name: np.load(f) for f in d.iterdir()}
+        assert sorted(got) == ["depth.npy", "illuminance.npy", "voxel_id.npy"]
+        assert sum(a.nbytes for a in got.values()) <= 64_000_000 and all(a.dtype in (np.float32, np.float64) for a in got.values())
+        ill = got["illuminance.npy"]
+        assert ill.shape == (1080, 1920, 4) and got["depth.npy"].shape == got["voxel_id.npy"].shape == (1080, 1920)
+        assert (ill[..., :3] != 0).any() and len(np.unique(got["voxel_id.npy"])) > 1   # a rendered frame, not an empty plane
+        dumps.append(got)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name], equal_nan=True), name

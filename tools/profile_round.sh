@@ -13,7 +13,7 @@ cd "$R" || exit 1
 { echo "# HEAD ${HEAD_STAMP:-unknown}"; python -m pytest tests -m gpu -x -q -p no:cacheprovider; } > "$out/${tag}_gpu_tests.log" 2>&1
 tail -2 "$out/${tag}_gpu_tests.log"
 
-python bench.py --no-extra-curves > "$out/${tag}_bench.log" 2> "$out/${tag}_bench.err"   # the headline: eight frames per launch (dust_hip_render_frames)
+python bench.py --full --no-extra-curves > "$out/${tag}_bench.log" 2> "$out/${tag}_bench.err"   # the headline: eight frames per launch (dust_hip_render_frames)
 tail -1 "$out/${tag}_bench.log" | cut -c1-600
 # round 6, second half: frames per launch -- 1 (rounds 1-5's headline: a launch per frame), 2, 3 (the reference's frames in flight), 4
 for k in 1 2 3 4; do
@@ -22,9 +22,9 @@ done
 python bench.py --width 3840 --height 2160 --steps 64 --frames-per-launch 1 --no-cpu-baseline --no-extra-curves > "$out/${tag}_bench_4k_fpl1.log" 2>> "$out/${tag}_bench.err"
 python bench.py --workload gi --no-cpu-baseline > "$out/${tag}_bench_gi.log" 2>> "$out/${tag}_bench.err"
 tail -1 "$out/${tag}_bench_gi.log" | cut -c1-600
-python bench.py --workload deep --steps 30 > "$out/${tag}_bench_deep.log" 2>> "$out/${tag}_bench.err"
+python bench.py --workload deep --steps 30 --full > "$out/${tag}_bench_deep.log" 2>> "$out/${tag}_bench.err"
 tail -1 "$out/${tag}_bench_deep.log" | cut -c1-600
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$out/${tag}_bench_driver_style.log" 2>> "$out/${tag}_bench.err"   # the driver's command line: the headline + curves.moving / primary_ao_4k / gi_1080p / deep
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out/${tag}_bench_driver_style.log" 2>> "$out/${tag}_bench.err"   # the driver's command line with --full: the headline + CPU baseline + curves.moving / primary_ao_4k / gi_1080p / deep
 python bench.py --camera orbit --steps 240 --no-cpu-baseline > "$out/${tag}_bench_moving.log" 2>> "$out/${tag}_bench.err"   # the moving view as the headline
 python bench.py --workload teapot_cpu > "$out/${tag}_bench_teapot_cpu.log" 2>> "$out/${tag}_bench.err"
 python bench.py --workload gi --width 3840 --height 2160 --steps 40 --no-cpu-baseline > "$out/${tag}_bench_gi_4k.log" 2>> "$out/${tag}_bench.err"
