@@ -107,6 +107,19 @@ class GiExchange(C.Structure):
                 ("slot_owner", C.c_void_p), ("touched", C.c_void_p), ("merged", C.c_void_p)]
 
 
+class Ray(C.Structure):       # DustHipRay, 32 bytes: a scene query's ray (world space; t in units of |direction|)
+    _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("direction", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class RayHit(C.Structure):    # DustHipRayHit, 32 bytes: instance == NO_HIT on a miss
+    _fields_ = [("t", C.c_float), ("instance", C.c_uint32), ("block", C.c_uint32), ("voxel", C.c_uint32), ("xyz", C.c_uint32 * 3),
+                ("face", C.c_uint8), ("palette", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+NO_HIT = 0xFFFFFFFF
+QUERY_ANY_HIT = 1
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("rays", C.c_uint64), ("instances_tested", C.c_uint64),
                 ("upper_descents", C.c_uint64), ("mid_descents", C.c_uint64), ("bricks_tested", C.c_uint64),
@@ -169,6 +182,8 @@ SYMBOLS = {
     "dust_hip_scene_add_instance": (C.c_int, [_P, _P, _f32p, _f32p, _u32p]),
     "dust_hip_scene_set_transform": (C.c_int, [_P, C.c_uint32, _f32p, _f32p]),
     "dust_hip_scene_commit": (C.c_int, [_P]),
+    "dust_hip_scene_trace_rays": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32]),
+    "dust_hip_scene_trace_rays_async": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32]),
     "dust_hip_top_level_build": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, _P, _u32p, C.c_size_t, C.POINTER(C.c_uint16), C.c_size_t, _u32p, _u32p]),
     "dust_hip_pipeline_create": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "dust_hip_pipeline_destroy": (None, [_P]),

@@ -16,6 +16,12 @@ BLOCK_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("w", "<u2"), 
                         ("material_ptr", "<u4"), ("avg_albedo", "<u4")])
 assert BLOCK_DTYPE.itemsize == 24
 SURFEL_DTYPE = np.dtype([("pos", "<f4", 3), ("direction", "<u4")])
+# scene ray queries (Scene.trace_rays): DustHipRay / DustHipRayHit
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("instance", "<u4"), ("block", "<u4"), ("voxel", "<u4"), ("xyz", "<u4", 3),
+                      ("face", "u1"), ("palette", "u1"), ("reserved", "<u2")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
+FLT_MAX = float(np.finfo(np.float32).max)
 
 PLANE_DTYPES = {
     L.PLANE_ILLUMINANCE: (np.uint16, 4), L.PLANE_DENOISED: (np.uint16, 4), L.PLANE_ALBEDO: (np.uint32, 1),
@@ -356,6 +362,40 @@ class Scene:
 
     def commit(self):
         L.check(self._lib.dust_hip_scene_commit(self._h))
+
+    def trace_rays(self, origins, directions=None, tmin=0.0, tmax=math.inf, any_hit=False, hits=None):
+        """What each ray hits in the committed scene (dust_hip_scene_trace_rays): origins / directions (n, 3) in world space, tmin /
+        tmax scalars or (n,). Returns a HIT_DTYPE array: t, instance (L.NO_HIT on a miss), block, voxel, xyz (the voxel in the model's
+        tree coordinates: what Model.set_voxels / get_voxels take), face (normal2FaceID of the hit face's model-space normal), palette.
+        any_hit: some hit in [tmin, tmax], not necessarily the closest. An unbounded tmax (inf) is passed as FLT_MAX: the ABI reports
+        a ray with a non-finite tmin or tmax as a miss.
+        Device path (dust_hip_scene_trace_rays_async): `origins` a contiguous device tensor of DustHipRay rows ((n, 8) float32, see
+        ray_records) and `hits` one of n DustHipRayHit rows; enqueued on the context's stream, valid after Context.sync()."""
+        flags = L.QUERY_ANY_HIT if any_hit else 0
+        if hits is not None:
+            n = origins.numel() * origins.element_size() // RAY_DTYPE.itemsize
+            assert directions is None and origins.is_contiguous() and hits.is_contiguous()
+            assert origins.numel() * origins.element_size() == n * RAY_DTYPE.itemsize
+            assert hits.numel() * hits.element_size() >= n * HIT_DTYPE.itemsize
+            L.check(self._lib.dust_hip_scene_trace_rays_async(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(hits.data_ptr()), n, flags))
+            return hits
+        rays = ray_records(origins, directions, tmin, tmax)
+        out = np.zeros(len(rays), HIT_DTYPE)
+        L.check(self._lib.dust_hip_scene_trace_rays(self._h, _ptr(rays), _ptr(out), len(rays), flags))
+        return out
+
+
+def ray_records(origins, directions, tmin=0.0, tmax=math.inf):
+    """DustHipRay records (RAY_DTYPE) for Scene.trace_rays; tmax = +inf becomes FLT_MAX (an unbounded ray)"""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    assert len(o) == len(d)
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["origin"], rays["direction"] = o, d
+    rays["tmin"] = np.broadcast_to(np.asarray(tmin, np.float32), (len(o),))
+    tm = np.broadcast_to(np.asarray(tmax, np.float32), (len(o),))
+    rays["tmax"] = np.where(tm == np.float32(np.inf), np.float32(FLT_MAX), tm)
+    return rays
 
 
 def top_level_build(boxes):

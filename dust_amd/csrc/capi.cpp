@@ -22,6 +22,7 @@
 #include "sky.hpp"
 #include "edit.hpp"
 #include "denoise.hpp"
+#include "query.hpp"
 #include <unordered_set>
 
 namespace dust {
@@ -201,6 +202,10 @@ struct DustHipContext : RefCounted {
   // every frame writes its sequence number into. `frame_seq` counts those launches as they are enqueued. 0 / null: not available.
   volatile uint32_t* started = nullptr;
   uint32_t frame_seq = 0;
+  // scene ray queries (dust_hip_scene_trace_rays): the synchronous call's device staging, grown on demand, and the launches' two ray
+  // counters (a launch takes rays from one and zeroes the other for the next: query_parity says which is whose)
+  DeviceBuffer query_rays, query_hits, query_counters;
+  uint32_t query_parity = 0;
 };
 // wait for everything enqueued on the context's stream (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)
@@ -239,6 +244,7 @@ static void release(DustHipContext* c) {
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_side_done) (void)hipEventDestroy(c->ev_side_done);
   c->srgb_lut.release();
+  c->query_rays.release(); c->query_hits.release(); c->query_counters.release();
   if (c->started) (void)hipHostFree(const_cast<uint32_t*>(c->started));
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -885,6 +891,7 @@ DustStatus dust_hip_context_create(const DustHipConfig* cfg, DustHipContext** ou
   const size_t cap = c->max_lds > reserve ? c->max_lds - reserve : 0;
   if (c->lds_root_bytes > cap) c->lds_root_bytes = uint32_t(cap);
   HIP_TRY(dust::configure_kernels(c->max_lds));
+  HIP_TRY(dust::configure_query_kernels(c->max_lds));
   {  // (a context without the word works as before: commits that find the host a ring ahead wait for the whole stream)
     void* w = nullptr;
     if (!diag_env("NO_START_WORD") && hipHostMalloc(&w, 64, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess && w) {
@@ -1863,6 +1870,33 @@ struct BatchJoin {
 };
 // Follower: frames 0 .. n - 2 of a launch, prepared in order; Lead: frame n - 1 -- prepared last, launches all of them
 enum class FrameRole { Single, Follower, Lead };
+// the scene half of a launch descriptor: the current image's arrays (frames and scene ray queries)
+static void scene_args(const DustHipScene* s, dust::FrameArgs& a) {
+  a.models = reinterpret_cast<const dust::DevModel*>(s->dev(s->layout.models));
+  a.instances = reinterpret_cast<const dust::DevInstance*>(s->dev(s->layout.instances));
+  a.n_models = uint32_t(s->models.size());
+  a.n_instances = uint32_t(s->instances.size());
+  a.n_lds_models = s->n_lds_models;
+  a.root_table = s->dev(s->layout.root_table);
+  a.boxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.boxes));
+  a.visits = reinterpret_cast<const dust::DevVisit*>(s->dev(s->layout.visits));
+  a.grid = s->grid;
+  // (a grid that could not list every box -- build_grid -- is not handed to the kernels at all: the packet kernels, which never read it, run instead)
+  a.grid.cells = s->grid_valid ? reinterpret_cast<const uint32_t*>(s->dev(s->layout.grid_cells)) : nullptr;
+  a.grid.items = s->grid_valid ? reinterpret_cast<const uint16_t*>(s->dev(s->layout.grid_items)) : nullptr;
+  a.enters = reinterpret_cast<const dust::DevEnter*>(s->dev(s->layout.enters));
+  a.gboxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.gboxes));
+  a.sboxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.sboxes));
+  a.n_groups = s->n_groups;
+}
+// a frame or a query reads the scene as committed: refused while it has uncommitted changes or a model was edited since
+static DustStatus check_scene_ready(const DustHipScene* s) {
+  if (!s->committed) return fail(DUST_ERR_NOT_READY, "scene has uncommitted changes (call dust_hip_scene_commit)");
+  for (size_t i = 0; i < s->models.size(); ++i)
+    if (s->models[i]->generation != s->model_generation[i])
+      return fail(DUST_ERR_NOT_READY, "a model of the scene was edited after the last dust_hip_scene_commit");
+  return DUST_OK;
+}
 // every argument check of a frame, before anything is enqueued or changed (a frame that has started is finished); fp_copy: the caller's
 // parameters widened to this library's struct
 static DustStatus check_frame(DustHipPipeline* p, const DustHipScene* s, const DustHipCamera* cam, const DustHipSky* sky,
@@ -1874,10 +1908,7 @@ static DustStatus check_frame(DustHipPipeline* p, const DustHipScene* s, const D
   std::memcpy(&fp_copy, fp_in, std::min<size_t>(fp_in->struct_size, sizeof fp_copy));
   const DustHipFrameParams* fp = &fp_copy;
   if (p->ctx != s->ctx) return fail(DUST_ERR_INVALID_ARGUMENT, "pipeline and scene belong to different contexts");
-  if (!s->committed) return fail(DUST_ERR_NOT_READY, "scene has uncommitted changes (call dust_hip_scene_commit)");
-  for (size_t i = 0; i < s->models.size(); ++i)
-    if (s->models[i]->generation != s->model_generation[i])
-      return fail(DUST_ERR_NOT_READY, "a model of the scene was edited after the last dust_hip_scene_commit");
+  { DustStatus rs = check_scene_ready(s); if (rs != DUST_OK) return rs; }
   const uint32_t need5 = DUST_PASS_AMBIENT_OCCLUSION | DUST_PASS_FINAL_GATHER | DUST_PASS_SURFEL;
   if ((fp->passes & need5) && !p->noise5.p)
     return fail(DUST_ERR_NOT_READY, "blue-noise texture 5 (unitvec3_cosine) not loaded");  // standard.rs:254
@@ -1919,22 +1950,7 @@ static DustStatus render_frame_impl(DustHipPipeline* p, const DustHipScene* s, c
   HIP_TRY(hipSetDevice(ctx->device));
   dust::FrameArgs a{};
   s->touch();
-  a.models = reinterpret_cast<const dust::DevModel*>(s->dev(s->layout.models));
-  a.instances = reinterpret_cast<const dust::DevInstance*>(s->dev(s->layout.instances));
-  a.n_models = uint32_t(s->models.size());
-  a.n_instances = uint32_t(s->instances.size());
-  a.n_lds_models = s->n_lds_models;
-  a.root_table = s->dev(s->layout.root_table);
-  a.boxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.boxes));
-  a.visits = reinterpret_cast<const dust::DevVisit*>(s->dev(s->layout.visits));
-  a.grid = s->grid;
-  // (a grid that could not list every box -- build_grid -- is not handed to the kernels at all: the packet kernels, which never read it, run instead)
-  a.grid.cells = s->grid_valid ? reinterpret_cast<const uint32_t*>(s->dev(s->layout.grid_cells)) : nullptr;
-  a.grid.items = s->grid_valid ? reinterpret_cast<const uint16_t*>(s->dev(s->layout.grid_items)) : nullptr;
-  a.enters = reinterpret_cast<const dust::DevEnter*>(s->dev(s->layout.enters));
-  a.gboxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.gboxes));
-  a.sboxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.sboxes));
-  a.n_groups = s->n_groups;
+  scene_args(s, a);
   a.stream_refill = p->tune.stream_refill; a.stream_top_iters = p->tune.stream_top_iters;
   {  // what the ray-stream kernels stage in LDS, as far as it goes. The ray-making kernels (256 threads, many workgroups per CU): grid cells,
      // items and instance boxes within 40 KB; k_ray_walk (one 1024-thread workgroup per CU): the enter records behind its roots.
@@ -2383,6 +2399,72 @@ DustStatus dust_hip_render_frames(uint32_t n_frames, DustHipPipeline* const* pip
   }
   return DUST_OK;
   });
+}
+
+// Scene ray queries (query.hip). Enqueued on the context's stream as a frame is: the launch reads the scene image's current slot, which
+// touch() marks, so that a commit DustHipScene::kImages commits later does not overwrite it while the query may still read it.
+static DustStatus check_query(const DustHipScene* s, const void* rays, const void* hits, uint32_t flags) {
+  if (!s || !rays || !hits) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (flags & ~DUST_HIP_QUERY_ANY_HIT) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown query flags");
+  return check_scene_ready(s);
+}
+static DustStatus trace_rays_impl(DustHipScene* s, const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, uint32_t flags) {
+  DustHipContext* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->query_counters.p) {
+    HIP_TRY(ctx->query_counters.alloc(2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(ctx->query_counters.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  }
+  dust::FrameArgs a{};
+  s->touch();
+  scene_args(s, a);
+  for (const DustHipModel* m : s->models) a.deep |= m->dev.n_levels == 3 ? 1u : 0u;
+  unsigned long long* counters = static_cast<unsigned long long*>(ctx->query_counters.p);
+  dust::QueryArgs q;
+  q.rays = reinterpret_cast<const float*>(d_rays);
+  q.hits = reinterpret_cast<uint32_t*>(d_hits);
+  q.n = n;
+  q.any_hit = (flags & DUST_HIP_QUERY_ANY_HIT) ? 1u : 0u;
+  q.counter = counters + ctx->query_parity;
+  q.next_counter = counters + (ctx->query_parity ^ 1u);
+  // persistent 1024-thread workgroups, at most one per CU (each stages the roots once); a picking query is one small workgroup
+  const uint32_t block = n >= 1024u ? 1024u : (n + 63u) / 64u * 64u;
+  const uint32_t grid = std::min<uint32_t>(uint32_t(ctx->num_cus), (n + 1023u) / 1024u);
+  HIP_TRY(dust::launch_ray_query(a, q, grid, block, ctx->stream));
+  ctx->query_parity ^= 1u;
+  return DUST_OK;
+}
+DustStatus dust_hip_scene_trace_rays(DustHipScene* s, const DustHipRay* rays, DustHipRayHit* hits, uint32_t n, uint32_t flags) {
+  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
+  if (n == 0) return DUST_OK;  // (whatever the arrays)
+  { DustStatus cs = check_query(s, rays, hits, flags); if (cs != DUST_OK) return cs; }
+  return guarded([&]() -> DustStatus {
+    DustHipContext* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = size_t(n) * sizeof(DustHipRay);
+    static_assert(sizeof(DustHipRay) == sizeof(DustHipRayHit), "one staging size for rays and hits");
+    if (c->query_rays.bytes < bytes || !c->query_rays.p || !c->query_hits.p) {  // grown on demand, kept until the context goes
+      if (c->query_rays.alloc(bytes) != hipSuccess || c->query_hits.alloc(bytes) != hipSuccess) {
+        c->query_rays.release(); c->query_hits.release();
+        (void)hipGetLastError();
+        return fail(DUST_ERR_OUT_OF_MEMORY, "device staging for the query's rays and hits");
+      }
+    }
+    HIP_TRY(hipMemcpyAsync(c->query_rays.p, rays, bytes, hipMemcpyHostToDevice, c->stream));
+    const DustStatus st = trace_rays_impl(s, static_cast<const DustHipRay*>(c->query_rays.p), static_cast<DustHipRayHit*>(c->query_hits.p), n, flags);
+    if (st != DUST_OK) return st;
+    HIP_TRY(hipMemcpyAsync(hits, c->query_hits.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DUST_OK;
+  });
+}
+DustStatus dust_hip_scene_trace_rays_async(DustHipScene* s, const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, uint32_t flags) {
+  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
+  if (n == 0) return DUST_OK;  // (whatever the arrays)
+  { DustStatus cs = check_query(s, d_rays, d_hits, flags); if (cs != DUST_OK) return cs; }
+  if ((reinterpret_cast<uintptr_t>(d_rays) | reinterpret_cast<uintptr_t>(d_hits)) & 15u)
+    return fail(DUST_ERR_INVALID_ARGUMENT, "the ray and hit arrays must be 16-byte aligned (the kernel moves records as 16-byte vectors)");
+  return guarded([&]() -> DustStatus { return trace_rays_impl(s, d_rays, d_hits, n, flags); });
 }
 
 DustStatus dust_hip_pipeline_pass_stats(DustHipPipeline* p, uint32_t pass, DustHipPassStats* out) {

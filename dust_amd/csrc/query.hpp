@@ -1,0 +1,20 @@
+// query.hpp -- the launch of the scene ray queries (query.hip), as the host runtime (capi.cpp) calls it
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "dust_dev.h"
+
+namespace dust {
+
+struct QueryArgs {  // the kernel's second argument, behind the launch descriptor (whose scene half the host fills as for a frame)
+  const float* rays;               // n DustHipRay records (8 words each; 16-byte aligned)
+  uint32_t* hits;                  // n DustHipRayHit records
+  uint32_t n, any_hit;
+  unsigned long long* counter;     // rays handed out so far (zero at launch)
+  unsigned long long* next_counter;  // the next launch's counter: zeroed by this one (launches of one stream run one after the other)
+};
+
+hipError_t launch_ray_query(const FrameArgs& a, const QueryArgs& q, uint32_t grid, uint32_t block, hipStream_t s);
+hipError_t configure_query_kernels(size_t max_lds);  // every variant may take the device's dynamic LDS (at context creation)
+
+}  // namespace dust

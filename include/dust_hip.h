@@ -240,6 +240,34 @@ typedef struct DustTopLevelInfo {
 DustStatus dust_hip_top_level_build(const float* boxes, uint32_t n, DustTopLevelInfo* info, uint32_t* cells, size_t cells_capacity, uint16_t* items,
                                 size_t items_capacity, uint32_t* ranges, uint32_t* slot_order);
 
+/* Scene ray queries: what a game's own ray-tracing pipeline traces against the TLAS (render/src/pipeline/mod.rs:64-98) -- picking,
+ * where an edit lands, line of sight, probes. Every ray is a primary-type ray: hit.rint's exact voxel DDA over the instances, with
+ * the frame's tie rule (equal t: the lower instance, then the lower block wins). */
+typedef struct DustHipRay {      /* 32 bytes */
+  float origin[3]; float tmin;   /* world space; t is measured in units of |direction| (it need not be normalised) */
+  float direction[3]; float tmax;
+} DustHipRay;
+typedef struct DustHipRayHit {   /* 32 bytes */
+  float t;                       /* tmax on a miss */
+  uint32_t instance;             /* gl_InstanceID; DUST_HIP_NO_HIT on a miss */
+  uint32_t block;                /* gl_PrimitiveID: index into the model's Block array */
+  uint32_t voxel;                /* voxel in the 4^3 brick, hit.rint's numbering: x << 4 | y << 2 | z */
+  uint32_t xyz[3];               /* that voxel in the model's tree coordinates: what the model's set_voxels / get_voxels take */
+  uint8_t face;                  /* normal2FaceID (normal.glsl:39-43) of the model-space normal hit.rchit computes */
+  uint8_t palette;               /* palette index (hit.rchit's material lookup) */
+  uint16_t reserved;             /* 0 */
+} DustHipRayHit;
+#define DUST_HIP_NO_HIT 0xFFFFFFFFu
+#define DUST_HIP_QUERY_ANY_HIT 1u   /* stop at the first accepted hit (gl_RayFlagsTerminateOnFirstHitEXT): some hit in [tmin, tmax],
+                                       not necessarily the closest; every field describes that one hit */
+/* A query reads the scene as last committed: DUST_ERR_NOT_READY with uncommitted changes or a model edited since the commit (as a
+ * frame). Degenerate rays -- a zero direction, any non-finite component, a non-finite tmin or tmax, tmin > tmax -- report a miss.
+ * A null scene is refused; n == 0 is a no-op, whatever the arrays. Synchronous: host arrays, returns with the hits written (device staging is the context's, grown on demand). */
+DustStatus dust_hip_scene_trace_rays(DustHipScene*, const DustHipRay* rays, DustHipRayHit* hits, uint32_t n, uint32_t flags);
+/* The same on device arrays (16-byte aligned), enqueued on the context's stream behind the frames already submitted; returns at once.
+ * The hits are valid after dust_hip_sync, or after an event recorded on the caller's stream when the context was given that stream. */
+DustStatus dust_hip_scene_trace_rays_async(DustHipScene*, const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, uint32_t flags);
+
 /* the members of CameraSettings the shaders read (standard.rs:277-302,813-827; layout.playout:20-33) */
 typedef struct DustHipCamera {
   float view_col0[3], view_col1[3], view_col2[3]; /* camera_view_col0..2 */

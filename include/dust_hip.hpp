@@ -228,6 +228,20 @@ class Scene {
     check(dust_hip_scene_set_transform(h_, id, obj_to_world_3x4, prev_mat4));
   }
   void commit() { check(dust_hip_scene_commit(h_)); }
+  // a game's own rays against the committed scene (the reference's RayTracingPipeline over the TLAS, pipeline/mod.rs:64-98): host
+  // arrays, returns with the hits (hit.instance == DUST_HIP_NO_HIT: a miss). any_hit: some hit in [tmin, tmax], not the closest
+  void trace_rays(const DustHipRay* rays, DustHipRayHit* hits, uint32_t n, bool any_hit = false) {
+    check(dust_hip_scene_trace_rays(h_, rays, hits, n, any_hit ? DUST_HIP_QUERY_ANY_HIT : 0u));
+  }
+  std::vector<DustHipRayHit> trace_rays(const std::vector<DustHipRay>& rays, bool any_hit = false) {
+    std::vector<DustHipRayHit> hits(rays.size());
+    trace_rays(rays.data(), hits.data(), uint32_t(rays.size()), any_hit);
+    return hits;
+  }
+  // device arrays, enqueued on the context's stream: the hits are there after RenderContext::sync (or an event on the caller's stream)
+  void trace_rays_async(const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, bool any_hit = false) {
+    check(dust_hip_scene_trace_rays_async(h_, d_rays, d_hits, n, any_hit ? DUST_HIP_QUERY_ANY_HIT : 0u));
+  }
   DustHipScene* raw() const { return h_; }
  private:
   DustHipScene* h_ = nullptr;
