@@ -491,9 +491,10 @@ struct DustHipPipeline {
   DeviceBuffer gi_rays_fg, gi_rays_sf, gi_hits_sf, gi_groups_fg, gi_groups_sf, gi_unbinned;
   DeviceBuffer gi_order, gi_order_count;  // final gather: live pixels of each 64x64 tile grouped by ray direction bin
   DeviceBuffer gi_touched, gi_merged;  // multi-GPU exchange buffers (dust_hip_pipeline_gi_exchange)
-  // sharded surfel trace (DustHipFrameParams::surfel_world >= 1): the records in slot order (made on first use), and what the pending
-  // pass's second half (dust_hip_gi_surfel_exchange_run) needs of its first
+  // sharded surfel trace (DustHipFrameParams::surfel_world >= 1): the records in slot order (made on first use, gi_stage_slots slots each;
+  // released by dust_hip_pipeline_configure_gi), and what the pending pass's second half (dust_hip_gi_surfel_exchange_run) needs of its first
   DeviceBuffer gi_stage_req, gi_stage_repl, gi_stage_sun;
+  size_t gi_stage_slots = 0;
   struct { bool pending = false; const uint32_t* perm = nullptr; uint32_t rank = 0, world = 0, slots_per_rank = 0; } sf_shard;
   uint32_t gi_touched_rows = 0;
   uint32_t gi_capacity = 0, gi_pool_size = 0;
@@ -1808,15 +1809,17 @@ static DustStatus run_surfel_pass(DustHipPipeline* p, const dust::FrameArgs& a, 
     const bool staged = shard_world >= 1;
     if (staged) {
       const uint32_t groups = (p->gi_pool_size + 63u) / 64u, per = (groups + shard_world - 1u) / shard_world;
-      if (!p->gi_stage_req.p) {   // room for any world up to 64: a rank's share ends on a group boundary
-        const size_t cap = size_t(groups + 64u) * 64u;
+      const size_t cap = size_t(groups + 64u) * 64u;   // room for any world up to 64: a rank's share ends on a group boundary
+      if (p->gi_stage_slots < cap) {   // (made for the pool size of the frame that needs them: the slots of every rank's share index all three)
         HIP_TRY(hipStreamSynchronize(st));
+        p->gi_stage_slots = 0;
         HIP_TRY(p->gi_stage_req.alloc(cap * sizeof(dust::DevHashRequest)));
         HIP_TRY(p->gi_stage_repl.alloc(cap * 16));
         HIP_TRY(p->gi_stage_sun.alloc(cap * 16));
         HIP_TRY(hipMemsetAsync(p->gi_stage_req.p, 0, cap * sizeof(dust::DevHashRequest), st));
         HIP_TRY(hipMemsetAsync(p->gi_stage_repl.p, 0xFF, cap * 16, st));   // direction 0xFFFFFFFF: "keep"
         HIP_TRY(hipMemsetAsync(p->gi_stage_sun.p, 0, cap * 16, st));
+        p->gi_stage_slots = cap;
       }
       b.sf_stage_req = static_cast<dust::DevHashRequest*>(p->gi_stage_req.p);
       b.sf_stage_repl = static_cast<dust::DevSurfel*>(p->gi_stage_repl.p);
@@ -1924,8 +1927,9 @@ static DustStatus check_frame(DustHipPipeline* p, const DustHipScene* s, const D
     return fail(DUST_ERR_UNSUPPORTED, "a GI pass on a row band needs DUST_PASS_GI_SHARDED and the exchange of dust_hip_pipeline_gi_exchange");
   if (sharded && (fp->passes & DUST_PASS_FINAL_GATHER) && (fp->passes & DUST_PASS_SURFEL))
     return fail(DUST_ERR_INVALID_ARGUMENT, "DUST_PASS_GI_SHARDED: the surfel pass runs after the exchange, in its own call");
-  if (fp->surfel_world != 0 && (fp->passes & DUST_PASS_SURFEL) && (!sharded || fp->surfel_world > 64 || fp->surfel_rank >= fp->surfel_world))
-    return fail(DUST_ERR_INVALID_ARGUMENT, "a sharded surfel trace wants DUST_PASS_GI_SHARDED, surfel_world <= 64 and surfel_rank < surfel_world");
+  if (fp->surfel_world != 0 && (fp->passes & DUST_PASS_SURFEL) &&
+      (!sharded || !(fp->passes & DUST_PASS_GI_ORDERED) || fp->surfel_world > 64 || fp->surfel_rank >= fp->surfel_world))
+    return fail(DUST_ERR_INVALID_ARGUMENT, "a sharded surfel trace wants DUST_PASS_GI_SHARDED, DUST_PASS_GI_ORDERED, surfel_world <= 64 and surfel_rank < surfel_world");
   if (p->sf_shard.pending && (fp->passes & (DUST_PASS_FINAL_GATHER | DUST_PASS_SURFEL)))
     return fail(DUST_ERR_NOT_READY, "a sharded surfel trace is pending on this pipeline: dust_hip_gi_surfel_exchange_run completes it before the next GI pass");
   if (sharded && (fp->passes & DUST_PASS_FINAL_GATHER) && !p->gi_touched.p)
@@ -2542,6 +2546,11 @@ DustStatus dust_hip_pipeline_configure_gi(DustHipPipeline* p, uint32_t hash_capa
   if (!p || hash_capacity < 4 || surfel_pool_size == 0) return fail(DUST_ERR_INVALID_ARGUMENT, "bad GI configuration");
   HIP_TRY(hipSetDevice(p->ctx->device));
   HIP_TRY(sync_stream(p->ctx));
+  // a pending sharded surfel trace is cancelled (its permutation lives in gi_sort_vals, re-made below), and its staging arrays, sized
+  // for the old pool, go (the next sharded trace makes them for the new one)
+  p->sf_shard = {};
+  for (DeviceBuffer* b : {&p->gi_stage_req, &p->gi_stage_repl, &p->gi_stage_sun}) b->release();
+  p->gi_stage_slots = 0;
   const size_t hash_bytes = (size_t(hash_capacity) + 2) * 12;  // probes run up to 2 past the end (spatial_hash.glsl:154-158)
   HIP_TRY(p->gi_hash.alloc(hash_bytes));
   HIP_TRY(hipMemsetAsync(p->gi_hash.p, 0, hash_bytes, p->ctx->stream));             // standard.rs:348-358 relies on a zeroed allocation
@@ -2639,6 +2648,8 @@ DustStatus dust_hip_pipeline_write_gi(DustHipPipeline* p, uint32_t which, const 
   if (!p || !src || which > 1 || !p->gi_hash.p) return fail(DUST_ERR_INVALID_ARGUMENT, "GI state not configured");
   const DeviceBuffer& b = which == 0 ? p->gi_hash : p->gi_pool;
   if (src_bytes != b.bytes) return fail(DUST_ERR_INVALID_ARGUMENT, "saved GI state does not match the configured capacity / pool size");
+  if (p->sf_shard.pending)   // (its completion would overwrite the pool and stamp the hash over what is restored here)
+    return fail(DUST_ERR_NOT_READY, "a sharded surfel trace is pending on this pipeline: complete it (dust_hip_gi_surfel_exchange_run) or cancel it (dust_hip_pipeline_clear) first");
   HIP_TRY(hipSetDevice(p->ctx->device));
   HIP_TRY(join_side(p->ctx));
   HIP_TRY(copy_wait(b.p, src, b.bytes, hipMemcpyHostToDevice, p->ctx->stream));
@@ -2784,6 +2795,7 @@ DustStatus dust_hip_pipeline_clear(DustHipPipeline* p) {
   for (int i = 0; i < DUST_PLANE_COUNT; ++i) HIP_TRY(hipMemsetAsync(p->plane(i), 0, p->planes[i].bytes, p->ctx->stream));
   p->have_history = false;
   p->accum_count = 0;
+  p->sf_shard = {};   // a pending sharded surfel trace is cancelled (its records are dropped)
   return DUST_OK;
 }
 

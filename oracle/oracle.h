@@ -171,6 +171,10 @@ OrcGI* orc_gi_new(uint32_t hash_capacity, uint32_t surfel_pool_size);
 void orc_gi_free(OrcGI*);
 void* orc_gi_hash_ptr(OrcGI*);  /* (capacity + 2) x {u32 fingerprint, u32 LogLuv, u16 last_frame, u16 count} */
 void* orc_gi_pool_ptr(OrcGI*);  /* pool_size x {vec3 position, u32 direction} */
+/* the surfel pass applies, of one frame's inserts of one hash key, the last `keep` in surfel order (default 8, the HIP path's
+ * DUST_PASS_GI_ORDERED); keep 0: every insert */
+void orc_gi_set_apply_keep(OrcGI*, uint32_t keep);
+uint32_t orc_gi_last_superseded(const OrcGI*);  /* insert requests the last surfel pass dropped under that rule */
 uint32_t orc_hash_fingerprint(const int32_t pos[3], uint32_t dir);
 uint32_t orc_hash_location(const int32_t pos[3], uint32_t dir, uint32_t capacity);
 void orc_hash_insert(OrcGI*, const int32_t pos[3], uint32_t dir, const float value[3], uint32_t frame_index);

@@ -863,19 +863,23 @@ void orc_pass_ao(const OrcScene* s, int mode, const OrcCamera* cam, const OrcSky
  *   surfel pass : phase 1 -- every surfel traces its rays and reads the hash AS IT WAS AT THE START OF THE PASS
  *                            (Get still stamps last_accessed_frame, a write of the same value from everyone);
  *                 phase 2 -- the SpatialHashInsert calls and pool replacements are applied in surfel-index order; of the frame's
- *                            inserts of ONE key the last ORC_APPLY_KEEP (surfel_apply: the concurrent invocations' lost updates).
+ *                            inserts of ONE key the last apply_keep (surfel_apply: the concurrent invocations' lost updates;
+ *                            ORC_APPLY_KEEP by default, 0 = every insert, as the reference means it: orc_gi_set_apply_keep).
  */
+#define ORC_APPLY_KEEP 8u  /* the default apply_keep: the HIP path's kApplyKeep (dust_dev.h) */
 typedef struct OrcHashEntry { uint32_t fingerprint, radiance; uint16_t last_accessed_frame, sample_count; } OrcHashEntry;
 typedef struct OrcSurfel { float pos[3]; uint32_t direction; } OrcSurfel;
 struct OrcGI {
   uint32_t capacity, pool_size;
   OrcHashEntry* hash; /* capacity + 2: probes run up to 2 past the end (spatial_hash.glsl:154-158) */
   OrcSurfel* pool;
+  uint32_t apply_keep;       /* surfel_apply: inserts of one key a frame applies (0: all of them) */
+  uint32_t last_superseded;  /* the requests the last surfel_apply dropped */
 };
 
 OrcGI* orc_gi_new(uint32_t capacity, uint32_t pool_size) {
   OrcGI* g = (OrcGI*)calloc(1, sizeof(OrcGI));
-  g->capacity = capacity; g->pool_size = pool_size;
+  g->capacity = capacity; g->pool_size = pool_size; g->apply_keep = ORC_APPLY_KEEP;
   g->hash = (OrcHashEntry*)calloc((size_t)capacity + 2, sizeof(OrcHashEntry)); /* standard.rs:348-358 relies on zeros */
   g->pool = (OrcSurfel*)malloc((size_t)pool_size * sizeof(OrcSurfel));
   memset(g->pool, 0xFF, (size_t)pool_size * sizeof(OrcSurfel)); /* fill_buffer(u32::MAX), standard.rs:345-347 */
@@ -884,6 +888,8 @@ OrcGI* orc_gi_new(uint32_t capacity, uint32_t pool_size) {
 void orc_gi_free(OrcGI* g) { if (g) { free(g->hash); free(g->pool); free(g); } }
 void* orc_gi_hash_ptr(OrcGI* g) { return g->hash; }
 void* orc_gi_pool_ptr(OrcGI* g) { return g->pool; }
+void orc_gi_set_apply_keep(OrcGI* g, uint32_t keep) { g->apply_keep = keep; }
+uint32_t orc_gi_last_superseded(const OrcGI* g) { return g->last_superseded; }
 
 typedef struct { int32_t x, y, z; uint32_t dir; } HashKey;
 static uint32_t key_fingerprint(HashKey k) { /* spatial_hash.glsl:128-135 */
@@ -1150,9 +1156,9 @@ static void surfel_trace_range(const OrcScene* s, int mode, const OrcSky* sky, c
  * atomically (spatial_hash.glsl:147-195): of the invocations that insert ONE key together, those that read the entry before the
  * others' stores see the same old state, and the last store wins. The defined order (DESIGN.md "GI order"; the HIP path's
  * k_surfel_apply_mark states the same rule): the frame's insert requests are sorted by (hash location, surfel index); a request is
- * SUPERSEDED -- not applied -- when the request ORC_APPLY_KEEP places further on in that order has the same location and the same key
- * (of a run of requests with one key, the last ORC_APPLY_KEEP stay); the others are applied in surfel-index order. */
-#define ORC_APPLY_KEEP 8u
+ * SUPERSEDED -- not applied -- when the request apply_keep places further on in that order has the same location and the same key
+ * (of a run of requests with one key, the last apply_keep stay); the others are applied in surfel-index order. apply_keep 0: none is
+ * superseded, every insert is applied (what the reference's concurrent stores would give if none were lost). */
 typedef struct { uint32_t loc, idx; } ApplyOrder;
 static int apply_order_cmp(const void* a, const void* b) {
   const ApplyOrder *x = (const ApplyOrder*)a, *y = (const ApplyOrder*)b;
@@ -1167,10 +1173,12 @@ static void surfel_apply(OrcGI* gi, const SurfelReq* req, uint32_t frame_index) 
   for (uint32_t i = 0; i < N; ++i)
     if (req[i].kind == 1) { ord[n].loc = key_location(req[i].key, gi->capacity); ord[n].idx = i; ++n; }
   qsort(ord, n, sizeof(ApplyOrder), apply_order_cmp);
-  for (uint32_t p = 0; p + ORC_APPLY_KEEP < n; ++p) {
-    const ApplyOrder *x = &ord[p], *y = &ord[p + ORC_APPLY_KEEP];
+  const uint32_t keep = gi->apply_keep;
+  gi->last_superseded = 0;
+  for (uint32_t p = 0; keep && p + keep < n; ++p) {
+    const ApplyOrder *x = &ord[p], *y = &ord[p + keep];
     const HashKey *kx = &req[x->idx].key, *ky = &req[y->idx].key;
-    if (x->loc == y->loc && kx->x == ky->x && kx->y == ky->y && kx->z == ky->z && kx->dir == ky->dir) dead[x->idx] = 1;
+    if (x->loc == y->loc && kx->x == ky->x && kx->y == ky->y && kx->z == ky->z && kx->dir == ky->dir) { dead[x->idx] = 1; ++gi->last_superseded; }
   }
   for (uint32_t i = 0; i < N; ++i) { /* phase 2: in surfel order */
     if (req[i].kind == 1 && !dead[i]) hash_insert(gi, req[i].key, req[i].value, frame_index);

@@ -117,6 +117,9 @@ def lib():
         l.orc_gi_hash_ptr.argtypes = [C.c_void_p]
         l.orc_gi_pool_ptr.restype = C.c_void_p
         l.orc_gi_pool_ptr.argtypes = [C.c_void_p]
+        l.orc_gi_set_apply_keep.argtypes = [C.c_void_p, C.c_uint32]
+        l.orc_gi_last_superseded.restype = C.c_uint32
+        l.orc_gi_last_superseded.argtypes = [C.c_void_p]
         l.orc_hash_fingerprint.restype = C.c_uint32
         l.orc_hash_fingerprint.argtypes = [C.POINTER(C.c_int32), C.c_uint32]
         l.orc_hash_location.restype = C.c_uint32
@@ -291,6 +294,15 @@ class GI:
         out, cnt = (C.c_float * 3)(), C.c_uint32()
         f = self.l.orc_hash_get(self.h, (C.c_int32 * 3)(*pos), direction, frame, out, C.byref(cnt))
         return bool(f), list(out), cnt.value
+
+    def set_apply_keep(self, keep):
+        """Of one frame's inserts of one hash key, the surfel pass applies the last `keep` (default 8, DUST_PASS_GI_ORDERED's rule);
+        0 applies every insert."""
+        self.l.orc_gi_set_apply_keep(self.h, keep)
+
+    def last_superseded(self):
+        """Insert requests the last surfel pass dropped under the keep rule."""
+        return self.l.orc_gi_last_superseded(self.h)
 
 
 class Denoiser:

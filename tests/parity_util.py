@@ -262,6 +262,93 @@ def sharded_gi_vs_single_device(ctx, scene, cam, sky, w, h, world, frames, n0, n
     return h_ref
 
 
+# The drift of DUST_PASS_GI_ORDERED's keep-8 rule against applying every insert (oracle GI.set_apply_keep(0), the reference's intent),
+# measured on the castle crop that the multi-GPU tests use: 96 x 64 pixels close to the walls, 6144 surfel slots over about 1200 hash
+# keys, so that one frame's surfels pile onto the same brick faces. After DRIFT_FRAMES frames with synth.frame_rand(DRIFT_SEED, f), the
+# oracle measures (keep 8 against keep 0):
+#   superseded requests per frame  0, 17, 189, 558, 866, 1087, 1289, 1450, 1540, 1622, 1702, 1756 (of 4809 live surfels)
+#   hash keys in both runs         1219 of 1219
+#   radiance luminance rel. diff.  median 0.0, p95 0.0527
+#   mean sample_count keep 8/0     0.673
+#   mean illuminance rel. diff.    0.0129
+#   per-pixel illuminance rel.     median 0.0, p95 0.127
+# DRIFT_BOUNDS are about twice that (the sample-count ratio: 0.1 below it); test_gi_oracle.py holds the oracle to them, test_gpu_gi.py
+# the device's ordered apply.
+DRIFT_W, DRIFT_H, DRIFT_CAP, DRIFT_POOL, DRIFT_FRAMES, DRIFT_SEED = 96, 64, 1 << 16, 6144, 12, 7
+
+
+def drift_setup():
+    """(SceneDesc, camera, sky, noise0, noise5) of the drift measurement"""
+    data, _ = synth.castle_scene(scale=0.15)
+    desc = SceneDesc.from_vox(data)
+    cam = camera_for((122.0 * 0.15, 300.61 * 0.15, 54.45 * 0.15))
+    return desc, cam, sky_state(), synth.stbn_scalar(layers=4), synth.stbn_unitvec3_cosine(layers=4)
+
+
+def drift_oracle(keep, oscene=None, gi_threads=8):
+    """DRIFT_FRAMES oracle GI frames with apply_keep = keep (None: the default) -> (GI, illuminance as float [h, w, 4], superseded requests
+    per frame)"""
+    desc, cam, sky, n0, n5 = drift_setup()
+    oscene = oscene or oracle_scene(desc)
+    gi = O.GI(DRIFT_CAP, DRIFT_POOL)
+    if keep is not None:
+        gi.set_apply_keep(keep)
+    passes = L.PASS_PRIMARY | L.PASS_AMBIENT_OCCLUSION | L.PASS_FINAL_GATHER | L.PASS_SURFEL
+    superseded = []
+    for f in range(1, DRIFT_FRAMES + 1):
+        g = render_oracle(oscene, cam, sky, DRIFT_W, DRIFT_H, passes, n5[f % 4], synth.frame_rand(DRIFT_SEED, f), noise0=n0[f % 4], gi=gi,
+                          frame_index=f, gi_threads=gi_threads)
+        superseded.append(gi.last_superseded())
+    return gi, half_to_float(g.illuminance), superseded
+
+
+def decode_radiance(words):
+    """LogLuv hash words -> float32 [n, 3] (the oracle's decoder)"""
+    l = O.lib()
+    out = np.zeros((len(words), 3), np.float32)
+    v = (C.c_float * 3)()
+    for i, w in enumerate(np.asarray(words, np.uint32).tolist()):
+        l.orc_logluv_decode(w, v)
+        out[i] = v[:]
+    return out
+
+
+def gi_drift(fingerprint_a, radiance_a, count_a, ill_a, fingerprint_b, radiance_b, count_b, ill_b):
+    """How far GI state a lies from GI state b (b: every insert applied). Over the hash keys both hold (matched by fingerprint): the
+    median and 95th percentile of the relative difference of the decoded radiance's luminance, and the ratio of the mean sample counts;
+    over the frame: the relative difference of the mean illuminance and the 95th percentile of the per-pixel relative difference."""
+    fa, fb = np.asarray(fingerprint_a), np.asarray(fingerprint_b)
+    ia = {int(f): i for i, f in enumerate(fa.tolist()) if f != 0}
+    ib = {int(f): i for i, f in enumerate(fb.tolist()) if f != 0}
+    common = sorted(set(ia) & set(ib))
+    xa, xb = np.array([ia[f] for f in common], np.int64), np.array([ib[f] for f in common], np.int64)
+    lum = np.array([0.2126, 0.7152, 0.0722], np.float64)
+    la = decode_radiance(np.asarray(radiance_a)[xa]).astype(np.float64) @ lum
+    lb = decode_radiance(np.asarray(radiance_b)[xb]).astype(np.float64) @ lum
+    rel = np.abs(la - lb) / np.maximum(np.abs(lb), 1e-6)
+    a, b = ill_a[..., :3].astype(np.float64) @ lum, ill_b[..., :3].astype(np.float64) @ lum
+    fin = np.isfinite(a) & np.isfinite(b)
+    px = np.abs(a[fin] - b[fin]) / np.maximum(np.abs(b[fin]), 1e-3)
+    return dict(keys=len(common), keys_a=len(ia), keys_b=len(ib),
+                radiance_rel_median=float(np.median(rel)), radiance_rel_p95=float(np.percentile(rel, 95)),
+                count_ratio=float(np.asarray(count_a)[xa].mean() / np.asarray(count_b)[xb].mean()),
+                mean_illuminance_rel=float(abs(a[fin].mean() - b[fin].mean()) / abs(b[fin].mean())),
+                pixel_rel_median=float(np.median(px)), pixel_rel_p95=float(np.percentile(px, 95)))
+
+
+DRIFT_BOUNDS = dict(radiance_rel_median=0.01, radiance_rel_p95=0.10, count_ratio=(0.57, 1.0), mean_illuminance_rel=0.03,
+                    pixel_rel_median=0.01, pixel_rel_p95=0.25)
+
+
+def assert_drift_within_bounds(d):
+    """gi_drift's result within DRIFT_BOUNDS"""
+    assert d["keys"] >= 0.9 * max(d["keys_a"], d["keys_b"]), d
+    lo, hi = DRIFT_BOUNDS["count_ratio"]
+    assert lo <= d["count_ratio"] <= hi, d
+    for k in ("radiance_rel_median", "radiance_rel_p95", "mean_illuminance_rel", "pixel_rel_median", "pixel_rel_p95"):
+        assert d[k] <= DRIFT_BOUNDS[k], (k, d)
+
+
 def run_smoke():
     """__graft_entry__.smoke(): one 96x64 primary + AO frame on device 0 against the oracle."""
     desc = small_scene(seed=3)

@@ -102,3 +102,42 @@ def test_threaded_gi_passes_equal_the_serial_ones():
     assert out[0][1].tobytes() == out[1][1].tobytes()
     assert out[0][2].tobytes() == out[1][2].tobytes()
     assert int((out[0][0]["fingerprint"] != 0).sum()) >= 10 and int((out[0][1]["direction"] < 6).sum()) >= 10
+
+
+def test_keep_eight_apply_drifts_boundedly_from_applying_every_insert():
+    """The ordered apply keeps, of one frame's inserts of one hash key, the last 8 in surfel order; the reference applies all of them.
+    On a frame whose surfels pile onto hot keys (supersession on most frames: the test is not vacuous) the converged hash and the
+    illuminance stay within the measured bounds of the apply-everything run, and only the rule makes the two differ."""
+    g8, ill8, sup8 = P.drift_oracle(8)
+    g0, ill0, sup0 = P.drift_oracle(0)
+    gd, _, supd = P.drift_oracle(None)
+    assert supd == sup8 and gd.hash().tobytes() == g8.hash().tobytes()   # keep 8 is the default
+    assert sup0 == [0] * P.DRIFT_FRAMES
+    assert sum(1 for n in sup8 if n > 0) >= 2 * P.DRIFT_FRAMES // 3, sup8
+    assert sup8[-1] >= 0.2 * int((g8.pool()["direction"] < 6).sum()), sup8
+    h8, h0 = g8.hash(), g0.hash()
+    assert int((h0["fingerprint"] != 0).sum()) > 500
+    d = P.gi_drift(h8["fingerprint"], h8["radiance"], h8["sample_count"], ill8, h0["fingerprint"], h0["radiance"], h0["sample_count"], ill0)
+    P.assert_drift_within_bounds(d)
+    assert d["count_ratio"] < 0.95 and d["radiance_rel_p95"] > 0.0, d   # the rule did drop samples
+
+
+def test_apply_keep_zero_only_changes_frames_with_superseded_inserts():
+    """apply_keep is the only difference: a default GI is keep 8, and a frame in which nothing is superseded leaves keep 8 and keep 0
+    in the same state (a sparse scene seen from afar)."""
+    desc = P.small_scene(seed=5, n_models=2, n_instances=4, size=(28, 28, 28))
+    s = P.oracle_scene(desc)
+    sky, cam = P.sky_state(), P.camera_for((80.0, 60.0, 90.0))
+    n0, n5 = synth.stbn_scalar(layers=4), synth.stbn_unitvec3_cosine(layers=4)
+    passes = L.PASS_PRIMARY | L.PASS_AMBIENT_OCCLUSION | L.PASS_FINAL_GATHER | L.PASS_SURFEL
+    out = []
+    for keep in (None, 8, 0):
+        gi = O.GI(1 << 14, 2048)
+        if keep is not None:
+            gi.set_apply_keep(keep)
+        for f in range(1, 6):
+            P.render_oracle(s, cam, sky, 96, 64, passes, n5[f % 4], synth.frame_rand(1, f), noise0=n0[f % 4], gi=gi, frame_index=f)
+            assert gi.last_superseded() == 0
+        out.append((gi.hash().tobytes(), gi.pool().tobytes()))
+    assert out[0] == out[1] == out[2]
+    assert int((np.frombuffer(out[0][0], O.HASH_DTYPE)["fingerprint"] != 0).sum()) > 20

@@ -329,3 +329,46 @@ def test_clustered_apply_equals_serial_apply(monkeypatch):
         assert (states[0][0][:, 0] != 0).sum() > 100
         for x, y in zip(*states):
             assert np.array_equal(x, y), capacity
+
+
+def test_ordered_apply_over_many_frames_and_its_drift_from_applying_every_insert():
+    """DUST_PASS_GI_ORDERED keeps, of one frame's inserts of one hash key, the last 8 in surfel order (k_surfel_apply_mark), where the
+    reference applies every insert. On parity_util's drift scene (surfels pile onto hot keys: most frames supersede inserts), over 12
+    frames of feedback: the ordered device run is the keep-8 oracle's (integer state bit for bit every frame, radiance within its
+    quantisation, illuminance at the north-star tolerance), it lies within the measured bounds (parity_util.DRIFT_BOUNDS) of the
+    apply-everything oracle, and the default concurrent apply stays statistically close to the apply-everything oracle too."""
+    desc, cam, sky, n0, n5 = P.drift_setup()
+    ctx = api.Context(device=0)
+    scene = P.hip_scene(ctx, desc)
+    oscene = P.oracle_scene(desc)
+    passes = L.PASS_PRIMARY | L.PASS_AMBIENT_OCCLUSION | L.PASS_FINAL_GATHER | L.PASS_SURFEL
+    w, h = P.DRIFT_W, P.DRIFT_H
+    pipes = {}
+    for flags in (L.PASS_GI_ORDERED, 0):
+        pipe = api.StandardPipeline(ctx, w, h)
+        pipe.set_noise(0, n0)
+        pipe.set_noise(5, n5)
+        pipe.configure_gi(P.DRIFT_CAP, P.DRIFT_POOL)
+        pipes[flags] = pipe
+    gi8 = O.GI(P.DRIFT_CAP, P.DRIFT_POOL)
+    superseded = []
+    for f in range(1, P.DRIFT_FRAMES + 1):
+        rnd = synth.frame_rand(P.DRIFT_SEED, f)
+        for flags, pipe in pipes.items():
+            pipe.render(scene, cam, sky, passes | flags, frame_index=f, rand=rnd)
+        g = P.render_oracle(oscene, cam, sky, w, h, passes, n5[f % 4], rnd, noise0=n0[f % 4], gi=gi8, frame_index=f, gi_threads=8)
+        superseded.append(gi8.last_superseded())
+        compare_gi(gi8, pipes[L.PASS_GI_ORDERED])
+    assert sum(1 for n in superseded if n > 0) >= 2 * P.DRIFT_FRAMES // 3, superseded
+    P.assert_parity(P.compare_gbuffers(g, P.read_hip_gbuffer(pipes[L.PASS_GI_ORDERED])))
+    gi0, ill0, _ = P.drift_oracle(0, oscene)
+    h0 = gi0.hash()
+    (hd, _), illd = pipes[L.PASS_GI_ORDERED].read_gi(), P.half_to_float(pipes[L.PASS_GI_ORDERED].read_plane(L.PLANE_ILLUMINANCE))
+    d = P.gi_drift(hd[:, 0], hd[:, 1], hd[:, 2] >> 16, illd, h0["fingerprint"], h0["radiance"], h0["sample_count"], ill0)
+    P.assert_drift_within_bounds(d)
+    (hr, _), illr = pipes[0].read_gi(), P.half_to_float(pipes[0].read_plane(L.PLANE_ILLUMINANCE))
+    fp_all, fp_racy = set(h0["fingerprint"][h0["fingerprint"] != 0].tolist()), set(hr[:, 0][hr[:, 0] != 0].tolist())
+    assert len(fp_all & fp_racy) >= 0.9 * len(fp_all)
+    a, b = ill0[..., :3], illr[..., :3]
+    fin = np.isfinite(a) & np.isfinite(b)
+    assert abs(a[fin].mean() - b[fin].mean()) <= 0.05 * abs(a[fin].mean())
