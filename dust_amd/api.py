@@ -21,6 +21,10 @@ RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4"
 HIT_DTYPE = np.dtype([("t", "<f4"), ("instance", "<u4"), ("block", "<u4"), ("voxel", "<u4"), ("xyz", "<u4", 3),
                       ("face", "u1"), ("palette", "u1"), ("reserved", "<u2")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
+# scene box queries (Scene.overlap_boxes): DustHipBoxQuery / DustHipVoxelRef
+BOX_QUERY_DTYPE = np.dtype([("lo", "<f4", 3), ("first", "<u4"), ("hi", "<f4", 3), ("capacity", "<u4")])
+VOXEL_REF_DTYPE = np.dtype([("instance", "<u4"), ("block", "<u4"), ("xyz", "<u2", 3), ("palette", "u1"), ("voxel", "u1")])
+assert BOX_QUERY_DTYPE.itemsize == 32 and VOXEL_REF_DTYPE.itemsize == 16
 FLT_MAX = float(np.finfo(np.float32).max)
 
 PLANE_DTYPES = {
@@ -384,6 +388,31 @@ class Scene:
         L.check(self._lib.dust_hip_scene_trace_rays(self._h, _ptr(rays), _ptr(out), len(rays), flags))
         return out
 
+    def overlap_boxes(self, lo, hi=None, capacity=64, any_hit=False, counts=None, records=None):
+        """The solid voxels inside world-space boxes (dust_hip_scene_overlap_boxes): lo / hi (n, 3), capacity an int or (n,). Returns
+        (counts, records_per_query): counts[i] every overlapping voxel, records_per_query[i] a VOXEL_REF_DTYPE array of the first
+        min(counts[i], capacity[i]) of them in (instance, block, voxel) order -- instance, block, xyz (the voxel in the model's tree
+        coordinates: what Model.set_voxels / get_voxels take), palette, voxel. any_hit: counts are 0 / 1, the record some overlapping voxel.
+        Device path (dust_hip_scene_overlap_boxes_async): `lo` a contiguous device tensor of DustHipBoxQuery rows ((n, 8) 32-bit words,
+        see box_queries), `counts` one of n uint32 and `records` one of DustHipVoxelRef rows ((m, 4) 32-bit words); enqueued on the
+        context's stream, valid after Context.sync(). Returns (counts, records) as given."""
+        flags = L.QUERY_ANY_HIT if any_hit else 0
+        if counts is not None:
+            assert hi is None and records is not None and lo.is_contiguous() and counts.is_contiguous() and records.is_contiguous()
+            n = lo.numel() * lo.element_size() // BOX_QUERY_DTYPE.itemsize
+            assert lo.numel() * lo.element_size() == n * BOX_QUERY_DTYPE.itemsize and counts.numel() * counts.element_size() >= 4 * n
+            n_rec = records.numel() * records.element_size() // VOXEL_REF_DTYPE.itemsize
+            L.check(self._lib.dust_hip_scene_overlap_boxes_async(self._h, C.c_void_p(lo.data_ptr()), n, C.c_void_p(counts.data_ptr()),
+                                                                 C.c_void_p(records.data_ptr()), n_rec, flags))
+            return counts, records
+        boxes = box_queries(lo, hi, capacity)
+        n_rec = int(boxes["capacity"].sum(dtype=np.int64))
+        out_counts = np.zeros(len(boxes), np.uint32)
+        out = np.zeros(max(n_rec, 1), VOXEL_REF_DTYPE)
+        L.check(self._lib.dust_hip_scene_overlap_boxes(self._h, _ptr(boxes), len(boxes), _ptr(out_counts), _ptr(out), n_rec, flags))
+        per = [out[int(f): int(f) + int(min(c, k))] for f, c, k in zip(boxes["first"], out_counts, boxes["capacity"])]
+        return out_counts, per
+
 
 def ray_records(origins, directions, tmin=0.0, tmax=math.inf):
     """DustHipRay records (RAY_DTYPE) for Scene.trace_rays; tmax = +inf becomes FLT_MAX (an unbounded ray)"""
@@ -396,6 +425,20 @@ def ray_records(origins, directions, tmin=0.0, tmax=math.inf):
     tm = np.broadcast_to(np.asarray(tmax, np.float32), (len(o),))
     rays["tmax"] = np.where(tm == np.float32(np.inf), np.float32(FLT_MAX), tm)
     return rays
+
+
+def box_queries(lo, hi, capacity=64):
+    """DustHipBoxQuery records (BOX_QUERY_DTYPE) for Scene.overlap_boxes: the slices [first, first + capacity) laid end to end"""
+    lo = np.asarray(lo, np.float32).reshape(-1, 3)
+    hi = np.asarray(hi, np.float32).reshape(-1, 3)
+    assert len(lo) == len(hi)
+    boxes = np.zeros(len(lo), BOX_QUERY_DTYPE)
+    boxes["lo"], boxes["hi"] = lo, hi
+    cap = np.broadcast_to(np.asarray(capacity, np.int64), (len(lo),))
+    assert np.all(cap >= 0) and int(cap.sum()) < 2 ** 32
+    boxes["capacity"] = cap
+    boxes["first"] = np.concatenate([[0], np.cumsum(cap)[:-1]]) if len(lo) else 0
+    return boxes
 
 
 def top_level_build(boxes):

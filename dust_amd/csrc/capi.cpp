@@ -206,6 +206,8 @@ struct DustHipContext : RefCounted {
   // counters (a launch takes rays from one and zeroes the other for the next: query_parity says which is whose)
   DeviceBuffer query_rays, query_hits, query_counters;
   uint32_t query_parity = 0;
+  // scene box queries (dust_hip_scene_overlap_boxes): the synchronous call's device staging for boxes, counts and records, grown on demand
+  DeviceBuffer overlap_boxes, overlap_counts, overlap_records;
 };
 // wait for everything enqueued on the context's stream (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)
@@ -245,6 +247,7 @@ static void release(DustHipContext* c) {
   if (c->ev_side_done) (void)hipEventDestroy(c->ev_side_done);
   c->srgb_lut.release();
   c->query_rays.release(); c->query_hits.release(); c->query_counters.release();
+  c->overlap_boxes.release(); c->overlap_counts.release(); c->overlap_records.release();
   if (c->started) (void)hipHostFree(const_cast<uint32_t*>(c->started));
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -2407,22 +2410,29 @@ DustStatus dust_hip_render_frames(uint32_t n_frames, DustHipPipeline* const* pip
 
 // Scene ray queries (query.hip). Enqueued on the context's stream as a frame is: the launch reads the scene image's current slot, which
 // touch() marks, so that a commit DustHipScene::kImages commits later does not overwrite it while the query may still read it.
-static DustStatus check_query(const DustHipScene* s, const void* rays, const void* hits, uint32_t flags) {
-  if (!s || !rays || !hits) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+static DustStatus check_query(const DustHipScene* s, const void* in, const void* out, uint32_t flags, const void* out2 = reinterpret_cast<const void*>(1)) {
+  if (!s || !in || !out || !out2) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
   if (flags & ~DUST_HIP_QUERY_ANY_HIT) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown query flags");
   return check_scene_ready(s);
+}
+// what a query launch shares: the pair of device counters (allocated once), the scene half of the descriptor, the scene image slot marked
+static hipError_t query_launch_args(DustHipScene* s, dust::FrameArgs& a) {
+  DustHipContext* ctx = s->ctx;
+  if (!ctx->query_counters.p) {
+    hipError_t e = ctx->query_counters.alloc(2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->query_counters.p, 0, 2 * sizeof(unsigned long long), ctx->stream);
+    if (e != hipSuccess) return e;
+  }
+  s->touch();
+  scene_args(s, a);
+  for (const DustHipModel* m : s->models) a.deep |= m->dev.n_levels == 3 ? 1u : 0u;
+  return hipSuccess;
 }
 static DustStatus trace_rays_impl(DustHipScene* s, const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, uint32_t flags) {
   DustHipContext* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
-  if (!ctx->query_counters.p) {
-    HIP_TRY(ctx->query_counters.alloc(2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(ctx->query_counters.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
-  }
   dust::FrameArgs a{};
-  s->touch();
-  scene_args(s, a);
-  for (const DustHipModel* m : s->models) a.deep |= m->dev.n_levels == 3 ? 1u : 0u;
+  HIP_TRY(query_launch_args(s, a));
   unsigned long long* counters = static_cast<unsigned long long*>(ctx->query_counters.p);
   dust::QueryArgs q;
   q.rays = reinterpret_cast<const float*>(d_rays);
@@ -2469,6 +2479,74 @@ DustStatus dust_hip_scene_trace_rays_async(DustHipScene* s, const DustHipRay* d_
   if ((reinterpret_cast<uintptr_t>(d_rays) | reinterpret_cast<uintptr_t>(d_hits)) & 15u)
     return fail(DUST_ERR_INVALID_ARGUMENT, "the ray and hit arrays must be 16-byte aligned (the kernel moves records as 16-byte vectors)");
   return guarded([&]() -> DustStatus { return trace_rays_impl(s, d_rays, d_hits, n, flags); });
+}
+
+// Scene box queries (overlap.hip): the same launch protocol as the ray queries (their counters, the scene image slot marked)
+static DustStatus overlap_boxes_impl(DustHipScene* s, const DustHipBoxQuery* d_boxes, uint32_t n, uint32_t* d_counts, DustHipVoxelRef* d_records,
+                                     uint32_t n_records, uint32_t flags) {
+  DustHipContext* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  dust::FrameArgs a{};
+  HIP_TRY(query_launch_args(s, a));
+  unsigned long long* counters = static_cast<unsigned long long*>(ctx->query_counters.p);
+  dust::OverlapArgs o{};
+  o.boxes = reinterpret_cast<const float*>(d_boxes);
+  o.counts = d_counts;
+  o.records = reinterpret_cast<uint32_t*>(d_records);
+  o.n = n;
+  o.n_records = n_records;
+  o.any_hit = (flags & DUST_HIP_QUERY_ANY_HIT) ? 1u : 0u;
+  o.counter = counters + ctx->query_parity;
+  o.next_counter = counters + (ctx->query_parity ^ 1u);
+  // a wave per query, kOverlapChunk queries per trip to the counter; persistent workgroups, up to 8 per CU; a single query is one wave
+  const uint32_t waves = (n + dust::kOverlapChunk - 1u) / dust::kOverlapChunk;
+  const uint32_t block = waves >= dust::kOverlapWaves ? dust::kOverlapWaves * 64u : waves * 64u;
+  const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(uint32_t(ctx->num_cus) * 8u, (waves + dust::kOverlapWaves - 1u) / dust::kOverlapWaves));
+  HIP_TRY(dust::launch_overlap_boxes(a, o, grid, block, ctx->stream));
+  ctx->query_parity ^= 1u;
+  return DUST_OK;
+}
+DustStatus dust_hip_scene_overlap_boxes(DustHipScene* s, const DustHipBoxQuery* boxes, uint32_t n, uint32_t* counts, DustHipVoxelRef* records,
+                                        uint32_t n_records, uint32_t flags) {
+  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
+  if (n == 0) return DUST_OK;  // (whatever the arrays)
+  { DustStatus cs = check_query(s, boxes, counts, flags, n_records ? static_cast<const void*>(records) : counts); if (cs != DUST_OK) return cs; }
+  for (uint32_t i = 0; i < n; ++i)  // every slice inside the records, before anything is launched
+    if (boxes[i].capacity && uint64_t(boxes[i].first) + boxes[i].capacity > n_records)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "a box query's slice [first, first + capacity) runs past n_records");
+  return guarded([&]() -> DustStatus {
+    DustHipContext* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t box_bytes = size_t(n) * sizeof(DustHipBoxQuery), count_bytes = size_t(n) * sizeof(uint32_t);
+    const size_t rec_bytes = size_t(std::max<uint32_t>(n_records, 1u)) * sizeof(DustHipVoxelRef);
+    auto grow = [](DeviceBuffer& b, size_t bytes) { return b.p && b.bytes >= bytes ? hipSuccess : b.alloc(bytes); };  // kept until the context goes
+    if (grow(c->overlap_boxes, box_bytes) != hipSuccess || grow(c->overlap_counts, count_bytes) != hipSuccess ||
+        grow(c->overlap_records, rec_bytes) != hipSuccess) {
+      c->overlap_boxes.release(); c->overlap_counts.release(); c->overlap_records.release();
+      (void)hipGetLastError();
+      return fail(DUST_ERR_OUT_OF_MEMORY, "device staging for the box queries, their counts and records");
+    }
+    DustHipVoxelRef* d_rec = static_cast<DustHipVoxelRef*>(c->overlap_records.p);
+    HIP_TRY(hipMemcpyAsync(c->overlap_boxes.p, boxes, box_bytes, hipMemcpyHostToDevice, c->stream));
+    // slots past a query's count are left as the caller has them: the records go up, and come back, whole
+    if (n_records) HIP_TRY(hipMemcpyAsync(d_rec, records, size_t(n_records) * sizeof(DustHipVoxelRef), hipMemcpyHostToDevice, c->stream));
+    const DustStatus st = overlap_boxes_impl(s, static_cast<const DustHipBoxQuery*>(c->overlap_boxes.p), n, static_cast<uint32_t*>(c->overlap_counts.p),
+                                             d_rec, n_records, flags);
+    if (st != DUST_OK) return st;
+    HIP_TRY(hipMemcpyAsync(counts, c->overlap_counts.p, count_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (n_records) HIP_TRY(hipMemcpyAsync(records, d_rec, size_t(n_records) * sizeof(DustHipVoxelRef), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DUST_OK;
+  });
+}
+DustStatus dust_hip_scene_overlap_boxes_async(DustHipScene* s, const DustHipBoxQuery* d_boxes, uint32_t n, uint32_t* d_counts, DustHipVoxelRef* d_records,
+                                              uint32_t n_records, uint32_t flags) {
+  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
+  if (n == 0) return DUST_OK;  // (whatever the arrays)
+  { DustStatus cs = check_query(s, d_boxes, d_counts, flags, n_records ? static_cast<const void*>(d_records) : d_counts); if (cs != DUST_OK) return cs; }
+  if ((reinterpret_cast<uintptr_t>(d_boxes) | reinterpret_cast<uintptr_t>(d_records)) & 15u)
+    return fail(DUST_ERR_INVALID_ARGUMENT, "the box and record arrays must be 16-byte aligned (the kernel moves records as 16-byte vectors)");
+  return guarded([&]() -> DustStatus { return overlap_boxes_impl(s, d_boxes, n, d_counts, d_records, n_records, flags); });
 }
 
 DustStatus dust_hip_pipeline_pass_stats(DustHipPipeline* p, uint32_t pass, DustHipPassStats* out) {

@@ -268,6 +268,47 @@ DustStatus dust_hip_scene_trace_rays(DustHipScene*, const DustHipRay* rays, Dust
  * The hits are valid after dust_hip_sync, or after an event recorded on the caller's stream when the context was given that stream. */
 DustStatus dust_hip_scene_trace_rays_async(DustHipScene*, const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, uint32_t flags);
 
+/* Scene box queries: the region counterpart of the ray queries -- every solid voxel of the committed scene inside a world-space box
+ * (collision, placement, area edits, trigger volumes).
+ *
+ * Voxel (x, y, z) of an instance is the model-space unit cube [x, x+1] x [y, y+1] x [z, z+1], mapped into world space by the instance's
+ * obj_to_world m (3 x 4, row-major).
+ * - Axis-aligned instances (the 3 x 3 part has exactly one nonzero entry per row and per column: 90-degree rotations, mirrors, any
+ *   scale) are EXACT on float32: a world corner coordinate is w_r = ((m[r][0]*px + m[r][1]*py) + m[r][2]*pz) + m[r][3], every operation
+ *   rounded to nearest, no fused multiply-add; the voxel's world box is the per-axis min and max of its corners. Per axis the voxel
+ *   overlaps the query when v_lo < hi && lo < v_hi; on an axis where lo == hi, when v_lo <= lo < v_hi (a point or a flat box names
+ *   exactly one voxel per axis). Touching faces do not count: a box standing on a floor does not report the floor.
+ * - Other instances (arbitrary rotations, shears) within tau = 1e-5 * (1 + M), M the largest magnitude of any coordinate of the box or
+ *   of the voxel's world corners: every voxel whose world cube overlaps the box shrunk by tau on every side is reported, none that does
+ *   not overlap the box grown by tau.
+ * counts[i]: the overlapping voxels over all instances (saturating at UINT32_MAX). Query i writes min(counts[i], capacity) records into
+ * records[first .. first + capacity); slots past counts[i] are left untouched. Nothing is ever written at an index >= n_records, whatever
+ * first and capacity say (the synchronous form refuses a slice that runs past n_records with DUST_ERR_INVALID_ARGUMENT before anything
+ * is launched). Overlapping slices of two queries have unspecified contents.
+ * Order (deterministic): ascending instance, then ascending block, then ascending voxel bit; a truncated query keeps the first capacity
+ * records in that order, and two runs give the same bytes. DUST_HIP_QUERY_ANY_HIT: counts[i] is 0 or 1, and the record (capacity >= 1)
+ * is one overlapping voxel, not necessarily the first in order ("is this space free"). Degenerate boxes -- a non-finite coordinate, or
+ * lo > hi on any axis -- report 0.
+ * As the ray queries: the scene as last committed (DUST_ERR_NOT_READY otherwise); a null scene is refused; n == 0 is a no-op, whatever
+ * the arrays; null arrays with n > 0 are refused; flags other than DUST_HIP_QUERY_ANY_HIT are refused. */
+typedef struct DustHipBoxQuery {   /* 32 bytes */
+  float lo[3]; uint32_t first;     /* world-space box; first: index of this query's first slot in `records` */
+  float hi[3]; uint32_t capacity;  /* slots this query may fill (0 = count only) */
+} DustHipBoxQuery;
+typedef struct DustHipVoxelRef {   /* 16 bytes */
+  uint32_t instance;               /* gl_InstanceID */
+  uint32_t block;                  /* gl_PrimitiveID: index into the model's Block array */
+  uint16_t xyz[3];                 /* the voxel in the model's tree coordinates: what the model's set_voxels / get_voxels take */
+  uint8_t palette;                 /* palette index (the material stream, as in DustHipRayHit) */
+  uint8_t voxel;                   /* voxel in the 4^3 brick, x << 4 | y << 2 | z (as DustHipRayHit.voxel) */
+} DustHipVoxelRef;
+/* Synchronous: host arrays, returns with counts and records written (device staging is the context's, grown on demand). */
+DustStatus dust_hip_scene_overlap_boxes(DustHipScene*, const DustHipBoxQuery* boxes, uint32_t n, uint32_t* counts,
+                                        DustHipVoxelRef* records, uint32_t n_records, uint32_t flags);
+/* The same on device arrays (16-byte aligned), enqueued on the context's stream; valid after dust_hip_sync (as trace_rays_async). */
+DustStatus dust_hip_scene_overlap_boxes_async(DustHipScene*, const DustHipBoxQuery* d_boxes, uint32_t n, uint32_t* d_counts,
+                                              DustHipVoxelRef* d_records, uint32_t n_records, uint32_t flags);
+
 /* the members of CameraSettings the shaders read (standard.rs:277-302,813-827; layout.playout:20-33) */
 typedef struct DustHipCamera {
   float view_col0[3], view_col1[3], view_col2[3]; /* camera_view_col0..2 */

@@ -242,6 +242,23 @@ class Scene {
   void trace_rays_async(const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, bool any_hit = false) {
     check(dust_hip_scene_trace_rays_async(h_, d_rays, d_hits, n, any_hit ? DUST_HIP_QUERY_ANY_HIT : 0u));
   }
+  // the solid voxels inside world-space boxes (collision, placement, area edits): host arrays, returns with counts[i] and query i's first
+  // min(counts[i], capacity) records at records[first ..], ordered by instance, block, voxel bit. any_hit: is the box free (count 0 / 1)
+  void overlap_boxes(const DustHipBoxQuery* boxes, uint32_t n, uint32_t* counts, DustHipVoxelRef* records, uint32_t n_records,
+                     bool any_hit = false) {
+    check(dust_hip_scene_overlap_boxes(h_, boxes, n, counts, records, n_records, any_hit ? DUST_HIP_QUERY_ANY_HIT : 0u));
+  }
+  // the same into `records` as it is sized (every box's slice [first, first + capacity) must lie inside it); returns the counts
+  std::vector<uint32_t> overlap_boxes(const std::vector<DustHipBoxQuery>& boxes, std::vector<DustHipVoxelRef>& records, bool any_hit = false) {
+    std::vector<uint32_t> counts(boxes.size());
+    overlap_boxes(boxes.data(), uint32_t(boxes.size()), counts.data(), records.data(), uint32_t(records.size()), any_hit);
+    return counts;
+  }
+  // device arrays, enqueued on the context's stream: valid after RenderContext::sync (or an event on the caller's stream)
+  void overlap_boxes_async(const DustHipBoxQuery* d_boxes, uint32_t n, uint32_t* d_counts, DustHipVoxelRef* d_records, uint32_t n_records,
+                           bool any_hit = false) {
+    check(dust_hip_scene_overlap_boxes_async(h_, d_boxes, n, d_counts, d_records, n_records, any_hit ? DUST_HIP_QUERY_ANY_HIT : 0u));
+  }
   DustHipScene* raw() const { return h_; }
  private:
   DustHipScene* h_ = nullptr;
