@@ -128,6 +128,19 @@ class VoxelRef(C.Structure):  # DustHipVoxelRef, 16 bytes: one solid voxel insid
     _fields_ = [("instance", C.c_uint32), ("block", C.c_uint32), ("xyz", C.c_uint16 * 3), ("palette", C.c_uint8), ("voxel", C.c_uint8)]
 
 
+class BoxSweep(C.Structure):  # DustHipBoxSweep, 48 bytes: a world-space box at t = 0 and its displacement over t in [0, 1]
+    _fields_ = [("lo", C.c_float * 3), ("reserved0", C.c_uint32), ("hi", C.c_float * 3), ("reserved1", C.c_uint32),
+                ("delta", C.c_float * 3), ("reserved2", C.c_uint32)]
+
+
+class SweepHit(C.Structure):  # DustHipSweepHit, 32 bytes: the first voxel a sweep touches
+    _fields_ = [("t", C.c_float), ("instance", C.c_uint32), ("block", C.c_uint32), ("xyz", C.c_uint16 * 3), ("palette", C.c_uint8),
+                ("voxel", C.c_uint8), ("normal", C.c_float * 3)]
+
+
+SWEEP_IGNORE_START = 2
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("rays", C.c_uint64), ("instances_tested", C.c_uint64),
                 ("upper_descents", C.c_uint64), ("mid_descents", C.c_uint64), ("bricks_tested", C.c_uint64),
@@ -194,6 +207,8 @@ SYMBOLS = {
     "dust_hip_scene_trace_rays_async": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32]),
     "dust_hip_scene_overlap_boxes": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32]),
     "dust_hip_scene_overlap_boxes_async": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32]),
+    "dust_hip_scene_sweep_boxes": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32]),
+    "dust_hip_scene_sweep_boxes_async": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32]),
     "dust_hip_top_level_build": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, _P, _u32p, C.c_size_t, C.POINTER(C.c_uint16), C.c_size_t, _u32p, _u32p]),
     "dust_hip_pipeline_create": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "dust_hip_pipeline_destroy": (None, [_P]),

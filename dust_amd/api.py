@@ -25,6 +25,12 @@ assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
 BOX_QUERY_DTYPE = np.dtype([("lo", "<f4", 3), ("first", "<u4"), ("hi", "<f4", 3), ("capacity", "<u4")])
 VOXEL_REF_DTYPE = np.dtype([("instance", "<u4"), ("block", "<u4"), ("xyz", "<u2", 3), ("palette", "u1"), ("voxel", "u1")])
 assert BOX_QUERY_DTYPE.itemsize == 32 and VOXEL_REF_DTYPE.itemsize == 16
+# scene box sweeps (Scene.sweep_boxes): DustHipBoxSweep / DustHipSweepHit
+BOX_SWEEP_DTYPE = np.dtype([("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3), ("reserved1", "<u4"), ("delta", "<f4", 3),
+                            ("reserved2", "<u4")])
+SWEEP_HIT_DTYPE = np.dtype([("t", "<f4"), ("instance", "<u4"), ("block", "<u4"), ("xyz", "<u2", 3), ("palette", "u1"), ("voxel", "u1"),
+                            ("normal", "<f4", 3)])
+assert BOX_SWEEP_DTYPE.itemsize == 48 and SWEEP_HIT_DTYPE.itemsize == 32
 FLT_MAX = float(np.finfo(np.float32).max)
 
 PLANE_DTYPES = {
@@ -413,6 +419,27 @@ class Scene:
         per = [out[int(f): int(f) + int(min(c, k))] for f, c, k in zip(boxes["first"], out_counts, boxes["capacity"])]
         return out_counts, per
 
+    def sweep_boxes(self, lo, hi=None, delta=None, any_hit=False, ignore_start=False, hits=None):
+        """The first solid voxel each world-space box touches as it moves by delta (dust_hip_scene_sweep_boxes): lo / hi / delta (n, 3).
+        Returns a SWEEP_HIT_DTYPE array: t (first contact in [0, 1); 1 on a miss), instance (NO_HIT on a miss), block, xyz (the voxel
+        in the model's tree coordinates), palette, voxel, normal (from the voxel toward the box; 0 when the box starts inside it).
+        any_hit: some hit voxel, not necessarily the first; ignore_start: voxels the box is inside at t = 0 do not stop it.
+        Device path (dust_hip_scene_sweep_boxes_async): `lo` a contiguous device tensor of DustHipBoxSweep rows ((n, 12) 32-bit words,
+        see box_sweeps) and `hits` one of DustHipSweepHit rows ((n, 8) 32-bit words); enqueued on the context's stream, valid after
+        Context.sync(). Returns `hits`."""
+        flags = (L.QUERY_ANY_HIT if any_hit else 0) | (L.SWEEP_IGNORE_START if ignore_start else 0)
+        if hits is not None:
+            assert hi is None and delta is None and lo.is_contiguous() and hits.is_contiguous()
+            n = lo.numel() * lo.element_size() // BOX_SWEEP_DTYPE.itemsize
+            assert lo.numel() * lo.element_size() == n * BOX_SWEEP_DTYPE.itemsize
+            assert hits.numel() * hits.element_size() >= n * SWEEP_HIT_DTYPE.itemsize
+            L.check(self._lib.dust_hip_scene_sweep_boxes_async(self._h, C.c_void_p(lo.data_ptr()), C.c_void_p(hits.data_ptr()), n, flags))
+            return hits
+        sweeps = box_sweeps(lo, hi, delta)
+        out = np.zeros(len(sweeps), SWEEP_HIT_DTYPE)
+        L.check(self._lib.dust_hip_scene_sweep_boxes(self._h, _ptr(sweeps), _ptr(out), len(sweeps), flags))
+        return out
+
 
 def ray_records(origins, directions, tmin=0.0, tmax=math.inf):
     """DustHipRay records (RAY_DTYPE) for Scene.trace_rays; tmax = +inf becomes FLT_MAX (an unbounded ray)"""
@@ -439,6 +466,17 @@ def box_queries(lo, hi, capacity=64):
     boxes["capacity"] = cap
     boxes["first"] = np.concatenate([[0], np.cumsum(cap)[:-1]]) if len(lo) else 0
     return boxes
+
+
+def box_sweeps(lo, hi, delta):
+    """DustHipBoxSweep records (BOX_SWEEP_DTYPE) for Scene.sweep_boxes: the box [lo, hi] at t = 0, moving by delta over t in [0, 1]"""
+    lo = np.asarray(lo, np.float32).reshape(-1, 3)
+    hi = np.asarray(hi, np.float32).reshape(-1, 3)
+    delta = np.asarray(delta, np.float32).reshape(-1, 3)
+    assert len(lo) == len(hi) == len(delta)
+    sweeps = np.zeros(len(lo), BOX_SWEEP_DTYPE)
+    sweeps["lo"], sweeps["hi"], sweeps["delta"] = lo, hi, delta
+    return sweeps
 
 
 def top_level_build(boxes):

@@ -208,6 +208,8 @@ struct DustHipContext : RefCounted {
   uint32_t query_parity = 0;
   // scene box queries (dust_hip_scene_overlap_boxes): the synchronous call's device staging for boxes, counts and records, grown on demand
   DeviceBuffer overlap_boxes, overlap_counts, overlap_records;
+  // scene box sweeps (dust_hip_scene_sweep_boxes): the synchronous call's device staging for sweeps and hits, grown on demand
+  DeviceBuffer sweep_queries, sweep_hits;
 };
 // wait for everything enqueued on the context's stream (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)
@@ -248,6 +250,7 @@ static void release(DustHipContext* c) {
   c->srgb_lut.release();
   c->query_rays.release(); c->query_hits.release(); c->query_counters.release();
   c->overlap_boxes.release(); c->overlap_counts.release(); c->overlap_records.release();
+  c->sweep_queries.release(); c->sweep_hits.release();
   if (c->started) (void)hipHostFree(const_cast<uint32_t*>(c->started));
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -2547,6 +2550,65 @@ DustStatus dust_hip_scene_overlap_boxes_async(DustHipScene* s, const DustHipBoxQ
   if ((reinterpret_cast<uintptr_t>(d_boxes) | reinterpret_cast<uintptr_t>(d_records)) & 15u)
     return fail(DUST_ERR_INVALID_ARGUMENT, "the box and record arrays must be 16-byte aligned (the kernel moves records as 16-byte vectors)");
   return guarded([&]() -> DustStatus { return overlap_boxes_impl(s, d_boxes, n, d_counts, d_records, n_records, flags); });
+}
+
+// Scene box sweeps (sweep.hip): the box queries' launch protocol and shape
+static DustStatus sweep_boxes_impl(DustHipScene* s, const DustHipBoxSweep* d_sweeps, DustHipSweepHit* d_hits, uint32_t n, uint32_t flags) {
+  DustHipContext* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  dust::FrameArgs a{};
+  HIP_TRY(query_launch_args(s, a));
+  unsigned long long* counters = static_cast<unsigned long long*>(ctx->query_counters.p);
+  dust::SweepArgs o{};
+  o.sweeps = reinterpret_cast<const float*>(d_sweeps);
+  o.hits = reinterpret_cast<uint32_t*>(d_hits);
+  o.n = n;
+  o.any_hit = (flags & DUST_HIP_QUERY_ANY_HIT) ? 1u : 0u;
+  o.ignore_start = (flags & DUST_HIP_SWEEP_IGNORE_START) ? 1u : 0u;
+  o.counter = counters + ctx->query_parity;
+  o.next_counter = counters + (ctx->query_parity ^ 1u);
+  // a wave per query, kSweepChunk queries per trip to the counter; persistent workgroups, up to 8 per CU; a single query is one wave
+  const uint32_t waves = (n + dust::kSweepChunk - 1u) / dust::kSweepChunk;
+  const uint32_t block = waves >= dust::kSweepWaves ? dust::kSweepWaves * 64u : waves * 64u;
+  const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(uint32_t(ctx->num_cus) * 8u, (waves + dust::kSweepWaves - 1u) / dust::kSweepWaves));
+  HIP_TRY(dust::launch_sweep_boxes(a, o, grid, block, ctx->stream));
+  ctx->query_parity ^= 1u;
+  return DUST_OK;
+}
+static DustStatus check_sweep(const DustHipScene* s, const void* sweeps, const void* hits, uint32_t flags) {
+  if (!sweeps || !hits) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (flags & ~(DUST_HIP_QUERY_ANY_HIT | DUST_HIP_SWEEP_IGNORE_START)) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown sweep flags");
+  return check_scene_ready(s);
+}
+DustStatus dust_hip_scene_sweep_boxes(DustHipScene* s, const DustHipBoxSweep* sweeps, DustHipSweepHit* hits, uint32_t n, uint32_t flags) {
+  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
+  if (n == 0) return DUST_OK;  // (whatever the arrays)
+  { DustStatus cs = check_sweep(s, sweeps, hits, flags); if (cs != DUST_OK) return cs; }
+  return guarded([&]() -> DustStatus {
+    DustHipContext* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t sweep_bytes = size_t(n) * sizeof(DustHipBoxSweep), hit_bytes = size_t(n) * sizeof(DustHipSweepHit);
+    auto grow = [](DeviceBuffer& b, size_t bytes) { return b.p && b.bytes >= bytes ? hipSuccess : b.alloc(bytes); };  // kept until the context goes
+    if (grow(c->sweep_queries, sweep_bytes) != hipSuccess || grow(c->sweep_hits, hit_bytes) != hipSuccess) {
+      c->sweep_queries.release(); c->sweep_hits.release();
+      (void)hipGetLastError();
+      return fail(DUST_ERR_OUT_OF_MEMORY, "device staging for the box sweeps and their hits");
+    }
+    HIP_TRY(hipMemcpyAsync(c->sweep_queries.p, sweeps, sweep_bytes, hipMemcpyHostToDevice, c->stream));
+    const DustStatus st = sweep_boxes_impl(s, static_cast<const DustHipBoxSweep*>(c->sweep_queries.p), static_cast<DustHipSweepHit*>(c->sweep_hits.p), n, flags);
+    if (st != DUST_OK) return st;
+    HIP_TRY(hipMemcpyAsync(hits, c->sweep_hits.p, hit_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DUST_OK;
+  });
+}
+DustStatus dust_hip_scene_sweep_boxes_async(DustHipScene* s, const DustHipBoxSweep* d_sweeps, DustHipSweepHit* d_hits, uint32_t n, uint32_t flags) {
+  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
+  if (n == 0) return DUST_OK;  // (whatever the arrays)
+  { DustStatus cs = check_sweep(s, d_sweeps, d_hits, flags); if (cs != DUST_OK) return cs; }
+  if ((reinterpret_cast<uintptr_t>(d_sweeps) | reinterpret_cast<uintptr_t>(d_hits)) & 15u)
+    return fail(DUST_ERR_INVALID_ARGUMENT, "the sweep and hit arrays must be 16-byte aligned (the kernel moves them as 16-byte vectors)");
+  return guarded([&]() -> DustStatus { return sweep_boxes_impl(s, d_sweeps, d_hits, n, flags); });
 }
 
 DustStatus dust_hip_pipeline_pass_stats(DustHipPipeline* p, uint32_t pass, DustHipPassStats* out) {

@@ -30,4 +30,16 @@ constexpr uint32_t kOverlapWaves = 4;   // waves per workgroup of k_overlap_boxe
 constexpr uint32_t kOverlapChunk = 4;   // queries a wave takes from the counter at a time
 hipError_t launch_overlap_boxes(const FrameArgs& a, const OverlapArgs& q, uint32_t grid, uint32_t block, hipStream_t s);
 
+// scene box sweeps (sweep.hip, dust_hip_scene_sweep_boxes / _async)
+struct SweepArgs {
+  const float* sweeps;             // n DustHipBoxSweep records (12 words each; 16-byte aligned)
+  uint32_t* hits;                  // n DustHipSweepHit records (8 words each; 16-byte aligned)
+  uint32_t n, any_hit, ignore_start, pad;
+  unsigned long long* counter;     // queries handed out so far (zero at launch): the ray queries' pair of counters, same protocol
+  unsigned long long* next_counter;
+};
+constexpr uint32_t kSweepWaves = 4;   // waves per workgroup of k_sweep_boxes (one query per wave at a time)
+constexpr uint32_t kSweepChunk = 4;   // queries a wave takes from the counter at a time
+hipError_t launch_sweep_boxes(const FrameArgs& a, const SweepArgs& q, uint32_t grid, uint32_t block, hipStream_t s);
+
 }  // namespace dust

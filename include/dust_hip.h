@@ -309,6 +309,54 @@ DustStatus dust_hip_scene_overlap_boxes(DustHipScene*, const DustHipBoxQuery* bo
 DustStatus dust_hip_scene_overlap_boxes_async(DustHipScene*, const DustHipBoxQuery* d_boxes, uint32_t n, uint32_t* d_counts,
                                               DustHipVoxelRef* d_records, uint32_t n_records, uint32_t flags);
 
+/* Scene box sweeps (shape casts): how far a world-space box can move along a straight path before it touches a solid voxel of the
+ * committed scene, and which face stops it -- a character controller's move-and-slide, a thrown prop, a camera spring arm.
+ *
+ * At t in [0, 1] the box is [lo + t delta, hi + t delta]. The voxels are the box queries' (above): the unit cube of voxel (x, y, z)
+ * through the instance's obj_to_world.
+ * - Axis-aligned instances are EXACT on float32. The voxel's world slab [a_r, b_r] on world axis r is the box queries' corner formula;
+ *   each - and / below is one float32 operation, rounded to nearest (IEEE division, no contraction). Per world axis r, d = delta[r]:
+ *     d > 0:  e_r = (a_r - hi_r) / d,  x_r = (b_r - lo_r) / d;
+ *     d < 0:  e_r = (b_r - lo_r) / d,  x_r = (a_r - hi_r) / d;
+ *     d == +-0 (a resting axis): in contact at every t when the box queries' per-axis rule holds (a < hi && lo < b; on lo == hi:
+ *     a <= lo < b), never otherwise.
+ *   T_in = the max of e_r over the moving axes (-inf if there are none), T_out = the min of x_r (+inf if there are none). The voxel is
+ *   HIT when every resting axis is in contact, T_in < T_out, T_in < 1 and T_out > 0 -- and, with DUST_HIP_SWEEP_IGNORE_START, T_in >= 0
+ *   (-0 passes). Its time is t = T_in if T_in > 0, else +0. Its normal is 0 if T_in < 0 (the box started inside it); otherwise
+ *   -sign(delta[r*]) on axis r*, the lowest moving axis with e_r == T_in (IEEE equality: -0 == +0).
+ *   So: touching faces do not count; a grazing edge (T_in == T_out) is not a hit; touching at t = 1 is not a hit; a box standing on a
+ *   floor slides along it freely, but moving down it reports t = 0 with normal +y. delta = 0 hits exactly when overlap_boxes counts
+ *   at least one voxel inside the box.
+ * - Other instances (rotations, shears) within the box queries' tau = 1e-5 * (1 + M), M the largest magnitude of the box's coordinates
+ *   at t = 0 and t = 1 and of the voxel's world corners. With t_v(s) the exact first contact time of voxel v against the box grown by s
+ *   on every side: a hit on v* at t satisfies t_v*(+tau) <= t <= min over v of t_v(-tau); a miss means that no voxel has contact with
+ *   the shrunk box; the normal is a unit vector with normal . delta <= 0. (There, delta = 0 agrees with overlap_boxes only within tau.)
+ * The answer is the hit voxel that minimises (t, instance, block, voxel bit): deterministic, two runs give the same bytes.
+ * DUST_HIP_QUERY_ANY_HIT: some hit voxel, with its own t and normal. A miss writes t = 1, instance = DUST_HIP_NO_HIT and zeros in every
+ * other field. Degenerate sweeps -- a non-finite coordinate or delta component, or lo > hi on any axis -- report a miss.
+ * As the box queries: the scene as last committed (DUST_ERR_NOT_READY otherwise); a null scene is refused; n == 0 is a no-op, whatever
+ * the arrays; null arrays with n > 0 are refused; flags other than DUST_HIP_QUERY_ANY_HIT | DUST_HIP_SWEEP_IGNORE_START are refused. */
+typedef struct DustHipBoxSweep {   /* 48 bytes */
+  float lo[3];    uint32_t reserved0;  /* world-space box at t = 0 */
+  float hi[3];    uint32_t reserved1;
+  float delta[3]; uint32_t reserved2;  /* displacement: at t in [0, 1] the box is [lo + t delta, hi + t delta]; reserved words ignored */
+} DustHipBoxSweep;
+typedef struct DustHipSweepHit {   /* 32 bytes */
+  float t;                         /* first contact in [0, 1); 1 on a miss */
+  uint32_t instance;               /* gl_InstanceID; DUST_HIP_NO_HIT on a miss */
+  uint32_t block;                  /* index into the model's Block array */
+  uint16_t xyz[3];                 /* the voxel in the model's tree coordinates (what set_voxels / get_voxels take) */
+  uint8_t palette;                 /* palette index */
+  uint8_t voxel;                   /* x << 4 | y << 2 | z in the brick */
+  float normal[3];                 /* world-space unit contact normal, pointing from the voxel toward the box (normal . delta < 0);
+                                      0 when the box starts inside the voxel, and on a miss */
+} DustHipSweepHit;                 /* bytes 4..19 have the layout of a DustHipVoxelRef */
+#define DUST_HIP_SWEEP_IGNORE_START 2u /* voxels the box is already inside at t = 0 do not stop it (a controller unsticking itself) */
+/* Synchronous: host arrays, returns with the hits written (device staging is the context's, grown on demand). */
+DustStatus dust_hip_scene_sweep_boxes(DustHipScene*, const DustHipBoxSweep* sweeps, DustHipSweepHit* hits, uint32_t n, uint32_t flags);
+/* The same on device arrays (16-byte aligned), enqueued on the context's stream; valid after dust_hip_sync (as trace_rays_async). */
+DustStatus dust_hip_scene_sweep_boxes_async(DustHipScene*, const DustHipBoxSweep* d_sweeps, DustHipSweepHit* d_hits, uint32_t n, uint32_t flags);
+
 /* the members of CameraSettings the shaders read (standard.rs:277-302,813-827; layout.playout:20-33) */
 typedef struct DustHipCamera {
   float view_col0[3], view_col1[3], view_col2[3]; /* camera_view_col0..2 */

@@ -259,8 +259,26 @@ class Scene {
                            bool any_hit = false) {
     check(dust_hip_scene_overlap_boxes_async(h_, d_boxes, n, d_counts, d_records, n_records, any_hit ? DUST_HIP_QUERY_ANY_HIT : 0u));
   }
+  // the first solid voxel each box touches as it moves by delta (a character controller's move, a thrown prop): host arrays, returns
+  // with hits[i] written (t = 1 and instance DUST_HIP_NO_HIT on a miss). any_hit: some hit, not necessarily the first; ignore_start:
+  // voxels a box is already inside at t = 0 do not stop it
+  void sweep_boxes(const DustHipBoxSweep* sweeps, DustHipSweepHit* hits, uint32_t n, bool any_hit = false, bool ignore_start = false) {
+    check(dust_hip_scene_sweep_boxes(h_, sweeps, hits, n, sweep_flags(any_hit, ignore_start)));
+  }
+  std::vector<DustHipSweepHit> sweep_boxes(const std::vector<DustHipBoxSweep>& sweeps, bool any_hit = false, bool ignore_start = false) {
+    std::vector<DustHipSweepHit> hits(sweeps.size());
+    sweep_boxes(sweeps.data(), hits.data(), uint32_t(sweeps.size()), any_hit, ignore_start);
+    return hits;
+  }
+  // device arrays (16-byte aligned), enqueued on the context's stream: valid after RenderContext::sync (or an event on the caller's stream)
+  void sweep_boxes_async(const DustHipBoxSweep* d_sweeps, DustHipSweepHit* d_hits, uint32_t n, bool any_hit = false, bool ignore_start = false) {
+    check(dust_hip_scene_sweep_boxes_async(h_, d_sweeps, d_hits, n, sweep_flags(any_hit, ignore_start)));
+  }
   DustHipScene* raw() const { return h_; }
  private:
+  static uint32_t sweep_flags(bool any_hit, bool ignore_start) {
+    return (any_hit ? DUST_HIP_QUERY_ANY_HIT : 0u) | (ignore_start ? DUST_HIP_SWEEP_IGNORE_START : 0u);
+  }
   DustHipScene* h_ = nullptr;
 };
 
