@@ -141,6 +141,16 @@ class SweepHit(C.Structure):  # DustHipSweepHit, 32 bytes: the first voxel a swe
 SWEEP_IGNORE_START = 2
 
 
+class EditShape(C.Structure):  # DustHipEditShape, 48 bytes: a box, sphere or capsule in a model's tree coordinates and what it does to the voxels it covers
+    _fields_ = [("a", C.c_float * 3), ("kind", C.c_uint32), ("b", C.c_float * 3), ("radius", C.c_float),
+                ("op", C.c_uint32), ("palette", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+SHAPE_BOX, SHAPE_SPHERE, SHAPE_CAPSULE = 0, 1, 2
+EDIT_CARVE, EDIT_FILL, EDIT_PAINT, EDIT_PLACE = 0, 1, 2, 3
+MAX_EDIT_SHAPES = 65536
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("rays", C.c_uint64), ("instances_tested", C.c_uint64),
                 ("upper_descents", C.c_uint64), ("mid_descents", C.c_uint64), ("bricks_tested", C.c_uint64),
@@ -196,6 +206,7 @@ SYMBOLS = {
     "dust_hip_model_destroy": (None, [_P]),
     "dust_hip_model_set_voxels": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_get_voxels": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "dust_hip_model_edit_shapes": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_scene_create": (C.c_int, [_P, C.POINTER(_P)]),

@@ -31,6 +31,9 @@ BOX_SWEEP_DTYPE = np.dtype([("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4"
 SWEEP_HIT_DTYPE = np.dtype([("t", "<f4"), ("instance", "<u4"), ("block", "<u4"), ("xyz", "<u2", 3), ("palette", "u1"), ("voxel", "u1"),
                             ("normal", "<f4", 3)])
 assert BOX_SWEEP_DTYPE.itemsize == 48 and SWEEP_HIT_DTYPE.itemsize == 32
+# dust_hip_model_edit_shapes: a shape in a model's tree coordinates and its operation
+EDIT_SHAPE_DTYPE = np.dtype([("a", "<f4", 3), ("kind", "<u4"), ("b", "<f4", 3), ("radius", "<f4"), ("op", "<u4"), ("palette", "<i4"),
+                             ("reserved", "<u4", 2)])
 FLT_MAX = float(np.finfo(np.float32).max)
 
 PLANE_DTYPES = {
@@ -328,6 +331,16 @@ class Model:
         L.check(self._lib.dust_hip_model_get_voxels(self._h, _ptr(xyz), _ptr(out), len(out)))
         return out
 
+    def edit_shapes(self, shapes):
+        """Carve / fill / paint / place boxes, spheres and capsules (dust_hip_model_edit_shapes): `shapes` an EDIT_SHAPE_DTYPE array
+        (see edit_shapes()), in the model's tree coordinates; a shape covers the voxels whose centre (x + 0.5, y + 0.5, z + 0.5) it
+        contains, and the shapes apply in order. Returns `changed`: per shape, the voxels whose value it changed. Scenes instancing
+        the model must be committed again afterwards."""
+        shapes = np.ascontiguousarray(shapes, EDIT_SHAPE_DTYPE).reshape(-1)
+        changed = np.zeros(len(shapes), np.uint32)
+        L.check(self._lib.dust_hip_model_edit_shapes(self._h, _ptr(shapes), len(shapes), _ptr(changed)))
+        return changed
+
     def read(self):
         """(blocks, materials) as they stand on the device"""
         nb, nm = C.c_uint32(), C.c_uint64()
@@ -477,6 +490,22 @@ def box_sweeps(lo, hi, delta):
     sweeps = np.zeros(len(lo), BOX_SWEEP_DTYPE)
     sweeps["lo"], sweeps["hi"], sweeps["delta"] = lo, hi, delta
     return sweeps
+
+
+def edit_shapes(kind, a, b=None, radius=0.0, op=L.EDIT_CARVE, palette=0):
+    """DustHipEditShape records (EDIT_SHAPE_DTYPE) for Model.edit_shapes: a (n, 3) is a box's lo, a sphere's centre or a capsule's
+    segment start; b (n, 3) a box's hi or a capsule's segment end (spheres: omitted); kind, radius, op and palette scalars or (n,).
+    Tree coordinates: a crater at a picked voxel is a = hit["xyz"] + 0.5."""
+    a = np.asarray(a, np.float32).reshape(-1, 3)
+    b = a if b is None else np.asarray(b, np.float32).reshape(-1, 3)
+    assert len(a) == len(b)
+    shapes = np.zeros(len(a), EDIT_SHAPE_DTYPE)
+    shapes["a"], shapes["b"] = a, b
+    shapes["kind"] = np.broadcast_to(np.asarray(kind, np.uint32), (len(a),))
+    shapes["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (len(a),))
+    shapes["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(a),))
+    shapes["palette"] = np.broadcast_to(np.asarray(palette, np.int32), (len(a),))
+    return shapes
 
 
 def top_level_build(boxes):

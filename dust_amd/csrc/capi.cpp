@@ -260,6 +260,8 @@ static void release(DustHipContext* c) {
 struct EditState {
   DeviceBuffer grid, brick_mask, flag_leaf, count_major, scan_tmp, header, xyz, values;
   uint32_t batch_capacity = 0;
+  // shape edits (dust_hip_model_edit_shapes): the call's shape records and counters, and one chunk's cell lists, grown on demand
+  DeviceBuffer shapes, changed, shape_cells, shape_starts, shape_ids;
 };
 
 struct DustHipModel : RefCounted {
@@ -1141,6 +1143,150 @@ DustStatus dust_hip_model_set_voxels(DustHipModel* m, const uint32_t* xyz, const
     a.n_edits = un;
     HIP_TRY(dust::launch_edit_apply(a, false, m->ctx->stream));
     return rebuild_and_refresh(m, *m->edit);  // synchronises: the host vectors above stay alive until the copies are done
+  });
+}
+
+// ---- shape edits (edit.hip k_edit_shapes)
+namespace {
+constexpr size_t kShapeChunkIds = size_t(1) << 21;  // cell-list entries (u16) one launch carries: 4 MiB, 512 whole-tree shapes
+
+// a buffer that only grows (the stream is drained before the old allocation goes)
+DustStatus grow(DustHipContext* ctx, DeviceBuffer& b, size_t bytes) {
+  if (b.p && b.bytes >= bytes) return DUST_OK;
+  HIP_TRY(sync_stream(ctx));
+  HIP_TRY(b.alloc(std::max(bytes + bytes / 2, size_t(4096))));
+  return DUST_OK;
+}
+
+// The caller's record -> the device's: the two grid bytes of the operation and conservative voxel bounds -- the shape's extent
+// padded by more than a voxel (the float32 formulas stay within a small fraction of a voxel of the real distance for
+// coordinates up to 65 536), clipped to the tree. false: the shape covers nothing.
+bool device_shape(const DustHipEditShape& s, dust::DevEditShape& d) {
+  const bool box = s.kind == DUST_HIP_SHAPE_BOX, sphere = s.kind == DUST_HIP_SHAPE_SPHERE;
+  double lo[3], hi[3];
+  for (int r = 0; r < 3; ++r) {
+    if (!std::isfinite(s.a[r]) || (!sphere && !std::isfinite(s.b[r]))) return false;
+    if (box) {
+      if (s.a[r] > s.b[r]) return false;
+      lo[r] = s.a[r]; hi[r] = s.b[r];
+    } else {
+      if (!std::isfinite(s.radius) || s.radius < 0.0f || s.radius > 65536.0f) return false;
+      if (std::fabs(s.a[r]) > 65536.0f || (!sphere && std::fabs(s.b[r]) > 65536.0f)) return false;
+      const double p = s.a[r], q = sphere ? p : double(s.b[r]);
+      lo[r] = std::min(p, q) - double(s.radius); hi[r] = std::max(p, q) + double(s.radius);
+    }
+  }
+  uint32_t vlo[3], vhi[3];
+  for (int r = 0; r < 3; ++r) {  // voxel x is covered when lo <= x + 0.5 <= hi
+    const double l = std::floor(lo[r] - 0.5) - 1.0, h = std::ceil(hi[r] - 0.5) + 1.0;
+    if (l > 255.0 || h < 0.0) return false;
+    vlo[r] = l < 0.0 ? 0u : uint32_t(l);
+    vhi[r] = h > 255.0 ? 255u : uint32_t(h);
+  }
+  std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.b, s.b, sizeof(d.b));
+  d.kind = s.kind;
+  d.radius = box ? 0.0f : s.radius;
+  if (sphere) std::memcpy(d.b, s.a, sizeof(d.b));
+  const uint32_t byte = uint32_t(s.palette) + 1u;
+  switch (s.op) {
+    case DUST_HIP_EDIT_CARVE: d.solid_to = 0; d.empty_to = 0; break;
+    case DUST_HIP_EDIT_FILL: d.solid_to = byte; d.empty_to = byte; break;
+    case DUST_HIP_EDIT_PAINT: d.solid_to = byte; d.empty_to = 0; break;
+    default: d.solid_to = dust::kEditKeep; d.empty_to = byte; break;  // PLACE
+  }
+  d.lo = vlo[0] | (vlo[1] << 8) | (vlo[2] << 16);
+  d.hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
+  return true;
+}
+inline size_t shape_cells(const dust::DevEditShape& d) {  // root cells (16^3 voxels) the bounds reach
+  size_t n = 1;
+  for (int r = 0; r < 3; ++r) n *= size_t((((d.hi >> (8 * r)) & 255u) >> 4) - (((d.lo >> (8 * r)) & 255u) >> 4) + 1u);
+  return n;
+}
+}  // namespace
+
+DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* shapes, uint32_t n, uint32_t* changed) {
+  if (!m || (n && !shapes)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (n > DUST_HIP_MAX_EDIT_SHAPES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_EDIT_SHAPES shapes in one call");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (shapes[i].kind > DUST_HIP_SHAPE_CAPSULE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown shape kind");
+    if (shapes[i].op > DUST_HIP_EDIT_PLACE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown edit op");
+    if (shapes[i].op != DUST_HIP_EDIT_CARVE && (shapes[i].palette < 0 || shapes[i].palette > 254))
+      return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254");
+  }
+  return guarded([&]() -> DustStatus {
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    HIP_TRY(join_side(m->ctx));
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK || n == 0) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = m->ctx->stream;
+    // the shapes that cover something, in call order: `index` maps them back to the caller's
+    std::vector<dust::DevEditShape> dev;
+    std::vector<uint32_t> index;
+    dev.reserve(n); index.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      dust::DevEditShape d{};
+      if (device_shape(shapes[i], d)) { dev.push_back(d); index.push_back(i); }
+    }
+    const size_t live = dev.size();
+    std::vector<uint32_t> counts(live, 0u);
+    if (live) {
+      if ((s = grow(m->ctx, es.shapes, live * sizeof(dust::DevEditShape))) != DUST_OK) return s;
+      if ((s = grow(m->ctx, es.changed, live * 4)) != DUST_OK) return s;
+      HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), live * sizeof(dust::DevEditShape), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
+    }
+    // Order-preserving chunks, each one launch: its shapes binned into the 4096 root cells, an ascending list of u16 shape
+    // ids per cell in CSR form, one workgroup per non-empty cell. A chunk ends where its lists would pass kShapeChunkIds.
+    std::vector<uint32_t> cells, starts, fill(4096);
+    std::vector<uint16_t> ids;
+    for (size_t c0 = 0; c0 < live;) {
+      size_t c1 = c0, total = 0;
+      while (c1 < live && c1 - c0 < 65536 && (c1 == c0 || total + shape_cells(dev[c1]) <= kShapeChunkIds)) total += shape_cells(dev[c1++]);
+      std::fill(fill.begin(), fill.end(), 0u);
+      auto each_cell = [&](const dust::DevEditShape& d, auto&& f) {
+        for (uint32_t x = (d.lo & 255u) >> 4; x <= (d.hi & 255u) >> 4; ++x)
+          for (uint32_t y = ((d.lo >> 8) & 255u) >> 4; y <= ((d.hi >> 8) & 255u) >> 4; ++y)
+            for (uint32_t z = (d.lo >> 16) >> 4; z <= (d.hi >> 16) >> 4; ++z) f((x << 8) | (y << 4) | z);
+      };
+      for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ++fill[cell]; });
+      if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
+      cells.clear(); starts.clear();
+      uint32_t run = 0;
+      for (uint32_t cell = 0; cell < 4096; ++cell) {
+        const uint32_t k = fill[cell];
+        fill[cell] = run;  // where the cell's next id goes
+        if (k) { cells.push_back(cell); starts.push_back(run); run += k; }
+      }
+      starts.push_back(run);
+      ids.resize(run);
+      for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
+      if ((s = grow(m->ctx, es.shape_cells, cells.size() * 4)) != DUST_OK) return s;
+      if ((s = grow(m->ctx, es.shape_starts, starts.size() * 4)) != DUST_OK) return s;
+      if ((s = grow(m->ctx, es.shape_ids, ids.size() * 2)) != DUST_OK) return s;
+      HIP_TRY(hipMemcpyAsync(es.shape_cells.p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(es.shape_starts.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(es.shape_ids.p, ids.data(), ids.size() * 2, hipMemcpyHostToDevice, st));
+      dust::EditShapeArgs a{};
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.shapes = static_cast<const dust::DevEditShape*>(es.shapes.p) + c0;
+      a.cells = static_cast<const uint32_t*>(es.shape_cells.p);
+      a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
+      a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
+      a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
+      a.n_cells = uint32_t(cells.size());
+      HIP_TRY(dust::launch_edit_shapes(a, st));
+      c0 = c1;
+    }
+    if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
+    s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
+    if (s != DUST_OK) return s;
+    if (changed) {
+      std::fill(changed, changed + n, 0u);
+      for (size_t k = 0; k < live; ++k) changed[index[k]] = counts[k];
+    }
+    return DUST_OK;
   });
 }
 

@@ -6,6 +6,7 @@
 // brick-major in Tree::iter_leaf order: 16 MiB for a 256^3 model, created from the model's own blocks the first time it is
 // edited); an edit batch is a scatter of bytes into that grid followed by a full rebuild of every array the traversal and
 // shading kernels read, with data-parallel scans instead of per-voxel inserts:
+//   k_edit_shapes        (dust_hip_model_edit_shapes) boxes, spheres and capsules written into the grid, a wavefront per brick
 //   k_edit_brick_masks   one thread per 4^3 brick of the lattice: occupancy mask + voxel count, in both orders that matter
 //                        (iter_leaf order for block indices, the collector's block-major order for material_ptr)
 //   scan                 exclusive prefix sums of the two 262 144-entry tables
@@ -69,6 +70,76 @@ __global__ void k_edit_read(EditArgs e) {
   if (i >= e.n_edits) return;
   const uint32_t x = e.xyz[i * 3], y = e.xyz[i * 3 + 1], z = e.xyz[i * 3 + 2];
   e.values_out[i] = (int32_t)e.grid[(size_t)leaf_code(x >> 2, y >> 2, z >> 2) * 64 + (((x & 3u) << 4) | ((y & 3u) << 2) | (z & 3u))] - 1;
+}
+
+// dust_hip_model_edit_shapes: carve / fill / paint / place boxes, spheres and capsules straight into the grid. One workgroup per
+// root cell (16^3 voxels) that some shape's bounds reach, four waves of 16 bricks each: wave w owns the cell's child bits
+// 16 w .. 16 w + 15 (one x slice of bricks), lane = voxel bit x<<4 | y<<2 | z, so a brick's 64 grid bytes are one coalesced
+// load. A lane keeps its 16 voxels in registers and walks the cell's shape list ONCE, in call order; every shape record is
+// wave-uniform (loaded by a uniform index), rejected by its integer brick bounds before any per-voxel arithmetic, and
+// counted per wave: one ordinary vector atomic add of the ballots' popcounts (integer adds: the counts do not depend on
+// the order the waves arrive in). Bricks are written back once, and only those in which some lane changed.
+// Membership is the header's float32 contract, operation for operation (-ffp-contract=off; `/` is the IEEE division).
+namespace {
+__device__ __forceinline__ float dot3(float u0, float u1, float u2, float v0, float v1, float v2) { return (u0 * v0 + u1 * v1) + u2 * v2; }
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_edit_shapes(EditShapeArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t cell = a.cells[blockIdx.x];
+  const uint32_t first = a.cell_start[blockIdx.x], last = a.cell_start[blockIdx.x + 1];
+  const uint32_t bx = ((cell >> 8) << 2) | wave, by0 = ((cell >> 4) & 15u) << 2, bz0 = (cell & 15u) << 2;  // brick coordinates
+  uint8_t* mine = a.grid + ((size_t)cell * 64u + wave * 16u) * 64u + lane;
+  // voxel centres: small integers + 0.5, exact in float32
+  const float cx = (float)(bx * 4u + (lane >> 4)) + 0.5f;
+  const float cy0 = (float)(by0 * 4u + ((lane >> 2) & 3u)) + 0.5f, cz0 = (float)(bz0 * 4u + (lane & 3u)) + 0.5f;
+  uint32_t v[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) v[k] = mine[k * 64];
+  uint32_t dirty = 0;
+  for (uint32_t j = first; j < last; ++j) {
+    const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.ids[j]);
+    const DevEditShape s = a.shapes[id];
+    const uint32_t lo_x = (s.lo & 255u) >> 2, lo_y = ((s.lo >> 8) & 255u) >> 2, lo_z = (s.lo >> 16) >> 2;
+    const uint32_t hi_x = (s.hi & 255u) >> 2, hi_y = ((s.hi >> 8) & 255u) >> 2, hi_z = (s.hi >> 16) >> 2;
+    if (bx < lo_x || bx > hi_x) continue;
+    const float rr = s.radius * s.radius;
+    const float ab0 = s.b[0] - s.a[0], ab1 = s.b[1] - s.a[1], ab2 = s.b[2] - s.a[2];
+    const float l = dot3(ab0, ab1, ab2, ab0, ab1, ab2);
+    const float d0 = cx - s.a[0];
+    uint32_t n = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const uint32_t by = by0 + (uint32_t)(k >> 2), bz = bz0 + (uint32_t)(k & 3);
+      if (by < lo_y || by > hi_y || bz < lo_z || bz > hi_z) continue;
+      const float cy = cy0 + (float)((k >> 2) * 4), cz = cz0 + (float)((k & 3) * 4);  // exact
+      bool in;
+      if (s.kind == 0u) {
+        in = s.a[0] <= cx && cx <= s.b[0] && s.a[1] <= cy && cy <= s.b[1] && s.a[2] <= cz && cz <= s.b[2];
+      } else {
+        const float d1 = cy - s.a[1], d2 = cz - s.a[2];
+        if (s.kind == 1u) {
+          in = dot3(d0, d1, d2, d0, d1, d2) <= rr;
+        } else {
+          const float h = l == 0.0f ? 0.0f : fminf(fmaxf(dot3(d0, d1, d2, ab0, ab1, ab2) / l, 0.0f), 1.0f);
+          const float q0 = d0 - ab0 * h, q1 = d1 - ab1 * h, q2 = d2 - ab2 * h;
+          in = dot3(q0, q1, q2, q0, q1, q2) <= rr;
+        }
+      }
+      const uint32_t g = v[k];
+      const uint32_t to = g ? (s.solid_to == kEditKeep ? g : s.solid_to) : s.empty_to;
+      const bool differs = in && to != g;
+      const uint64_t m = __ballot(differs);
+      if (differs) v[k] = to;
+      n += (uint32_t)__popcll(m);
+      dirty |= (m != 0ull ? 1u : 0u) << k;
+    }
+    if (n && lane == 0) atomicAdd(&a.changed[id], n);
+  }
+#pragma unroll
+  for (int k = 0; k < 16; ++k)
+    if ((dirty >> k) & 1u) mine[k * 64] = (uint8_t)v[k];
 }
 
 __global__ void __launch_bounds__(256) k_edit_brick_masks(EditArgs e) {
@@ -230,6 +301,10 @@ hipError_t launch_edit_apply(const EditArgs& e, bool read, hipStream_t s) {
   if (e.n_edits == 0) return hipSuccess;
   if (read) hipLaunchKernelGGL(k_edit_read, dim3((e.n_edits + 255u) / 256u), dim3(256), 0, s, e);
   else hipLaunchKernelGGL(k_edit_apply, dim3((e.n_edits + 255u) / 256u), dim3(256), 0, s, e);
+  return hipGetLastError();
+}
+hipError_t launch_edit_shapes(const EditShapeArgs& a, hipStream_t s) {
+  if (a.n_cells) hipLaunchKernelGGL(k_edit_shapes, dim3(a.n_cells), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_edit_rebuild(const EditArgs& e, hipStream_t s) {

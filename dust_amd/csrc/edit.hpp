@@ -39,8 +39,28 @@ struct EditArgs {
   uint32_t n_edits;
 };
 
+// One shape of dust_hip_model_edit_shapes as the device reads it: the caller's 48-byte record with the operation resolved into the
+// two grid bytes it writes and the shape's conservative voxel bounds. Shapes that cover nothing are never listed in a cell.
+constexpr uint32_t kEditKeep = 256;  // solid_to: a solid voxel keeps its byte (PLACE)
+struct DevEditShape {  // 48 bytes
+  float a[3]; uint32_t kind;
+  float b[3]; float radius;
+  uint32_t solid_to, empty_to;  // the grid byte (palette index + 1, 0 = None) a covered solid / empty voxel takes
+  uint32_t lo, hi;              // inclusive voxel bounds, x | y << 8 | z << 16, clipped to the tree: they cull, the float32 formulas decide
+};
+struct EditShapeArgs {
+  uint8_t* grid;                // EditArgs::grid
+  const DevEditShape* shapes;   // the chunk's shapes, in call order
+  const uint32_t* cells;        // n_cells root cells (16^3 voxels, (x>>4)<<8 | (y>>4)<<4 | (z>>4)) some shape's bounds reach
+  const uint32_t* cell_start;   // n_cells + 1: each cell's slice of `ids`
+  const uint16_t* ids;          // ascending indices into `shapes`
+  uint32_t* changed;            // per shape of the chunk, zeroed by the caller
+  uint32_t n_cells;
+};
+
 hipError_t launch_edit_expand(const EditArgs& e, const DustHipBlock* blocks, const uint8_t* materials, uint32_t n_blocks, hipStream_t s);
 hipError_t launch_edit_apply(const EditArgs& e, bool read, hipStream_t s);
 hipError_t launch_edit_rebuild(const EditArgs& e, hipStream_t s);
+hipError_t launch_edit_shapes(const EditShapeArgs& a, hipStream_t s);
 
 }  // namespace dust

@@ -204,6 +204,51 @@ void dust_hip_model_destroy(DustHipModel*);
  * DUST_ERR_UNSUPPORTED for 4096^3 models. */
 DustStatus dust_hip_model_set_voxels(DustHipModel*, const uint32_t* xyz, const int32_t* values, uint32_t n);
 DustStatus dust_hip_model_get_voxels(DustHipModel*, const uint32_t* xyz, int32_t* values /* palette index, or -1 = None */, uint32_t n);
+/* Shape edits: the edit the scene queries lead up to -- dig a crater where a picking ray hit, place a block, paint a region -- from a
+ * description of the shape (48 bytes) instead of one set_voxels entry per voxel; the device decides which voxels the shape covers and
+ * reports how many it changed (debris, resources, damage).
+ *
+ * Coordinates: the model's tree coordinates -- what set_voxels takes and DustHipRayHit.xyz / DustHipVoxelRef.xyz report. Voxel (x, y, z)
+ * is the cube [x, x+1]^3; a shape covers a voxel when it contains the voxel's centre c = (x + 0.5, y + 0.5, z + 0.5) (exact in float32),
+ * so a crater at a picked voxel has a = hit.xyz + 0.5. Shapes are clipped to the tree.
+ * Membership is EXACT on float32: every -, *, +, / below is one float32 operation rounded to nearest (IEEE division, no contraction),
+ * and dot(u, v) = ((u0*v0 + u1*v1) + u2*v2).
+ *   BOX:      a[r] <= c[r] && c[r] <= b[r] on every axis (comparisons only; radius is ignored).
+ *   SPHERE:   d = c - a; covered when dot(d, d) <= radius*radius (b is ignored).
+ *   CAPSULE:  ab = b - a, ap = c - a, l = dot(ab, ab); h = (l == 0) ? 0 : min(max(dot(ap, ab) / l, 0), 1); q = ap - ab*h, per component
+ *             one multiply and one subtract; covered when dot(q, q) <= radius*radius.
+ * Shapes that cover nothing (changed[i] = 0, not an error, as the queries' degenerate inputs): a non-finite value in a field the kind
+ * reads; a[r] > b[r] on a box; radius < 0 on a sphere or capsule; and, for spheres and capsules, any |coordinate| or radius above
+ * 65 536 (every intermediate of the formulas stays finite, so they need no NaN rule). Boxes have no such limit: [-1e30, 1e30]^3 is
+ * the whole model.
+ * Operations on a covered voxel (values are a palette index or None): CARVE solid -> None; FILL every voxel -> palette; PAINT solid ->
+ * palette, empty stays empty; PLACE empty -> palette, solid keeps its material.
+ * Order: the shapes of a call apply in array order, as n successive calls would. changed[i] is the number of voxels whose value after
+ * shape i differs from their value before it (a FILL that repaints a voxel in its own colour does not count; neither does a PLACE over
+ * solid or a CARVE of nothing). Deterministic: two runs give the same bytes and the same counts. `changed` may be NULL.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything changes: a null model; null shapes with n > 0; n > DUST_HIP_MAX_EDIT_SHAPES; an
+ * unknown kind or op; a palette outside 0..254 on an op that uses it. n == 0 is a no-op, whatever the arrays (as with set_voxels, it
+ * may move the model into its editable form). DUST_ERR_UNSUPPORTED exactly where set_voxels returns it: 4096^3 trees, and models that
+ * hold material byte 255.
+ * Synchronous, like set_voxels: the call returns with the model rebuilt -- the device arrays byte for byte what dust_hip_model_create
+ * builds from the same voxels -- and changed written. Scenes that instance the model must be committed again; until then frames and
+ * queries answer DUST_ERR_NOT_READY, exactly as after set_voxels. A model is shared by its instances: an edit shows in all of them. */
+#define DUST_HIP_SHAPE_BOX     0u
+#define DUST_HIP_SHAPE_SPHERE  1u
+#define DUST_HIP_SHAPE_CAPSULE 2u
+#define DUST_HIP_EDIT_CARVE 0u   /* solid -> None                      (palette ignored) */
+#define DUST_HIP_EDIT_FILL  1u   /* every voxel -> palette                               */
+#define DUST_HIP_EDIT_PAINT 2u   /* solid -> palette, empty stays empty                  */
+#define DUST_HIP_EDIT_PLACE 3u   /* empty -> palette, solid keeps its material           */
+#define DUST_HIP_MAX_EDIT_SHAPES 65536u
+typedef struct DustHipEditShape {   /* 48 bytes */
+  float a[3]; uint32_t kind;        /* BOX: lo;  SPHERE: centre;  CAPSULE: segment start */
+  float b[3]; float radius;         /* BOX: hi (radius ignored);  SPHERE: b ignored;  CAPSULE: segment end */
+  uint32_t op; int32_t palette;     /* palette 0..254 for FILL / PAINT / PLACE */
+  uint32_t reserved[2];             /* ignored */
+} DustHipEditShape;
+DustStatus dust_hip_model_edit_shapes(DustHipModel*, const DustHipEditShape* shapes, uint32_t n,
+                                      uint32_t* changed /* n entries, may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

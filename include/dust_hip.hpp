@@ -140,6 +140,15 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
   }
   void set(UVec3 c, std::optional<uint8_t> palette_index) { set(std::vector<UVec3>{c}, {palette_index}); }
+  // Shape edits (dust_hip_model_edit_shapes): boxes, spheres and capsules in tree coordinates, carved, filled, painted or placed in
+  // array order; returns, per shape, the voxels whose value it changed. Scenes that instance the geometry must commit() again.
+  std::vector<uint32_t> edit_shapes(const std::vector<DustHipEditShape>& shapes) {
+    std::vector<uint32_t> changed(shapes.size());
+    check(dust_hip_model_edit_shapes(h_, shapes.data(), uint32_t(shapes.size()), changed.data()));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
   std::optional<uint8_t> get(UVec3 c) {
     int32_t v = -1;
     check(dust_hip_model_get_voxels(h_, c.data(), &v, 1));
