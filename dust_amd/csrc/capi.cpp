@@ -426,6 +426,7 @@ struct Tuning {
   uint32_t in_flight_oversub = 0;  // IN_FLIGHT_OVERSUB (percent)
   bool wide_share = false;         // WIDE_SHARE: two frames in flight on half of the slots each as 1024-thread workgroups, one per CU (experiment)
   bool no_stream_lds = false;   // NO_STREAM_LDS: the ray streams read grid, boxes and enter records from memory
+  bool no_shared_view = false;  // NO_SHARED_VIEW: same-view frames of a launch each trace their own camera and sun rays (k_primary_ao_batch, never k_primary_ao_runs)
   bool packet_gi() const { return gi_path != DUST_GI_PATH_STREAMS; }    // the GI passes a packet of 64 rays at a time (k_final_gather, k_surfel_trace)
   bool packet_only() const { return gi_path == DUST_GI_PATH_PACKETS; }  // ... even where the streams are the default
   static uint32_t num(const char* name, uint32_t dflt) {
@@ -457,6 +458,7 @@ struct Tuning {
     t.force_moving = flag("FORCE_MOVING");
     t.in_flight_oversub = std::min(100u, num("IN_FLIGHT_OVERSUB", 0));
     t.wide_share = flag("WIDE_SHARE");
+    t.no_shared_view = flag("NO_SHARED_VIEW");
     return t;
   }
 };
@@ -2019,6 +2021,14 @@ static DustStatus run_surfel_pass(DustHipPipeline* p, const dust::FrameArgs& a, 
 struct BatchJoin {
   dust::FrameArgs frames[dust::kMaxBatch];
   uint32_t image_of[dust::kMaxBatch] = {};   // which of the scene's ring of device images each frame reads (the scene may be committed between two frames of a launch)
+  // View runs (dust_dev.h, FrameArgs::view_run): frame i CONTINUES frame i - 1's run when camera and sky are byte-identical and both read the same scene
+  // image. Decided while frame i is prepared -- a follower of a run takes no tile order and measures nothing: the launch reads its leader's --, turned
+  // into run lengths by the Lead.
+  const DustHipCamera* cams[dust::kMaxBatch] = {};
+  const DustHipSky* skies[dust::kMaxBatch] = {};
+  bool continues[dust::kMaxBatch] = {};
+  bool took_counters[dust::kMaxBatch] = {};  // the frame's pipeline has flipped its counter parity for this launch (dust_hip_render_frames gives it back if the launch is never made)
+  bool launched = false;                     // the launch was enqueued: the counter sets are in use as taken
   DustHipPipeline* timer = nullptr;          // frame 0's pipeline: its HIP-event pair brackets the launch
   uint32_t n = 0;      // frames of the launch
   uint32_t slot = 0;   // the frame being prepared
@@ -2278,7 +2288,23 @@ static DustStatus render_frame_impl(DustHipPipeline* p, const DustHipScene* s, c
   if (role != FrameRole::Single && (!fuse || count)) return fail(DUST_ERR_INVALID_ARGUMENT, "a batched frame must be a fused primary + AO frame");  // (dust_hip_render_frames checks)
   if (fuse) {
     take_counters(p, 0, a);
-    { DustStatus os = order_tiles(p, 0, a, st); if (os != DUST_OK) return os; }
+    bool continues = false;
+    if (role != FrameRole::Single) {
+      const uint32_t i = join->slot;
+      join->took_counters[i] = true;
+      join->cams[i] = cam; join->skies[i] = sky;
+      continues = i > 0 && !tune.no_shared_view && join->image_of[i - 1] == s->current &&
+                  std::memcmp(cam, join->cams[i - 1], sizeof *cam) == 0 && std::memcmp(sky, join->skies[i - 1], sizeof *sky) == 0;
+      join->continues[i] = continues;
+    }
+    if (continues) {
+      // a follower of a view run: the launch hands out the run's tiles by its leader's order and writes the leader's cost buffer. This pipeline's tile
+      // history is left as it stands -- nothing of it is read, nothing is measured for it --, valid for its next launch, alone or grouped differently.
+      a.tile_order = nullptr; a.tile_cost = nullptr; a.band_cuts = nullptr;
+    } else {
+      DustStatus os = order_tiles(p, 0, a, st);
+      if (os != DUST_OK) return os;
+    }
     a.stats = static_cast<dust::DevStats*>(p->stats.p);
     if (role != FrameRole::Single) {   // a frame of a launch of several: prepared; the last one launches them all
       join->frames[join->slot] = a;
@@ -2316,6 +2342,14 @@ static DustStatus render_frame_impl(DustHipPipeline* p, const DustHipScene* s, c
         // the boxes staged in LDS are frame 0's image's: a frame of another image (an instance moved in between) reads its own from memory
         if (join->image_of[i] != join->image_of[0]) join->frames[i].n_lds_boxes = 0;
       }
+      for (uint32_t i = 0; i < join->n;) {   // view runs: the leader says how many frames follow it with the same view, a follower says 0
+        uint32_t run = 1;
+        while (i + run < join->n && join->continues[i + run]) ++run;
+        join->frames[i].view_run = run;
+        for (uint32_t m = 1; m < run; ++m) join->frames[i + m].view_run = 0;
+        i += run;
+      }
+      join->launched = true;
       if ((tune.debug & 32u) || dust::launch_primary_ao_batch(join->frames, join->n, fgrid, fblock, st) != hipSuccess) {   // (DUST_HIP_DEBUG bit 32: as if refused)
         // (the launch carries 8.5 KB of kernel arguments -- probed on this runtime, which takes 16 KB. Should a runtime refuse it: the prepared
         //  frames one launch each, the same results)
@@ -2488,7 +2522,7 @@ static bool batchable(uint32_t n, DustHipPipeline* const* pipes, const DustHipSc
     if (p->ctx != p0->ctx || p->width != p0->width || p->height != p0->height) return false;
     if (fps[i].passes != want || fps[i].row_begin != fps[0].row_begin || fps[i].row_end != fps[0].row_end) return false;
     if (t.no_fuse || t.block != t0.block || t.blocks_per_cu != t0.blocks_per_cu || t.no_lds_boxes != t0.no_lds_boxes || t.wide_fused != t0.wide_fused ||
-        t.debug != t0.debug || t.static_rounds != t0.static_rounds || t.reserve_blocks != t0.reserve_blocks || p->in_collective != p0->in_collective ||
+        t.debug != t0.debug || t.static_rounds != t0.static_rounds || t.no_shared_view != t0.no_shared_view || t.reserve_blocks != t0.reserve_blocks || p->in_collective != p0->in_collective ||
         p->frames_in_flight != p0->frames_in_flight || (p->frames_in_flight > 1 && t.in_flight_slots != t0.in_flight_slots))
       return false;
     for (uint32_t j = 0; j < i; ++j)
@@ -2547,7 +2581,9 @@ DustStatus dust_hip_render_frames(uint32_t n_frames, DustHipPipeline* const* pip
         // (a HIP failure or a commit that could not grow the scene: the frames prepared so far are never launched -- their pipelines took a set of
         //  work counters for nothing, and no launch zeroed the other one: give it back, or their next launch would pull tiles from a set that an
         //  earlier launch has counted up)
-        for (uint32_t j = 0; j < i; ++j) pipelines[at + j]->counter_parity[0] ^= 1u;
+        // (frame i's own too, when it failed behind take_counters; not once the launch is enqueued: the sets are then in use as taken)
+        for (uint32_t j = 0; j <= i && !join.launched; ++j)
+          if (join.took_counters[j]) pipelines[at + j]->counter_parity[0] ^= 1u;
         return rs;
       }
     }

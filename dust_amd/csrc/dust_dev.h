@@ -288,7 +288,13 @@ struct FrameArgs {
                               // holds many rounds of tiles for its workgroups, 4 in the launch's last frame and in small frames)
   uint32_t batch_queue_base;  // every descriptor of a BatchArgs: LDS byte offset of frame 1's tile queue (frame f: + 16 (f - 1)) -- the end of frame 0's LDS layout, which a
                               // frame that reads another scene image (n_lds_boxes = 0: its boxes come from memory) cannot work out from its own fields
+  // ---- appended: view runs (k_primary_ao_runs). Consecutive frames of a BatchArgs with byte-identical camera and sky that read the same scene image
+  // form a VIEW RUN: their camera and sun rays -- and everything primary_shade works out -- are the same bit for bit, only the AO ray (rand, noise5) and the
+  // planes are each frame's own. The run's first descriptor, its LEADER, holds the run's length here (1: a frame on its own); its followers hold 0.
+  uint32_t view_run;
+  uint32_t pad_end[3];        // (a descriptor stays a multiple of 16 bytes: those of a BatchArgs all start as the first does)
 };
+static_assert(sizeof(FrameArgs) % 16 == 0, "the descriptors of a BatchArgs keep the alignment of the first");
 
 // The kernel argument of k_primary_ao_batch: up to kMaxBatch whole launch descriptors, one per frame, side by side in the kernel-argument segment
 // (8.5 KB; the runtime takes 16 KB, probed on an MI355X). The frames share scene, frame size, rows and launch geometry -- what is staged in LDS and

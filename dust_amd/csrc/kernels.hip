@@ -298,6 +298,135 @@ __global__ void __launch_bounds__(DUST_PAO_THREADS, DUST_PAO_WAVES) k_primary_ao
   prof_end();
 }
 
+// View runs (dust_dev.h, FrameArgs::view_run): consecutive frames of a launch with the same camera, sky and scene image. Everything but the AO ray
+// is the same for all of them, bit for bit -- the camera ray's cull, walk and shading, the sun ray's cull and walk and what it adds to the payload --, so
+// a tile is ONE work item for the whole run: the leader's descriptor traces the camera and sun rays once, every member's planes get the texels, and
+// only the AO ray (its direction reads the member's rand and noise slice) is traced per member. primary_packet + ao_packet, regrouped:
+//   camera ray, primary_shade<KEEP>  ->  for each member: its G-buffer texels  ->  sun ray  ->  for each member: AO ray, its illuminance texel.
+// The static texels wait in registers only from primary_shade to the member loop right behind it (six VGPRs, nothing of a trace is live there): the
+// stores stand outside primary_shade's one-instance-at-a-time loop, and no trace carries them.
+// The sun ray and the members' AO rays go through ONE trace_ray<1> (k = 0: sun, k = 1 + m: member m), as ao_packet's two rays do.
+template <int MODE>
+__device__ __forceinline__ void view_run_packet(ArgsRef a, const DUST_CONST_AS FrameArgs* members, uint32_t run, const Packet& p, uint32_t* cand, LaneStats& st) {
+  float hitT;
+  uint32_t normal_packed;
+  {
+    const V3 o = mk(a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]);
+    const V3 d = camera_ray_dir(a, p.px, p.py);
+    const uint32_t ncand = (a.debug & 2u) ? 0u : cull_instances<MODE>(a, __any(p.valid), point_range(o), wave_range(p.valid, d), a.cam.far_, cand);
+    Hit h;
+    h.found = false;
+    if (!(a.debug & 1u)) trace_ray<0, MODE>(a, p.valid, o, d, a.cam.near_, a.cam.far_, false, cand, ncand, h, st);
+    __builtin_amdgcn_wave_barrier();
+    PROF_ENTER(P_PRIMARY_SHADE);
+    PrimaryTexels tx;
+    primary_shade<MODE, true>(reload_args(a), p, o, d, h, false, hitT, normal_packed, &tx);
+#pragma unroll 1
+    for (uint32_t m = 0; m < run; ++m) {
+      const DUST_CONST_AS FrameArgs* mq = members + (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
+      asm volatile("" : "+s"(mq));
+      store_primary_texels(*mq, p, hitT, normal_packed, tx);
+    }
+    PROF_LEAVE(P_PRIMARY_SHADE);
+  }
+  PROF_ENTER(P_AO_SETUP);
+  ArgsRef a1 = reload_args(a);
+  const V3 sun = mk(a1.sky[48], a1.sky[49], a1.sky[50]);
+  const size_t pix = p.valid ? (size_t)p.py * a1.width + p.px : 0;
+  const bool live = p.valid && !(hitT == INFINITY);
+  V3 n = mk(0, 0, 1), loc = mk(0, 0, 0);
+  if (live) {
+    n = nrd_unpack_normal(normal_packed);
+    const V3 d = camera_ray_dir(a1, p.px, p.py);
+    loc = mk((hitT * d.x + a1.cam.pos[0]) + n.x * 0.01f, (hitT * d.y + a1.cam.pos[1]) + n.y * 0.01f,
+             (hitT * d.z + a1.cam.pos[2]) + n.z * 0.01f);
+  }
+  const bool sun_live = live && dot3(sun, n) > 0.0f;
+  const V3 sd = mk(a1.sun_dir[0], a1.sun_dir[1], a1.sun_dir[2]);
+  const Range3 org = wave_range(live, loc);
+  V3 payload = mk(0, 0, 0);
+  PROF_LEAVE(P_AO_SETUP);
+  Hit h;
+#pragma unroll 1
+  for (uint32_t k = 0; k <= run; ++k) {
+    ArgsRef b = reload_args(a);
+    const DUST_CONST_AS FrameArgs* mq = members + (uint32_t)__builtin_amdgcn_readfirstlane((int)(k ? k - 1u : 0u));   // the member whose AO ray this is (k = 0, the sun ray: nobody's)
+    asm volatile("" : "+s"(mq));
+    V3 ad = mk(0, 0, 1);
+    if (k != 0u && live) {  // ambient_occlusion.rgen:52-58 with the member's frame index: its noise slice and rand
+      const uint32_t nx = (p.px + 7u + mq->rand) % 128u, ny = (p.py + 183u + mq->rand) % 128u;
+      const uint32_t tex = ((DUST_RO(uint32_t))mq->noise5)[ny * 128u + nx];
+      V3 ns = mk(div_const((float)(tex & 255u), 255.0f) * 2.0f - 1.0f, div_const((float)((tex >> 8) & 255u), 255.0f) * 2.0f - 1.0f,
+                 div_const((float)((tex >> 16) & 255u), 255.0f) * 2.0f - 1.0f);
+      ad = normalize3(rotate_by_normal(n, ns));
+    }
+    const bool act = k == 0u ? sun_live : live;
+    const V3 dir = k == 0u ? sd : ad;
+    const float tmax = k == 0u ? 10000.0f : 8.0f;
+    const uint32_t ncand = cull_instances<MODE>(b, __any(act), org, k == 0u ? point_range(sd) : wave_range(live, ad), tmax, cand);
+    LaneStats cur = {0, 0, 0, 0, 0, 0};
+    trace_ray<1, MODE>(b, act, loc, dir, 0.1f, tmax, k == 0u, cand, ncand, h, cur);
+    __builtin_amdgcn_wave_barrier();
+    if (k == 0u && sun_live && !h.found) {
+      const float dn = dot3(n, sd);
+      payload.x += b.sun_term[0] * dn; payload.y += b.sun_term[1] * dn; payload.z += b.sun_term[2] * dn;
+    }
+    if (k != 0u && live) store_radiance(mq->g.illuminance, pix, payload, h.found ? h.t : 0.0f);
+  }
+}
+// k_primary_ao_batch over view runs instead of frames (launch_primary_ao_batch launches it when a run of the launch is longer than one frame). A run
+// takes its LEADER's tile queue, tile order, band cuts, cost buffer and work counters -- the followers' are not read --; the next launch's counters
+// are zeroed for every member, as k_primary_ao_batch does for every frame. A run of one frame is what a frame is there; the rules of the launch's
+// last frame (every band, refills of kGrabBatch) are those of its last RUN.
+template <int MODE>
+__global__ void __launch_bounds__(DUST_PAO_THREADS, DUST_PAO_WAVES) k_primary_ao_runs(const BatchArgs) {
+  ArgsRef lead = launch_args();
+#ifdef DUST_WAVE_TIMES
+  const unsigned long long wt0 = __builtin_amdgcn_s_memtime(), ww0 = wall_clock64();
+  unsigned long long wt_tiles = 0;
+#endif
+  stage_roots_of<true>(lead);
+#ifdef DUST_WAVE_TIMES
+  const unsigned long long wt1 = __builtin_amdgcn_s_memtime();
+#endif
+  uint32_t* cand = wave_cand_list(lead);
+  LaneStats st = {0, 0, 0, 0, 0, 0};  // (never a counting build: dead)
+  const uint32_t n_frames = lead.batch_frames;
+#pragma unroll 1
+  for (uint32_t f = 0; f < n_frames;) {
+    const DUST_CONST_AS FrameArgs* fq = &launch_args() + f;
+    asm volatile("" : "+s"(fq));
+    ArgsRef a0 = *fq;
+    uint32_t run = a0.view_run ? a0.view_run : 1u;
+    if (run > n_frames - f) run = n_frames - f;   // (the launcher checks the runs against the frame count: a run never leaves the BatchArgs)
+    if (blockIdx.x == 0 && threadIdx.x < kRegions)
+      for (uint32_t m = f ? 0u : 1u; m < run; ++m) fq[m].next_work_counters[threadIdx.x * kCounterStride] = 0u;   // (frame 0's: stage_roots)
+    WorkCursor wc = cursor_begin();
+    wc.frame = f;
+    wc.grab = a0.batch_grab;
+    wc.tries = f + run == n_frames ? kRegions : 1u;
+    Packet p;
+    while (next_packet_of<true>(a0, wc, p)) {
+#ifdef DUST_WAVE_TIMES
+      wt_tiles += 1;
+#endif
+      view_run_packet<MODE>(reload_args(a0), fq, run, p, cand, st);
+    }
+    f += run;
+  }
+#ifdef DUST_WAVE_TIMES
+  if ((threadIdx.x & 63u) == 0) {
+    const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (w < 8192u) {
+      g_wave_times[w][0] = wt0; g_wave_times[w][1] = wt1; g_wave_times[w][2] = __builtin_amdgcn_s_memtime();
+      g_wave_times[w][3] = ww0; g_wave_times[w][4] = wall_clock64(); g_wave_times[w][5] = wt_tiles;
+      for (int k = 6; k < 12; ++k) g_wave_times[w][k] = 0;
+    }
+  }
+#endif
+  prof_end();
+}
+
 // ==================================================================== N-frame mean (stands in for NRD)
 __global__ void k_accumulate(const FrameArgs) {
   ArgsRef a = launch_args();
@@ -733,8 +862,21 @@ hipError_t launch_primary_ao(const FrameArgs& a_in, uint32_t grid, uint32_t bloc
   return hipGetLastError();
 }
 // n frames (2 .. kMaxBatch) in one launch; frames[0] decides the kernel variant and the geometry. Frames after the first: no dealt round.
+// A frame whose view_run is above 1 leads a view run (dust_dev.h): the launch then goes to k_primary_ao_runs, which hands out tiles per run.
 hipError_t launch_primary_ao_batch(const FrameArgs* frames, uint32_t n, uint32_t grid, uint32_t block, hipStream_t s) {
   if (n < 1u || n > kMaxBatch) return hipErrorInvalidValue;
+  bool runs = false;
+  for (uint32_t i = 0; i < n; ++i) runs = runs || frames[i].view_run > 1u;
+  uint32_t last_lead = n - 1u;   // first frame of the launch's last run (no runs: its last frame)
+  if (runs)
+    for (uint32_t i = 0; i < n;) {
+      const uint32_t run = frames[i].view_run;
+      if (run < 1u || run > n - i) return hipErrorInvalidValue;   // every run starts at a leader and ends inside the launch
+      for (uint32_t m = 1; m < run; ++m)
+        if (frames[i + m].view_run != 0u) return hipErrorInvalidValue;
+      last_lead = i;
+      i += run;
+    }
   const size_t lds = lds_bytes(frames[0], block) + 16u * (n - 1u);   // + a tile queue per further frame (frame_queue)
   BatchArgs b;
   for (uint32_t i = 0; i < n; ++i) {
@@ -747,12 +889,18 @@ hipError_t launch_primary_ao_batch(const FrameArgs* frames, uint32_t n, uint32_t
     {  // tickets per refill: a quarter of what a workgroup's share of a band comes to, between kGrabBatch and kBatchGrabMax; the last frame: kGrabBatch
       const uint32_t groups_per_band = (grid + kRegions - 1u) / kRegions;
       const uint32_t share = b.f[i].tiles_per_band / (4u * (groups_per_band ? groups_per_band : 1u));
-      b.f[i].batch_grab = i + 1u == n ? kGrabBatch : (share < kGrabBatch ? kGrabBatch : (share > kBatchGrabMax ? kBatchGrabMax : share));
+      b.f[i].batch_grab = i >= last_lead ? kGrabBatch : (share < kGrabBatch ? kGrabBatch : (share > kBatchGrabMax ? kBatchGrabMax : share));
     }
     b.f[i].batch_queue_base = (uint32_t)lds_bytes(frames[0], block);
   }
   for (uint32_t i = n; i < kMaxBatch; ++i) b.f[i] = b.f[0];   // (never read)
-  switch ((b.f[0].deep ? 2 : 0) | (b.f[0].n_groups ? 4 : 0)) {
+  if (runs) switch ((b.f[0].deep ? 2 : 0) | (b.f[0].n_groups ? 4 : 0)) {
+    case 0: hipLaunchKernelGGL(k_primary_ao_runs<0>, dim3(grid), dim3(block), lds, s, b); break;
+    case 2: hipLaunchKernelGGL(k_primary_ao_runs<2>, dim3(grid), dim3(block), lds, s, b); break;
+    case 4: hipLaunchKernelGGL(k_primary_ao_runs<4>, dim3(grid), dim3(block), lds, s, b); break;
+    default: hipLaunchKernelGGL(k_primary_ao_runs<6>, dim3(grid), dim3(block), lds, s, b); break;
+  }
+  else switch ((b.f[0].deep ? 2 : 0) | (b.f[0].n_groups ? 4 : 0)) {
     case 0: hipLaunchKernelGGL(k_primary_ao_batch<0>, dim3(grid), dim3(block), lds, s, b); break;
     case 2: hipLaunchKernelGGL(k_primary_ao_batch<2>, dim3(grid), dim3(block), lds, s, b); break;
     case 4: hipLaunchKernelGGL(k_primary_ao_batch<4>, dim3(grid), dim3(block), lds, s, b); break;
@@ -782,7 +930,8 @@ hipError_t configure_kernels(size_t max_lds) {
       (const void*)k_primary<0>, (const void*)k_primary<1>, (const void*)k_primary<2>, (const void*)k_primary<3>, (const void*)k_primary<4>, (const void*)k_primary<5>, (const void*)k_primary<6>, (const void*)k_primary<7>,
       (const void*)k_ambient_occlusion<0>, (const void*)k_ambient_occlusion<1>, (const void*)k_ambient_occlusion<2>, (const void*)k_ambient_occlusion<3>, (const void*)k_ambient_occlusion<4>, (const void*)k_ambient_occlusion<5>, (const void*)k_ambient_occlusion<6>, (const void*)k_ambient_occlusion<7>,
       (const void*)k_primary_ao<0>, (const void*)k_primary_ao<1>, (const void*)k_primary_ao<2>, (const void*)k_primary_ao<3>, (const void*)k_primary_ao<4>, (const void*)k_primary_ao<5>, (const void*)k_primary_ao<6>, (const void*)k_primary_ao<7>,
-      (const void*)k_primary_ao_batch<0>, (const void*)k_primary_ao_batch<2>, (const void*)k_primary_ao_batch<4>, (const void*)k_primary_ao_batch<6>};
+      (const void*)k_primary_ao_batch<0>, (const void*)k_primary_ao_batch<2>, (const void*)k_primary_ao_batch<4>, (const void*)k_primary_ao_batch<6>,
+      (const void*)k_primary_ao_runs<0>, (const void*)k_primary_ao_runs<2>, (const void*)k_primary_ao_runs<4>, (const void*)k_primary_ao_runs<6>};
   for (const void* f : fns) {
     e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
     if (e != hipSuccess) return e;

@@ -1867,16 +1867,29 @@ __device__ void brick_surfel(ArgsRef a, const Hit& h, V3 o, V3 d, HashKey& key, 
 // Returns, per lane, what the later passes read back from the G-buffer: the hit distance (INFINITY on a miss) and the packed normal texel.
 // store_illuminance: hit.rchit:57 zeroes img_illuminance; the fused kernel skips that store because the ambient occlusion pass
 // overwrites the texel of every hit pixel anyway.
-template <int MODE>
+// KEEP (a view run, k_primary_ao_runs): nothing is stored; the texels come back in `keep` as the bits the stores would have written, and
+// store_primary_texels writes them to the planes of every frame of the run. The default instantiation is the storing code, unchanged.
+struct PrimaryTexels {
+  u32x2 motion, sky;          // the motion texel; a miss pixel's texel of the denoised plane (miss.rmiss:13)
+  uint32_t albedo, voxel_id;  // (the depth and normal texels are primary_shade's hitT and normal_packed)
+  bool found;
+};
+template <int MODE, bool KEEP = false>
 __device__ __forceinline__ void primary_shade(ArgsRef a, const Packet& p, V3 o, V3 d, const Hit& h, bool store_illuminance,
-                                              float& hitT, uint32_t& normal_packed) {
+                                              float& hitT, uint32_t& normal_packed, PrimaryTexels* keep = nullptr) {
   hitT = INFINITY;
   normal_packed = 0;
+  if constexpr (KEEP) { keep->motion = u32x2{0u, 0u}; keep->sky = u32x2{0u, 0u}; keep->albedo = 0xFFFFFFFFu; keep->voxel_id = 0u; keep->found = false; }
   if (!p.valid) return;
   const size_t pix = (size_t)p.py * a.width + p.px;
   if (!h.found) {
     const V3 dir = normalize3(d);
     const V3 s0 = sky_radiance(a.sky, dir), s1 = sun_radiance(a.sky, dir);
+    if constexpr (KEEP) {
+      keep->sky = pack_radiance(mk(div_const(s0.x + s1.x, 3.14f), div_const(s0.y + s1.y, 3.14f), div_const(s0.z + s1.z, 3.14f)), 100000.0f);
+      keep->motion = pack_half4(0.0f, 0.0f, 0.0f, 0.0f);
+      return;
+    }
     store_radiance(a.g.denoised, pix, mk(div_const(s0.x + s1.x, 3.14f), div_const(s0.y + s1.y, 3.14f), div_const(s0.z + s1.z, 3.14f)), 100000.0f);
     DUST_NT_STORE(0xFFFFFFFFu, &a.g.albedo[pix]);
     DUST_NT_STORE(INFINITY, &a.g.depth[pix]);
@@ -1908,13 +1921,21 @@ __device__ __forceinline__ void primary_shade(ArgsRef a, const Packet& p, V3 o, 
     const uint32_t voff = (uint32_t)__popc(ma) + (uint32_t)__popc(mb);
     const uint32_t pal = m.materials[b.material_ptr + voff];
     const uint32_t col = m.palette[pal];
-    DUST_NT_STORE(pack_rgb10a2(div_const((float)(col & 255u), 255.0f), div_const((float)((col >> 8) & 255u), 255.0f),
-                                             div_const((float)((col >> 16) & 255u), 255.0f), 1.0f), &a.g.albedo[pix]);
-    DUST_NT_STORE(h.t, &a.g.depth[pix]);
+    const uint32_t albedo = pack_rgb10a2(div_const((float)(col & 255u), 255.0f), div_const((float)((col >> 8) & 255u), 255.0f),
+                                         div_const((float)((col >> 16) & 255u), 255.0f), 1.0f);
+    if constexpr (!KEEP) {
+      DUST_NT_STORE(albedo, &a.g.albedo[pix]);
+      DUST_NT_STORE(h.t, &a.g.depth[pix]);
+    }
     hitT = h.t;
     normal_packed = nrd_pack_normal(nw, 1.0f, (float)pal);
-    DUST_NT_STORE(normal_packed, &a.g.normal[pix]);
-    DUST_NT_STORE((h.voxel << 24) | (h.inst & 0xFFFFu) | (pal << 16), &a.g.voxel_id[pix]);
+    const uint32_t voxel_id = (h.voxel << 24) | (h.inst & 0xFFFFu) | (pal << 16);
+    if constexpr (KEEP) {
+      keep->albedo = albedo; keep->voxel_id = voxel_id; keep->found = true;
+    } else {
+      DUST_NT_STORE(normal_packed, &a.g.normal[pix]);
+      DUST_NT_STORE(voxel_id, &a.g.voxel_id[pix]);
+    }
     const V3 hpw = mk(h.t * d.x + o.x, h.t * d.y + o.y, h.t * d.z + o.z);
     const V3 hpm = xform_point(in.w2o, hpw);
     DUST_RO(float) P = in.prev;
@@ -1923,8 +1944,26 @@ __device__ __forceinline__ void primary_shade(ArgsRef a, const Packet& p, V3 o, 
     const float hz = ((P[2] * hpm.x + P[6] * hpm.y) + P[10] * hpm.z) + P[14];
     const float hw = ((P[3] * hpm.x + P[7] * hpm.y) + P[11] * hpm.z) + P[15];
     const V3 hp = div3(mk(hx, hy, hz), hw);
-    store_half4(a.g.motion, pix, hp.x - hpw.x, hp.y - hpw.y, hp.z - hpw.z, 0.0f);
+    if constexpr (KEEP) keep->motion = pack_half4(hp.x - hpw.x, hp.y - hpw.y, hp.z - hpw.z, 0.0f);
+    else store_half4(a.g.motion, pix, hp.x - hpw.x, hp.y - hpw.y, hp.z - hpw.z, 0.0f);
   }
+}
+// the stores primary_shade<MODE, true> left out, into the planes of one frame of the view run (`f`: that frame's descriptor): same values, same non-temporal stores
+__device__ __forceinline__ void store_primary_texels(ArgsRef f, const Packet& p, float hitT, uint32_t normal_packed, const PrimaryTexels& t) {
+  if (!p.valid) return;
+  const size_t pix = (size_t)p.py * f.width + p.px;
+  if (!t.found) {
+    DUST_NT_STORE(t.sky, (DUST_GLOBAL_AS u32x2*)(f.g.denoised + pix * 4));
+    DUST_NT_STORE(0xFFFFFFFFu, &f.g.albedo[pix]);
+    DUST_NT_STORE(INFINITY, &f.g.depth[pix]);
+    DUST_NT_STORE(t.motion, (DUST_GLOBAL_AS u32x2*)(f.g.motion + pix * 4));
+    return;
+  }
+  DUST_NT_STORE(t.albedo, &f.g.albedo[pix]);
+  DUST_NT_STORE(hitT, &f.g.depth[pix]);
+  DUST_NT_STORE(normal_packed, &f.g.normal[pix]);
+  DUST_NT_STORE(t.voxel_id, &f.g.voxel_id[pix]);
+  DUST_NT_STORE(t.motion, (DUST_GLOBAL_AS u32x2*)(f.g.motion + pix * 4));
 }
 
 }  // namespace

@@ -510,7 +510,11 @@ typedef struct DustHipFrameMoves {
  * frame's gather reads the hash its predecessor's surfel pass wrote) is enqueued frame after frame as dust_hip_render_frame would. Every
  * frame's arguments are checked before the scene is touched and the first frame is enqueued; params[i].struct_size must be
  * sizeof(DustHipFrameParams). With DUST_HIP_CONTEXT_TIMING the launch's time is reported by pipelines[0] (pass 0), once for all frames of
- * the launch. After the call the scene is as the last frame saw it. */
+ * the launch. After the call the scene is as the last frame saw it.
+ * Same-view frames: consecutive frames of a launch whose cameras[i] and skies[i] are byte-identical and between which no moves were committed
+ * (N samples per pixel of one view, a viewer whose camera rests) differ only in their AO rays -- frame_index and rand feed nothing else. Their
+ * camera rays, the shading and their sun shadow rays are traced ONCE per launch; every frame's pipeline still gets all of its planes, with the
+ * bits dust_hip_render_frame writes, and each frame's AO ray is its own. A frame whose camera, sky or scene differs starts a new run of its own. */
 DustStatus dust_hip_render_frames(uint32_t n_frames, DustHipPipeline* const* pipelines, DustHipScene*, const DustHipCamera* cameras,
                                   const DustHipSky* skies, const DustHipFrameParams* params, const DustHipFrameMoves* moves);
 /* pass: 0 primary, 1 AO-pass sun-shadow rays, 2 AO rays, 3 final gather, 4 surfel sun rays, 5 surfel cosine rays.
