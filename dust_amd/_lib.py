@@ -151,6 +151,21 @@ EDIT_CARVE, EDIT_FILL, EDIT_PAINT, EDIT_PLACE = 0, 1, 2, 3
 MAX_EDIT_SHAPES = 65536
 
 
+class IslandQuery(C.Structure):  # DustHipIslandQuery, 32 bytes: the connectivity of a labelling and the inclusive voxel box that anchors islands
+    _fields_ = [("struct_size", C.c_uint32), ("connectivity", C.c_uint32), ("anchor_lo", C.c_uint32 * 3), ("anchor_hi", C.c_uint32 * 3)]
+
+
+class Island(C.Structure):  # DustHipIsland, 40 bytes: one connected set of solid voxels, named by its smallest x << 16 | y << 8 | z
+    _fields_ = [("key", C.c_uint32), ("voxels", C.c_uint32), ("lo", C.c_uint8 * 3), ("flags", C.c_uint8), ("hi", C.c_uint8 * 3),
+                ("reserved", C.c_uint8), ("sum", C.c_uint64 * 3)]
+
+
+ISLANDS_FACES, ISLANDS_CORNERS = 0, 1
+ISLAND_ANCHORED = 1
+NO_ISLAND = 0xFFFFFFFF
+DETACH_KEEP_SOURCE = 1
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("rays", C.c_uint64), ("instances_tested", C.c_uint64),
                 ("upper_descents", C.c_uint64), ("mid_descents", C.c_uint64), ("bricks_tested", C.c_uint64),
@@ -207,6 +222,9 @@ SYMBOLS = {
     "dust_hip_model_set_voxels": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_get_voxels": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_edit_shapes": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "dust_hip_model_find_islands": (C.c_int, [_P, _P, _u32p, _P, C.c_uint32]),
+    "dust_hip_model_island_of": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "dust_hip_model_detach_islands": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_scene_create": (C.c_int, [_P, C.POINTER(_P)]),

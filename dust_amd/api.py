@@ -34,6 +34,8 @@ assert BOX_SWEEP_DTYPE.itemsize == 48 and SWEEP_HIT_DTYPE.itemsize == 32
 # dust_hip_model_edit_shapes: a shape in a model's tree coordinates and its operation
 EDIT_SHAPE_DTYPE = np.dtype([("a", "<f4", 3), ("kind", "<u4"), ("b", "<f4", 3), ("radius", "<f4"), ("op", "<u4"), ("palette", "<i4"),
                              ("reserved", "<u4", 2)])
+# DustHipIsland, 40 bytes: one island of dust_hip_model_find_islands
+ISLAND_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("flags", "u1"), ("hi", "u1", 3), ("reserved", "u1"), ("sum", "<u8", 3)])
 FLT_MAX = float(np.finfo(np.float32).max)
 
 PLANE_DTYPES = {
@@ -340,6 +342,50 @@ class Model:
         changed = np.zeros(len(shapes), np.uint32)
         L.check(self._lib.dust_hip_model_edit_shapes(self._h, _ptr(shapes), len(shapes), _ptr(changed)))
         return changed
+
+    def find_islands(self, connectivity=L.ISLANDS_FACES, anchor=None, capacity=None, records=None):
+        """Label the model's connected solid voxels (dust_hip_model_find_islands): returns (n, records) -- n the number of islands,
+        records the first min(n, capacity) of them as an ISLAND_DTYPE array in ascending key order (key: x << 16 | y << 8 | z of the
+        island's smallest voxel). anchor: (lo, hi), an inclusive voxel box; islands with a voxel inside carry L.ISLAND_ANCHORED.
+        capacity None: every island (counted first; the second call keeps the first one's labelling); 0: count only. records: an array to fill instead of a fresh one (slots past n
+        are left as they are). The labelling stays on the device for island_of and detach_islands until the next edit."""
+        q = L.IslandQuery(struct_size=C.sizeof(L.IslandQuery), connectivity=connectivity)
+        lo, hi = ((1, 1, 1), (0, 0, 0)) if anchor is None else anchor
+        q.anchor_lo[:] = [int(v) for v in lo]
+        q.anchor_hi[:] = [int(v) for v in hi]
+        n = C.c_uint32()
+        if records is not None:
+            assert records.dtype == ISLAND_DTYPE and records.flags.c_contiguous
+            capacity = len(records)
+        elif capacity is None:
+            L.check(self._lib.dust_hip_model_find_islands(self._h, C.byref(q), C.byref(n), None, 0))
+            capacity = n.value
+        if records is None:
+            records = np.zeros(capacity, ISLAND_DTYPE)
+        L.check(self._lib.dust_hip_model_find_islands(self._h, C.byref(q), C.byref(n), _ptr(records) if capacity else None, capacity))
+        return n.value, records[: min(n.value, capacity)]
+
+    def island_of(self, xyz):
+        """the key of each voxel's island under the last find_islands (dust_hip_model_island_of); L.NO_ISLAND where the voxel is empty"""
+        xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
+        keys = np.zeros(len(xyz), np.uint32)
+        L.check(self._lib.dust_hip_model_island_of(self._h, _ptr(xyz), _ptr(keys), len(keys)))
+        return keys
+
+    def detach_islands(self, keys, keep_source=False, want_model=True):
+        """Move the islands named by `keys` (of the last find_islands) out of the model (dust_hip_model_detach_islands). Returns a new
+        Model holding exactly their voxels at the same tree coordinates -- or None with want_model=False (the islands are deleted) or
+        with no keys. keep_source: copy, the source stays as it is. Otherwise scenes instancing the source must be committed again;
+        its labelling stays valid for the islands that remain."""
+        keys = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+        h = C.c_void_p()
+        L.check(self._lib.dust_hip_model_detach_islands(self._h, _ptr(keys), len(keys), L.DETACH_KEEP_SOURCE if keep_source else 0,
+                                                        C.byref(h) if want_model else None))
+        if not h:
+            return None
+        piece = Model.__new__(Model)
+        piece._ctx, piece._lib, piece._h = self._ctx, self._lib, h
+        return piece
 
     def read(self):
         """(blocks, materials) as they stand on the device"""

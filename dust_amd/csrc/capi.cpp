@@ -21,6 +21,7 @@
 #include "vox.hpp"
 #include "sky.hpp"
 #include "edit.hpp"
+#include "island.hpp"
 #include "denoise.hpp"
 #include "query.hpp"
 #include <unordered_set>
@@ -210,6 +211,9 @@ struct DustHipContext : RefCounted {
   DeviceBuffer overlap_boxes, overlap_counts, overlap_records;
   // scene box sweeps (dust_hip_scene_sweep_boxes): the synchronous call's device staging for sweeps and hits, grown on demand
   DeviceBuffer sweep_queries, sweep_hits;
+  // model islands (island.hip): what a labelling or a detach needs besides the model's own label array -- a bit and a counter per 64
+  // keys, block sums, the records being accumulated, and the call's staging for keys and coordinates, grown on demand
+  DeviceBuffer island_mask, island_count, island_tmp, island_acc, island_records, island_in, island_out;
 };
 // wait for everything enqueued on the context's stream (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)
@@ -251,6 +255,8 @@ static void release(DustHipContext* c) {
   c->query_rays.release(); c->query_hits.release(); c->query_counters.release();
   c->overlap_boxes.release(); c->overlap_counts.release(); c->overlap_records.release();
   c->sweep_queries.release(); c->sweep_hits.release();
+  c->island_mask.release(); c->island_count.release(); c->island_tmp.release(); c->island_acc.release(); c->island_records.release();
+  c->island_in.release(); c->island_out.release();
   if (c->started) (void)hipHostFree(const_cast<uint32_t*>(c->started));
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -262,6 +268,11 @@ struct EditState {
   uint32_t batch_capacity = 0;
   // shape edits (dust_hip_model_edit_shapes): the call's shape records and counters, and one chunk's cell lists, grown on demand
   DeviceBuffer shapes, changed, shape_cells, shape_starts, shape_ids;
+  // model islands (dust_hip_model_find_islands): per voxel, indexed by x << 16 | y << 8 | z, the key of its island (64 MiB, allocated by
+  // the first labelling); valid until the next set_voxels / edit_shapes that may change a voxel
+  DeviceBuffer labels;
+  bool labels_valid = false;
+  uint32_t labels_corners = 0;  // the connectivity of that labelling
 };
 
 struct DustHipModel : RefCounted {
@@ -1056,11 +1067,17 @@ DustStatus rebuild_and_refresh(DustHipModel* m, EditState& es) {
 
 // first edit: move the model into full-capacity buffers and expand its voxels into the dense grid. The model becomes
 // editable (m->edit set) only when every step has succeeded: a failure leaves it exactly as it was.
-DustStatus make_editable(DustHipModel* m) {
-  if (m->edit) return DUST_OK;
+DustStatus editable_kind(const DustHipModel* m) {
   if (m->dev.extent != 256) return fail(DUST_ERR_UNSUPPORTED, "device-side edits cover hierarchy (4,2,2) models (256^3); rebuild larger trees with dust_hip_model_create");
   if (m->has_material_255) return fail(DUST_ERR_UNSUPPORTED, "the model holds material byte 255 (the edit grid stores palette index + 1 in a byte; dust_hip_model_set_voxels takes 0..254)");
-  DustStatus s = ensure_srgb_lut(m->ctx);
+  return DUST_OK;
+}
+// (`rebuild` false: the caller fills the grid and rebuilds itself -- a model born editable, dust_hip_model_detach_islands)
+DustStatus make_editable(DustHipModel* m, bool rebuild = true) {
+  if (m->edit) return DUST_OK;
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  s = ensure_srgb_lut(m->ctx);
   if (s != DUST_OK) return s;
   hipStream_t st = m->ctx->stream;
   std::unique_ptr<EditState> e(new EditState);
@@ -1092,7 +1109,7 @@ DustStatus make_editable(DustHipModel* m) {
   };
   swap_all();
   // the same voxels, now in the full-capacity arrays (bumps the generation: scenes holding the old addresses commit again)
-  s = rebuild_and_refresh(m, *e);
+  s = rebuild ? rebuild_and_refresh(m, *e) : DUST_OK;
   if (s != DUST_OK) { swap_all(); return s; }  // back to the tightly sized originals, untouched
   m->edit = std::move(e);
   return DUST_OK;
@@ -1137,6 +1154,7 @@ DustStatus dust_hip_model_set_voxels(DustHipModel* m, const uint32_t* xyz, const
       uv.push_back(values[k]);
     }
     const uint32_t un = uint32_t(uv.size());
+    m->edit->labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
     s = upload_batch(m, ux.data(), uv.data(), un, true);
     if (s != DUST_OK) return s;
     dust::EditArgs a = edit_args(m, *m->edit);
@@ -1222,6 +1240,7 @@ DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* s
     DustStatus s = make_editable(m);
     if (s != DUST_OK || n == 0) return s;
     EditState& es = *m->edit;
+    es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
     hipStream_t st = m->ctx->stream;
     // the shapes that cover something, in call order: `index` maps them back to the caller's
     std::vector<dust::DevEditShape> dev;
@@ -1311,6 +1330,152 @@ DustStatus dust_hip_model_get_voxels(DustHipModel* m, const uint32_t* xyz, int32
     HIP_TRY(dust::launch_edit_apply(a, true, m->ctx->stream));
     HIP_TRY(hipMemcpyAsync(values, m->edit->values.p, size_t(n) * 4, hipMemcpyDeviceToHost, m->ctx->stream));
     HIP_TRY(sync_stream(m->ctx));
+    return DUST_OK;
+  });
+}
+
+// ---- model islands (island.hip): label the grid's connected voxels, look labels up, move whole islands into a model of their own
+static_assert(sizeof(DustHipIslandQuery) == 32 && sizeof(DustHipIsland) == 40 && sizeof(DustHipIsland) == sizeof(dust::DevIsland), "island records");
+
+DustStatus dust_hip_model_find_islands(DustHipModel* m, const DustHipIslandQuery* q, uint32_t* n_islands, DustHipIsland* islands, uint32_t capacity) {
+  if (!m || !q || !n_islands || (!islands && capacity)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipIslandQuery");
+  if (q->connectivity > DUST_HIP_ISLANDS_CORNERS) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown island connectivity");
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    const uint32_t corners = q->connectivity == DUST_HIP_ISLANDS_CORNERS ? 1u : 0u;
+    // a labelling that still stands (no edit since; detached islands only left it) is not computed again: a count-only call followed by
+    // a call with room for every record labels once
+    const bool relabel = !(es.labels_valid && es.labels_corners == corners);
+    es.labels_valid = false;  // until this labelling is complete
+    if (!es.labels.p) {
+      const hipError_t e = es.labels.alloc(size_t(dust::kIslandKeys) * 4);
+      if (e != hipSuccess) { es.labels.release(); return hip_fail(e, "the island label array (64 MiB)"); }
+    }
+    if ((s = grow(ctx, ctx->island_mask, size_t(dust::kIslandRows) * 8)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->island_count, size_t(dust::kIslandRows) * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->island_tmp, 260 * 4)) != DUST_OK) return s;
+    dust::IslandArgs a{};
+    a.grid = static_cast<const uint8_t*>(es.grid.p);
+    a.label = static_cast<uint32_t*>(es.labels.p);
+    a.root_mask = static_cast<uint64_t*>(ctx->island_mask.p);
+    a.root_count = static_cast<uint32_t*>(ctx->island_count.p);
+    a.scan_tmp = static_cast<uint32_t*>(ctx->island_tmp.p);
+    a.corners = corners;
+    for (int r = 0; r < 3; ++r) { a.anchor_lo[r] = q->anchor_lo[r]; a.anchor_hi[r] = std::min(q->anchor_hi[r], 255u); }
+    HIP_TRY(dust::launch_island_label(a, relabel, st));
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, a.scan_tmp + 256, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    a.capacity = std::min(total, capacity);
+    if (a.capacity) {
+      if ((s = grow(ctx, ctx->island_acc, size_t(a.capacity) * sizeof(dust::IslandAcc))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->island_records, size_t(a.capacity) * sizeof(dust::DevIsland))) != DUST_OK) return s;
+      a.acc = static_cast<dust::IslandAcc*>(ctx->island_acc.p);
+      a.records = static_cast<dust::DevIsland*>(ctx->island_records.p);
+      HIP_TRY(hipMemsetAsync(a.acc, 0, size_t(a.capacity) * sizeof(dust::IslandAcc), st));
+      HIP_TRY(dust::launch_island_records(a, st));
+      HIP_TRY(hipMemcpyAsync(islands, a.records, size_t(a.capacity) * sizeof(dust::DevIsland), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    es.labels_valid = true;
+    es.labels_corners = corners;
+    *n_islands = total;
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_island_of(DustHipModel* m, const uint32_t* xyz, uint32_t* keys, uint32_t n) {
+  if (!m || (n && (!xyz || !keys))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  for (uint32_t i = 0; i < n; ++i)
+    if (xyz[i * 3] >= 256u || xyz[i * 3 + 1] >= 256u || xyz[i * 3 + 2] >= 256u)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
+  if (!m->edit || !m->edit->labels_valid)
+    return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)");
+  if (n == 0) return DUST_OK;
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((s = grow(ctx, ctx->island_in, size_t(n) * 12)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->island_out, size_t(n) * 4)) != DUST_OK) return s;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(ctx->island_in.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(dust::launch_island_lookup(static_cast<const uint32_t*>(m->edit->labels.p), static_cast<const uint32_t*>(ctx->island_in.p),
+                                       static_cast<uint32_t*>(ctx->island_out.p), n, st));
+    HIP_TRY(hipMemcpyAsync(keys, ctx->island_out.p, size_t(n) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, uint32_t n, uint32_t flags, DustHipModel** out) {
+  if (!m || (n && !keys)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (flags & ~DUST_HIP_DETACH_KEEP_SOURCE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown detach flags");
+  const bool keep = (flags & DUST_HIP_DETACH_KEEP_SOURCE) != 0;
+  if (keep && !out) return fail(DUST_ERR_INVALID_ARGUMENT, "DUST_HIP_DETACH_KEEP_SOURCE without a model to receive the islands does nothing");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (n == 0) { if (out) *out = nullptr; return DUST_OK; }
+  if (!m->edit || !m->edit->labels_valid)
+    return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)");
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    // which keys name an island: a bit per selected key, and the number of keys that name none
+    if ((s = grow(ctx, ctx->island_mask, size_t(dust::kIslandRows) * 8)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->island_tmp, 260 * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->island_in, size_t(n) * 4)) != DUST_OK) return s;
+    uint32_t* bad_dev = static_cast<uint32_t*>(ctx->island_tmp.p) + 257;
+    HIP_TRY(hipMemcpyAsync(ctx->island_in.p, keys, size_t(n) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ctx->island_mask.p, 0, size_t(dust::kIslandRows) * 8, st));
+    HIP_TRY(hipMemsetAsync(bad_dev, 0, 4, st));
+    HIP_TRY(dust::launch_island_select(static_cast<const uint32_t*>(es.labels.p), static_cast<const uint32_t*>(ctx->island_in.p), n,
+                                       static_cast<uint64_t*>(ctx->island_mask.p), bad_dev, st));
+    uint32_t bad = 0;
+    uint32_t pal[256];
+    HIP_TRY(hipMemcpyAsync(&bad, bad_dev, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pal, m->palette.p, sizeof(pal), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(DUST_ERR_INVALID_ARGUMENT, "a key does not name an island of the model's current labelling");
+    // the new model: empty, editable, its grid filled by the detach kernel and then rebuilt like any edit
+    struct Drop { DustHipModel* m; ~Drop() { release(m); } } fresh{nullptr};
+    if (out) {
+      s = dust_hip_model_create(ctx, nullptr, 0, nullptr, 0, reinterpret_cast<const uint8_t*>(pal), 8, &fresh.m);
+      if (s == DUST_OK) s = make_editable(fresh.m, false);
+      if (s != DUST_OK) return s;
+    }
+    dust::IslandDetachArgs a{};
+    a.src = static_cast<uint8_t*>(es.grid.p);
+    a.dst = fresh.m ? static_cast<uint8_t*>(fresh.m->edit->grid.p) : nullptr;
+    a.label = static_cast<uint32_t*>(es.labels.p);
+    a.selected = static_cast<const uint64_t*>(ctx->island_mask.p);
+    // copy first and build the new model from the copy; the source is carved only once the voxels have somewhere to live, so a failure
+    // up to there leaves it as it was
+    if (fresh.m) {
+      a.carve = 0u;
+      HIP_TRY(dust::launch_island_detach(a, st));
+      if ((s = rebuild_and_refresh(fresh.m, *fresh.m->edit)) != DUST_OK) return s;
+    }
+    if (!keep) {
+      a.dst = nullptr;
+      a.carve = 1u;
+      HIP_TRY(dust::launch_island_detach(a, st));
+      // (whole islands left: the labelling of the rest stands.) A failure in here is that of a shape edit's rebuild: the grid is
+      // changed, the arrays are not; the new model is dropped with the error
+      if ((s = rebuild_and_refresh(m, es)) != DUST_OK) { es.labels_valid = false; return s; }
+    }
+    if (out) *out = retain(fresh.m);  // the caller's reference (the guard drops the builder's)
     return DUST_OK;
   });
 }

@@ -249,6 +249,77 @@ typedef struct DustHipEditShape {   /* 48 bytes */
 } DustHipEditShape;
 DustStatus dust_hip_model_edit_shapes(DustHipModel*, const DustHipEditShape* shapes, uint32_t n,
                                       uint32_t* changed /* n entries, may be NULL */);
+/* Model islands: what a destructive edit leaves behind -- which solid voxels still hang together, which pieces were cut loose, and the
+ * loose pieces as models of their own (debris that falls, a tower whose base was blown out).
+ *
+ * An island is a maximal set of solid voxels connected under the query's connectivity: DUST_HIP_ISLANDS_FACES joins voxels that share
+ * a face (6 neighbours), DUST_HIP_ISLANDS_CORNERS voxels that share a face, an edge or a corner (26 neighbours). Coordinates are the
+ * model's tree coordinates (what set_voxels takes). An island's name is its key: x << 16 | y << 8 | z of its voxel with the smallest
+ * such value. DUST_HIP_NO_ISLAND (no voxel has that key) stands for "empty".
+ *
+ * dust_hip_model_find_islands labels the model and describes the islands. *n_islands is the total number of islands, whatever the
+ * capacity; the first min(total, capacity) records are written in ascending key order and the slots past them are left untouched;
+ * capacity == 0 (islands may then be NULL) only counts. Per record: key; voxels, the number of voxels; lo / hi, the inclusive bounds
+ * of its voxels; flags, DUST_HIP_ISLAND_ANCHORED when at least one of its voxels lies in the query's anchor box and 0 otherwise;
+ * reserved, 0; sum, the sums of x, of y and of z over its voxels (centre of mass = sum / voxels + 0.5). The anchor box is inclusive,
+ * in voxels, and clipped to the tree; anchor_lo > anchor_hi on any axis anchors nothing. An empty model has 0 islands. Everything is
+ * integer arithmetic: two runs give the same bytes.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything changes: a null model, query or n_islands; a struct_size below
+ * sizeof(DustHipIslandQuery); a connectivity other than the two above; null islands with capacity > 0. DUST_ERR_UNSUPPORTED exactly
+ * where set_voxels returns it (4096^3 trees, models that hold material byte 255) -- from all three calls, before they look at
+ * coordinates, keys or the model's state.
+ * Synchronous, like edit_shapes. A model that is not yet editable is moved into its editable form first, exactly as an n == 0 edit
+ * does (scenes that instance it must then be committed again); on an editable model the call changes nothing a scene reads, and
+ * committed scenes stay valid. The labelling stays on the device with the model -- per voxel, the key of its island: 64 MiB on top of
+ * the editable form, allocated by the first call, released with the model -- and replaces the previous one, whatever its connectivity.
+ * It is invalidated by every set_voxels or edit_shapes with n > 0 (whether or not a voxel changed), and by a find_islands that fails.
+ * While it stands, a further find_islands with the same connectivity keeps it and only counts and describes the islands again (other
+ * anchor box, other capacity): counting with capacity == 0 and then asking for every record labels once.
+ *
+ * dust_hip_model_island_of answers, per coordinate triple, the key of the voxel's island under the last labelling; an empty voxel
+ * answers DUST_HIP_NO_ISLAND (a picking ray's hit.xyz names the island that was hit). Refused with DUST_ERR_INVALID_ARGUMENT: a null
+ * model; null arrays with n > 0; a coordinate >= 256 (nothing is written then). DUST_ERR_NOT_READY when the model was never labelled
+ * or its labelling was invalidated, also with n == 0.
+ *
+ * dust_hip_model_detach_islands moves the union of the named islands out of the model. keys are keys of the CURRENT labelling;
+ * duplicates are allowed. Checked in this order, before anything changes: DUST_ERR_INVALID_ARGUMENT for a null model, null keys with
+ * n > 0, flags other than DUST_HIP_DETACH_KEEP_SOURCE, or DUST_HIP_DETACH_KEEP_SOURCE with out == NULL; n == 0 is a no-op in every
+ * state (*out, if given, is set to NULL); DUST_ERR_NOT_READY without a valid labelling; DUST_ERR_INVALID_ARGUMENT when some key does
+ * not name an island (the key of an empty voxel, of a voxel that is not its island's smallest, of an island detached earlier, or a
+ * value >= 1 << 24). On any refusal or failure *out is left as it was. The new model is built before the source is carved, so a
+ * failure up to there leaves the source as it was too; a device failure while the carved source is rebuilt leaves the source as a
+ * failed edit does (not to be used further) and invalidates its labelling, and the new model is not delivered.
+ * out != NULL: *out is a new model on the same context holding exactly the named islands' voxels, at the same tree coordinates, with
+ * the source's palette and their materials -- an instance added with the source's transform shows the pieces where they were. Its
+ * arrays are byte for byte what dust_hip_model_create builds from those voxels. It is born in editable form, at the editable form's
+ * memory cost (~44 MB, as a model after its first edit), unlabelled, and is the caller's to destroy.
+ * Without DUST_HIP_DETACH_KEEP_SOURCE the voxels are carved from the source: it is rebuilt as after an edit, and scenes that instance
+ * it must be committed again. With out == NULL that simply deletes the islands (debris clean-up). With DUST_HIP_DETACH_KEEP_SOURCE
+ * the source is not touched at all: committed scenes stay valid.
+ * Removing whole islands leaves every other island as it was, so the source's labelling STAYS VALID: the removed voxels answer
+ * DUST_HIP_NO_ISLAND, the removed keys are refused from then on, and the remaining keys can be detached by later calls without
+ * labelling again (every floating piece into a model of its own after one find_islands). Synchronous. */
+#define DUST_HIP_ISLANDS_FACES   0u   /* 6-connectivity: voxels sharing a face */
+#define DUST_HIP_ISLANDS_CORNERS 1u   /* 26-connectivity: sharing a face, an edge or a corner */
+#define DUST_HIP_ISLAND_ANCHORED 1u   /* DustHipIsland.flags */
+#define DUST_HIP_NO_ISLAND 0xFFFFFFFFu
+typedef struct DustHipIslandQuery {   /* 32 bytes */
+  uint32_t struct_size, connectivity;
+  uint32_t anchor_lo[3], anchor_hi[3]; /* inclusive voxel box in tree coordinates, clipped to the tree; lo > hi on any axis: nothing is anchored */
+} DustHipIslandQuery;
+typedef struct DustHipIsland {        /* 40 bytes */
+  uint32_t key;                       /* x << 16 | y << 8 | z of the island's voxel with the smallest such value: its name */
+  uint32_t voxels;
+  uint8_t lo[3], flags;               /* inclusive bounds; DUST_HIP_ISLAND_ANCHORED: some voxel lies in the anchor box */
+  uint8_t hi[3], reserved;            /* 0 */
+  uint64_t sum[3];                    /* sum of x, of y, of z over its voxels: centre of mass = sum / voxels + 0.5 */
+} DustHipIsland;
+DustStatus dust_hip_model_find_islands(DustHipModel*, const DustHipIslandQuery*, uint32_t* n_islands,
+                                       DustHipIsland* islands, uint32_t capacity);
+DustStatus dust_hip_model_island_of(DustHipModel*, const uint32_t* xyz, uint32_t* keys, uint32_t n);
+#define DUST_HIP_DETACH_KEEP_SOURCE 1u /* copy the islands into *out and leave the source as it is */
+DustStatus dust_hip_model_detach_islands(DustHipModel*, const uint32_t* keys, uint32_t n, uint32_t flags,
+                                         DustHipModel** out /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

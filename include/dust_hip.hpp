@@ -149,6 +149,33 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model islands (dust_hip_model_find_islands / island_of / detach_islands): every connected set of solid voxels in ascending key
+  // order; the key of the island a voxel belongs to (DUST_HIP_NO_ISLAND where it is empty); and the named islands moved into a
+  // geometry of their own, at the same tree coordinates -- or only removed with want_geometry = false (nullptr comes back, as it
+  // does for no keys). Unless DUST_HIP_DETACH_KEEP_SOURCE is given, scenes that instance this geometry must commit() again.
+  std::vector<DustHipIsland> find_islands(DustHipIslandQuery query) {
+    query.struct_size = sizeof(query);
+    uint32_t n = 0;
+    check(dust_hip_model_find_islands(h_, &query, &n, nullptr, 0));  // labels and counts
+    std::vector<DustHipIsland> islands(n);                          // (the second call keeps that labelling: it only describes)
+    if (n) check(dust_hip_model_find_islands(h_, &query, &n, islands.data(), uint32_t(islands.size())));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return islands;
+  }
+  std::vector<uint32_t> island_of(const std::vector<UVec3>& coords) {
+    std::vector<uint32_t> xyz, keys(coords.size());
+    for (const UVec3& c : coords) xyz.insert(xyz.end(), c.begin(), c.end());
+    check(dust_hip_model_island_of(h_, xyz.data(), keys.data(), uint32_t(keys.size())));
+    return keys;
+  }
+  std::unique_ptr<VoxGeometry> detach_islands(const std::vector<uint32_t>& keys, uint32_t flags = 0, bool want_geometry = true) {
+    DustHipModel* piece = nullptr;
+    check(dust_hip_model_detach_islands(h_, keys.data(), uint32_t(keys.size()), flags, want_geometry ? &piece : nullptr));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return piece ? std::unique_ptr<VoxGeometry>(new VoxGeometry(piece)) : nullptr;
+  }
   std::optional<uint8_t> get(UVec3 c) {
     int32_t v = -1;
     check(dust_hip_model_get_voxels(h_, c.data(), &v, 1));
@@ -156,6 +183,10 @@ class VoxGeometry {
   }
   uint32_t num_blocks;
  private:
+  explicit VoxGeometry(DustHipModel* adopted) : num_blocks(0), h_(adopted) {  // (detach_islands: the handle is already ours)
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+  }
   DustHipModel* h_ = nullptr;
 };
 
