@@ -1,30 +1,18 @@
-// capi.cpp -- the extern "C" boundary (include/dust_hip.h) and the host runtime behind it:
-// device-side VDB hierarchy build, instance records, persistent pipeline buffers, pass scheduling.
-#include <hip/hip_runtime.h>
-
+// capi.cpp -- the extern "C" boundary (include/dust_hip.h) and the host runtime behind it: the host-side wrappers, the context,
+// persistent pipeline buffers, pass scheduling. Models live in capi_model.cpp, scenes and scene queries in capi_scene.cpp.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
-#include <memory>
-#include <new>
-#include <string>
-#include <vector>
 
 #include "capi_internal.hpp"
-#include "dust_dev.h"
 #include "vdb.hpp"
 #include "png.hpp"
-#include "vox.hpp"
 #include "sky.hpp"
-#include "edit.hpp"
-#include "island.hpp"
 #include "denoise.hpp"
 #include "query.hpp"
-#include <unordered_set>
 
 namespace dust {
 hipError_t launch_primary(const FrameArgs& a, uint32_t grid, uint32_t block, bool count, hipStream_t);
@@ -89,88 +77,7 @@ void sun_constants(const float* s, float* dir, float* term) {
 }
 }  // namespace
 
-namespace {
-
-thread_local std::string g_last_error;
-
-DustStatus fail(DustStatus s, const std::string& msg) {
-  g_last_error = msg;
-  return s;
-}
-DustStatus hip_fail(hipError_t e, const char* what) {
-  return fail(DUST_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIP_TRY(expr)                                   \
-  do {                                                  \
-    hipError_t e_ = (expr);                             \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr);   \
-  } while (0)
-
-// struct_size is the caller's sizeof of a versioned struct: at least the layout this build knows (a newer caller may pass
-// more; the known prefix is what is read)
-template <class T>
-bool struct_ok(const T* s) { return s->struct_size >= sizeof(T); }
-#define STRUCT_TRY(ptr, name) \
-  do { if (!struct_ok(ptr)) return fail(DUST_ERR_INVALID_ARGUMENT, name ".struct_size is smaller than this library's " name); } while (0)
-
-template <class F>
-DustStatus guarded(F&& f) {  // nothing may unwind across the C boundary
-  try {
-    return f();
-  } catch (const dust::vox::ParseError& e) {
-    return fail(e.unsupported ? DUST_ERR_UNSUPPORTED : DUST_ERR_PARSE, e.what);
-  } catch (const std::bad_alloc&) {
-    return fail(DUST_ERR_OUT_OF_MEMORY, "host allocation failed");
-  } catch (const std::exception& e) {
-    return fail(DUST_ERR_INVALID_ARGUMENT, e.what());
-  } catch (...) {
-    return fail(DUST_ERR_INVALID_ARGUMENT, "unknown error");
-  }
-}
-
-struct DeviceBuffer {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DeviceBuffer() = default;
-  DeviceBuffer(const DeviceBuffer&) = delete;
-  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
-  ~DeviceBuffer() { release(); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-  hipError_t alloc(size_t n) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    bytes = n;
-    return hipMalloc(&p, n ? n : 16);
-  }
-  // Host -> device on the CONTEXT's stream, then wait: a blocking hipMemcpy is a null-stream operation, which a
-  // hipStreamNonBlocking stream is not ordered against (and from pageable memory it may return before the DMA has landed).
-  hipError_t upload(const void* src, size_t n, hipStream_t st) {
-    hipError_t e = alloc(n);
-    if (e != hipSuccess || n == 0) return e;
-    e = hipMemcpyAsync(p, src, n, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(st);
-  }
-};
-
-// Copies between host and device go through the context's stream and wait for it: the blocking hipMemcpy / hipMemset are
-// null-stream operations, and the context's stream is created hipStreamNonBlocking, i.e. NOT ordered against those.
-hipError_t copy_wait(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  const hipError_t e = hipMemcpyAsync(dst, src, n, kind, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-// Lifetimes. Every handle of the device side is reference-counted inside the library: a model, scene or pipeline keeps its
-// context alive, a scene keeps the models it instances alive. dust_hip_*_destroy gives up the CALLER's reference; the object
-// (and its device memory) goes when the last user does. So handles may be destroyed in any order -- a garbage collector
-// finalising a context before its models (Python's cycle collector does exactly that, in creation order) is fine.
-struct RefCounted {
-  std::atomic<uint32_t> refs{1};
-};
-template <class T> T* retain(T* o) { if (o) o->refs.fetch_add(1, std::memory_order_relaxed); return o; }
-// (release() per type below: what dies with the last reference differs)
-
-}  // namespace
+static thread_local std::string g_last_error;  // dust_hip_last_error() of the calling thread (dust_internal::set_error writes it)
 
 struct DustVdbTree { dust::vdb::Tree tree; DustVdbTree(const uint32_t* f, int n) : tree(f, n) {} };
 struct DustVdbAccessor { dust::vdb::Tree::Accessor acc; explicit DustVdbAccessor(const dust::vdb::Tree& t) : acc(t) {} };
@@ -178,46 +85,7 @@ struct DustVdbPool { dust::vdb::Pool pool; DustVdbPool(size_t b, unsigned c) : p
 struct DustVoxScene { dust::vox::Scene scene; };
 struct DustSkyDataset { dust::sky::Dataset data; };
 
-struct DustHipContext : RefCounted {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  uint32_t lds_root_bytes = 64 * 1024;
-  bool timing = false;
-  uint32_t timing_stride = 1;  // DUST_HIP_CONTEXT_TIMING_SPARSE: event pairs around the launches of every 4th frame only
-  int num_cus = 256;
-  size_t max_lds = 64 * 1024;
-  DeviceBuffer srgb_lut;  // edit.hip: avg_albedo's linear->sRGB curve per (voxel count, colour sum), built on first use
-  uint64_t sync_epoch = 1;  // bumped whenever the library has waited for the stream: what was enqueued before is done
-  // The surfel pass of a frame runs on a second stream of the context (run_surfel_pass): it is launched in its own frame, behind
-  // that frame's final gather, and only has to be complete before the NEXT final gather reads the hash -- so the next frame's
-  // primary / AO kernel runs beside it, each side on its share of the workgroup slots. Nothing is kept back:
-  // what conflicts with it on the main stream (the next gather, a scene commit, anything that touches the GI state) waits
-  // for `ev_side_done` first (join_side); every wait for the context covers both streams (sync_stream).
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_side_done = nullptr;
-  bool side_busy = false;
-  std::vector<hipStream_t> extra_streams;  // communicators' gather streams (comm.hip): they read pipelines' planes, so every wait for the context covers them
-  hipStream_t copy = nullptr;  // scene commits upload on a stream of their own (the copy engine), beside the frame in flight -- never between two frames
-  // Which frames of the stream have STARTED (FrameArgs::started_word): a word of pinned host memory that the first traversal launch of
-  // every frame writes its sequence number into. `frame_seq` counts those launches as they are enqueued. 0 / null: not available.
-  volatile uint32_t* started = nullptr;
-  uint32_t frame_seq = 0;
-  // scene ray queries (dust_hip_scene_trace_rays): the synchronous call's device staging, grown on demand, and the launches' two ray
-  // counters (a launch takes rays from one and zeroes the other for the next: query_parity says which is whose)
-  DeviceBuffer query_rays, query_hits, query_counters;
-  uint32_t query_parity = 0;
-  // scene box queries (dust_hip_scene_overlap_boxes): the synchronous call's device staging for boxes, counts and records, grown on demand
-  DeviceBuffer overlap_boxes, overlap_counts, overlap_records;
-  // scene box sweeps (dust_hip_scene_sweep_boxes): the synchronous call's device staging for sweeps and hits, grown on demand
-  DeviceBuffer sweep_queries, sweep_hits;
-  // model islands (island.hip): what a labelling or a detach needs besides the model's own label array -- a bit and a counter per 64
-  // keys, block sums, the records being accumulated, and the call's staging for keys and coordinates, grown on demand
-  DeviceBuffer island_mask, island_count, island_tmp, island_acc, island_records, island_in, island_out;
-};
-// wait for everything enqueued on the context's stream (and remember that we did: scene commits recycle their pinned staging
-// slots by this, without an event per commit)
-static hipError_t sync_stream(DustHipContext* c) {
+hipError_t sync_stream(DustHipContext* c) {
   hipError_t e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess && c->side) { e = hipStreamSynchronize(c->side); c->side_busy = false; }
   for (hipStream_t x : c->extra_streams)
@@ -225,14 +93,12 @@ static hipError_t sync_stream(DustHipContext* c) {
   if (e == hipSuccess) ++c->sync_epoch;
   return e;
 }
-// main stream: wait (on the device) for the side stream's pass, if one may still be running
-static hipError_t join_side(DustHipContext* c) {
+hipError_t join_side(DustHipContext* c) {
   if (!c->side_busy) return hipSuccess;
   c->side_busy = false;
   return hipStreamWaitEvent(c->stream, c->ev_side_done, 0);
 }
-// side stream: everything enqueued on the main stream so far comes first
-static hipError_t fork_side(DustHipContext* c) {
+hipError_t fork_side(DustHipContext* c) {
   hipError_t e = hipSuccess;
   if (!c->side) {
     e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
@@ -243,7 +109,17 @@ static hipError_t fork_side(DustHipContext* c) {
   e = hipEventRecord(c->ev_fork, c->stream);
   return e != hipSuccess ? e : hipStreamWaitEvent(c->side, c->ev_fork, 0);
 }
-static void release(DustHipContext* c) {
+DustStatus grow(DustHipContext* ctx, DeviceBuffer& b, size_t bytes) {
+  if (b.p && b.bytes >= bytes) return DUST_OK;
+  HIP_TRY(sync_stream(ctx));
+  const hipError_t e = b.alloc(std::max(bytes + bytes / 2, size_t(4096)));
+  if (e == hipSuccess) return DUST_OK;
+  b.release();
+  if (e != hipErrorOutOfMemory) return hip_fail(e, "growing a device buffer");
+  (void)hipGetLastError();  // (the error is sticky until read)
+  return fail(DUST_ERR_OUT_OF_MEMORY, "device memory for a buffer that grows on demand");
+}
+void release(DustHipContext* c) {
   if (!c || c->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -251,149 +127,9 @@ static void release(DustHipContext* c) {
   if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_side_done) (void)hipEventDestroy(c->ev_side_done);
-  c->srgb_lut.release();
-  c->query_rays.release(); c->query_hits.release(); c->query_counters.release();
-  c->overlap_boxes.release(); c->overlap_counts.release(); c->overlap_records.release();
-  c->sweep_queries.release(); c->sweep_hits.release();
-  c->island_mask.release(); c->island_count.release(); c->island_tmp.release(); c->island_acc.release(); c->island_records.release();
-  c->island_in.release(); c->island_out.release();
   if (c->started) (void)hipHostFree(const_cast<uint32_t*>(c->started));
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
-
-// device-side voxel edits (edit.hip): the dense voxel grid and the scratch tables of the rebuild, created on a model's first edit
-struct EditState {
-  DeviceBuffer grid, brick_mask, flag_leaf, count_major, scan_tmp, header, xyz, values;
-  uint32_t batch_capacity = 0;
-  // shape edits (dust_hip_model_edit_shapes): the call's shape records and counters, and one chunk's cell lists, grown on demand
-  DeviceBuffer shapes, changed, shape_cells, shape_starts, shape_ids;
-  // model islands (dust_hip_model_find_islands): per voxel, indexed by x << 16 | y << 8 | z, the key of its island (64 MiB, allocated by
-  // the first labelling); valid until the next set_voxels / edit_shapes that may change a voxel
-  DeviceBuffer labels;
-  bool labels_valid = false;
-  uint32_t labels_corners = 0;  // the connectivity of that labelling
-};
-
-struct DustHipModel : RefCounted {
-  DustHipContext* ctx = nullptr;  // retained
-  DeviceBuffer root, l2, l2_cells, mid, dense_mask, blocks, materials, palette;
-  std::vector<uint8_t> host_root;  // 640 B: mask + prefix, what the kernels stage in LDS
-  dust::DevModel dev{};
-  uint32_t id = 0;
-  uint64_t n_materials = 0;
-  uint32_t generation = 0;  // bumped by every edit: scenes record it at commit and refuse to render a stale copy
-  bool has_material_255 = false;  // the edit grid stores palette index + 1 in a byte: such a model cannot become editable
-  std::unique_ptr<EditState> edit;
-};
-static void release(const DustHipModel* cm) {
-  DustHipModel* m = const_cast<DustHipModel*>(cm);
-  if (!m || m->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
-  DustHipContext* c = m->ctx;
-  (void)hipSetDevice(c->device);
-  (void)sync_stream(c);  // launches that read the arrays are done before they go
-  delete m;
-  release(c);
-}
-
-struct HostInstance {
-  const DustHipModel* model;  // retained
-  float o2w[12];
-  float prev[16];
-};
-
-// Where a committed scene lives on the device: ONE allocation, the arrays at offsets inside it -- what depends on the models
-// first, what depends on the instance transforms behind it. A commit fills a pinned host image of the same layout and sends
-// it (all of it after a structural change, the transform-dependent tail otherwise) with one asynchronous copy on the context's
-// stream (tlas.rs:37-65 rebuilds the TLAS inside the frame's command stream the same way): no allocation, no wait, and the
-// kernels' pointers stay what they were until instances are added.
-struct SceneLayout {
-  size_t models = 0, root_table = 0, instances = 0, boxes = 0, visits = 0, enters = 0, gboxes = 0, sboxes = 0, grid_cells = 0, grid_items = 0, total = 0;
-  size_t cap_cells = 0, cap_items = 0;  // entries the two grid sections hold (a commit that needs more lays the image out again)
-  static SceneLayout make(size_t n_inst, size_t n_models, size_t n_roots, size_t n_cells, size_t n_items) {
-    SceneLayout l;
-    auto place = [&l](size_t bytes) { const size_t at = l.total; l.total = (l.total + bytes + 255) & ~size_t(255); return at; };
-    l.models = place(n_models * sizeof(dust::DevModel));
-    l.root_table = place(n_roots * dust::kN16LdsBytes);
-    l.instances = place(n_inst * sizeof(dust::DevInstance));
-    l.boxes = place((n_inst + 1) * sizeof(dust::DevBox));
-    l.visits = place((n_inst + 1) * sizeof(dust::DevVisit));
-    l.enters = place((n_inst + 1) * sizeof(dust::DevEnter));
-    l.gboxes = place(((n_inst + 63) / 64 + 1) * sizeof(dust::DevBox));  // the packet cull's hierarchy (scenes beyond kFlatCullMax instances)
-    l.sboxes = place((n_inst + 1) * sizeof(dust::DevBox));
-    // the top-level grid last, with room to spare: its size follows the instances' positions, not only their number
-    l.cap_cells = n_cells + n_cells / 2 + 64;
-    l.cap_items = n_items + n_items / 2 + 256;
-    l.grid_cells = place((l.cap_cells + 4) * sizeof(uint32_t));
-    l.grid_items = place((l.cap_items + 8) * sizeof(uint16_t));
-    return l;
-  }
-};
-
-struct DustHipScene : RefCounted {
-  DustHipContext* ctx = nullptr;  // retained
-  std::vector<HostInstance> instances;
-  std::vector<uint8_t> dirty;                // per instance: transform changed since the last commit
-  std::vector<const DustHipModel*> models;   // distinct models, index == DevModel slot (kept alive through `instances`)
-  std::vector<uint32_t> model_generation;    // their edit generations when the scene was committed
-  std::vector<uint32_t> instance_slot;       // per instance: its model's slot
-  bool structure_dirty = true;               // instances were added (or a model edited): slots, roots and capacity are re-derived
-  // The device image is a RING of kImages copies, each with a pinned host twin. A commit writes the whole image into the next
-  // slot -- on the context's copy stream, waited for by the host, so nothing is enqueued between two frames on the launch stream
-  // (one stream-ordered copy per frame used to cost a moving scene ~25 us of a 230 us frame: wait for the frame, copy, start the
-  // next) -- and frames enqueued from then on read that slot. A slot is rewritten kImages commits later: the frames that read it
-  // are done if the library has waited for the streams since they were enqueued (a frame loop does, to read its result or pace
-  // itself); otherwise the host is kImages commits ahead of the GPU and waits here (the reference's host runs <= 3 frames ahead).
-#ifndef DUST_SCENE_IMAGES
-#define DUST_SCENE_IMAGES 16   // (8 until dust_hip_render_frames took moves: a launch of eight frames, each with an image of its own, left the host no image to
-#endif                        //  prepare the next launch in while that one ran -- 0.2457 ms per frame of a moving view against 0.2257 with 16; an image is ~150 KB for the castle)
-  static constexpr int kImages = DUST_SCENE_IMAGES;
-  struct Slot {
-    DeviceBuffer dev;
-    void* host = nullptr;
-    mutable uint64_t epoch = 0;  // the context's sync_epoch when a frame reading the slot was last enqueued
-    mutable uint32_t last_seq = 0;  // ... and that frame's start sequence number (DustHipContext::frame_seq), 0 = it has none (no traversal launch, or no word)
-  } slots[kImages];
-  int current = -1;           // the slot frames read
-  uint32_t next_slot = 0;
-  SceneLayout layout;
-  size_t image_capacity = 0;  // bytes per slot
-  std::vector<uint8_t> master;   // host master copy of the image (dirty instances are re-derived in place)
-  float world_min[3] = {0, 0, 0}, world_max[3] = {0, 0, 0};  // union of the instances' world boxes
-  // the top-level grid over the instance boxes (dust_dev.h DevGrid; rebuilt by every commit): its header, and the two arrays
-  // that are copied into the image
-  dust::DevGrid grid{};
-  bool grid_valid = true;            // false: some cell would list more instances than a cell word counts (the ray streams then stay off)
-  std::vector<uint32_t> grid_cells;
-  std::vector<uint16_t> grid_items;
-  std::vector<uint32_t> slot_order;  // large scenes: the instances along a space-filling curve (made by a structural commit; a moved instance keeps its slot)
-  uint32_t n_groups = 0;             // ... and how many groups of 64 consecutive slots (0: the cull tests every box)
-  std::vector<float> world_boxes;  // per instance {lo[3], hi[3]}: what derive_instance writes into the image, kept for the grid
-  uint32_t n_lds_models = 0;
-  uint64_t revision = 0;  // bumped by every commit (what the cost-ordered hand-out keys its view on)
-  bool committed = false;
-  const uint8_t* dev(size_t off) const { return static_cast<const uint8_t*>(slots[current].dev.p) + off; }
-  void touch() const { slots[current].epoch = ctx->sync_epoch; slots[current].last_seq = 0; }  // a frame reading the current slot is being enqueued
-  void free_images() {  // (the caller has waited for the streams)
-    for (Slot& sl : slots) {
-      if (sl.host) { (void)hipHostFree(sl.host); sl.host = nullptr; }
-      sl.dev.release();
-      sl.epoch = 0; sl.last_seq = 0;
-    }
-    current = -1;
-    image_capacity = 0;
-  }
-};
-static void release(const DustHipScene* cs) {
-  DustHipScene* s = const_cast<DustHipScene*>(cs);
-  if (!s || s->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
-  DustHipContext* c = s->ctx;
-  (void)hipSetDevice(c->device);
-  (void)sync_stream(c);  // both streams: the surfel pass reads the scene image on the second one
-  s->free_images();
-  for (HostInstance& hi : s->instances) release(hi.model);
-  delete s;
-  release(c);
+  delete c;  // (and with it the context's device buffers)
 }
 
 // What decides which kernels a pipeline's frames run. Two kinds, kept apart:
@@ -401,7 +137,7 @@ static void release(const DustHipScene* cs) {
 //    kernels, which form the GI passes take, the surfel pass's second stream and its share, how several frames in flight split the slots;
 //  * DIAGNOSTIC switches (ablations, A/B runs, the stress drivers' random draws) come from the environment, read ONCE when a pipeline
 //    is created through the one lookup below. None of them is needed for any production frame; DESIGN.md section 9 lists them.
-static const char* diag_env(const char* name) {   // "NO_FUSE" -> $DUST_HIP_NO_FUSE (the library's only environment lookup besides DUST_HIP_DEBUG-class reads here)
+const char* diag_env(const char* name) {   // "NO_FUSE" -> $DUST_HIP_NO_FUSE (the library's only environment lookup besides DUST_HIP_DEBUG-class reads here)
   char full[64];
   std::snprintf(full, sizeof full, "DUST_HIP_%s", name);
   return std::getenv(full);
@@ -550,127 +286,6 @@ struct DustHipPipeline {
 };
 
 static const size_t kPlaneBytesPerPixel[DUST_PLANE_COUNT] = {8, 8, 4, 4, 4, 8, 4, 16, 8};
-// ------------------------------------------------------------------ device hierarchy build
-namespace {
-
-struct N16Builder {
-  std::vector<uint8_t> bytes;  // kN16Bytes per node
-  uint8_t* node(size_t i) { return bytes.data() + i * dust::kN16Bytes; }
-  size_t add() {
-    bytes.resize(bytes.size() + dust::kN16Bytes, 0);
-    return bytes.size() / dust::kN16Bytes - 1;
-  }
-  void finish(size_t i, uint32_t child_base) {  // rank prefix per 64-bit word + base of the first child
-    uint64_t* mask = reinterpret_cast<uint64_t*>(node(i));
-    uint16_t* pre = reinterpret_cast<uint16_t*>(node(i) + 512);
-    uint32_t run = 0;
-    for (int w = 0; w < 64; ++w) {
-      pre[w] = static_cast<uint16_t>(run);
-      run += static_cast<uint32_t>(__builtin_popcountll(mask[w]));
-    }
-    std::memcpy(node(i) + 640, &child_base, 4);
-  }
-};
-
-// Builds root / l2 / mid arrays from blocks given in Tree::iter_leaf order (depth-first, ascending bits).
-DustStatus build_hierarchy(const DustHipBlock* blocks, uint32_t n, uint32_t extent_log2, N16Builder& root,
-                           N16Builder& l2, std::vector<dust::DevN4>& mid, std::vector<uint64_t>& dense_mask,
-                           float bmin[3], float bmax[3]) {
-  const bool deep = extent_log2 == 12;
-  const uint32_t extent = 1u << extent_log2;
-  root.add();
-  uint64_t prev_key = 0;
-  int64_t cur_l2 = -1, cur_mid = -1;
-  uint32_t cur_l2_cell = 0xFFFFFFFFu, cur_mid_cell = 0xFFFFFFFFu;
-  for (int a = 0; a < 3; ++a) { bmin[a] = 1e30f; bmax[a] = -1e30f; }
-  auto idx16 = [](uint32_t x, uint32_t y, uint32_t z) { return (x << 8) | (y << 4) | z; };
-  for (uint32_t i = 0; i < n; ++i) {
-    const DustHipBlock& b = blocks[i];
-    if ((b.x & 3) || (b.y & 3) || (b.z & 3) || b.x >= extent || b.y >= extent || b.z >= extent)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "block position is not a 4-aligned coordinate inside the tree extent");
-    if (b.mask == 0) return fail(DUST_ERR_INVALID_ARGUMENT, "block with empty occupancy mask");
-    // depth-first order key: per level, x slowest (node/internal.rs:78-81)
-    uint64_t key = 0;
-    const uint32_t shifts_deep[3] = {8, 4, 2}, bits_deep[3] = {4, 4, 2};
-    const uint32_t shifts_std[2] = {4, 2}, bits_std[2] = {4, 2};
-    const uint32_t* sh = deep ? shifts_deep : shifts_std;
-    const uint32_t* bt = deep ? bits_deep : bits_std;
-    const int nl = deep ? 3 : 2;
-    for (int l = 0; l < nl; ++l) {
-      const uint32_t m = (1u << bt[l]) - 1;
-      key = (key << (3 * bt[l])) | (uint64_t(((b.x >> sh[l]) & m)) << (2 * bt[l])) | (uint64_t((b.y >> sh[l]) & m) << bt[l]) |
-            uint64_t((b.z >> sh[l]) & m);
-    }
-    if (i > 0 && key <= prev_key)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "blocks are not in Tree::iter_leaf order (depth-first, ascending child bits)");
-    prev_key = key;
-    const float p[3] = {float(b.x), float(b.y), float(b.z)};
-    for (int a = 0; a < 3; ++a) {
-      bmin[a] = std::min(bmin[a], p[a]);
-      bmax[a] = std::max(bmax[a], p[a] + 4.0f);
-    }
-    // descend, creating nodes on first touch (children of a node are contiguous because of the order)
-    size_t n16 = 0;           // node holding the 16-cell bit
-    N16Builder* holder = &root;
-    if (deep) {
-      const uint32_t cell = idx16(b.x >> 8, b.y >> 8, b.z >> 8);
-      if (cell != cur_l2_cell) {
-        cur_l2 = int64_t(l2.add());
-        cur_l2_cell = cell;
-        dust::vdb::bit_set(reinterpret_cast<uint64_t*>(root.node(0)), cell, true);
-        cur_mid_cell = 0xFFFFFFFFu;
-      }
-      holder = &l2;
-      n16 = size_t(cur_l2);
-    }
-    const uint32_t cell16 = idx16((b.x >> 4) & 15, (b.y >> 4) & 15, (b.z >> 4) & 15);
-    const uint32_t mid_cell_key = deep ? uint32_t(cur_l2) * 4096u + cell16 : cell16;
-    if (mid_cell_key != cur_mid_cell) {
-      dust::vdb::bit_set(reinterpret_cast<uint64_t*>(holder->node(n16)), cell16, true);
-      dust::DevN4 nd{0, 0, i, 0};
-      mid.push_back(nd);
-      cur_mid = int64_t(mid.size()) - 1;
-      cur_mid_cell = mid_cell_key;
-    }
-    const uint32_t bit = (((b.x >> 2) & 3) << 4) | (((b.y >> 2) & 3) << 2) | ((b.z >> 2) & 3);
-    if (bit < 32) mid[size_t(cur_mid)].mask_lo |= 1u << bit;
-    else mid[size_t(cur_mid)].mask_hi |= 1u << (bit - 32);
-    if (dense_mask.size() < mid.size() * 64) dense_mask.resize(mid.size() * 64, 0);
-    dense_mask[size_t(cur_mid) * 64 + bit] = b.mask;
-  }
-  // prefixes and child bases: children were appended in order, so base = running count
-  if (deep) {
-    root.finish(0, 0);
-    uint32_t run = 0;
-    for (size_t i = 0; i < l2.bytes.size() / dust::kN16Bytes; ++i) {
-      l2.finish(i, run);
-      const uint64_t* mask = reinterpret_cast<const uint64_t*>(l2.node(i));
-      for (int w = 0; w < 64; ++w) run += uint32_t(__builtin_popcountll(mask[w]));
-    }
-  } else {
-    root.finish(0, 0);
-  }
-  if (n == 0) { for (int a = 0; a < 3; ++a) { bmin[a] = 0.0f; bmax[a] = 0.0f; } }
-  return DUST_OK;
-}
-
-// inverse of a 3x4 affine transform, evaluated in double and rounded once
-void invert_affine(const float m[12], float out[12]) {
-  const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], i = m[10];
-  const double A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
-  const double det = a * A + b * B + c * C;
-  const double id = 1.0 / det;
-  const double r[9] = {A * id, -(b * i - c * h) * id, (b * f - c * e) * id,
-                       B * id, (a * i - c * g) * id, -(a * f - c * d) * id,
-                       C * id, -(a * h - b * g) * id, (a * e - b * d) * id};
-  const double tx = m[3], ty = m[7], tz = m[11];
-  for (int k = 0; k < 3; ++k) {
-    out[k * 4 + 0] = float(r[k * 3 + 0]); out[k * 4 + 1] = float(r[k * 3 + 1]); out[k * 4 + 2] = float(r[k * 3 + 2]);
-    out[k * 4 + 3] = float(-(r[k * 3 + 0] * tx + r[k * 3 + 1] * ty + r[k * 3 + 2] * tz));
-  }
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -930,972 +545,6 @@ DustStatus dust_hip_sync(DustHipContext* c) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_stream(c));
   return DUST_OK;
-}
-
-DustStatus dust_hip_model_create(DustHipContext* ctx, const DustHipBlock* blocks, uint32_t n_blocks,
-                                 const uint8_t* materials, uint64_t n_materials, const uint8_t* palette,
-                                 uint32_t tree_extent_log2, DustHipModel** out) {
-  if (!ctx || !out || (!blocks && n_blocks) || (!materials && n_materials) || !palette)
-    return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  if (tree_extent_log2 != 8 && tree_extent_log2 != 12)
-    return fail(DUST_ERR_INVALID_ARGUMENT, "tree_extent_log2 must be 8 (hierarchy 4,2,2) or 12 (hierarchy 4,4,2,2)");
-  return guarded([&]() -> DustStatus {
-    N16Builder root, l2;
-    std::vector<dust::DevN4> mid;
-    std::vector<uint64_t> dense_mask;
-    float bmin[3], bmax[3];
-    DustStatus s = build_hierarchy(blocks, n_blocks, tree_extent_log2, root, l2, mid, dense_mask, bmin, bmax);
-    if (s != DUST_OK) return s;
-    for (uint32_t i = 0; i < n_blocks; ++i) {
-      const uint64_t need = uint64_t(blocks[i].material_ptr) + uint64_t(__builtin_popcountll(blocks[i].mask));
-      if (need > n_materials) return fail(DUST_ERR_INVALID_ARGUMENT, "block material_ptr runs past the material buffer");
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    // (owned through the reference count from here on: an early return releases it, and with it the context reference)
-    struct Drop { DustHipModel* m; ~Drop() { release(m); } } owner{new DustHipModel};
-    DustHipModel* m = owner.m;
-    m->ctx = retain(ctx);
-    const hipStream_t up = ctx->stream;
-    HIP_TRY(m->root.upload(root.bytes.data(), root.bytes.size(), up));
-    m->host_root.assign(root.bytes.begin(), root.bytes.begin() + dust::kN16LdsBytes);
-    HIP_TRY(m->l2.upload(l2.bytes.data(), l2.bytes.size(), up));
-    if (tree_extent_log2 == 12) {  // the per-cell table the DEEP kernel variants look 16-cells up in: {mid index, child mask} per cell
-      const size_t n_l2 = l2.bytes.size() / dust::kN16Bytes;
-      std::vector<dust::DevL2Cell> cells(n_l2 * 4096, dust::DevL2Cell{0xFFFFFFFFu, 0u, 0ull});
-      for (size_t i = 0; i < n_l2; ++i) {
-        const uint64_t* mask = reinterpret_cast<const uint64_t*>(l2.node(i));
-        uint32_t base;
-        std::memcpy(&base, l2.node(i) + 640, 4);
-        uint32_t run = base;  // children of a node are contiguous, in ascending bit order
-        for (uint32_t w = 0; w < 64; ++w)
-          for (uint64_t bits = mask[w]; bits; bits &= bits - 1) {
-            dust::DevL2Cell& c = cells[i * 4096 + w * 64 + uint32_t(__builtin_ctzll(bits))];
-            c.mid = run;
-            c.child_mask = (uint64_t(mid[run].mask_hi) << 32) | mid[run].mask_lo;
-            uint32_t lo[3] = {3, 3, 3}, hi[3] = {0, 0, 0};
-            for (uint64_t cm = c.child_mask; cm; cm &= cm - 1) {
-              const uint32_t b = uint32_t(__builtin_ctzll(cm)), xyz[3] = {b >> 4, (b >> 2) & 3u, b & 3u};
-              for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], xyz[k]); hi[k] = std::max(hi[k], xyz[k]); }
-            }
-            c.bounds = lo[0] | (lo[1] << 2) | (lo[2] << 4) | (hi[0] << 6) | (hi[1] << 8) | (hi[2] << 10);
-            ++run;
-          }
-      }
-      HIP_TRY(m->l2_cells.upload(cells.data(), cells.size() * sizeof(dust::DevL2Cell), up));
-    }
-    HIP_TRY(m->mid.upload(mid.data(), mid.size() * sizeof(dust::DevN4), up));
-    HIP_TRY(m->dense_mask.upload(dense_mask.data(), dense_mask.size() * 8, up));
-    HIP_TRY(m->blocks.upload(blocks, size_t(n_blocks) * sizeof(DustHipBlock), up));
-    HIP_TRY(m->materials.upload(materials, size_t(n_materials), up));
-    m->has_material_255 = n_materials && std::memchr(materials, 255, size_t(n_materials)) != nullptr;
-    uint32_t pal[256];
-    std::memset(pal, 0, sizeof(pal));
-    std::memcpy(pal, palette, 255 * 4);  // loader.rs:214-218: entries 0..254
-    HIP_TRY(m->palette.upload(pal, sizeof(pal), up));
-    dust::DevModel& d = m->dev;
-    d.root = static_cast<const uint8_t*>(m->root.p);
-    d.l2 = tree_extent_log2 == 12 ? static_cast<const uint8_t*>(m->l2.p) : nullptr;
-    d.l2_cells = tree_extent_log2 == 12 ? static_cast<const dust::DevL2Cell*>(m->l2_cells.p) : nullptr;
-    d.mid = static_cast<const dust::DevN4*>(m->mid.p);
-    d.dense_mask = static_cast<const uint64_t*>(m->dense_mask.p);
-    d.blocks = static_cast<const DustHipBlock*>(m->blocks.p);
-    d.materials = static_cast<const uint8_t*>(m->materials.p);
-    d.palette = static_cast<const uint32_t*>(m->palette.p);
-    std::memcpy(d.bmin, bmin, sizeof(bmin));
-    std::memcpy(d.bmax, bmax, sizeof(bmax));
-    d.extent = 1u << tree_extent_log2;
-    d.n_levels = tree_extent_log2 == 12 ? 3 : 2;
-    d.n_blocks = n_blocks;
-    d.lds_slot = -1;
-    m->n_materials = n_materials;
-    *out = retain(m);  // the caller's reference (the guard drops the builder's)
-    return DUST_OK;
-  });
-}
-void dust_hip_model_destroy(DustHipModel* m) { release(m); }  // (a scene that instances it keeps it alive)
-
-// ---------------------------------------------------------------- device-side edits (edit.hip)
-namespace {
-float linear2srgb_host(float c) { return c <= 0.0031308f ? 12.92f * c : 1.055f * std::pow(c, 1.0f / 2.4f) - 0.055f; }  // geometry.rs:99-105
-
-DustStatus ensure_srgb_lut(DustHipContext* ctx) {
-  if (ctx->srgb_lut.p) return DUST_OK;
-  std::vector<uint16_t> lut(size_t(64) * dust::kSrgbRow, 0);
-  for (uint32_t n = 1; n <= 64; ++n) {
-    const float denom = float(n) * 255.0f;
-    for (uint32_t sum = 0; sum <= n * 255u; ++sum)
-      lut[size_t(n - 1) * dust::kSrgbRow + sum] = uint16_t(uint32_t(linear2srgb_host(float(sum) / denom) * 1023.0f));
-  }
-  HIP_TRY(ctx->srgb_lut.upload(lut.data(), lut.size() * 2, ctx->stream));
-  return DUST_OK;
-}
-
-dust::EditArgs edit_args(DustHipModel* m, EditState& st) {
-  dust::EditArgs e{};
-  e.grid = static_cast<uint8_t*>(st.grid.p);
-  e.brick_mask = static_cast<uint64_t*>(st.brick_mask.p);
-  e.flag_leaf = static_cast<uint32_t*>(st.flag_leaf.p);
-  e.count_major = static_cast<uint32_t*>(st.count_major.p);
-  e.scan_tmp = static_cast<uint32_t*>(st.scan_tmp.p);
-  e.blocks = static_cast<DustHipBlock*>(m->blocks.p);
-  e.materials = static_cast<uint8_t*>(m->materials.p);
-  e.palette = static_cast<const uint32_t*>(m->palette.p);
-  e.srgb_lut = static_cast<const uint16_t*>(m->ctx->srgb_lut.p);
-  e.root = static_cast<uint8_t*>(m->root.p);
-  e.mid = static_cast<dust::DevN4*>(m->mid.p);
-  e.dense_mask = static_cast<uint64_t*>(m->dense_mask.p);
-  e.header = static_cast<dust::EditHeader*>(st.header.p);
-  return e;
-}
-
-// run the rebuild kernels and bring the model record up to date (sizes, bounds, the root the scene stages in LDS)
-DustStatus rebuild_and_refresh(DustHipModel* m, EditState& es) {
-  hipStream_t st = m->ctx->stream;
-  HIP_TRY(dust::launch_edit_rebuild(edit_args(m, es), st));
-  dust::EditHeader h{};
-  HIP_TRY(hipMemcpyAsync(&h, es.header.p, sizeof(h), hipMemcpyDeviceToHost, st));
-  m->host_root.resize(dust::kN16LdsBytes);
-  HIP_TRY(hipMemcpyAsync(m->host_root.data(), m->root.p, dust::kN16LdsBytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  m->dev.n_blocks = h.n_blocks;
-  m->n_materials = h.n_materials;
-  std::memcpy(m->dev.bmin, h.bmin, sizeof(h.bmin));
-  std::memcpy(m->dev.bmax, h.bmax, sizeof(h.bmax));
-  m->generation += 1;
-  return DUST_OK;
-}
-
-// first edit: move the model into full-capacity buffers and expand its voxels into the dense grid. The model becomes
-// editable (m->edit set) only when every step has succeeded: a failure leaves it exactly as it was.
-DustStatus editable_kind(const DustHipModel* m) {
-  if (m->dev.extent != 256) return fail(DUST_ERR_UNSUPPORTED, "device-side edits cover hierarchy (4,2,2) models (256^3); rebuild larger trees with dust_hip_model_create");
-  if (m->has_material_255) return fail(DUST_ERR_UNSUPPORTED, "the model holds material byte 255 (the edit grid stores palette index + 1 in a byte; dust_hip_model_set_voxels takes 0..254)");
-  return DUST_OK;
-}
-// (`rebuild` false: the caller fills the grid and rebuilds itself -- a model born editable, dust_hip_model_detach_islands)
-DustStatus make_editable(DustHipModel* m, bool rebuild = true) {
-  if (m->edit) return DUST_OK;
-  DustStatus s = editable_kind(m);
-  if (s != DUST_OK) return s;
-  s = ensure_srgb_lut(m->ctx);
-  if (s != DUST_OK) return s;
-  hipStream_t st = m->ctx->stream;
-  std::unique_ptr<EditState> e(new EditState);
-  const size_t L = dust::kLattice;
-  HIP_TRY(e->grid.alloc(L * 64));
-  HIP_TRY(hipMemsetAsync(e->grid.p, 0, L * 64, st));
-  HIP_TRY(e->brick_mask.alloc(L * 8));
-  HIP_TRY(e->flag_leaf.alloc(L * 4));
-  HIP_TRY(e->count_major.alloc(L * 4));
-  HIP_TRY(e->scan_tmp.alloc(512 * 4));
-  HIP_TRY(e->header.alloc(sizeof(dust::EditHeader)));
-  DeviceBuffer blocks, materials, mid, dense_mask;
-  HIP_TRY(blocks.alloc(L * sizeof(DustHipBlock)));
-  HIP_TRY(materials.alloc(L * 64));
-  HIP_TRY(mid.alloc(4096 * sizeof(dust::DevN4)));
-  HIP_TRY(dense_mask.alloc(size_t(4096) * 64 * 8));
-  dust::EditArgs a = edit_args(m, *e);  // (expand only writes the grid)
-  HIP_TRY(dust::launch_edit_expand(a, static_cast<const DustHipBlock*>(m->blocks.p), static_cast<const uint8_t*>(m->materials.p), m->dev.n_blocks, st));
-  HIP_TRY(sync_stream(m->ctx));  // every launch that reads the old arrays is done (both streams of the context)
-  auto swap_all = [&] {
-    std::swap(m->blocks.p, blocks.p); std::swap(m->blocks.bytes, blocks.bytes);
-    std::swap(m->materials.p, materials.p); std::swap(m->materials.bytes, materials.bytes);
-    std::swap(m->mid.p, mid.p); std::swap(m->mid.bytes, mid.bytes);
-    std::swap(m->dense_mask.p, dense_mask.p); std::swap(m->dense_mask.bytes, dense_mask.bytes);
-    m->dev.mid = static_cast<const dust::DevN4*>(m->mid.p);
-    m->dev.dense_mask = static_cast<const uint64_t*>(m->dense_mask.p);
-    m->dev.blocks = static_cast<const DustHipBlock*>(m->blocks.p);
-    m->dev.materials = static_cast<const uint8_t*>(m->materials.p);
-  };
-  swap_all();
-  // the same voxels, now in the full-capacity arrays (bumps the generation: scenes holding the old addresses commit again)
-  s = rebuild ? rebuild_and_refresh(m, *e) : DUST_OK;
-  if (s != DUST_OK) { swap_all(); return s; }  // back to the tightly sized originals, untouched
-  m->edit = std::move(e);
-  return DUST_OK;
-}
-
-DustStatus upload_batch(DustHipModel* m, const uint32_t* xyz, const int32_t* values, uint32_t n, bool with_values) {
-  EditState& e = *m->edit;
-  if (n > e.batch_capacity) {
-    const uint32_t cap = std::max(n, 1024u);
-    HIP_TRY(sync_stream(m->ctx));
-    HIP_TRY(e.xyz.alloc(size_t(cap) * 12));
-    HIP_TRY(e.values.alloc(size_t(cap) * 4));
-    e.batch_capacity = cap;
-  }
-  HIP_TRY(hipMemcpyAsync(e.xyz.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, m->ctx->stream));
-  if (with_values) HIP_TRY(hipMemcpyAsync(e.values.p, values, size_t(n) * 4, hipMemcpyHostToDevice, m->ctx->stream));
-  return DUST_OK;
-}
-}  // namespace
-
-DustStatus dust_hip_model_set_voxels(DustHipModel* m, const uint32_t* xyz, const int32_t* values, uint32_t n) {
-  if (!m || (n && (!xyz || !values))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  for (uint32_t i = 0; i < n; ++i) {
-    if (xyz[i * 3] >= m->dev.extent || xyz[i * 3 + 1] >= m->dev.extent || xyz[i * 3 + 2] >= m->dev.extent)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
-    if (values[i] > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxel)");
-  }
-  return guarded([&]() -> DustStatus {
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    HIP_TRY(join_side(m->ctx));  // (a surfel pass on the second stream still traces the model as it is)
-    DustStatus s = make_editable(m);
-    if (s != DUST_OK || n == 0) return s;
-    // a voxel named more than once takes its LAST value (what a sequence of set calls would leave): keep the last entry
-    std::vector<uint32_t> ux;
-    std::vector<int32_t> uv;
-    std::unordered_set<uint32_t> seen;
-    ux.reserve(size_t(n) * 3); uv.reserve(n);
-    for (uint32_t k = n; k-- > 0;) {
-      const uint32_t key = (xyz[k * 3] << 16) | (xyz[k * 3 + 1] << 8) | xyz[k * 3 + 2];
-      if (!seen.insert(key).second) continue;
-      ux.push_back(xyz[k * 3]); ux.push_back(xyz[k * 3 + 1]); ux.push_back(xyz[k * 3 + 2]);
-      uv.push_back(values[k]);
-    }
-    const uint32_t un = uint32_t(uv.size());
-    m->edit->labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
-    s = upload_batch(m, ux.data(), uv.data(), un, true);
-    if (s != DUST_OK) return s;
-    dust::EditArgs a = edit_args(m, *m->edit);
-    a.xyz = static_cast<const uint32_t*>(m->edit->xyz.p);
-    a.values = static_cast<const int32_t*>(m->edit->values.p);
-    a.n_edits = un;
-    HIP_TRY(dust::launch_edit_apply(a, false, m->ctx->stream));
-    return rebuild_and_refresh(m, *m->edit);  // synchronises: the host vectors above stay alive until the copies are done
-  });
-}
-
-// ---- shape edits (edit.hip k_edit_shapes)
-namespace {
-constexpr size_t kShapeChunkIds = size_t(1) << 21;  // cell-list entries (u16) one launch carries: 4 MiB, 512 whole-tree shapes
-
-// a buffer that only grows (the stream is drained before the old allocation goes)
-DustStatus grow(DustHipContext* ctx, DeviceBuffer& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return DUST_OK;
-  HIP_TRY(sync_stream(ctx));
-  HIP_TRY(b.alloc(std::max(bytes + bytes / 2, size_t(4096))));
-  return DUST_OK;
-}
-
-// The caller's record -> the device's: the two grid bytes of the operation and conservative voxel bounds -- the shape's extent
-// padded by more than a voxel (the float32 formulas stay within a small fraction of a voxel of the real distance for
-// coordinates up to 65 536), clipped to the tree. false: the shape covers nothing.
-bool device_shape(const DustHipEditShape& s, dust::DevEditShape& d) {
-  const bool box = s.kind == DUST_HIP_SHAPE_BOX, sphere = s.kind == DUST_HIP_SHAPE_SPHERE;
-  double lo[3], hi[3];
-  for (int r = 0; r < 3; ++r) {
-    if (!std::isfinite(s.a[r]) || (!sphere && !std::isfinite(s.b[r]))) return false;
-    if (box) {
-      if (s.a[r] > s.b[r]) return false;
-      lo[r] = s.a[r]; hi[r] = s.b[r];
-    } else {
-      if (!std::isfinite(s.radius) || s.radius < 0.0f || s.radius > 65536.0f) return false;
-      if (std::fabs(s.a[r]) > 65536.0f || (!sphere && std::fabs(s.b[r]) > 65536.0f)) return false;
-      const double p = s.a[r], q = sphere ? p : double(s.b[r]);
-      lo[r] = std::min(p, q) - double(s.radius); hi[r] = std::max(p, q) + double(s.radius);
-    }
-  }
-  uint32_t vlo[3], vhi[3];
-  for (int r = 0; r < 3; ++r) {  // voxel x is covered when lo <= x + 0.5 <= hi
-    const double l = std::floor(lo[r] - 0.5) - 1.0, h = std::ceil(hi[r] - 0.5) + 1.0;
-    if (l > 255.0 || h < 0.0) return false;
-    vlo[r] = l < 0.0 ? 0u : uint32_t(l);
-    vhi[r] = h > 255.0 ? 255u : uint32_t(h);
-  }
-  std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.b, s.b, sizeof(d.b));
-  d.kind = s.kind;
-  d.radius = box ? 0.0f : s.radius;
-  if (sphere) std::memcpy(d.b, s.a, sizeof(d.b));
-  const uint32_t byte = uint32_t(s.palette) + 1u;
-  switch (s.op) {
-    case DUST_HIP_EDIT_CARVE: d.solid_to = 0; d.empty_to = 0; break;
-    case DUST_HIP_EDIT_FILL: d.solid_to = byte; d.empty_to = byte; break;
-    case DUST_HIP_EDIT_PAINT: d.solid_to = byte; d.empty_to = 0; break;
-    default: d.solid_to = dust::kEditKeep; d.empty_to = byte; break;  // PLACE
-  }
-  d.lo = vlo[0] | (vlo[1] << 8) | (vlo[2] << 16);
-  d.hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
-  return true;
-}
-inline size_t shape_cells(const dust::DevEditShape& d) {  // root cells (16^3 voxels) the bounds reach
-  size_t n = 1;
-  for (int r = 0; r < 3; ++r) n *= size_t((((d.hi >> (8 * r)) & 255u) >> 4) - (((d.lo >> (8 * r)) & 255u) >> 4) + 1u);
-  return n;
-}
-}  // namespace
-
-DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* shapes, uint32_t n, uint32_t* changed) {
-  if (!m || (n && !shapes)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  if (n > DUST_HIP_MAX_EDIT_SHAPES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_EDIT_SHAPES shapes in one call");
-  for (uint32_t i = 0; i < n; ++i) {
-    if (shapes[i].kind > DUST_HIP_SHAPE_CAPSULE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown shape kind");
-    if (shapes[i].op > DUST_HIP_EDIT_PLACE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown edit op");
-    if (shapes[i].op != DUST_HIP_EDIT_CARVE && (shapes[i].palette < 0 || shapes[i].palette > 254))
-      return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254");
-  }
-  return guarded([&]() -> DustStatus {
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    HIP_TRY(join_side(m->ctx));
-    DustStatus s = make_editable(m);
-    if (s != DUST_OK || n == 0) return s;
-    EditState& es = *m->edit;
-    es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
-    hipStream_t st = m->ctx->stream;
-    // the shapes that cover something, in call order: `index` maps them back to the caller's
-    std::vector<dust::DevEditShape> dev;
-    std::vector<uint32_t> index;
-    dev.reserve(n); index.reserve(n);
-    for (uint32_t i = 0; i < n; ++i) {
-      dust::DevEditShape d{};
-      if (device_shape(shapes[i], d)) { dev.push_back(d); index.push_back(i); }
-    }
-    const size_t live = dev.size();
-    std::vector<uint32_t> counts(live, 0u);
-    if (live) {
-      if ((s = grow(m->ctx, es.shapes, live * sizeof(dust::DevEditShape))) != DUST_OK) return s;
-      if ((s = grow(m->ctx, es.changed, live * 4)) != DUST_OK) return s;
-      HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), live * sizeof(dust::DevEditShape), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
-    }
-    // Order-preserving chunks, each one launch: its shapes binned into the 4096 root cells, an ascending list of u16 shape
-    // ids per cell in CSR form, one workgroup per non-empty cell. A chunk ends where its lists would pass kShapeChunkIds.
-    std::vector<uint32_t> cells, starts, fill(4096);
-    std::vector<uint16_t> ids;
-    for (size_t c0 = 0; c0 < live;) {
-      size_t c1 = c0, total = 0;
-      while (c1 < live && c1 - c0 < 65536 && (c1 == c0 || total + shape_cells(dev[c1]) <= kShapeChunkIds)) total += shape_cells(dev[c1++]);
-      std::fill(fill.begin(), fill.end(), 0u);
-      auto each_cell = [&](const dust::DevEditShape& d, auto&& f) {
-        for (uint32_t x = (d.lo & 255u) >> 4; x <= (d.hi & 255u) >> 4; ++x)
-          for (uint32_t y = ((d.lo >> 8) & 255u) >> 4; y <= ((d.hi >> 8) & 255u) >> 4; ++y)
-            for (uint32_t z = (d.lo >> 16) >> 4; z <= (d.hi >> 16) >> 4; ++z) f((x << 8) | (y << 4) | z);
-      };
-      for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ++fill[cell]; });
-      if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
-      cells.clear(); starts.clear();
-      uint32_t run = 0;
-      for (uint32_t cell = 0; cell < 4096; ++cell) {
-        const uint32_t k = fill[cell];
-        fill[cell] = run;  // where the cell's next id goes
-        if (k) { cells.push_back(cell); starts.push_back(run); run += k; }
-      }
-      starts.push_back(run);
-      ids.resize(run);
-      for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
-      if ((s = grow(m->ctx, es.shape_cells, cells.size() * 4)) != DUST_OK) return s;
-      if ((s = grow(m->ctx, es.shape_starts, starts.size() * 4)) != DUST_OK) return s;
-      if ((s = grow(m->ctx, es.shape_ids, ids.size() * 2)) != DUST_OK) return s;
-      HIP_TRY(hipMemcpyAsync(es.shape_cells.p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(es.shape_starts.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(es.shape_ids.p, ids.data(), ids.size() * 2, hipMemcpyHostToDevice, st));
-      dust::EditShapeArgs a{};
-      a.grid = static_cast<uint8_t*>(es.grid.p);
-      a.shapes = static_cast<const dust::DevEditShape*>(es.shapes.p) + c0;
-      a.cells = static_cast<const uint32_t*>(es.shape_cells.p);
-      a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
-      a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
-      a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
-      a.n_cells = uint32_t(cells.size());
-      HIP_TRY(dust::launch_edit_shapes(a, st));
-      c0 = c1;
-    }
-    if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
-    s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
-    if (s != DUST_OK) return s;
-    if (changed) {
-      std::fill(changed, changed + n, 0u);
-      for (size_t k = 0; k < live; ++k) changed[index[k]] = counts[k];
-    }
-    return DUST_OK;
-  });
-}
-
-DustStatus dust_hip_model_get_voxels(DustHipModel* m, const uint32_t* xyz, int32_t* values, uint32_t n) {
-  if (!m || (n && (!xyz || !values))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  for (uint32_t i = 0; i < n; ++i)
-    if (xyz[i * 3] >= m->dev.extent || xyz[i * 3 + 1] >= m->dev.extent || xyz[i * 3 + 2] >= m->dev.extent)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
-  return guarded([&]() -> DustStatus {
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    HIP_TRY(join_side(m->ctx));
-    DustStatus s = make_editable(m);
-    if (s != DUST_OK || n == 0) return s;
-    s = upload_batch(m, xyz, nullptr, n, false);
-    if (s != DUST_OK) return s;
-    dust::EditArgs a = edit_args(m, *m->edit);
-    a.xyz = static_cast<const uint32_t*>(m->edit->xyz.p);
-    a.values_out = static_cast<int32_t*>(m->edit->values.p);
-    a.n_edits = n;
-    HIP_TRY(dust::launch_edit_apply(a, true, m->ctx->stream));
-    HIP_TRY(hipMemcpyAsync(values, m->edit->values.p, size_t(n) * 4, hipMemcpyDeviceToHost, m->ctx->stream));
-    HIP_TRY(sync_stream(m->ctx));
-    return DUST_OK;
-  });
-}
-
-// ---- model islands (island.hip): label the grid's connected voxels, look labels up, move whole islands into a model of their own
-static_assert(sizeof(DustHipIslandQuery) == 32 && sizeof(DustHipIsland) == 40 && sizeof(DustHipIsland) == sizeof(dust::DevIsland), "island records");
-
-DustStatus dust_hip_model_find_islands(DustHipModel* m, const DustHipIslandQuery* q, uint32_t* n_islands, DustHipIsland* islands, uint32_t capacity) {
-  if (!m || !q || !n_islands || (!islands && capacity)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  STRUCT_TRY(q, "DustHipIslandQuery");
-  if (q->connectivity > DUST_HIP_ISLANDS_CORNERS) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown island connectivity");
-  return guarded([&]() -> DustStatus {
-    DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(join_side(ctx));
-    DustStatus s = make_editable(m);
-    if (s != DUST_OK) return s;
-    EditState& es = *m->edit;
-    hipStream_t st = ctx->stream;
-    const uint32_t corners = q->connectivity == DUST_HIP_ISLANDS_CORNERS ? 1u : 0u;
-    // a labelling that still stands (no edit since; detached islands only left it) is not computed again: a count-only call followed by
-    // a call with room for every record labels once
-    const bool relabel = !(es.labels_valid && es.labels_corners == corners);
-    es.labels_valid = false;  // until this labelling is complete
-    if (!es.labels.p) {
-      const hipError_t e = es.labels.alloc(size_t(dust::kIslandKeys) * 4);
-      if (e != hipSuccess) { es.labels.release(); return hip_fail(e, "the island label array (64 MiB)"); }
-    }
-    if ((s = grow(ctx, ctx->island_mask, size_t(dust::kIslandRows) * 8)) != DUST_OK) return s;
-    if ((s = grow(ctx, ctx->island_count, size_t(dust::kIslandRows) * 4)) != DUST_OK) return s;
-    if ((s = grow(ctx, ctx->island_tmp, 260 * 4)) != DUST_OK) return s;
-    dust::IslandArgs a{};
-    a.grid = static_cast<const uint8_t*>(es.grid.p);
-    a.label = static_cast<uint32_t*>(es.labels.p);
-    a.root_mask = static_cast<uint64_t*>(ctx->island_mask.p);
-    a.root_count = static_cast<uint32_t*>(ctx->island_count.p);
-    a.scan_tmp = static_cast<uint32_t*>(ctx->island_tmp.p);
-    a.corners = corners;
-    for (int r = 0; r < 3; ++r) { a.anchor_lo[r] = q->anchor_lo[r]; a.anchor_hi[r] = std::min(q->anchor_hi[r], 255u); }
-    HIP_TRY(dust::launch_island_label(a, relabel, st));
-    uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, a.scan_tmp + 256, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    a.capacity = std::min(total, capacity);
-    if (a.capacity) {
-      if ((s = grow(ctx, ctx->island_acc, size_t(a.capacity) * sizeof(dust::IslandAcc))) != DUST_OK) return s;
-      if ((s = grow(ctx, ctx->island_records, size_t(a.capacity) * sizeof(dust::DevIsland))) != DUST_OK) return s;
-      a.acc = static_cast<dust::IslandAcc*>(ctx->island_acc.p);
-      a.records = static_cast<dust::DevIsland*>(ctx->island_records.p);
-      HIP_TRY(hipMemsetAsync(a.acc, 0, size_t(a.capacity) * sizeof(dust::IslandAcc), st));
-      HIP_TRY(dust::launch_island_records(a, st));
-      HIP_TRY(hipMemcpyAsync(islands, a.records, size_t(a.capacity) * sizeof(dust::DevIsland), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-    }
-    es.labels_valid = true;
-    es.labels_corners = corners;
-    *n_islands = total;
-    return DUST_OK;
-  });
-}
-
-DustStatus dust_hip_model_island_of(DustHipModel* m, const uint32_t* xyz, uint32_t* keys, uint32_t n) {
-  if (!m || (n && (!xyz || !keys))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  DustStatus s = editable_kind(m);
-  if (s != DUST_OK) return s;
-  for (uint32_t i = 0; i < n; ++i)
-    if (xyz[i * 3] >= 256u || xyz[i * 3 + 1] >= 256u || xyz[i * 3 + 2] >= 256u)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
-  if (!m->edit || !m->edit->labels_valid)
-    return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)");
-  if (n == 0) return DUST_OK;
-  return guarded([&]() -> DustStatus {
-    DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if ((s = grow(ctx, ctx->island_in, size_t(n) * 12)) != DUST_OK) return s;
-    if ((s = grow(ctx, ctx->island_out, size_t(n) * 4)) != DUST_OK) return s;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->island_in.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
-    HIP_TRY(dust::launch_island_lookup(static_cast<const uint32_t*>(m->edit->labels.p), static_cast<const uint32_t*>(ctx->island_in.p),
-                                       static_cast<uint32_t*>(ctx->island_out.p), n, st));
-    HIP_TRY(hipMemcpyAsync(keys, ctx->island_out.p, size_t(n) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DUST_OK;
-  });
-}
-
-DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, uint32_t n, uint32_t flags, DustHipModel** out) {
-  if (!m || (n && !keys)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  if (flags & ~DUST_HIP_DETACH_KEEP_SOURCE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown detach flags");
-  const bool keep = (flags & DUST_HIP_DETACH_KEEP_SOURCE) != 0;
-  if (keep && !out) return fail(DUST_ERR_INVALID_ARGUMENT, "DUST_HIP_DETACH_KEEP_SOURCE without a model to receive the islands does nothing");
-  DustStatus s = editable_kind(m);
-  if (s != DUST_OK) return s;
-  if (n == 0) { if (out) *out = nullptr; return DUST_OK; }
-  if (!m->edit || !m->edit->labels_valid)
-    return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)");
-  return guarded([&]() -> DustStatus {
-    DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
-    EditState& es = *m->edit;
-    hipStream_t st = ctx->stream;
-    // which keys name an island: a bit per selected key, and the number of keys that name none
-    if ((s = grow(ctx, ctx->island_mask, size_t(dust::kIslandRows) * 8)) != DUST_OK) return s;
-    if ((s = grow(ctx, ctx->island_tmp, 260 * 4)) != DUST_OK) return s;
-    if ((s = grow(ctx, ctx->island_in, size_t(n) * 4)) != DUST_OK) return s;
-    uint32_t* bad_dev = static_cast<uint32_t*>(ctx->island_tmp.p) + 257;
-    HIP_TRY(hipMemcpyAsync(ctx->island_in.p, keys, size_t(n) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(ctx->island_mask.p, 0, size_t(dust::kIslandRows) * 8, st));
-    HIP_TRY(hipMemsetAsync(bad_dev, 0, 4, st));
-    HIP_TRY(dust::launch_island_select(static_cast<const uint32_t*>(es.labels.p), static_cast<const uint32_t*>(ctx->island_in.p), n,
-                                       static_cast<uint64_t*>(ctx->island_mask.p), bad_dev, st));
-    uint32_t bad = 0;
-    uint32_t pal[256];
-    HIP_TRY(hipMemcpyAsync(&bad, bad_dev, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(pal, m->palette.p, sizeof(pal), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bad) return fail(DUST_ERR_INVALID_ARGUMENT, "a key does not name an island of the model's current labelling");
-    // the new model: empty, editable, its grid filled by the detach kernel and then rebuilt like any edit
-    struct Drop { DustHipModel* m; ~Drop() { release(m); } } fresh{nullptr};
-    if (out) {
-      s = dust_hip_model_create(ctx, nullptr, 0, nullptr, 0, reinterpret_cast<const uint8_t*>(pal), 8, &fresh.m);
-      if (s == DUST_OK) s = make_editable(fresh.m, false);
-      if (s != DUST_OK) return s;
-    }
-    dust::IslandDetachArgs a{};
-    a.src = static_cast<uint8_t*>(es.grid.p);
-    a.dst = fresh.m ? static_cast<uint8_t*>(fresh.m->edit->grid.p) : nullptr;
-    a.label = static_cast<uint32_t*>(es.labels.p);
-    a.selected = static_cast<const uint64_t*>(ctx->island_mask.p);
-    // copy first and build the new model from the copy; the source is carved only once the voxels have somewhere to live, so a failure
-    // up to there leaves it as it was
-    if (fresh.m) {
-      a.carve = 0u;
-      HIP_TRY(dust::launch_island_detach(a, st));
-      if ((s = rebuild_and_refresh(fresh.m, *fresh.m->edit)) != DUST_OK) return s;
-    }
-    if (!keep) {
-      a.dst = nullptr;
-      a.carve = 1u;
-      HIP_TRY(dust::launch_island_detach(a, st));
-      // (whole islands left: the labelling of the rest stands.) A failure in here is that of a shape edit's rebuild: the grid is
-      // changed, the arrays are not; the new model is dropped with the error
-      if ((s = rebuild_and_refresh(m, es)) != DUST_OK) { es.labels_valid = false; return s; }
-    }
-    if (out) *out = retain(fresh.m);  // the caller's reference (the guard drops the builder's)
-    return DUST_OK;
-  });
-}
-
-DustStatus dust_hip_model_info(const DustHipModel* m, uint32_t* n_blocks, uint64_t* n_materials) {
-  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
-  if (n_blocks) *n_blocks = m->dev.n_blocks;
-  if (n_materials) *n_materials = m->n_materials;
-  return DUST_OK;
-}
-
-DustStatus dust_hip_model_read(const DustHipModel* m, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity) {
-  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
-  if ((blocks && block_capacity < m->dev.n_blocks) || (materials && material_capacity < m->n_materials))
-    return fail(DUST_ERR_INVALID_ARGUMENT, "destination too small (see dust_hip_model_info)");
-  HIP_TRY(hipSetDevice(m->ctx->device));
-  const hipStream_t st = m->ctx->stream;
-  if (blocks && m->dev.n_blocks) HIP_TRY(hipMemcpyAsync(blocks, m->blocks.p, size_t(m->dev.n_blocks) * sizeof(DustHipBlock), hipMemcpyDeviceToHost, st));
-  if (materials && m->n_materials) HIP_TRY(hipMemcpyAsync(materials, m->materials.p, size_t(m->n_materials), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return DUST_OK;
-}
-
-DustStatus dust_hip_scene_create(DustHipContext* ctx, DustHipScene** out) {
-  if (!ctx || !out) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  return guarded([&] {
-    DustHipScene* s = new DustHipScene;
-    s->ctx = retain(ctx);
-    *out = s;
-    return DUST_OK;
-  });
-}
-void dust_hip_scene_destroy(DustHipScene* s) { release(s); }
-
-static DustStatus check_affine(const float m[12]) {
-  for (int i = 0; i < 12; ++i)
-    if (!std::isfinite(m[i])) return fail(DUST_ERR_INVALID_ARGUMENT, "non-finite instance transform");
-  const double det = double(m[0]) * (double(m[5]) * m[10] - double(m[6]) * m[9]) -
-                     double(m[1]) * (double(m[4]) * m[10] - double(m[6]) * m[8]) +
-                     double(m[2]) * (double(m[4]) * m[9] - double(m[5]) * m[8]);
-  if (!(std::fabs(det) > 1e-20)) return fail(DUST_ERR_INVALID_ARGUMENT, "singular instance transform");
-  return DUST_OK;
-}
-
-DustStatus dust_hip_scene_add_instance(DustHipScene* s, const DustHipModel* model, const float o2w[12],
-                                       const float prev[16], uint32_t* instance_id) {
-  if (!s || !model || !o2w) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  if (model->ctx != s->ctx) return fail(DUST_ERR_INVALID_ARGUMENT, "model belongs to another context");
-  if (s->instances.size() >= 65535) return fail(DUST_ERR_INVALID_ARGUMENT, "too many instances (voxel_id holds 16 bits)");
-  DustStatus st = check_affine(o2w);
-  if (st != DUST_OK) return st;
-  return guarded([&] {
-    HostInstance hi;
-    hi.model = model;
-    std::memcpy(hi.o2w, o2w, sizeof(hi.o2w));
-    if (prev) std::memcpy(hi.prev, prev, sizeof(hi.prev));
-    else {  // first frame: previous transform == current (standard.rs:856-878), column-major mat4
-      for (int c = 0; c < 4; ++c)
-        for (int r = 0; r < 4; ++r) hi.prev[c * 4 + r] = r < 3 ? o2w[r * 4 + c] : (c == 3 ? 1.0f : 0.0f);
-    }
-    s->instances.reserve(s->instances.size() + 1);
-    s->dirty.reserve(s->dirty.size() + 1);
-    if (instance_id) *instance_id = uint32_t(s->instances.size());
-    s->instances.push_back(hi);
-    s->dirty.push_back(1);
-    retain(const_cast<DustHipModel*>(model));  // the scene keeps what it instances alive
-    s->structure_dirty = true;
-    s->committed = false;
-    return DUST_OK;
-  });
-}
-DustStatus dust_hip_scene_set_transform(DustHipScene* s, uint32_t id, const float o2w[12], const float prev[16]) {
-  if (!s || !o2w || id >= s->instances.size()) return fail(DUST_ERR_INVALID_ARGUMENT, "bad instance id");
-  DustStatus st = check_affine(o2w);
-  if (st != DUST_OK) return st;
-  HostInstance& hi = s->instances[id];
-  std::memcpy(hi.o2w, o2w, sizeof(hi.o2w));
-  if (prev) std::memcpy(hi.prev, prev, sizeof(hi.prev));
-  s->dirty[id] = 1;
-  s->committed = false;
-  return DUST_OK;
-}
-
-namespace {
-// conservative world box of instance i: the eight corners of its model's tight bounds, each padded by 1e-4 of its size
-void world_box(const HostInstance& hi, float wmin[3], float wmax[3]) {
-  const dust::DevModel& m = hi.model->dev;
-  for (int a = 0; a < 3; ++a) { wmin[a] = 1e30f; wmax[a] = -1e30f; }
-  for (int c = 0; c < 8; ++c) {
-    const double p[3] = {(c & 1) ? m.bmax[0] : m.bmin[0], (c & 2) ? m.bmax[1] : m.bmin[1], (c & 4) ? m.bmax[2] : m.bmin[2]};
-    for (int a = 0; a < 3; ++a) {
-      const float* r = hi.o2w + a * 4;
-      const double w = double(r[0]) * p[0] + double(r[1]) * p[1] + double(r[2]) * p[2] + double(r[3]);
-      const double pad = 1e-4 * (std::fabs(w) + 1.0);
-      wmin[a] = std::min(wmin[a], float(w - pad));
-      wmax[a] = std::max(wmax[a], float(w + pad));
-    }
-  }
-}
-// the device records of instance i, re-derived in the host master image (instance, box, visit)
-void derive_instance(DustHipScene* s, size_t i) {
-  const HostInstance& hi = s->instances[i];
-  uint8_t* img = s->master.data();
-  dust::DevInstance& d = reinterpret_cast<dust::DevInstance*>(img + s->layout.instances)[i];
-  std::memcpy(d.o2w, hi.o2w, sizeof(d.o2w));
-  std::memcpy(d.prev, hi.prev, sizeof(d.prev));
-  invert_affine(hi.o2w, d.w2o);
-  d.model = s->instance_slot[i];
-  d.pad = 0;
-  world_box(hi, d.wmin, d.wmax);
-  // the world box again, packed 32 bytes apiece: what the packet culling streams through (coalesced) and the candidate
-  // loop reads with one scalar load; and the flattened visit record (box, world -> object, model)
-  dust::DevBox& bx = reinterpret_cast<dust::DevBox*>(img + s->layout.boxes)[i];
-  dust::DevVisit& v = reinterpret_cast<dust::DevVisit*>(img + s->layout.visits)[i];
-  for (int a = 0; a < 3; ++a) { bx.lo[a] = v.lo[a] = d.wmin[a]; bx.hi[a] = v.hi[a] = d.wmax[a]; }
-  bx.pad0 = bx.pad1 = v.pad0 = v.pad1 = 0.0f;
-  std::memcpy(v.w2o, d.w2o, sizeof(v.w2o));
-  v.m = reinterpret_cast<const dust::DevModel*>(img + s->layout.models)[d.model];
-  // and what the ray streams' instance set-up reads, in 80 bytes (the model's bounds are multiples of 4 up to 4096: exact in 16 bits)
-  dust::DevEnter& e = reinterpret_cast<dust::DevEnter*>(img + s->layout.enters)[i];
-  std::memcpy(e.w2o, d.w2o, sizeof(e.w2o));
-  for (int a = 0; a < 3; ++a) { e.bmin[a] = uint16_t(v.m.bmin[a]); e.bmax[a] = uint16_t(v.m.bmax[a]); }
-  e.model = uint16_t(d.model);
-  e.lds_slot = v.m.lds_slot >= 0 && v.m.lds_slot < 255 ? uint8_t(v.m.lds_slot) : uint8_t(255);
-  e.extent_log2 = v.m.extent > 256u ? 12 : 8;
-  e.root = v.m.root;
-  e.dense_mask = v.m.dense_mask;
-}
-
-// The top-level grid over the instances' world boxes (DevGrid; tlas.rs:37-65 rebuilds the TLAS every frame the same way).
-// About `density` cells per instance (DUST_HIP_GRID_DENSITY, default 12; at most 256 per axis, 2^18 in all), cubes as nearly
-// as the scene's proportions allow. An instance is listed in every cell its box, grown by kGridMargin of the scene's size,
-// overlaps: the margin is what lets the per-ray walk (gi.hip, top_next) trust its single-precision cell steps.
-// boxes: n x {lo[3], hi[3]}. ranges: per instance the block of cells it is listed in, {lo, hi} as x | y << 9 | z << 18.
-constexpr double kGridMargin = 2e-5;
-void build_grid(DustHipScene* s, const std::vector<float>& boxes, std::vector<uint32_t>& ranges) {
-  const size_t n = boxes.size() / 6;
-  dust::DevGrid& g = s->grid;
-  double ext[3], big = 0.0;
-  for (int a = 0; a < 3; ++a) big = std::max(big, double(s->world_max[a]) - double(s->world_min[a]));
-  const double margin = kGridMargin * big + 0.01;
-  for (int a = 0; a < 3; ++a) {
-    g.lo[a] = float(double(s->world_min[a]) - 2.0 * margin);
-    ext[a] = std::max(double(s->world_max[a]) + 2.0 * margin - double(g.lo[a]), 1e-3 * big + 1.0);
-  }
-  const char* density_env = diag_env("GRID_DENSITY");  // (per commit: ~100 ns, and tests vary it)
-  const double density0 = density_env ? std::max(0.001, std::atof(density_env)) : 12.0;
-  ranges.resize(n * 2);
-  std::vector<uint32_t> count;
-  uint32_t last_dim[3] = {0, 0, 0}, halvings = 0;
-  bool force_one = false;
-  for (double density = density0;; density *= 0.5) {
-    const double target = std::min(262144.0, std::max(1.0, density * double(std::max<size_t>(n, 1))));
-    const double edge = std::cbrt(ext[0] * ext[1] * ext[2] / target);
-    for (int a = 0; a < 3; ++a) {
-      g.dim[a] = force_one ? 1u : uint32_t(std::min(256.0, std::max(1.0, std::floor(ext[a] / edge + 0.5))));
-      g.cell[a] = float(ext[a] / double(g.dim[a]));
-      g.inv_cell[a] = float(double(g.dim[a]) / ext[a]);
-      g.hi[a] = float(double(g.lo[a]) + ext[a]);
-    }
-    const size_t n_cells = size_t(g.dim[0]) * g.dim[1] * g.dim[2];
-    count.assign(n_cells, 0u);
-    auto cell_of = [&](double w, int a) {
-      const double c = std::floor((w - double(g.lo[a])) / ext[a] * double(g.dim[a]));
-      return uint32_t(std::min(double(g.dim[a] - 1), std::max(0.0, c)));
-    };
-    size_t total = 0;
-    uint32_t most = 0;
-    for (size_t i = 0; i < n; ++i) {
-      uint32_t lo[3], hi[3];
-      for (int a = 0; a < 3; ++a) { lo[a] = cell_of(double(boxes[i * 6 + a]) - margin, a); hi[a] = cell_of(double(boxes[i * 6 + 3 + a]) + margin, a); }
-      ranges[i * 2] = lo[0] | (lo[1] << 9) | (lo[2] << 18);
-      ranges[i * 2 + 1] = hi[0] | (hi[1] << 9) | (hi[2] << 18);
-      for (uint32_t z = lo[2]; z <= hi[2]; ++z)
-        for (uint32_t y = lo[1]; y <= hi[1]; ++y)
-          for (uint32_t x = lo[0]; x <= hi[0]; ++x) most = std::max(most, ++count[(size_t(z) * g.dim[1] + y) * g.dim[0] + x]);
-      total += size_t(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1);
-    }
-    // (coarser until the item array fits the packed cell word's 20 index bits: never, for scenes of any sane shape. More than 4095 boxes over
-    //  ONE cell cannot be listed at any resolution that helps: the grid is then marked unusable and the single-ray paths are not taken)
-    s->grid_valid = most <= dust::kGridMaxCellItems;
-    if (total < (size_t(1) << dust::kGridItemBits) || n_cells == 1) break;
-    // (a fuse: an elongated scene whose rounded dims stop shrinking -- density x n <= 1 clamps the target to one cell, which ext / cbrt(V)
-    //  never reaches for aspects above ~2 -- or 40 halvings: ONE cell then; should even that list 2^20 items or more -- 2^20 boxes do not
-    //  exist, 65 535 instances at most --, the grid is marked unusable like a cell of more than 4095)
-    const bool stuck = g.dim[0] == last_dim[0] && g.dim[1] == last_dim[1] && g.dim[2] == last_dim[2];
-    for (int a = 0; a < 3; ++a) last_dim[a] = g.dim[a];
-    if (force_one) { s->grid_valid = false; break; }
-    if (stuck || ++halvings >= 40) force_one = true;
-  }
-  const size_t n_cells = count.size();
-  s->grid_cells.assign(n_cells, 0u);
-  std::vector<uint32_t> at(n_cells);
-  uint32_t run = 0;
-  for (size_t c = 0; c < n_cells; ++c) {
-    at[c] = run;
-    s->grid_cells[c] = run | (std::min(count[c], dust::kGridMaxCellItems) << dust::kGridItemBits);
-    run += count[c];
-  }
-  g.n_items = run;
-  s->grid_items.assign(run, 0);
-  for (size_t i = 0; i < n; ++i) {  // ascending instance order inside every cell
-    const uint32_t rl = ranges[i * 2], rh = ranges[i * 2 + 1];
-    for (uint32_t z = rl >> 18; z <= (rh >> 18); ++z)
-      for (uint32_t y = (rl >> 9) & 255u; y <= ((rh >> 9) & 255u); ++y)
-        for (uint32_t x = rl & 255u; x <= (rh & 255u); ++x) s->grid_items[at[(size_t(z) * g.dim[1] + y) * g.dim[0] + x]++] = uint16_t(i);
-  }
-}
-// the instances in the order of a Hilbert curve through their boxes' centres (10 bits per axis over the scene's bounds; Skilling's
-// transform): the packet cull's groups are runs of 64 consecutive slots, and consecutive cells of this curve are always neighbours
-// (along a Z-order a run that crosses a block boundary jumps across the scene, and the group's box with it)
-void order_slots(DustHipScene* s) {
-  const size_t n = s->world_boxes.size() / 6;
-  std::vector<std::pair<uint32_t, uint32_t>> keyed(n);
-  auto spread = [](uint32_t v) { v &= 1023u; v = (v | (v << 16)) & 0x030000FFu; v = (v | (v << 8)) & 0x0300F00Fu; v = (v | (v << 4)) & 0x030C30C3u; return (v | (v << 2)) & 0x09249249u; };
-  for (size_t i = 0; i < n; ++i) {
-    uint32_t c[3];
-    for (int a = 0; a < 3; ++a) {
-      const double span = std::max(1e-6, double(s->world_max[a]) - double(s->world_min[a]));
-      const double mid = 0.5 * (double(s->world_boxes[i * 6 + a]) + double(s->world_boxes[i * 6 + 3 + a]));
-      c[a] = uint32_t(std::min(1023.0, std::max(0.0, (mid - double(s->world_min[a])) / span * 1024.0)));
-    }
-    uint32_t X[3] = {c[0], c[1], c[2]};
-    for (uint32_t Q = 512u; Q > 1u; Q >>= 1) {
-      const uint32_t P = Q - 1u;
-      for (int a = 0; a < 3; ++a) {
-        if (X[a] & Q) X[0] ^= P;
-        else { const uint32_t t = (X[0] ^ X[a]) & P; X[0] ^= t; X[a] ^= t; }
-      }
-    }
-    X[1] ^= X[0]; X[2] ^= X[1];
-    uint32_t t = 0;
-    for (uint32_t Q = 512u; Q > 1u; Q >>= 1) if (X[2] & Q) t ^= Q - 1u;
-    for (uint32_t& x : X) x ^= t;
-    keyed[i] = {(spread(X[0]) << 2) | (spread(X[1]) << 1) | spread(X[2]), uint32_t(i)};
-  }
-  std::sort(keyed.begin(), keyed.end());
-  s->slot_order.resize(n);
-  for (size_t k = 0; k < n; ++k) s->slot_order[k] = keyed[k].second;
-}
-}  // namespace
-
-DustStatus dust_hip_scene_commit(DustHipScene* s) {
-  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
-  return guarded([&]() -> DustStatus {
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    const size_t n = s->instances.size();
-    // a model edited since the last commit changes its record (bounds, sizes, maybe addresses): everything is derived again
-    for (size_t i = 0; i < s->models.size() && !s->structure_dirty; ++i)
-      if (s->models[i]->generation != s->model_generation[i]) s->structure_dirty = true;
-    bool full = s->structure_dirty;
-    if (full) {
-      s->committed = false;  // (until the new image is up: what follows replaces the layout the current one was made with)
-      s->models.clear();
-      s->instance_slot.resize(n);
-      for (size_t i = 0; i < n; ++i) {
-        const DustHipModel* m = s->instances[i].model;
-        auto it = std::find(s->models.begin(), s->models.end(), m);
-        s->instance_slot[i] = uint32_t(it - s->models.begin());
-        if (it == s->models.end()) s->models.push_back(m);
-      }
-      // roots of the first models go to LDS, as many as the budget holds
-      s->n_lds_models = std::min<uint32_t>(uint32_t(s->models.size()), s->ctx->lds_root_bytes / dust::kN16LdsBytes);
-    }
-    // the instances' world boxes (those that moved, or all), the scene's bounds, and the top-level grid over them: the grid's
-    // size decides the image's layout
-    s->world_boxes.resize(n * 6);
-    for (size_t i = 0; i < n; ++i)
-      if (full || s->dirty[i]) world_box(s->instances[i], &s->world_boxes[i * 6], &s->world_boxes[i * 6 + 3]);
-    for (int a = 0; a < 3; ++a) { s->world_min[a] = 1e30f; s->world_max[a] = -1e30f; }
-    for (size_t i = 0; i < n; ++i)
-      for (int a = 0; a < 3; ++a) { s->world_min[a] = std::min(s->world_min[a], s->world_boxes[i * 6 + a]); s->world_max[a] = std::max(s->world_max[a], s->world_boxes[i * 6 + 3 + a]); }
-    if (n == 0) for (int a = 0; a < 3; ++a) s->world_min[a] = s->world_max[a] = 0.0f;
-    std::vector<uint32_t> ranges;
-    build_grid(s, s->world_boxes, ranges);
-    const size_t n_cells = s->grid_cells.size(), n_items = s->grid_items.size();
-    if (!full && (n_cells > s->layout.cap_cells || n_items > s->layout.cap_items)) full = true;  // the grid outgrew its sections
-    if (full) {
-      s->committed = false;
-      s->structure_dirty = true;
-      s->layout = SceneLayout::make(n, s->models.size(), s->n_lds_models, n_cells, n_items);
-      if (s->layout.total > s->image_capacity || s->current < 0) {
-        // grow (rare: instances were added). Launches that read the old images are done before they go; the new ones are
-        // allocated into locals first, so a failed allocation leaves the scene as it was (and the next commit tries again).
-        HIP_TRY(sync_stream(s->ctx));
-        const size_t cap = s->layout.total + s->layout.total / 2 + 4096;
-        DustHipScene::Slot fresh[DustHipScene::kImages];
-        hipError_t ge = hipSuccess;
-        for (DustHipScene::Slot& sl : fresh) {
-          if (ge == hipSuccess) ge = sl.dev.alloc(cap);
-          if (ge == hipSuccess) ge = hipHostMalloc(&sl.host, cap, hipHostMallocDefault);
-        }
-        if (ge != hipSuccess) {
-          for (DustHipScene::Slot& sl : fresh) { if (sl.host) (void)hipHostFree(sl.host); sl.dev.release(); }
-          s->structure_dirty = true;  // (the layout above is not the images': the next commit starts over)
-          s->committed = false;
-          return hip_fail(ge, "scene image allocation");
-        }
-        s->committed = false;  // no current image until the upload below has succeeded (a frame must not index slot -1)
-        s->structure_dirty = true;
-        s->free_images();
-        for (int i = 0; i < DustHipScene::kImages; ++i) {
-          s->slots[i].dev.p = fresh[i].dev.p; s->slots[i].dev.bytes = fresh[i].dev.bytes;
-          fresh[i].dev.p = nullptr; fresh[i].dev.bytes = 0;  // (ownership moved: the local's destructor frees nothing)
-          s->slots[i].host = fresh[i].host; s->slots[i].epoch = 0;
-        }
-        s->image_capacity = cap;
-        s->next_slot = 0;
-      }
-      s->master.assign(s->layout.total, 0);
-      uint8_t* img = s->master.data();
-      dust::DevModel* dm = reinterpret_cast<dust::DevModel*>(img + s->layout.models);
-      for (size_t i = 0; i < s->models.size(); ++i) {
-        dm[i] = s->models[i]->dev;
-        dm[i].lds_slot = i < s->n_lds_models ? int32_t(i) : -1;
-      }
-      for (uint32_t i = 0; i < s->n_lds_models; ++i)
-        std::memcpy(img + s->layout.root_table + size_t(i) * dust::kN16LdsBytes, s->models[i]->host_root.data(), dust::kN16LdsBytes);
-      s->model_generation.clear();
-      for (const DustHipModel* m : s->models) s->model_generation.push_back(m->generation);
-    }
-    uint8_t* img = s->master.data();
-    for (size_t i = 0; i < n; ++i)
-      if (full || s->dirty[i]) { derive_instance(s, i); s->dirty[i] = 0; }
-    // (the record behind the last instance stays zero: the cull reads boxes 64 at a time)
-    // every instance's block of grid cells into the spare words of its box record (the grid is new: so are the blocks), the grid behind the records
-    {
-      dust::DevBox* bx = reinterpret_cast<dust::DevBox*>(img + s->layout.boxes);
-      dust::DevVisit* vs = reinterpret_cast<dust::DevVisit*>(img + s->layout.visits);
-      for (size_t i = 0; i < n; ++i) {
-        std::memcpy(&bx[i].pad0, &ranges[i * 2], 4); std::memcpy(&bx[i].pad1, &ranges[i * 2 + 1], 4);
-        vs[i].pad0 = bx[i].pad0; vs[i].pad1 = bx[i].pad1;
-      }
-      std::memcpy(img + s->layout.grid_cells, s->grid_cells.data(), s->grid_cells.size() * sizeof(uint32_t));
-      // the packet cull's 64-wide hierarchy (kernels: cull_instances): slots along a Morton curve through the boxes' centres -- ordered
-      // by structural commits, refitted by every commit --, a box per 64 consecutive slots
-      s->n_groups = n > dust::kFlatCullMax && !diag_env("FLAT_CULL") ? uint32_t((n + 63) / 64) : 0u;  // (DUST_HIP_FLAT_CULL: every box for every packet, for A/B runs)
-      if (s->n_groups) {
-        if (full || s->slot_order.size() != n) {
-          order_slots(s);
-        }
-        dust::DevBox* sb = reinterpret_cast<dust::DevBox*>(img + s->layout.sboxes);
-        dust::DevBox* gb = reinterpret_cast<dust::DevBox*>(img + s->layout.gboxes);
-        for (uint32_t g = 0; g < s->n_groups; ++g) {
-          dust::DevBox u;
-          for (int a = 0; a < 3; ++a) { u.lo[a] = 1e30f; u.hi[a] = -1e30f; }
-          u.pad0 = u.pad1 = 0.0f;
-          for (size_t k = size_t(g) * 64; k < std::min(n, size_t(g + 1) * 64); ++k) {
-            const uint32_t i = s->slot_order[k];
-            sb[k] = bx[i];
-            std::memcpy(&sb[k].pad0, &i, 4);
-            for (int a = 0; a < 3; ++a) { u.lo[a] = std::min(u.lo[a], bx[i].lo[a]); u.hi[a] = std::max(u.hi[a], bx[i].hi[a]); }
-          }
-          gb[g] = u;
-        }
-      } else {
-        s->slot_order.clear();
-      }
-      if (n_items) std::memcpy(img + s->layout.grid_items, s->grid_items.data(), n_items * sizeof(uint16_t));
-    }
-    // upload: the whole image into the next slot of the ring, on the copy stream, and wait for it here (a ~100 KB copy: ~20 us of host
-    // time, none of the launch stream's); frames in flight keep reading the slot they were enqueued with
-    if (!s->ctx->copy) HIP_TRY(hipStreamCreateWithFlags(&s->ctx->copy, hipStreamNonBlocking));
-    const int slot = int(s->next_slot++ % DustHipScene::kImages);
-    DustHipScene::Slot& sl = s->slots[slot];
-    if (sl.epoch == s->ctx->sync_epoch) {  // nobody has waited since a frame last read this slot: the host is a ring ahead
-      // The frame AFTER that one has started => that one is done (one stream, launches in order; only the plain case: nothing outstanding on the
-      // side stream or on communicators' streams). The GPU keeps the rest of the ring to work on meanwhile:
-      // waiting for the whole stream instead left it idle for the ~50 us the host needs to enqueue again, every 8th frame (2 % of a moving view).
-      DustHipContext* c = s->ctx;
-      bool waited = false;
-      const uint32_t need = sl.last_seq + (c->side ? 2u : 1u);  // (a surfel pass on the side stream is joined in the course of the NEXT frame: one more)
-      if (c->started && sl.last_seq != 0 && !c->side_busy && c->extra_streams.empty() && int32_t(c->frame_seq - need) >= 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spin = 0;; ++spin) {
-          if (int32_t(*c->started - need) >= 0) { waited = true; break; }
-          if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;  // (something else holds the queue: wait for all of it)
-        }
-      }
-      if (!waited) HIP_TRY(sync_stream(c));
-    }
-    const size_t used = s->layout.grid_items + n_items * sizeof(uint16_t);  // (the sections' spare room is not sent)
-    std::memcpy(sl.host, img, used);
-    HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host, used, hipMemcpyHostToDevice, s->ctx->copy));
-    HIP_TRY(hipStreamSynchronize(s->ctx->copy));
-    s->current = slot;
-    ++s->revision;
-    s->structure_dirty = false;
-    s->committed = true;
-    return DUST_OK;
-  });
-}
-
-DustStatus dust_hip_top_level_build(const float* boxes, uint32_t n, DustTopLevelInfo* info, uint32_t* cells, size_t cells_capacity, uint16_t* items,
-                                size_t items_capacity, uint32_t* ranges, uint32_t* slot_order) {
-  if (!boxes || !info || n == 0 || n > 65535) return fail(DUST_ERR_INVALID_ARGUMENT, "bad top-level build arguments");
-  STRUCT_TRY(info, "DustTopLevelInfo");
-  return guarded([&]() -> DustStatus {
-    DustHipScene s;   // (a bare scene record: no context, no device: only what build_grid / order_slots read and write)
-    s.world_boxes.assign(boxes, boxes + size_t(n) * 6);
-    for (int a = 0; a < 3; ++a) { s.world_min[a] = 1e30f; s.world_max[a] = -1e30f; }
-    for (uint32_t i = 0; i < n; ++i)
-      for (int a = 0; a < 3; ++a) {
-        if (!(boxes[i * 6 + a] <= boxes[i * 6 + 3 + a])) return fail(DUST_ERR_INVALID_ARGUMENT, "a box with lo > hi (or NaN)");
-        s.world_min[a] = std::min(s.world_min[a], boxes[i * 6 + a]); s.world_max[a] = std::max(s.world_max[a], boxes[i * 6 + 3 + a]);
-      }
-    std::vector<uint32_t> rg;
-    build_grid(&s, s.world_boxes, rg);
-    if (!s.grid_valid) return fail(DUST_ERR_UNSUPPORTED, "more than 4095 boxes over one grid cell: no grid lists them (a scene renders by the packet kernels then)");
-    order_slots(&s);
-    for (int a = 0; a < 3; ++a) { info->dim[a] = s.grid.dim[a]; info->lo[a] = s.grid.lo[a]; info->cell[a] = s.grid.cell[a]; }
-    info->n_cells = uint32_t(s.grid_cells.size());
-    info->n_items = uint32_t(s.grid_items.size());
-    info->n_groups = n > dust::kFlatCullMax ? (n + 63) / 64 : 0;
-    if (cells) { if (cells_capacity < s.grid_cells.size()) return fail(DUST_ERR_INVALID_ARGUMENT, "cells buffer too small"); std::memcpy(cells, s.grid_cells.data(), s.grid_cells.size() * 4); }
-    if (items) { if (items_capacity < s.grid_items.size()) return fail(DUST_ERR_INVALID_ARGUMENT, "items buffer too small"); std::memcpy(items, s.grid_items.data(), s.grid_items.size() * 2); }
-    if (ranges) std::memcpy(ranges, rg.data(), size_t(n) * 8);
-    if (slot_order) std::memcpy(slot_order, s.slot_order.data(), size_t(n) * 4);
-    return DUST_OK;
-  });
 }
 
 static void destroy_pipeline(DustHipPipeline* p) {
@@ -2200,33 +849,6 @@ struct BatchJoin {
 };
 // Follower: frames 0 .. n - 2 of a launch, prepared in order; Lead: frame n - 1 -- prepared last, launches all of them
 enum class FrameRole { Single, Follower, Lead };
-// the scene half of a launch descriptor: the current image's arrays (frames and scene ray queries)
-static void scene_args(const DustHipScene* s, dust::FrameArgs& a) {
-  a.models = reinterpret_cast<const dust::DevModel*>(s->dev(s->layout.models));
-  a.instances = reinterpret_cast<const dust::DevInstance*>(s->dev(s->layout.instances));
-  a.n_models = uint32_t(s->models.size());
-  a.n_instances = uint32_t(s->instances.size());
-  a.n_lds_models = s->n_lds_models;
-  a.root_table = s->dev(s->layout.root_table);
-  a.boxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.boxes));
-  a.visits = reinterpret_cast<const dust::DevVisit*>(s->dev(s->layout.visits));
-  a.grid = s->grid;
-  // (a grid that could not list every box -- build_grid -- is not handed to the kernels at all: the packet kernels, which never read it, run instead)
-  a.grid.cells = s->grid_valid ? reinterpret_cast<const uint32_t*>(s->dev(s->layout.grid_cells)) : nullptr;
-  a.grid.items = s->grid_valid ? reinterpret_cast<const uint16_t*>(s->dev(s->layout.grid_items)) : nullptr;
-  a.enters = reinterpret_cast<const dust::DevEnter*>(s->dev(s->layout.enters));
-  a.gboxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.gboxes));
-  a.sboxes = reinterpret_cast<const dust::DevBox*>(s->dev(s->layout.sboxes));
-  a.n_groups = s->n_groups;
-}
-// a frame or a query reads the scene as committed: refused while it has uncommitted changes or a model was edited since
-static DustStatus check_scene_ready(const DustHipScene* s) {
-  if (!s->committed) return fail(DUST_ERR_NOT_READY, "scene has uncommitted changes (call dust_hip_scene_commit)");
-  for (size_t i = 0; i < s->models.size(); ++i)
-    if (s->models[i]->generation != s->model_generation[i])
-      return fail(DUST_ERR_NOT_READY, "a model of the scene was edited after the last dust_hip_scene_commit");
-  return DUST_OK;
-}
 // every argument check of a frame, before anything is enqueued or changed (a frame that has started is finished); fp_copy: the caller's
 // parameters widened to this library's struct
 static DustStatus check_frame(DustHipPipeline* p, const DustHipScene* s, const DustHipCamera* cam, const DustHipSky* sky,
@@ -2758,206 +1380,6 @@ DustStatus dust_hip_render_frames(uint32_t n_frames, DustHipPipeline* const* pip
   });
 }
 
-// Scene ray queries (query.hip). Enqueued on the context's stream as a frame is: the launch reads the scene image's current slot, which
-// touch() marks, so that a commit DustHipScene::kImages commits later does not overwrite it while the query may still read it.
-static DustStatus check_query(const DustHipScene* s, const void* in, const void* out, uint32_t flags, const void* out2 = reinterpret_cast<const void*>(1)) {
-  if (!s || !in || !out || !out2) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  if (flags & ~DUST_HIP_QUERY_ANY_HIT) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown query flags");
-  return check_scene_ready(s);
-}
-// what a query launch shares: the pair of device counters (allocated once), the scene half of the descriptor, the scene image slot marked
-static hipError_t query_launch_args(DustHipScene* s, dust::FrameArgs& a) {
-  DustHipContext* ctx = s->ctx;
-  if (!ctx->query_counters.p) {
-    hipError_t e = ctx->query_counters.alloc(2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->query_counters.p, 0, 2 * sizeof(unsigned long long), ctx->stream);
-    if (e != hipSuccess) return e;
-  }
-  s->touch();
-  scene_args(s, a);
-  for (const DustHipModel* m : s->models) a.deep |= m->dev.n_levels == 3 ? 1u : 0u;
-  return hipSuccess;
-}
-static DustStatus trace_rays_impl(DustHipScene* s, const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, uint32_t flags) {
-  DustHipContext* ctx = s->ctx;
-  HIP_TRY(hipSetDevice(ctx->device));
-  dust::FrameArgs a{};
-  HIP_TRY(query_launch_args(s, a));
-  unsigned long long* counters = static_cast<unsigned long long*>(ctx->query_counters.p);
-  dust::QueryArgs q;
-  q.rays = reinterpret_cast<const float*>(d_rays);
-  q.hits = reinterpret_cast<uint32_t*>(d_hits);
-  q.n = n;
-  q.any_hit = (flags & DUST_HIP_QUERY_ANY_HIT) ? 1u : 0u;
-  q.counter = counters + ctx->query_parity;
-  q.next_counter = counters + (ctx->query_parity ^ 1u);
-  // persistent 1024-thread workgroups, at most one per CU (each stages the roots once); a picking query is one small workgroup
-  const uint32_t block = n >= 1024u ? 1024u : (n + 63u) / 64u * 64u;
-  const uint32_t grid = std::min<uint32_t>(uint32_t(ctx->num_cus), (n + 1023u) / 1024u);
-  HIP_TRY(dust::launch_ray_query(a, q, grid, block, ctx->stream));
-  ctx->query_parity ^= 1u;
-  return DUST_OK;
-}
-DustStatus dust_hip_scene_trace_rays(DustHipScene* s, const DustHipRay* rays, DustHipRayHit* hits, uint32_t n, uint32_t flags) {
-  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
-  if (n == 0) return DUST_OK;  // (whatever the arrays)
-  { DustStatus cs = check_query(s, rays, hits, flags); if (cs != DUST_OK) return cs; }
-  return guarded([&]() -> DustStatus {
-    DustHipContext* c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = size_t(n) * sizeof(DustHipRay);
-    static_assert(sizeof(DustHipRay) == sizeof(DustHipRayHit), "one staging size for rays and hits");
-    if (c->query_rays.bytes < bytes || !c->query_rays.p || !c->query_hits.p) {  // grown on demand, kept until the context goes
-      if (c->query_rays.alloc(bytes) != hipSuccess || c->query_hits.alloc(bytes) != hipSuccess) {
-        c->query_rays.release(); c->query_hits.release();
-        (void)hipGetLastError();
-        return fail(DUST_ERR_OUT_OF_MEMORY, "device staging for the query's rays and hits");
-      }
-    }
-    HIP_TRY(hipMemcpyAsync(c->query_rays.p, rays, bytes, hipMemcpyHostToDevice, c->stream));
-    const DustStatus st = trace_rays_impl(s, static_cast<const DustHipRay*>(c->query_rays.p), static_cast<DustHipRayHit*>(c->query_hits.p), n, flags);
-    if (st != DUST_OK) return st;
-    HIP_TRY(hipMemcpyAsync(hits, c->query_hits.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DUST_OK;
-  });
-}
-DustStatus dust_hip_scene_trace_rays_async(DustHipScene* s, const DustHipRay* d_rays, DustHipRayHit* d_hits, uint32_t n, uint32_t flags) {
-  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
-  if (n == 0) return DUST_OK;  // (whatever the arrays)
-  { DustStatus cs = check_query(s, d_rays, d_hits, flags); if (cs != DUST_OK) return cs; }
-  if ((reinterpret_cast<uintptr_t>(d_rays) | reinterpret_cast<uintptr_t>(d_hits)) & 15u)
-    return fail(DUST_ERR_INVALID_ARGUMENT, "the ray and hit arrays must be 16-byte aligned (the kernel moves records as 16-byte vectors)");
-  return guarded([&]() -> DustStatus { return trace_rays_impl(s, d_rays, d_hits, n, flags); });
-}
-
-// Scene box queries (overlap.hip): the same launch protocol as the ray queries (their counters, the scene image slot marked)
-static DustStatus overlap_boxes_impl(DustHipScene* s, const DustHipBoxQuery* d_boxes, uint32_t n, uint32_t* d_counts, DustHipVoxelRef* d_records,
-                                     uint32_t n_records, uint32_t flags) {
-  DustHipContext* ctx = s->ctx;
-  HIP_TRY(hipSetDevice(ctx->device));
-  dust::FrameArgs a{};
-  HIP_TRY(query_launch_args(s, a));
-  unsigned long long* counters = static_cast<unsigned long long*>(ctx->query_counters.p);
-  dust::OverlapArgs o{};
-  o.boxes = reinterpret_cast<const float*>(d_boxes);
-  o.counts = d_counts;
-  o.records = reinterpret_cast<uint32_t*>(d_records);
-  o.n = n;
-  o.n_records = n_records;
-  o.any_hit = (flags & DUST_HIP_QUERY_ANY_HIT) ? 1u : 0u;
-  o.counter = counters + ctx->query_parity;
-  o.next_counter = counters + (ctx->query_parity ^ 1u);
-  // a wave per query, kOverlapChunk queries per trip to the counter; persistent workgroups, up to 8 per CU; a single query is one wave
-  const uint32_t waves = (n + dust::kOverlapChunk - 1u) / dust::kOverlapChunk;
-  const uint32_t block = waves >= dust::kOverlapWaves ? dust::kOverlapWaves * 64u : waves * 64u;
-  const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(uint32_t(ctx->num_cus) * 8u, (waves + dust::kOverlapWaves - 1u) / dust::kOverlapWaves));
-  HIP_TRY(dust::launch_overlap_boxes(a, o, grid, block, ctx->stream));
-  ctx->query_parity ^= 1u;
-  return DUST_OK;
-}
-DustStatus dust_hip_scene_overlap_boxes(DustHipScene* s, const DustHipBoxQuery* boxes, uint32_t n, uint32_t* counts, DustHipVoxelRef* records,
-                                        uint32_t n_records, uint32_t flags) {
-  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
-  if (n == 0) return DUST_OK;  // (whatever the arrays)
-  { DustStatus cs = check_query(s, boxes, counts, flags, n_records ? static_cast<const void*>(records) : counts); if (cs != DUST_OK) return cs; }
-  for (uint32_t i = 0; i < n; ++i)  // every slice inside the records, before anything is launched
-    if (boxes[i].capacity && uint64_t(boxes[i].first) + boxes[i].capacity > n_records)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "a box query's slice [first, first + capacity) runs past n_records");
-  return guarded([&]() -> DustStatus {
-    DustHipContext* c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t box_bytes = size_t(n) * sizeof(DustHipBoxQuery), count_bytes = size_t(n) * sizeof(uint32_t);
-    const size_t rec_bytes = size_t(std::max<uint32_t>(n_records, 1u)) * sizeof(DustHipVoxelRef);
-    auto grow = [](DeviceBuffer& b, size_t bytes) { return b.p && b.bytes >= bytes ? hipSuccess : b.alloc(bytes); };  // kept until the context goes
-    if (grow(c->overlap_boxes, box_bytes) != hipSuccess || grow(c->overlap_counts, count_bytes) != hipSuccess ||
-        grow(c->overlap_records, rec_bytes) != hipSuccess) {
-      c->overlap_boxes.release(); c->overlap_counts.release(); c->overlap_records.release();
-      (void)hipGetLastError();
-      return fail(DUST_ERR_OUT_OF_MEMORY, "device staging for the box queries, their counts and records");
-    }
-    DustHipVoxelRef* d_rec = static_cast<DustHipVoxelRef*>(c->overlap_records.p);
-    HIP_TRY(hipMemcpyAsync(c->overlap_boxes.p, boxes, box_bytes, hipMemcpyHostToDevice, c->stream));
-    // slots past a query's count are left as the caller has them: the records go up, and come back, whole
-    if (n_records) HIP_TRY(hipMemcpyAsync(d_rec, records, size_t(n_records) * sizeof(DustHipVoxelRef), hipMemcpyHostToDevice, c->stream));
-    const DustStatus st = overlap_boxes_impl(s, static_cast<const DustHipBoxQuery*>(c->overlap_boxes.p), n, static_cast<uint32_t*>(c->overlap_counts.p),
-                                             d_rec, n_records, flags);
-    if (st != DUST_OK) return st;
-    HIP_TRY(hipMemcpyAsync(counts, c->overlap_counts.p, count_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (n_records) HIP_TRY(hipMemcpyAsync(records, d_rec, size_t(n_records) * sizeof(DustHipVoxelRef), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DUST_OK;
-  });
-}
-DustStatus dust_hip_scene_overlap_boxes_async(DustHipScene* s, const DustHipBoxQuery* d_boxes, uint32_t n, uint32_t* d_counts, DustHipVoxelRef* d_records,
-                                              uint32_t n_records, uint32_t flags) {
-  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
-  if (n == 0) return DUST_OK;  // (whatever the arrays)
-  { DustStatus cs = check_query(s, d_boxes, d_counts, flags, n_records ? static_cast<const void*>(d_records) : d_counts); if (cs != DUST_OK) return cs; }
-  if ((reinterpret_cast<uintptr_t>(d_boxes) | reinterpret_cast<uintptr_t>(d_records)) & 15u)
-    return fail(DUST_ERR_INVALID_ARGUMENT, "the box and record arrays must be 16-byte aligned (the kernel moves records as 16-byte vectors)");
-  return guarded([&]() -> DustStatus { return overlap_boxes_impl(s, d_boxes, n, d_counts, d_records, n_records, flags); });
-}
-
-// Scene box sweeps (sweep.hip): the box queries' launch protocol and shape
-static DustStatus sweep_boxes_impl(DustHipScene* s, const DustHipBoxSweep* d_sweeps, DustHipSweepHit* d_hits, uint32_t n, uint32_t flags) {
-  DustHipContext* ctx = s->ctx;
-  HIP_TRY(hipSetDevice(ctx->device));
-  dust::FrameArgs a{};
-  HIP_TRY(query_launch_args(s, a));
-  unsigned long long* counters = static_cast<unsigned long long*>(ctx->query_counters.p);
-  dust::SweepArgs o{};
-  o.sweeps = reinterpret_cast<const float*>(d_sweeps);
-  o.hits = reinterpret_cast<uint32_t*>(d_hits);
-  o.n = n;
-  o.any_hit = (flags & DUST_HIP_QUERY_ANY_HIT) ? 1u : 0u;
-  o.ignore_start = (flags & DUST_HIP_SWEEP_IGNORE_START) ? 1u : 0u;
-  o.counter = counters + ctx->query_parity;
-  o.next_counter = counters + (ctx->query_parity ^ 1u);
-  // a wave per query, kSweepChunk queries per trip to the counter; persistent workgroups, up to 8 per CU; a single query is one wave
-  const uint32_t waves = (n + dust::kSweepChunk - 1u) / dust::kSweepChunk;
-  const uint32_t block = waves >= dust::kSweepWaves ? dust::kSweepWaves * 64u : waves * 64u;
-  const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(uint32_t(ctx->num_cus) * 8u, (waves + dust::kSweepWaves - 1u) / dust::kSweepWaves));
-  HIP_TRY(dust::launch_sweep_boxes(a, o, grid, block, ctx->stream));
-  ctx->query_parity ^= 1u;
-  return DUST_OK;
-}
-static DustStatus check_sweep(const DustHipScene* s, const void* sweeps, const void* hits, uint32_t flags) {
-  if (!sweeps || !hits) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  if (flags & ~(DUST_HIP_QUERY_ANY_HIT | DUST_HIP_SWEEP_IGNORE_START)) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown sweep flags");
-  return check_scene_ready(s);
-}
-DustStatus dust_hip_scene_sweep_boxes(DustHipScene* s, const DustHipBoxSweep* sweeps, DustHipSweepHit* hits, uint32_t n, uint32_t flags) {
-  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
-  if (n == 0) return DUST_OK;  // (whatever the arrays)
-  { DustStatus cs = check_sweep(s, sweeps, hits, flags); if (cs != DUST_OK) return cs; }
-  return guarded([&]() -> DustStatus {
-    DustHipContext* c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t sweep_bytes = size_t(n) * sizeof(DustHipBoxSweep), hit_bytes = size_t(n) * sizeof(DustHipSweepHit);
-    auto grow = [](DeviceBuffer& b, size_t bytes) { return b.p && b.bytes >= bytes ? hipSuccess : b.alloc(bytes); };  // kept until the context goes
-    if (grow(c->sweep_queries, sweep_bytes) != hipSuccess || grow(c->sweep_hits, hit_bytes) != hipSuccess) {
-      c->sweep_queries.release(); c->sweep_hits.release();
-      (void)hipGetLastError();
-      return fail(DUST_ERR_OUT_OF_MEMORY, "device staging for the box sweeps and their hits");
-    }
-    HIP_TRY(hipMemcpyAsync(c->sweep_queries.p, sweeps, sweep_bytes, hipMemcpyHostToDevice, c->stream));
-    const DustStatus st = sweep_boxes_impl(s, static_cast<const DustHipBoxSweep*>(c->sweep_queries.p), static_cast<DustHipSweepHit*>(c->sweep_hits.p), n, flags);
-    if (st != DUST_OK) return st;
-    HIP_TRY(hipMemcpyAsync(hits, c->sweep_hits.p, hit_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DUST_OK;
-  });
-}
-DustStatus dust_hip_scene_sweep_boxes_async(DustHipScene* s, const DustHipBoxSweep* d_sweeps, DustHipSweepHit* d_hits, uint32_t n, uint32_t flags) {
-  if (!s) return fail(DUST_ERR_INVALID_ARGUMENT, "null scene");
-  if (n == 0) return DUST_OK;  // (whatever the arrays)
-  { DustStatus cs = check_sweep(s, d_sweeps, d_hits, flags); if (cs != DUST_OK) return cs; }
-  if ((reinterpret_cast<uintptr_t>(d_sweeps) | reinterpret_cast<uintptr_t>(d_hits)) & 15u)
-    return fail(DUST_ERR_INVALID_ARGUMENT, "the sweep and hit arrays must be 16-byte aligned (the kernel moves them as 16-byte vectors)");
-  return guarded([&]() -> DustStatus { return sweep_boxes_impl(s, d_sweeps, d_hits, n, flags); });
-}
-
 DustStatus dust_hip_pipeline_pass_stats(DustHipPipeline* p, uint32_t pass, DustHipPassStats* out) {
   if (!p || !out || pass > 5) return fail(DUST_ERR_INVALID_ARGUMENT, "bad pass index");
   std::memset(out, 0, sizeof(*out));
@@ -3290,7 +1712,7 @@ DustStatus dust_hip_pipeline_clear(DustHipPipeline* p) {
 
 // ---- what comm.hip needs of the handles (capi_internal.hpp)
 namespace dust_internal {
-DustStatus set_error(DustStatus status, const std::string& message) { return fail(status, message); }
+DustStatus set_error(DustStatus status, const std::string& message) { g_last_error = message; return status; }
 hipStream_t context_stream(DustHipContext* c) { return c->stream; }
 int context_device(DustHipContext* c) { return c->device; }
 void context_retain(DustHipContext* c) { retain(c); }

@@ -1,0 +1,686 @@
+// capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the device hierarchy build, device-side voxel and shape
+// edits (edit.hip) and model islands (island.hip).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <unordered_set>
+
+#include "capi_internal.hpp"
+#include "vdb.hpp"
+#include "edit.hpp"
+#include "island.hpp"
+
+// ------------------------------------------------------------------ device hierarchy build
+namespace {
+
+struct N16Builder {
+  std::vector<uint8_t> bytes;  // kN16Bytes per node
+  uint8_t* node(size_t i) { return bytes.data() + i * dust::kN16Bytes; }
+  size_t add() {
+    bytes.resize(bytes.size() + dust::kN16Bytes, 0);
+    return bytes.size() / dust::kN16Bytes - 1;
+  }
+  void finish(size_t i, uint32_t child_base) {  // rank prefix per 64-bit word + base of the first child
+    uint64_t* mask = reinterpret_cast<uint64_t*>(node(i));
+    uint16_t* pre = reinterpret_cast<uint16_t*>(node(i) + 512);
+    uint32_t run = 0;
+    for (int w = 0; w < 64; ++w) {
+      pre[w] = static_cast<uint16_t>(run);
+      run += static_cast<uint32_t>(__builtin_popcountll(mask[w]));
+    }
+    std::memcpy(node(i) + 640, &child_base, 4);
+  }
+};
+
+// Builds root / l2 / mid arrays from blocks given in Tree::iter_leaf order (depth-first, ascending bits).
+DustStatus build_hierarchy(const DustHipBlock* blocks, uint32_t n, uint32_t extent_log2, N16Builder& root,
+                           N16Builder& l2, std::vector<dust::DevN4>& mid, std::vector<uint64_t>& dense_mask,
+                           float bmin[3], float bmax[3]) {
+  const bool deep = extent_log2 == 12;
+  const uint32_t extent = 1u << extent_log2;
+  root.add();
+  uint64_t prev_key = 0;
+  int64_t cur_l2 = -1, cur_mid = -1;
+  uint32_t cur_l2_cell = 0xFFFFFFFFu, cur_mid_cell = 0xFFFFFFFFu;
+  for (int a = 0; a < 3; ++a) { bmin[a] = 1e30f; bmax[a] = -1e30f; }
+  auto idx16 = [](uint32_t x, uint32_t y, uint32_t z) { return (x << 8) | (y << 4) | z; };
+  for (uint32_t i = 0; i < n; ++i) {
+    const DustHipBlock& b = blocks[i];
+    if ((b.x & 3) || (b.y & 3) || (b.z & 3) || b.x >= extent || b.y >= extent || b.z >= extent)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "block position is not a 4-aligned coordinate inside the tree extent");
+    if (b.mask == 0) return fail(DUST_ERR_INVALID_ARGUMENT, "block with empty occupancy mask");
+    // depth-first order key: per level, x slowest (node/internal.rs:78-81)
+    uint64_t key = 0;
+    const uint32_t shifts_deep[3] = {8, 4, 2}, bits_deep[3] = {4, 4, 2};
+    const uint32_t shifts_std[2] = {4, 2}, bits_std[2] = {4, 2};
+    const uint32_t* sh = deep ? shifts_deep : shifts_std;
+    const uint32_t* bt = deep ? bits_deep : bits_std;
+    const int nl = deep ? 3 : 2;
+    for (int l = 0; l < nl; ++l) {
+      const uint32_t m = (1u << bt[l]) - 1;
+      key = (key << (3 * bt[l])) | (uint64_t(((b.x >> sh[l]) & m)) << (2 * bt[l])) | (uint64_t((b.y >> sh[l]) & m) << bt[l]) |
+            uint64_t((b.z >> sh[l]) & m);
+    }
+    if (i > 0 && key <= prev_key)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "blocks are not in Tree::iter_leaf order (depth-first, ascending child bits)");
+    prev_key = key;
+    const float p[3] = {float(b.x), float(b.y), float(b.z)};
+    for (int a = 0; a < 3; ++a) {
+      bmin[a] = std::min(bmin[a], p[a]);
+      bmax[a] = std::max(bmax[a], p[a] + 4.0f);
+    }
+    // descend, creating nodes on first touch (children of a node are contiguous because of the order)
+    size_t n16 = 0;           // node holding the 16-cell bit
+    N16Builder* holder = &root;
+    if (deep) {
+      const uint32_t cell = idx16(b.x >> 8, b.y >> 8, b.z >> 8);
+      if (cell != cur_l2_cell) {
+        cur_l2 = int64_t(l2.add());
+        cur_l2_cell = cell;
+        dust::vdb::bit_set(reinterpret_cast<uint64_t*>(root.node(0)), cell, true);
+        cur_mid_cell = 0xFFFFFFFFu;
+      }
+      holder = &l2;
+      n16 = size_t(cur_l2);
+    }
+    const uint32_t cell16 = idx16((b.x >> 4) & 15, (b.y >> 4) & 15, (b.z >> 4) & 15);
+    const uint32_t mid_cell_key = deep ? uint32_t(cur_l2) * 4096u + cell16 : cell16;
+    if (mid_cell_key != cur_mid_cell) {
+      dust::vdb::bit_set(reinterpret_cast<uint64_t*>(holder->node(n16)), cell16, true);
+      dust::DevN4 nd{0, 0, i, 0};
+      mid.push_back(nd);
+      cur_mid = int64_t(mid.size()) - 1;
+      cur_mid_cell = mid_cell_key;
+    }
+    const uint32_t bit = (((b.x >> 2) & 3) << 4) | (((b.y >> 2) & 3) << 2) | ((b.z >> 2) & 3);
+    if (bit < 32) mid[size_t(cur_mid)].mask_lo |= 1u << bit;
+    else mid[size_t(cur_mid)].mask_hi |= 1u << (bit - 32);
+    if (dense_mask.size() < mid.size() * 64) dense_mask.resize(mid.size() * 64, 0);
+    dense_mask[size_t(cur_mid) * 64 + bit] = b.mask;
+  }
+  // prefixes and child bases: children were appended in order, so base = running count
+  if (deep) {
+    root.finish(0, 0);
+    uint32_t run = 0;
+    for (size_t i = 0; i < l2.bytes.size() / dust::kN16Bytes; ++i) {
+      l2.finish(i, run);
+      const uint64_t* mask = reinterpret_cast<const uint64_t*>(l2.node(i));
+      for (int w = 0; w < 64; ++w) run += uint32_t(__builtin_popcountll(mask[w]));
+    }
+  } else {
+    root.finish(0, 0);
+  }
+  if (n == 0) { for (int a = 0; a < 3; ++a) { bmin[a] = 0.0f; bmax[a] = 0.0f; } }
+  return DUST_OK;
+}
+
+}  // namespace
+
+void release(const DustHipModel* cm) {
+  DustHipModel* m = const_cast<DustHipModel*>(cm);
+  if (!m || m->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+  DustHipContext* c = m->ctx;
+  (void)hipSetDevice(c->device);
+  (void)sync_stream(c);  // launches that read the arrays are done before they go
+  delete m;
+  release(c);
+}
+
+extern "C" {
+
+DustStatus dust_hip_model_create(DustHipContext* ctx, const DustHipBlock* blocks, uint32_t n_blocks,
+                                 const uint8_t* materials, uint64_t n_materials, const uint8_t* palette,
+                                 uint32_t tree_extent_log2, DustHipModel** out) {
+  if (!ctx || !out || (!blocks && n_blocks) || (!materials && n_materials) || !palette)
+    return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (tree_extent_log2 != 8 && tree_extent_log2 != 12)
+    return fail(DUST_ERR_INVALID_ARGUMENT, "tree_extent_log2 must be 8 (hierarchy 4,2,2) or 12 (hierarchy 4,4,2,2)");
+  return guarded([&]() -> DustStatus {
+    N16Builder root, l2;
+    std::vector<dust::DevN4> mid;
+    std::vector<uint64_t> dense_mask;
+    float bmin[3], bmax[3];
+    DustStatus s = build_hierarchy(blocks, n_blocks, tree_extent_log2, root, l2, mid, dense_mask, bmin, bmax);
+    if (s != DUST_OK) return s;
+    for (uint32_t i = 0; i < n_blocks; ++i) {
+      const uint64_t need = uint64_t(blocks[i].material_ptr) + uint64_t(__builtin_popcountll(blocks[i].mask));
+      if (need > n_materials) return fail(DUST_ERR_INVALID_ARGUMENT, "block material_ptr runs past the material buffer");
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    // (owned through the reference count from here on: an early return releases it, and with it the context reference)
+    struct Drop { DustHipModel* m; ~Drop() { release(m); } } owner{new DustHipModel};
+    DustHipModel* m = owner.m;
+    m->ctx = retain(ctx);
+    const hipStream_t up = ctx->stream;
+    HIP_TRY(m->root.upload(root.bytes.data(), root.bytes.size(), up));
+    m->host_root.assign(root.bytes.begin(), root.bytes.begin() + dust::kN16LdsBytes);
+    HIP_TRY(m->l2.upload(l2.bytes.data(), l2.bytes.size(), up));
+    if (tree_extent_log2 == 12) {  // the per-cell table the DEEP kernel variants look 16-cells up in: {mid index, child mask} per cell
+      const size_t n_l2 = l2.bytes.size() / dust::kN16Bytes;
+      std::vector<dust::DevL2Cell> cells(n_l2 * 4096, dust::DevL2Cell{0xFFFFFFFFu, 0u, 0ull});
+      for (size_t i = 0; i < n_l2; ++i) {
+        const uint64_t* mask = reinterpret_cast<const uint64_t*>(l2.node(i));
+        uint32_t base;
+        std::memcpy(&base, l2.node(i) + 640, 4);
+        uint32_t run = base;  // children of a node are contiguous, in ascending bit order
+        for (uint32_t w = 0; w < 64; ++w)
+          for (uint64_t bits = mask[w]; bits; bits &= bits - 1) {
+            dust::DevL2Cell& c = cells[i * 4096 + w * 64 + uint32_t(__builtin_ctzll(bits))];
+            c.mid = run;
+            c.child_mask = (uint64_t(mid[run].mask_hi) << 32) | mid[run].mask_lo;
+            uint32_t lo[3] = {3, 3, 3}, hi[3] = {0, 0, 0};
+            for (uint64_t cm = c.child_mask; cm; cm &= cm - 1) {
+              const uint32_t b = uint32_t(__builtin_ctzll(cm)), xyz[3] = {b >> 4, (b >> 2) & 3u, b & 3u};
+              for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], xyz[k]); hi[k] = std::max(hi[k], xyz[k]); }
+            }
+            c.bounds = lo[0] | (lo[1] << 2) | (lo[2] << 4) | (hi[0] << 6) | (hi[1] << 8) | (hi[2] << 10);
+            ++run;
+          }
+      }
+      HIP_TRY(m->l2_cells.upload(cells.data(), cells.size() * sizeof(dust::DevL2Cell), up));
+    }
+    HIP_TRY(m->mid.upload(mid.data(), mid.size() * sizeof(dust::DevN4), up));
+    HIP_TRY(m->dense_mask.upload(dense_mask.data(), dense_mask.size() * 8, up));
+    HIP_TRY(m->blocks.upload(blocks, size_t(n_blocks) * sizeof(DustHipBlock), up));
+    HIP_TRY(m->materials.upload(materials, size_t(n_materials), up));
+    m->has_material_255 = n_materials && std::memchr(materials, 255, size_t(n_materials)) != nullptr;
+    uint32_t pal[256];
+    std::memset(pal, 0, sizeof(pal));
+    std::memcpy(pal, palette, 255 * 4);  // loader.rs:214-218: entries 0..254
+    HIP_TRY(m->palette.upload(pal, sizeof(pal), up));
+    dust::DevModel& d = m->dev;
+    d.root = static_cast<const uint8_t*>(m->root.p);
+    d.l2 = tree_extent_log2 == 12 ? static_cast<const uint8_t*>(m->l2.p) : nullptr;
+    d.l2_cells = tree_extent_log2 == 12 ? static_cast<const dust::DevL2Cell*>(m->l2_cells.p) : nullptr;
+    d.mid = static_cast<const dust::DevN4*>(m->mid.p);
+    d.dense_mask = static_cast<const uint64_t*>(m->dense_mask.p);
+    d.blocks = static_cast<const DustHipBlock*>(m->blocks.p);
+    d.materials = static_cast<const uint8_t*>(m->materials.p);
+    d.palette = static_cast<const uint32_t*>(m->palette.p);
+    std::memcpy(d.bmin, bmin, sizeof(bmin));
+    std::memcpy(d.bmax, bmax, sizeof(bmax));
+    d.extent = 1u << tree_extent_log2;
+    d.n_levels = tree_extent_log2 == 12 ? 3 : 2;
+    d.n_blocks = n_blocks;
+    d.lds_slot = -1;
+    m->n_materials = n_materials;
+    *out = retain(m);  // the caller's reference (the guard drops the builder's)
+    return DUST_OK;
+  });
+}
+void dust_hip_model_destroy(DustHipModel* m) { release(m); }  // (a scene that instances it keeps it alive)
+
+// ---------------------------------------------------------------- device-side edits (edit.hip)
+namespace {
+float linear2srgb_host(float c) { return c <= 0.0031308f ? 12.92f * c : 1.055f * std::pow(c, 1.0f / 2.4f) - 0.055f; }  // geometry.rs:99-105
+
+DustStatus ensure_srgb_lut(DustHipContext* ctx) {
+  if (ctx->srgb_lut.p) return DUST_OK;
+  std::vector<uint16_t> lut(size_t(64) * dust::kSrgbRow, 0);
+  for (uint32_t n = 1; n <= 64; ++n) {
+    const float denom = float(n) * 255.0f;
+    for (uint32_t sum = 0; sum <= n * 255u; ++sum)
+      lut[size_t(n - 1) * dust::kSrgbRow + sum] = uint16_t(uint32_t(linear2srgb_host(float(sum) / denom) * 1023.0f));
+  }
+  HIP_TRY(ctx->srgb_lut.upload(lut.data(), lut.size() * 2, ctx->stream));
+  return DUST_OK;
+}
+
+dust::EditArgs edit_args(DustHipModel* m, EditState& st) {
+  dust::EditArgs e{};
+  e.grid = static_cast<uint8_t*>(st.grid.p);
+  e.brick_mask = static_cast<uint64_t*>(st.brick_mask.p);
+  e.flag_leaf = static_cast<uint32_t*>(st.flag_leaf.p);
+  e.count_major = static_cast<uint32_t*>(st.count_major.p);
+  e.scan_tmp = static_cast<uint32_t*>(st.scan_tmp.p);
+  e.blocks = static_cast<DustHipBlock*>(m->blocks.p);
+  e.materials = static_cast<uint8_t*>(m->materials.p);
+  e.palette = static_cast<const uint32_t*>(m->palette.p);
+  e.srgb_lut = static_cast<const uint16_t*>(m->ctx->srgb_lut.p);
+  e.root = static_cast<uint8_t*>(m->root.p);
+  e.mid = static_cast<dust::DevN4*>(m->mid.p);
+  e.dense_mask = static_cast<uint64_t*>(m->dense_mask.p);
+  e.header = static_cast<dust::EditHeader*>(st.header.p);
+  return e;
+}
+
+// run the rebuild kernels and bring the model record up to date (sizes, bounds, the root the scene stages in LDS)
+DustStatus rebuild_and_refresh(DustHipModel* m, EditState& es) {
+  hipStream_t st = m->ctx->stream;
+  HIP_TRY(dust::launch_edit_rebuild(edit_args(m, es), st));
+  dust::EditHeader h{};
+  HIP_TRY(hipMemcpyAsync(&h, es.header.p, sizeof(h), hipMemcpyDeviceToHost, st));
+  m->host_root.resize(dust::kN16LdsBytes);
+  HIP_TRY(hipMemcpyAsync(m->host_root.data(), m->root.p, dust::kN16LdsBytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  m->dev.n_blocks = h.n_blocks;
+  m->n_materials = h.n_materials;
+  std::memcpy(m->dev.bmin, h.bmin, sizeof(h.bmin));
+  std::memcpy(m->dev.bmax, h.bmax, sizeof(h.bmax));
+  m->generation += 1;
+  return DUST_OK;
+}
+
+// first edit: move the model into full-capacity buffers and expand its voxels into the dense grid. The model becomes
+// editable (m->edit set) only when every step has succeeded: a failure leaves it exactly as it was.
+DustStatus editable_kind(const DustHipModel* m) {
+  if (m->dev.extent != 256) return fail(DUST_ERR_UNSUPPORTED, "device-side edits cover hierarchy (4,2,2) models (256^3); rebuild larger trees with dust_hip_model_create");
+  if (m->has_material_255) return fail(DUST_ERR_UNSUPPORTED, "the model holds material byte 255 (the edit grid stores palette index + 1 in a byte; dust_hip_model_set_voxels takes 0..254)");
+  return DUST_OK;
+}
+// (`rebuild` false: the caller fills the grid and rebuilds itself -- a model born editable, dust_hip_model_detach_islands)
+DustStatus make_editable(DustHipModel* m, bool rebuild = true) {
+  if (m->edit) return DUST_OK;
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  s = ensure_srgb_lut(m->ctx);
+  if (s != DUST_OK) return s;
+  hipStream_t st = m->ctx->stream;
+  std::unique_ptr<EditState> e(new EditState);
+  const size_t L = dust::kLattice;
+  HIP_TRY(e->grid.alloc(L * 64));
+  HIP_TRY(hipMemsetAsync(e->grid.p, 0, L * 64, st));
+  HIP_TRY(e->brick_mask.alloc(L * 8));
+  HIP_TRY(e->flag_leaf.alloc(L * 4));
+  HIP_TRY(e->count_major.alloc(L * 4));
+  HIP_TRY(e->scan_tmp.alloc(512 * 4));
+  HIP_TRY(e->header.alloc(sizeof(dust::EditHeader)));
+  DeviceBuffer blocks, materials, mid, dense_mask;
+  HIP_TRY(blocks.alloc(L * sizeof(DustHipBlock)));
+  HIP_TRY(materials.alloc(L * 64));
+  HIP_TRY(mid.alloc(4096 * sizeof(dust::DevN4)));
+  HIP_TRY(dense_mask.alloc(size_t(4096) * 64 * 8));
+  dust::EditArgs a = edit_args(m, *e);  // (expand only writes the grid)
+  HIP_TRY(dust::launch_edit_expand(a, static_cast<const DustHipBlock*>(m->blocks.p), static_cast<const uint8_t*>(m->materials.p), m->dev.n_blocks, st));
+  HIP_TRY(sync_stream(m->ctx));  // every launch that reads the old arrays is done (both streams of the context)
+  auto swap_all = [&] {
+    std::swap(m->blocks.p, blocks.p); std::swap(m->blocks.bytes, blocks.bytes);
+    std::swap(m->materials.p, materials.p); std::swap(m->materials.bytes, materials.bytes);
+    std::swap(m->mid.p, mid.p); std::swap(m->mid.bytes, mid.bytes);
+    std::swap(m->dense_mask.p, dense_mask.p); std::swap(m->dense_mask.bytes, dense_mask.bytes);
+    m->dev.mid = static_cast<const dust::DevN4*>(m->mid.p);
+    m->dev.dense_mask = static_cast<const uint64_t*>(m->dense_mask.p);
+    m->dev.blocks = static_cast<const DustHipBlock*>(m->blocks.p);
+    m->dev.materials = static_cast<const uint8_t*>(m->materials.p);
+  };
+  swap_all();
+  // the same voxels, now in the full-capacity arrays (bumps the generation: scenes holding the old addresses commit again)
+  s = rebuild ? rebuild_and_refresh(m, *e) : DUST_OK;
+  if (s != DUST_OK) { swap_all(); return s; }  // back to the tightly sized originals, untouched
+  m->edit = std::move(e);
+  return DUST_OK;
+}
+
+DustStatus upload_batch(DustHipModel* m, const uint32_t* xyz, const int32_t* values, uint32_t n, bool with_values) {
+  EditState& e = *m->edit;
+  DustStatus s = grow(m->ctx, e.xyz, size_t(n) * 12);
+  if (s == DUST_OK) s = grow(m->ctx, e.values, size_t(n) * 4);
+  if (s != DUST_OK) return s;
+  HIP_TRY(hipMemcpyAsync(e.xyz.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, m->ctx->stream));
+  if (with_values) HIP_TRY(hipMemcpyAsync(e.values.p, values, size_t(n) * 4, hipMemcpyHostToDevice, m->ctx->stream));
+  return DUST_OK;
+}
+}  // namespace
+
+DustStatus dust_hip_model_set_voxels(DustHipModel* m, const uint32_t* xyz, const int32_t* values, uint32_t n) {
+  if (!m || (n && (!xyz || !values))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (xyz[i * 3] >= m->dev.extent || xyz[i * 3 + 1] >= m->dev.extent || xyz[i * 3 + 2] >= m->dev.extent)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
+    if (values[i] > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxel)");
+  }
+  return guarded([&]() -> DustStatus {
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    HIP_TRY(join_side(m->ctx));  // (a surfel pass on the second stream still traces the model as it is)
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK || n == 0) return s;
+    // a voxel named more than once takes its LAST value (what a sequence of set calls would leave): keep the last entry
+    std::vector<uint32_t> ux;
+    std::vector<int32_t> uv;
+    std::unordered_set<uint32_t> seen;
+    ux.reserve(size_t(n) * 3); uv.reserve(n);
+    for (uint32_t k = n; k-- > 0;) {
+      const uint32_t key = (xyz[k * 3] << 16) | (xyz[k * 3 + 1] << 8) | xyz[k * 3 + 2];
+      if (!seen.insert(key).second) continue;
+      ux.push_back(xyz[k * 3]); ux.push_back(xyz[k * 3 + 1]); ux.push_back(xyz[k * 3 + 2]);
+      uv.push_back(values[k]);
+    }
+    const uint32_t un = uint32_t(uv.size());
+    m->edit->labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
+    s = upload_batch(m, ux.data(), uv.data(), un, true);
+    if (s != DUST_OK) return s;
+    dust::EditArgs a = edit_args(m, *m->edit);
+    a.xyz = static_cast<const uint32_t*>(m->edit->xyz.p);
+    a.values = static_cast<const int32_t*>(m->edit->values.p);
+    a.n_edits = un;
+    HIP_TRY(dust::launch_edit_apply(a, false, m->ctx->stream));
+    return rebuild_and_refresh(m, *m->edit);  // synchronises: the host vectors above stay alive until the copies are done
+  });
+}
+
+// ---- shape edits (edit.hip k_edit_shapes)
+namespace {
+constexpr size_t kShapeChunkIds = size_t(1) << 21;  // cell-list entries (u16) one launch carries: 4 MiB, 512 whole-tree shapes
+
+// The caller's record -> the device's: the two grid bytes of the operation and conservative voxel bounds -- the shape's extent
+// padded by more than a voxel (the float32 formulas stay within a small fraction of a voxel of the real distance for
+// coordinates up to 65 536), clipped to the tree. false: the shape covers nothing.
+bool device_shape(const DustHipEditShape& s, dust::DevEditShape& d) {
+  const bool box = s.kind == DUST_HIP_SHAPE_BOX, sphere = s.kind == DUST_HIP_SHAPE_SPHERE;
+  double lo[3], hi[3];
+  for (int r = 0; r < 3; ++r) {
+    if (!std::isfinite(s.a[r]) || (!sphere && !std::isfinite(s.b[r]))) return false;
+    if (box) {
+      if (s.a[r] > s.b[r]) return false;
+      lo[r] = s.a[r]; hi[r] = s.b[r];
+    } else {
+      if (!std::isfinite(s.radius) || s.radius < 0.0f || s.radius > 65536.0f) return false;
+      if (std::fabs(s.a[r]) > 65536.0f || (!sphere && std::fabs(s.b[r]) > 65536.0f)) return false;
+      const double p = s.a[r], q = sphere ? p : double(s.b[r]);
+      lo[r] = std::min(p, q) - double(s.radius); hi[r] = std::max(p, q) + double(s.radius);
+    }
+  }
+  uint32_t vlo[3], vhi[3];
+  for (int r = 0; r < 3; ++r) {  // voxel x is covered when lo <= x + 0.5 <= hi
+    const double l = std::floor(lo[r] - 0.5) - 1.0, h = std::ceil(hi[r] - 0.5) + 1.0;
+    if (l > 255.0 || h < 0.0) return false;
+    vlo[r] = l < 0.0 ? 0u : uint32_t(l);
+    vhi[r] = h > 255.0 ? 255u : uint32_t(h);
+  }
+  std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.b, s.b, sizeof(d.b));
+  d.kind = s.kind;
+  d.radius = box ? 0.0f : s.radius;
+  if (sphere) std::memcpy(d.b, s.a, sizeof(d.b));
+  const uint32_t byte = uint32_t(s.palette) + 1u;
+  switch (s.op) {
+    case DUST_HIP_EDIT_CARVE: d.solid_to = 0; d.empty_to = 0; break;
+    case DUST_HIP_EDIT_FILL: d.solid_to = byte; d.empty_to = byte; break;
+    case DUST_HIP_EDIT_PAINT: d.solid_to = byte; d.empty_to = 0; break;
+    default: d.solid_to = dust::kEditKeep; d.empty_to = byte; break;  // PLACE
+  }
+  d.lo = vlo[0] | (vlo[1] << 8) | (vlo[2] << 16);
+  d.hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
+  return true;
+}
+inline size_t shape_cells(const dust::DevEditShape& d) {  // root cells (16^3 voxels) the bounds reach
+  size_t n = 1;
+  for (int r = 0; r < 3; ++r) n *= size_t((((d.hi >> (8 * r)) & 255u) >> 4) - (((d.lo >> (8 * r)) & 255u) >> 4) + 1u);
+  return n;
+}
+}  // namespace
+
+DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* shapes, uint32_t n, uint32_t* changed) {
+  if (!m || (n && !shapes)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (n > DUST_HIP_MAX_EDIT_SHAPES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_EDIT_SHAPES shapes in one call");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (shapes[i].kind > DUST_HIP_SHAPE_CAPSULE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown shape kind");
+    if (shapes[i].op > DUST_HIP_EDIT_PLACE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown edit op");
+    if (shapes[i].op != DUST_HIP_EDIT_CARVE && (shapes[i].palette < 0 || shapes[i].palette > 254))
+      return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254");
+  }
+  return guarded([&]() -> DustStatus {
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    HIP_TRY(join_side(m->ctx));
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK || n == 0) return s;
+    EditState& es = *m->edit;
+    es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
+    hipStream_t st = m->ctx->stream;
+    // the shapes that cover something, in call order: `index` maps them back to the caller's
+    std::vector<dust::DevEditShape> dev;
+    std::vector<uint32_t> index;
+    dev.reserve(n); index.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      dust::DevEditShape d{};
+      if (device_shape(shapes[i], d)) { dev.push_back(d); index.push_back(i); }
+    }
+    const size_t live = dev.size();
+    std::vector<uint32_t> counts(live, 0u);
+    if (live) {
+      if ((s = grow(m->ctx, es.shapes, live * sizeof(dust::DevEditShape))) != DUST_OK) return s;
+      if ((s = grow(m->ctx, es.changed, live * 4)) != DUST_OK) return s;
+      HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), live * sizeof(dust::DevEditShape), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
+    }
+    // Order-preserving chunks, each one launch: its shapes binned into the 4096 root cells, an ascending list of u16 shape
+    // ids per cell in CSR form, one workgroup per non-empty cell. A chunk ends where its lists would pass kShapeChunkIds.
+    std::vector<uint32_t> cells, starts, fill(4096);
+    std::vector<uint16_t> ids;
+    for (size_t c0 = 0; c0 < live;) {
+      size_t c1 = c0, total = 0;
+      while (c1 < live && c1 - c0 < 65536 && (c1 == c0 || total + shape_cells(dev[c1]) <= kShapeChunkIds)) total += shape_cells(dev[c1++]);
+      std::fill(fill.begin(), fill.end(), 0u);
+      auto each_cell = [&](const dust::DevEditShape& d, auto&& f) {
+        for (uint32_t x = (d.lo & 255u) >> 4; x <= (d.hi & 255u) >> 4; ++x)
+          for (uint32_t y = ((d.lo >> 8) & 255u) >> 4; y <= ((d.hi >> 8) & 255u) >> 4; ++y)
+            for (uint32_t z = (d.lo >> 16) >> 4; z <= (d.hi >> 16) >> 4; ++z) f((x << 8) | (y << 4) | z);
+      };
+      for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ++fill[cell]; });
+      if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
+      cells.clear(); starts.clear();
+      uint32_t run = 0;
+      for (uint32_t cell = 0; cell < 4096; ++cell) {
+        const uint32_t k = fill[cell];
+        fill[cell] = run;  // where the cell's next id goes
+        if (k) { cells.push_back(cell); starts.push_back(run); run += k; }
+      }
+      starts.push_back(run);
+      ids.resize(run);
+      for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
+      if ((s = grow(m->ctx, es.shape_cells, cells.size() * 4)) != DUST_OK) return s;
+      if ((s = grow(m->ctx, es.shape_starts, starts.size() * 4)) != DUST_OK) return s;
+      if ((s = grow(m->ctx, es.shape_ids, ids.size() * 2)) != DUST_OK) return s;
+      HIP_TRY(hipMemcpyAsync(es.shape_cells.p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(es.shape_starts.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(es.shape_ids.p, ids.data(), ids.size() * 2, hipMemcpyHostToDevice, st));
+      dust::EditShapeArgs a{};
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.shapes = static_cast<const dust::DevEditShape*>(es.shapes.p) + c0;
+      a.cells = static_cast<const uint32_t*>(es.shape_cells.p);
+      a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
+      a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
+      a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
+      a.n_cells = uint32_t(cells.size());
+      HIP_TRY(dust::launch_edit_shapes(a, st));
+      c0 = c1;
+    }
+    if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
+    s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
+    if (s != DUST_OK) return s;
+    if (changed) {
+      std::fill(changed, changed + n, 0u);
+      for (size_t k = 0; k < live; ++k) changed[index[k]] = counts[k];
+    }
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_get_voxels(DustHipModel* m, const uint32_t* xyz, int32_t* values, uint32_t n) {
+  if (!m || (n && (!xyz || !values))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  for (uint32_t i = 0; i < n; ++i)
+    if (xyz[i * 3] >= m->dev.extent || xyz[i * 3 + 1] >= m->dev.extent || xyz[i * 3 + 2] >= m->dev.extent)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
+  return guarded([&]() -> DustStatus {
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    HIP_TRY(join_side(m->ctx));
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK || n == 0) return s;
+    s = upload_batch(m, xyz, nullptr, n, false);
+    if (s != DUST_OK) return s;
+    dust::EditArgs a = edit_args(m, *m->edit);
+    a.xyz = static_cast<const uint32_t*>(m->edit->xyz.p);
+    a.values_out = static_cast<int32_t*>(m->edit->values.p);
+    a.n_edits = n;
+    HIP_TRY(dust::launch_edit_apply(a, true, m->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(values, m->edit->values.p, size_t(n) * 4, hipMemcpyDeviceToHost, m->ctx->stream));
+    HIP_TRY(sync_stream(m->ctx));
+    return DUST_OK;
+  });
+}
+
+// ---- model islands (island.hip): label the grid's connected voxels, look labels up, move whole islands into a model of their own
+static_assert(sizeof(DustHipIslandQuery) == 32 && sizeof(DustHipIsland) == 40 && sizeof(DustHipIsland) == sizeof(dust::DevIsland), "island records");
+
+DustStatus dust_hip_model_find_islands(DustHipModel* m, const DustHipIslandQuery* q, uint32_t* n_islands, DustHipIsland* islands, uint32_t capacity) {
+  if (!m || !q || !n_islands || (!islands && capacity)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipIslandQuery");
+  if (q->connectivity > DUST_HIP_ISLANDS_CORNERS) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown island connectivity");
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    const uint32_t corners = q->connectivity == DUST_HIP_ISLANDS_CORNERS ? 1u : 0u;
+    // a labelling that still stands (no edit since; detached islands only left it) is not computed again: a count-only call followed by
+    // a call with room for every record labels once
+    const bool relabel = !(es.labels_valid && es.labels_corners == corners);
+    es.labels_valid = false;  // until this labelling is complete
+    if (!es.labels.p) {
+      const hipError_t e = es.labels.alloc(size_t(dust::kIslandKeys) * 4);
+      if (e != hipSuccess) { es.labels.release(); return hip_fail(e, "the island label array (64 MiB)"); }
+    }
+    if ((s = grow(ctx, ctx->island_mask, size_t(dust::kIslandRows) * 8)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->island_count, size_t(dust::kIslandRows) * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->island_tmp, 260 * 4)) != DUST_OK) return s;
+    dust::IslandArgs a{};
+    a.grid = static_cast<const uint8_t*>(es.grid.p);
+    a.label = static_cast<uint32_t*>(es.labels.p);
+    a.root_mask = static_cast<uint64_t*>(ctx->island_mask.p);
+    a.root_count = static_cast<uint32_t*>(ctx->island_count.p);
+    a.scan_tmp = static_cast<uint32_t*>(ctx->island_tmp.p);
+    a.corners = corners;
+    for (int r = 0; r < 3; ++r) { a.anchor_lo[r] = q->anchor_lo[r]; a.anchor_hi[r] = std::min(q->anchor_hi[r], 255u); }
+    HIP_TRY(dust::launch_island_label(a, relabel, st));
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, a.scan_tmp + 256, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    a.capacity = std::min(total, capacity);
+    if (a.capacity) {
+      if ((s = grow(ctx, ctx->island_acc, size_t(a.capacity) * sizeof(dust::IslandAcc))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->island_records, size_t(a.capacity) * sizeof(dust::DevIsland))) != DUST_OK) return s;
+      a.acc = static_cast<dust::IslandAcc*>(ctx->island_acc.p);
+      a.records = static_cast<dust::DevIsland*>(ctx->island_records.p);
+      HIP_TRY(hipMemsetAsync(a.acc, 0, size_t(a.capacity) * sizeof(dust::IslandAcc), st));
+      HIP_TRY(dust::launch_island_records(a, st));
+      HIP_TRY(hipMemcpyAsync(islands, a.records, size_t(a.capacity) * sizeof(dust::DevIsland), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    es.labels_valid = true;
+    es.labels_corners = corners;
+    *n_islands = total;
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_island_of(DustHipModel* m, const uint32_t* xyz, uint32_t* keys, uint32_t n) {
+  if (!m || (n && (!xyz || !keys))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  for (uint32_t i = 0; i < n; ++i)
+    if (xyz[i * 3] >= 256u || xyz[i * 3 + 1] >= 256u || xyz[i * 3 + 2] >= 256u)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
+  if (!m->edit || !m->edit->labels_valid)
+    return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)");
+  if (n == 0) return DUST_OK;
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((s = grow(ctx, ctx->stage_in, size_t(n) * 12)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_out, size_t(n) * 4)) != DUST_OK) return s;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(dust::launch_island_lookup(static_cast<const uint32_t*>(m->edit->labels.p), static_cast<const uint32_t*>(ctx->stage_in.p),
+                                       static_cast<uint32_t*>(ctx->stage_out.p), n, st));
+    HIP_TRY(hipMemcpyAsync(keys, ctx->stage_out.p, size_t(n) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, uint32_t n, uint32_t flags, DustHipModel** out) {
+  if (!m || (n && !keys)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (flags & ~DUST_HIP_DETACH_KEEP_SOURCE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown detach flags");
+  const bool keep = (flags & DUST_HIP_DETACH_KEEP_SOURCE) != 0;
+  if (keep && !out) return fail(DUST_ERR_INVALID_ARGUMENT, "DUST_HIP_DETACH_KEEP_SOURCE without a model to receive the islands does nothing");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (n == 0) { if (out) *out = nullptr; return DUST_OK; }
+  if (!m->edit || !m->edit->labels_valid)
+    return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)");
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    // which keys name an island: a bit per selected key, and the number of keys that name none
+    if ((s = grow(ctx, ctx->island_mask, size_t(dust::kIslandRows) * 8)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->island_tmp, 260 * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_in, size_t(n) * 4)) != DUST_OK) return s;
+    uint32_t* bad_dev = static_cast<uint32_t*>(ctx->island_tmp.p) + 257;
+    HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, keys, size_t(n) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ctx->island_mask.p, 0, size_t(dust::kIslandRows) * 8, st));
+    HIP_TRY(hipMemsetAsync(bad_dev, 0, 4, st));
+    HIP_TRY(dust::launch_island_select(static_cast<const uint32_t*>(es.labels.p), static_cast<const uint32_t*>(ctx->stage_in.p), n,
+                                       static_cast<uint64_t*>(ctx->island_mask.p), bad_dev, st));
+    uint32_t bad = 0;
+    uint32_t pal[256];
+    HIP_TRY(hipMemcpyAsync(&bad, bad_dev, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pal, m->palette.p, sizeof(pal), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(DUST_ERR_INVALID_ARGUMENT, "a key does not name an island of the model's current labelling");
+    // the new model: empty, editable, its grid filled by the detach kernel and then rebuilt like any edit
+    struct Drop { DustHipModel* m; ~Drop() { release(m); } } fresh{nullptr};
+    if (out) {
+      s = dust_hip_model_create(ctx, nullptr, 0, nullptr, 0, reinterpret_cast<const uint8_t*>(pal), 8, &fresh.m);
+      if (s == DUST_OK) s = make_editable(fresh.m, false);
+      if (s != DUST_OK) return s;
+    }
+    dust::IslandDetachArgs a{};
+    a.src = static_cast<uint8_t*>(es.grid.p);
+    a.dst = fresh.m ? static_cast<uint8_t*>(fresh.m->edit->grid.p) : nullptr;
+    a.label = static_cast<uint32_t*>(es.labels.p);
+    a.selected = static_cast<const uint64_t*>(ctx->island_mask.p);
+    // copy first and build the new model from the copy; the source is carved only once the voxels have somewhere to live, so a failure
+    // up to there leaves it as it was
+    if (fresh.m) {
+      a.carve = 0u;
+      HIP_TRY(dust::launch_island_detach(a, st));
+      if ((s = rebuild_and_refresh(fresh.m, *fresh.m->edit)) != DUST_OK) return s;
+    }
+    if (!keep) {
+      a.dst = nullptr;
+      a.carve = 1u;
+      HIP_TRY(dust::launch_island_detach(a, st));
+      // (whole islands left: the labelling of the rest stands.) A failure in here is that of a shape edit's rebuild: the grid is
+      // changed, the arrays are not; the new model is dropped with the error
+      if ((s = rebuild_and_refresh(m, es)) != DUST_OK) { es.labels_valid = false; return s; }
+    }
+    if (out) *out = retain(fresh.m);  // the caller's reference (the guard drops the builder's)
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_info(const DustHipModel* m, uint32_t* n_blocks, uint64_t* n_materials) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  if (n_blocks) *n_blocks = m->dev.n_blocks;
+  if (n_materials) *n_materials = m->n_materials;
+  return DUST_OK;
+}
+
+DustStatus dust_hip_model_read(const DustHipModel* m, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  if ((blocks && block_capacity < m->dev.n_blocks) || (materials && material_capacity < m->n_materials))
+    return fail(DUST_ERR_INVALID_ARGUMENT, "destination too small (see dust_hip_model_info)");
+  HIP_TRY(hipSetDevice(m->ctx->device));
+  const hipStream_t st = m->ctx->stream;
+  if (blocks && m->dev.n_blocks) HIP_TRY(hipMemcpyAsync(blocks, m->blocks.p, size_t(m->dev.n_blocks) * sizeof(DustHipBlock), hipMemcpyDeviceToHost, st));
+  if (materials && m->n_materials) HIP_TRY(hipMemcpyAsync(materials, m->materials.p, size_t(m->n_materials), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DUST_OK;
+}
+
+}  // extern "C"

@@ -83,8 +83,6 @@ DustStatus nccl_fail(ncclResult_t e, const char* what) {
   return set_error(DUST_ERR_HIP, std::string(what) + ": " + (r ? r->GetErrorString(e) : "rccl error"));
 }
 #endif
-DustStatus hip_fail(hipError_t e, const char* what) { return set_error(DUST_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(e_, #expr); } while (0)
 #define NCCL_TRY(expr) do { ncclResult_t e_ = (expr); if (e_ != ncclSuccess) return nccl_fail(e_, #expr); } while (0)
 #define DUST_TRY(expr) do { DustStatus s_ = (expr); if (s_ != DUST_OK) return s_; } while (0)
 

@@ -262,7 +262,7 @@ struct FrameArgs {
   // A frame's FIRST traversal launch on the context's stream says that it has started: workgroup 0 writes `started_seq` into a word of
   // pinned host memory (null: this launch says nothing). Launches of one stream run one after the other, so the host then knows that
   // every earlier frame of the stream is done -- which is how dust_hip_scene_commit recycles a scene image without waiting for the
-  // whole queue when the host runs a ring of commits ahead (capi.cpp).
+  // whole queue when the host runs a ring of commits ahead (capi_scene.cpp).
   DUST_RW(uint32_t) started_word;
   uint32_t started_seq;
   // ---- round 6, appended: the surfel TRACE sharded over the ranks of an N-GPU job (DustHipFrameParams::surfel_rank / surfel_world).

@@ -13,7 +13,7 @@
 //   k_edit_emit_blocks   Block records (position, mask, material_ptr, avg_albedo) + the compacted material stream
 //   k_edit_upper_levels  root mask / rank prefixes, mid nodes, dense_mask, tight bounds, counts (one workgroup)
 // The result is, array for array, what dust_hip_model_create builds on the host from the same voxels
-// (loader.rs:244-274 + collector.rs + geometry.rs:68-128 + capi.cpp build_hierarchy): tests compare them byte for byte.
+// (loader.rs:244-274 + collector.rs + geometry.rs:68-128 + capi_model.cpp build_hierarchy): tests compare them byte for byte.
 // avg_albedo's linear->sRGB curve is a table the HOST evaluates (the same powf the host-side flatten calls), indexed by
 // (voxel count, colour sum): the device only adds and looks up, so not one bit depends on a device transcendental.
 #include <hip/hip_runtime.h>
@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(256) k_edit_emit_blocks(EditArgs e) {
   e.blocks[index] = b;
 }
 
-// root node, mid nodes, dense_mask, bounds: one workgroup of 1024 threads, four root cells each (capi.cpp build_hierarchy)
+// root node, mid nodes, dense_mask, bounds: one workgroup of 1024 threads, four root cells each (capi_model.cpp build_hierarchy)
 __global__ void __launch_bounds__(1024) k_edit_upper_levels(EditArgs e) {
   __shared__ uint32_t part[1024];
   __shared__ uint64_t root_mask[64];
@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(1024) k_edit_upper_levels(EditArgs e) {
   }
 }
 
-// ------------------------------------------------------------------ launchers (capi.cpp)
+// ------------------------------------------------------------------ launchers (capi_model.cpp)
 hipError_t launch_edit_expand(const EditArgs& e, const DustHipBlock* blocks, const uint8_t* materials, uint32_t n_blocks, hipStream_t s) {
   if (n_blocks) hipLaunchKernelGGL(k_edit_expand, dim3((n_blocks * 64u + 255u) / 256u), dim3(256), 0, s, e, blocks, materials, n_blocks);
   return hipGetLastError();

@@ -1,4 +1,4 @@
-// edit.hpp -- interface between the host runtime (capi.cpp) and the device-side tree rebuild (edit.hip).
+// edit.hpp -- interface between the host runtime (capi_model.cpp) and the device-side tree rebuild (edit.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -293,7 +293,7 @@ __global__ void __launch_bounds__(256) k_island_detach(IslandDetachArgs a) {
   }
 }
 
-// ------------------------------------------------------------------ launchers (capi.cpp)
+// ------------------------------------------------------------------ launchers (capi_model.cpp)
 hipError_t launch_island_label(const IslandArgs& a, bool relabel, hipStream_t s) {
   if (relabel) {
     hipLaunchKernelGGL(k_island_local, dim3(kLattice / 4), dim3(256), 0, s, a);

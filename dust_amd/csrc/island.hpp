@@ -1,4 +1,4 @@
-// island.hpp -- interface between the host runtime (capi.cpp) and the connected-component labelling of an editable model (island.hip).
+// island.hpp -- interface between the host runtime (capi_model.cpp) and the connected-component labelling of an editable model (island.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(1024, 4) k_ray_query(const FrameArgs, const Qu
   }
 }
 
-// grid, block: the host's choice (capi.cpp trace_rays_impl); the dynamic LDS is the staged roots
+// grid, block: the host's choice (capi_scene.cpp trace_rays_impl); the dynamic LDS is the staged roots
 hipError_t launch_ray_query(const FrameArgs& a, const QueryArgs& q, uint32_t grid, uint32_t block, hipStream_t s) {
   const size_t lds = (size_t)a.n_lds_models * kN16LdsBytes;
   switch ((a.deep ? 2 : 0) | (a.n_groups ? 4 : 0)) {

@@ -1,4 +1,4 @@
-// query.hpp -- the launch of the scene ray queries (query.hip), as the host runtime (capi.cpp) calls it
+// query.hpp -- the launch of the scene ray queries (query.hip), as the host runtime (capi_scene.cpp) calls it
 #pragma once
 #include <hip/hip_runtime.h>
 

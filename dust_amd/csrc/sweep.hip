@@ -643,7 +643,7 @@ __global__ void __launch_bounds__(kSweepWaves * 64) k_sweep_boxes(const FrameArg
   }
 }
 
-// grid, block: the host's choice (capi.cpp sweep_boxes_impl); no dynamic LDS
+// grid, block: the host's choice (capi_scene.cpp sweep_boxes_impl); no dynamic LDS
 hipError_t launch_sweep_boxes(const FrameArgs& a, const SweepArgs& o, uint32_t grid, uint32_t block, hipStream_t s) {
   switch ((a.deep ? 2 : 0) | (a.n_groups ? 4 : 0)) {
     case 0: hipLaunchKernelGGL(k_sweep_boxes<0>, dim3(grid), dim3(block), 0, s, a, o); break;

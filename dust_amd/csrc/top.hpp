@@ -9,7 +9,7 @@ namespace dust {
 // instances of a cell are taken in list order; an instance is skipped when the PREVIOUS cell of the path lies inside the block
 // of cells the instance is listed in: it was dealt with there. (The cells of a block that lie on a monotone path are
 // consecutive, so "listed in the previous cell" is the same as "listed in any earlier cell"; the block rides in the box
-// record's spare words.) Boxes are grown by kGridMargin of the scene's size when they are listed (capi.cpp, build_grid): far
+// record's spare words.) Boxes are grown by kGridMargin of the scene's size when they are listed (capi_scene.cpp, build_grid): far
 // more than the rounding of the cell steps, so a ray that grazes a cell the steps skipped meets no box listed only there.
 enum : uint32_t { RS_EMPTY = 0, RS_FETCH, RS_NEXT, RS_TOP, RS_BEGIN, RS_WALK, RS_DONE };
 constexpr uint32_t kNoCell = 0xFFFFFFFFu;
