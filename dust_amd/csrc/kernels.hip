@@ -346,7 +346,19 @@ __device__ __forceinline__ void view_run_packet(ArgsRef a, const DUST_CONST_AS F
   const Range3 org = wave_range(live, loc);
   V3 payload = mk(0, 0, 0);
   PROF_LEAVE(P_AO_SETUP);
+  // ONE AO cull per tile and run. The members' AO rays leave from the same points (org) with the same reach (8) and differ only in direction, so the
+  // list is built once, at k = 1, for EVERY unit direction: the cube [-1, 1]^3 widened by a hair (normalize3's components end within 3 ulp of
+  // [-1, 1]: three roundings in the dot product, halved by the root, one in the root, one in the division; 1.000001f is 1 + 8 ulp), which leaves of
+  // cull_instances' test "the box lies within Chebyshev distance 8 of the box of the tile's hit points". A superset of every member's own list with
+  // entry times no later than the member's own, so trace_ray's walk and its early exit stay conservative and the texels are what they were (the order
+  // of a list decides the work, not the hit). 64 cosine directions already fill most of the cube: the lists are hardly longer than a member's own.
+  // Nothing between two members' traces writes the wave's list, the sort staging or a LARGE scene's group mask behind it: cull_instances is their
+  // only writer, trace_ray takes them as const, and the wave takes no new tile (next_packet, the tile accounts) before the loop is done.
+  Range3 cube;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) { cube.lo[q] = -1.000001f; cube.hi[q] = 1.000001f; }
   Hit h;
+  uint32_t ncand = 0;
 #pragma unroll 1
   for (uint32_t k = 0; k <= run; ++k) {
     ArgsRef b = reload_args(a);
@@ -363,7 +375,7 @@ __device__ __forceinline__ void view_run_packet(ArgsRef a, const DUST_CONST_AS F
     const bool act = k == 0u ? sun_live : live;
     const V3 dir = k == 0u ? sd : ad;
     const float tmax = k == 0u ? 10000.0f : 8.0f;
-    const uint32_t ncand = cull_instances<MODE>(b, __any(act), org, k == 0u ? point_range(sd) : wave_range(live, ad), tmax, cand);
+    if (k <= 1u) ncand = cull_instances<MODE>(b, __any(act), org, k == 0u ? point_range(sd) : cube, tmax, cand);   // k >= 2: member 0's list
     LaneStats cur = {0, 0, 0, 0, 0, 0};
     trace_ray<1, MODE>(b, act, loc, dir, 0.1f, tmax, k == 0u, cand, ncand, h, cur);
     __builtin_amdgcn_wave_barrier();

@@ -3,6 +3,9 @@
 
   python tools/kernel_sections.py --build      # here (cross-compiles dust_amd/libdust_hip_prof.so, which travels with gpurun)
   gpurun -- 'python tools/kernel_sections.py [--deep]'  # on the GPU box (--deep: the 4096^3 stress tree instead of the castle)
+  --frames-per-launch K: the primary + AO table is that of ONE launch of K same-view frames (dust_hip_render_frames: k_primary_ao_runs), as
+                         bench.py's headline runs them; the GI kernels' tables stay a single frame's
+  --lib PATH:            another -DDUST_PROFILE build than dust_amd/libdust_hip_prof.so (a parent revision's, for a before / after pair)
 
   DUST_HIP_DEBUG=$(( (cycles / 1024) << 12 )) python tools/kernel_sections.py   # k_surfel_trace: only the work items that took at least
                                                         # `cycles` (of this instrumented build) stay in the buckets: what the longest items are made of
@@ -25,6 +28,9 @@ if "--build" in sys.argv:
     print("built", PROF_LIB, "(delete it afterwards: it travels with every gpurun push)")
     sys.exit(0)
 
+if "--lib" in sys.argv:
+    PROF_LIB = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
+K = int(sys.argv[sys.argv.index("--frames-per-launch") + 1]) if "--frames-per-launch" in sys.argv else 1
 os.environ["DUST_HIP_LIB"] = PROF_LIB
 from dust_amd import scenes as P  # noqa: E402
 from dust_amd import _lib as L, api, synth  # noqa: E402
@@ -112,6 +118,20 @@ def main():
         pipe.render(scene, cam, sky, full, f, synth.frame_rand(1, f))
     ctx.sync()
     read(lib)
+    if K > 1:   # the headline's launch: K frames of this view with frame indices and rands of their own, the camera and sun rays traced once
+        pipes = [pipe]
+        for _ in range(K - 1):
+            pipes.append(api.StandardPipeline(ctx, W, H))
+            pipes[-1].set_noise(5, synth.stbn_unitvec3_cosine())
+        pao = L.PASS_PRIMARY | L.PASS_AMBIENT_OCCLUSION
+        for first in (5, 5 + K, 5 + 2 * K):   # (the first launches measure the tile order the later ones run in)
+            idx = [first + i for i in range(K)]
+            ctx.sync()
+            read(lib)
+            api.StandardPipeline.render_frames(pipes, scene, cam, sky, pao, idx, [synth.frame_rand(1, v) for v in idx])
+            ctx.sync()
+            b = read(lib)
+        report(f"k_primary_ao_runs ({K} same-view frames in one launch: camera + sun once, AO per frame)", b, pipe.pass_stats(0).ms)
     for title, passes, slot in (("k_primary_ao (fused primary + sun + AO)", L.PASS_PRIMARY | L.PASS_AMBIENT_OCCLUSION, 0),
                                 ("k_final_gather", L.PASS_FINAL_GATHER, 3), ("k_surfel_trace", L.PASS_SURFEL, 4)):
         pipe.render(scene, cam, sky, passes, 5, synth.frame_rand(1, 5))
