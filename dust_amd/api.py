@@ -292,7 +292,10 @@ class Context:
         L.check(self._lib.dust_hip_sync(self._h))
 
     def device_eval(self, fn, rows, out_words):
-        """dust_hip_device_eval: rows is an (n, in_words) array of 32-bit words (float32 or uint32); returns (n, out_words) uint32."""
+        """dust_hip_device_eval: rows is an (n, in_words) array of 32-bit words (float32 or uint32); returns (n, out_words) uint32.
+        The functions and their rows are tabulated in include/dust_hip.h: 0..2 the brick walks, 3..11 the codecs, 12..14 the sorters, 15 sky and
+        16 sun radiance of a direction (the 56 floats of the sky state in rows 0..18, three to a row; those rows come back zero), 17 the albedo
+        modulation, 18 the spatial hash's fingerprint and location, 19 its insert on a three-entry probe window."""
         rows = np.ascontiguousarray(rows)
         assert rows.dtype.itemsize == 4 and rows.ndim == 2
         out = np.zeros((rows.shape[0], out_words), np.uint32)

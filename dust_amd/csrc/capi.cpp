@@ -43,7 +43,8 @@ constexpr uint32_t kTileOrderMaxBand = 65536;  // (kernels.hip)
 hipError_t launch_tile_order(const uint32_t* cost, uint32_t* order, uint32_t* cuts, bool reuse_cuts, uint32_t total, uint32_t per, hipStream_t s);
 hipError_t launch_cost_blend(const uint32_t* raw, uint32_t* smooth, uint32_t total, uint32_t keep_shift, hipStream_t s);
 hipError_t launch_cost_dilate(const uint32_t* in, uint32_t* out, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s);
-hipError_t launch_device_eval(uint32_t fn, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words, uint32_t n, hipStream_t s);
+hipError_t launch_device_eval(uint32_t fn, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words, uint32_t n, const float* sky,
+                              hipStream_t s);
 }  // namespace dust
 
 namespace {
@@ -1590,10 +1591,14 @@ DustStatus dust_hip_pipeline_exposure(DustHipPipeline* p, float* avg_luminance, 
 }
 DustStatus dust_hip_device_eval(DustHipContext* ctx, uint32_t fn, const uint32_t* in, uint32_t in_words, uint32_t* out,
                                 uint32_t out_words, uint32_t n) {
-  static const uint32_t kWords[15][2] = {{9, 3}, {9, 3}, {9, 3}, {3, 1}, {1, 3}, {4, 1}, {1, 3}, {4, 2}, {2, 4}, {4, 1}, {3, 4}, {6, 3}, {2, 2}, {1, 1}, {1, 2}};
-  if (!ctx || !in || !out || fn >= 15) return fail(DUST_ERR_INVALID_ARGUMENT, "bad device function");
+  static const uint32_t kWords[20][2] = {{9, 3}, {9, 3}, {9, 3}, {3, 1}, {1, 3}, {4, 1}, {1, 3}, {4, 2}, {2, 4}, {4, 1}, {3, 4}, {6, 3}, {2, 2}, {1, 1}, {1, 2},
+                                         {3, 3}, {3, 3}, {4, 6}, {5, 2}, {14, 9}};
+  if (!ctx || !in || !out || fn >= 20) return fail(DUST_ERR_INVALID_ARGUMENT, "bad device function");
   if (in_words != kWords[fn][0] || out_words != kWords[fn][1]) return fail(DUST_ERR_INVALID_ARGUMENT, "row width does not match the function");
   if (n == 0) return DUST_OK;
+  // fns 15, 16: the 56 floats of the sky state ride in the first 19 rows (3 words each, the last word padding) and go into the kernel argument
+  const bool with_sky = fn == 15 || fn == 16;
+  if (with_sky && n < 19) return fail(DUST_ERR_INVALID_ARGUMENT, "fns 15 and 16 want the sky state in rows 0..18");
   HIP_TRY(hipSetDevice(ctx->device));
   if (fn == 12) {  // the surfel pass's radix sort on caller-given (key, value) rows, all 32 key bits
     std::vector<uint32_t> k(n), v(n);
@@ -1633,7 +1638,8 @@ DustStatus dust_hip_device_eval(DustHipContext* ctx, uint32_t fn, const uint32_t
   HIP_TRY(din.upload(in, size_t(n) * in_words * 4, ctx->stream));
   HIP_TRY(dout.alloc(size_t(n) * out_words * 4));
   HIP_TRY(hipMemsetAsync(dout.p, 0, size_t(n) * out_words * 4, ctx->stream));
-  HIP_TRY(dust::launch_device_eval(fn, static_cast<const uint32_t*>(din.p), in_words, static_cast<uint32_t*>(dout.p), out_words, n, ctx->stream));
+  HIP_TRY(dust::launch_device_eval(fn, static_cast<const uint32_t*>(din.p), in_words, static_cast<uint32_t*>(dout.p), out_words, n,
+                                   with_sky ? reinterpret_cast<const float*>(in) : nullptr, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   HIP_TRY(copy_wait(out, dout.p, size_t(n) * out_words * 4, hipMemcpyDeviceToHost, ctx->stream));
   return DUST_OK;

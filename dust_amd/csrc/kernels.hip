@@ -574,10 +574,13 @@ struct EvalArgs {
   const uint32_t* in;
   uint32_t* out;
   uint32_t fn, in_words, out_words, n;
+  float sky[56];  // fns 15, 16: the sky state of the call (the leading rows of its input), read as the frame kernels read theirs
 };
+constexpr uint32_t kEvalSkyRows = 19;  // 56 floats in rows of 3 words, the last word padding
 __global__ void __launch_bounds__(256) k_device_eval(EvalArgs e) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= e.n) return;
+  if ((e.fn == 15 || e.fn == 16) && i < kEvalSkyRows) return;  // the state's rows: their output stays zero
   const uint32_t* in = e.in + (size_t)i * e.in_words;
   uint32_t* out = e.out + (size_t)i * e.out_words;
   auto f = [&](int k) { return __uint_as_float(in[k]); };
@@ -620,11 +623,46 @@ __global__ void __launch_bounds__(256) k_device_eval(EvalArgs e) {
       break;
     }
     case 11: put3(rotate_by_normal(mk(f(0), f(1), f(2)), mk(f(3), f(4), f(5)))); break;
+    case 15: case 16: {  // in: dir[3] -> rgb[3], the state through the constant address space off the kernel argument
+      const DUST_CONST_AS EvalArgs& ka = *(const DUST_CONST_AS EvalArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+      const V3 dir = mk(f(0), f(1), f(2));
+      V3 c;  // (inlined here as in the frame kernels: no out-of-line copy of either body joins the code object)
+      if (e.fn == 15) { [[clang::always_inline]] c = sky_radiance(ka.sky, dir); }
+      else { [[clang::always_inline]] c = sun_radiance(ka.sky, dir); }
+      put3(c);
+      break;
+    }
+    case 17: {  // in: r[3], packed avg_albedo -> the three srgb_to_linear results, then the modulated colour
+      const uint32_t p = in[3];
+      put3(mk(srgb_to_linear(div_const((float)((p >> 22) & 1023u), 1023.0f)), srgb_to_linear(div_const((float)((p >> 12) & 1023u), 1023.0f)),
+              srgb_to_linear(div_const((float)((p >> 2) & 1023u), 1023.0f))));
+      const V3 m = modulate_by_avg_albedo(mk(f(0), f(1), f(2)), p);
+      out[3] = __float_as_uint(m.x); out[4] = __float_as_uint(m.y); out[5] = __float_as_uint(m.z);
+      break;
+    }
+    case 18: {  // in: x y z (int32) dir capacity -> fingerprint, location (0 for a capacity of 0)
+      HashKey k;
+      k.x = (int)in[0]; k.y = (int)in[1]; k.z = (int)in[2]; k.dir = in[3];
+      out[0] = key_fingerprint(k);
+      out[1] = in[4] ? key_location(k, in[4]) : 0u;
+      break;
+    }
+    case 19: {  // in: the 9 words of a probe window, fingerprint, value[3], frame_index -> the window after the insert
+      HashWindow win;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) win.w[k] = in[k];
+      hash_insert_window(win, in[9], mk(f(10), f(11), f(12)), in[13]);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) out[k] = win.w[k];
+      break;
+    }
     default: break;
   }
 }
-hipError_t launch_device_eval(uint32_t fn, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words, uint32_t n, hipStream_t s) {
+hipError_t launch_device_eval(uint32_t fn, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words, uint32_t n, const float* sky,
+                              hipStream_t s) {
   EvalArgs e;
+  for (int i = 0; i < 56; ++i) e.sky[i] = sky ? sky[i] : 0.0f;
   e.in = in; e.out = out; e.fn = fn; e.in_words = in_words; e.out_words = out_words; e.n = n;
   hipLaunchKernelGGL(k_device_eval, dim3((n + 255) / 256), dim3(256), 0, s, e);
   return hipGetLastError();

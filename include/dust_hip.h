@@ -804,7 +804,16 @@ DustStatus dust_hip_gi_surfel_exchange_run(DustHipPipeline*, DustHipComm*, uint3
  *   11  rotateVectorByNormal (normal.glsl:31-37)                       n[3] target[3]                    v[3]
  *   12  (not per row) the surfel pass's stable radix sort of the n rows by key    key value              key value
  *   13  (not per row) the cost-ordered hand-out's sorter: the n rows are tile costs in tile order, 8 bands     cycles     tile index
- *   14  (not per row) the same with the bands cut at equal measured cost (what a frame uses), n >= 9           cycles     tile index, cut (the 9 band cuts in rows 0..8) */
+ *   14  (not per row) the same with the bands cut at equal measured cost (what a frame uses), n >= 9           cycles     tile index, cut (the 9 band cuts in rows 0..8)
+ *   15  arhosek_sky_radiance (sky.glsl:18-79)                          dir[3]                            rgb[3]
+ *   16  arhosek_sun_radiance (sky.glsl:81-113)                         dir[3]                            rgb[3]
+ *       15, 16: the 56 floats of the sky state, shared by the rows of a call, ride in rows 0..18 (3 words a row, the last word padding; n >= 19)
+ *       and reach the functions through the kernel argument, as a frame's do; the output rows 0..18 are zero
+ *   17  SRGBToLinear of the block's average albedo and sRGB2AECScg(AECScg2sRGB(r) * albedo) (color.glsl:1-23, final_gather.rchit:68-80)
+ *                                                                      r[3] packed_albedo                albedo[3] rgb[3]
+ *   18  SpatialHashKeyGetFingerprint, ...GetLocation (spatial_hash.glsl:128-142)   x y z (int32) dir capacity   fingerprint location (0 for capacity 0)
+ *   19  SpatialHashInsert (spatial_hash.glsl:147-195) on a copy of the probe window in registers, as the deterministic apply runs it: three
+ *       entries of (fingerprint, radiance, last_accessed_frame | sample_count << 16)   window[9] fingerprint value[3] frame_index   window[9] */
 DustStatus dust_hip_device_eval(DustHipContext*, uint32_t fn, const uint32_t* in, uint32_t in_words, uint32_t* out,
                                 uint32_t out_words, uint32_t n);
 

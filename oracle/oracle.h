@@ -12,7 +12,8 @@
  *   - loader flatten, DDA, shading, sky evaluation, spatial hash: the reference holds no test or
  *     golden vector for them and cannot be built here (Rust nightly + Vulkan RT + shaderc absent),
  *     so for those rows PARITY WITH THE REAL VULKAN OUTPUT IS UNPINNED; parity is defined against
- *     this restatement.
+ *     this restatement. The DDA and the codecs, and the sky, the sun, the hash keys and the hash insert, are held to a second,
+ *     independent numpy witness (tests/golden/make_shader_fixtures.py, tests/radiance_witness.py): two witnesses, still unpinned.
  *   - sky bake: pinned against fixtures generated in-container from the reference's own
  *     dataset.bin / datasetSolar.bin (tests/golden/make_sky_fixtures.py).
  */

@@ -31,8 +31,7 @@ def compare_gi(gi, pipe):
     return int(used.sum()), int(v.sum())
 
 
-@pytest.mark.parametrize("capacity,pool", [(1 << 14, 2048), (97, 777), (16, 333)])
-def test_gi_sequence_matches_oracle(capacity, pool):
+def run_gi_sequence(capacity, pool, frames):
     desc = P.small_scene(seed=5, n_models=2, n_instances=4, size=(28, 28, 28))
     ctx = api.Context(device=0)
     scene = P.hip_scene(ctx, desc)
@@ -48,7 +47,7 @@ def test_gi_sequence_matches_oracle(capacity, pool):
     gi = O.GI(capacity, pool)
     passes = L.PASS_PRIMARY | L.PASS_AMBIENT_OCCLUSION | L.PASS_FINAL_GATHER | L.PASS_SURFEL
     used = valid = 0
-    for f in range(1, 6):
+    for f in frames:
         rnd = synth.frame_rand(1, f)
         pipe.render(scene, cam, sky, passes | L.PASS_GI_ORDERED, frame_index=f, rand=rnd)
         g = P.render_oracle(oscene, cam, sky, w, h, passes, n5[f % 4], rnd, noise0=n0[f % 4], gi=gi, frame_index=f)
@@ -57,6 +56,18 @@ def test_gi_sequence_matches_oracle(capacity, pool):
         used, valid = compare_gi(gi, pipe)
     assert valid > 20
     assert used > 20 or (capacity == 16 and used >= 12)   # the 16-entry table lives on probing + LRU eviction
+
+
+@pytest.mark.parametrize("capacity,pool", [(1 << 14, 2048), (97, 777), (16, 333)])
+def test_gi_sequence_matches_oracle(capacity, pool):
+    run_gi_sequence(capacity, pool, range(1, 6))
+
+
+def test_gi_sequence_across_the_16_bit_stamp_wrap():
+    """last_accessed_frame is 16 bits: from frame 65536 on the stamps written are small again, and to the eviction's
+    `current_frame_index < minFrameIndex` the entries just used look the oldest of their probe window. The crowded 97-entry table
+    through the real apply path, with test_gi_sequence_matches_oracle's assertions."""
+    run_gi_sequence(97, 777, range(65533, 65539))
 
 
 def test_gi_racy_mode_is_statistically_close():
