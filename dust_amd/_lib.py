@@ -166,6 +166,15 @@ NO_ISLAND = 0xFFFFFFFF
 DETACH_KEEP_SOURCE = 1
 
 
+class Stamp(C.Structure):  # DustHipStamp, 32 bytes: a sub-box of a source model, a signed axis permutation and where its image lands in the destination
+    _fields_ = [("offset", C.c_int32 * 3), ("orient", C.c_uint32), ("op", C.c_uint32), ("src_lo", C.c_uint8 * 3), ("pad0", C.c_uint8),
+                ("src_hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+STAMP_PLACE, STAMP_OVERWRITE, STAMP_REPLACE, STAMP_CARVE, STAMP_PAINT = 0, 1, 2, 3, 4
+MAX_STAMPS = 65536
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("rays", C.c_uint64), ("instances_tested", C.c_uint64),
                 ("upper_descents", C.c_uint64), ("mid_descents", C.c_uint64), ("bricks_tested", C.c_uint64),
@@ -225,6 +234,7 @@ SYMBOLS = {
     "dust_hip_model_find_islands": (C.c_int, [_P, _P, _u32p, _P, C.c_uint32]),
     "dust_hip_model_island_of": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_detach_islands": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "dust_hip_model_stamp": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_scene_create": (C.c_int, [_P, C.POINTER(_P)]),

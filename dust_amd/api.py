@@ -35,6 +35,9 @@ assert BOX_SWEEP_DTYPE.itemsize == 48 and SWEEP_HIT_DTYPE.itemsize == 32
 EDIT_SHAPE_DTYPE = np.dtype([("a", "<f4", 3), ("kind", "<u4"), ("b", "<f4", 3), ("radius", "<f4"), ("op", "<u4"), ("palette", "<i4"),
                              ("reserved", "<u4", 2)])
 # DustHipIsland, 40 bytes: one island of dust_hip_model_find_islands
+STAMP_DTYPE = np.dtype([("offset", "<i4", 3), ("orient", "<u4"), ("op", "<u4"), ("src_lo", "u1", 3), ("pad0", "u1"), ("src_hi", "u1", 3), ("pad1", "u1"),
+                        ("reserved", "<u4")])   # DustHipStamp
+ORIENT_IDENTITY = 0x24   # p = (0, 1, 2), no flips
 ISLAND_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("flags", "u1"), ("hi", "u1", 3), ("reserved", "u1"), ("sum", "<u8", 3)])
 FLT_MAX = float(np.finfo(np.float32).max)
 
@@ -390,6 +393,20 @@ class Model:
         piece._ctx, piece._lib, piece._h = self._ctx, self._lib, h
         return piece
 
+    def stamp(self, source, stamps, palette_map=None):
+        """Paste voxels of `source` (another Model of the same context, or this one) into this model (dust_hip_model_stamp): `stamps` a
+        STAMP_DTYPE array (see stamps()), applied in order; every stamp reads the source as it stood when the call began. palette_map:
+        255 palette indices, the index a source voxel of index i arrives with (None: its own). Returns `changed`: per stamp, the
+        voxels whose value it changed. The source is not modified; scenes instancing this model must be committed again afterwards."""
+        stamps = np.ascontiguousarray(stamps, STAMP_DTYPE).reshape(-1)
+        changed = np.zeros(len(stamps), np.uint32)
+        pm = None
+        if palette_map is not None:
+            pm = np.ascontiguousarray(palette_map, np.uint8).reshape(-1)
+            assert len(pm) == 255
+        L.check(self._lib.dust_hip_model_stamp(self._h, source._h, _ptr(stamps), len(stamps), None if pm is None else _ptr(pm), _ptr(changed)))
+        return changed
+
     def read(self):
         """(blocks, materials) as they stand on the device"""
         nb, nm = C.c_uint32(), C.c_uint64()
@@ -555,6 +572,26 @@ def edit_shapes(kind, a, b=None, radius=0.0, op=L.EDIT_CARVE, palette=0):
     shapes["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(a),))
     shapes["palette"] = np.broadcast_to(np.asarray(palette, np.int32), (len(a),))
     return shapes
+
+
+def orientation(perm=(0, 1, 2), flips=(False, False, False)):
+    """DustHipStamp.orient: destination axis r reads source axis perm[r], backwards where flips[r] (48 signed axis permutations)"""
+    perm = [int(p) for p in perm]
+    assert sorted(perm) == [0, 1, 2] and len(flips) == 3
+    return perm[0] | (perm[1] << 2) | (perm[2] << 4) | sum((1 << (6 + r)) for r in range(3) if flips[r])
+
+
+def stamps(offset, orient=ORIENT_IDENTITY, op=L.STAMP_PLACE, src_lo=(0, 0, 0), src_hi=(255, 255, 255)):
+    """DustHipStamp records (STAMP_DTYPE) for Model.stamp: offset (n, 3), where the lowest corner of each image box lands in the
+    destination; src_lo / src_hi (3,) or (n, 3), the inclusive sub-box of the source; orient (see orientation()) and op scalars or (n,)."""
+    offset = np.asarray(offset, np.int32).reshape(-1, 3)
+    out = np.zeros(len(offset), STAMP_DTYPE)
+    out["offset"] = offset
+    out["orient"] = np.broadcast_to(np.asarray(orient, np.uint32), (len(offset),))
+    out["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(offset),))
+    out["src_lo"] = np.broadcast_to(np.asarray(src_lo, np.uint8), (len(offset), 3))
+    out["src_hi"] = np.broadcast_to(np.asarray(src_hi, np.uint8), (len(offset), 3))
+    return out
 
 
 def top_level_build(boxes):

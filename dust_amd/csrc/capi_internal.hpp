@@ -145,6 +145,10 @@ struct DustHipContext : RefCounted {
   // model islands (island.hip): the device-side scratch of a labelling or a detach besides the model's own label array -- a bit and a
   // counter per 64 keys, block sums, the records being accumulated
   DeviceBuffer island_mask, island_count, island_tmp, island_acc, island_records;
+  // model stamps (stamp.hip): the source of a dust_hip_model_stamp call as a brick-major grid (16 MiB, allocated by the first call that
+  // needs it) -- expanded from a source that is not editable, or the copy of a model stamped onto itself. Filled by every such call:
+  // nothing is cached across calls
+  DeviceBuffer stamp_grid;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)

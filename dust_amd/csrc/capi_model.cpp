@@ -1,5 +1,5 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the device hierarchy build, device-side voxel and shape
-// edits (edit.hip) and model islands (island.hip).
+// edits (edit.hip), model stamps (stamp.hip) and model islands (island.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -9,6 +9,7 @@
 #include "vdb.hpp"
 #include "edit.hpp"
 #include "island.hpp"
+#include "stamp.hpp"
 
 // ------------------------------------------------------------------ device hierarchy build
 namespace {
@@ -402,11 +403,59 @@ bool device_shape(const DustHipEditShape& s, dust::DevEditShape& d) {
   d.hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
   return true;
 }
-inline size_t shape_cells(const dust::DevEditShape& d) {  // root cells (16^3 voxels) the bounds reach
+extern "C++" {  // (templates: no C linkage)
+// ---- the cell lists of a launch, shared by the shape edits and the stamps: a record's packed inclusive voxel bounds (lo, hi:
+// x | y << 8 | z << 16) binned into the 4096 root cells
+template <class Rec>
+inline size_t shape_cells(const Rec& d) {  // root cells (16^3 voxels) the bounds reach
   size_t n = 1;
   for (int r = 0; r < 3; ++r) n *= size_t((((d.hi >> (8 * r)) & 255u) >> 4) - (((d.lo >> (8 * r)) & 255u) >> 4) + 1u);
   return n;
 }
+// where the order-preserving chunk that begins at record c0 ends: before its lists would pass kShapeChunkIds entries or its ids a u16
+template <class Rec>
+size_t chunk_end(const std::vector<Rec>& dev, size_t c0) {
+  size_t c1 = c0, total = 0;
+  while (c1 < dev.size() && c1 - c0 < 65536 && (c1 == c0 || total + shape_cells(dev[c1]) <= kShapeChunkIds)) total += shape_cells(dev[c1++]);
+  return c1;
+}
+// the chunk's lists on the host: the non-empty cells, and per cell an ascending list of u16 record ids (relative to c0) in CSR form
+struct CellLists {
+  std::vector<uint32_t> cells, starts, fill = std::vector<uint32_t>(4096);
+  std::vector<uint16_t> ids;
+  template <class Rec>
+  void bin(const std::vector<Rec>& dev, size_t c0, size_t c1) {
+    std::fill(fill.begin(), fill.end(), 0u);
+    auto each_cell = [&](const Rec& d, auto&& f) {
+      for (uint32_t x = (d.lo & 255u) >> 4; x <= (d.hi & 255u) >> 4; ++x)
+        for (uint32_t y = ((d.lo >> 8) & 255u) >> 4; y <= ((d.hi >> 8) & 255u) >> 4; ++y)
+          for (uint32_t z = (d.lo >> 16) >> 4; z <= (d.hi >> 16) >> 4; ++z) f((x << 8) | (y << 4) | z);
+    };
+    for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ++fill[cell]; });
+    cells.clear(); starts.clear();
+    uint32_t run = 0;
+    for (uint32_t cell = 0; cell < 4096; ++cell) {
+      const uint32_t k = fill[cell];
+      fill[cell] = run;  // where the cell's next id goes
+      if (k) { cells.push_back(cell); starts.push_back(run); run += k; }
+    }
+    starts.push_back(run);
+    ids.resize(run);
+    for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
+  }
+  // into the model's staging buffers, on the context's stream (the host lists must stay as they are until the stream has been waited for)
+  DustStatus upload(DustHipContext* ctx, EditState& es) {
+    DustStatus s;
+    if ((s = grow(ctx, es.shape_cells, cells.size() * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, es.shape_starts, starts.size() * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, es.shape_ids, ids.size() * 2)) != DUST_OK) return s;
+    HIP_TRY(hipMemcpyAsync(es.shape_cells.p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(es.shape_starts.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(es.shape_ids.p, ids.data(), ids.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+    return DUST_OK;
+  }
+};
+}  // extern "C++"
 }  // namespace
 
 DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* shapes, uint32_t n, uint32_t* changed) {
@@ -444,35 +493,12 @@ DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* s
     }
     // Order-preserving chunks, each one launch: its shapes binned into the 4096 root cells, an ascending list of u16 shape
     // ids per cell in CSR form, one workgroup per non-empty cell. A chunk ends where its lists would pass kShapeChunkIds.
-    std::vector<uint32_t> cells, starts, fill(4096);
-    std::vector<uint16_t> ids;
+    CellLists lists;
     for (size_t c0 = 0; c0 < live;) {
-      size_t c1 = c0, total = 0;
-      while (c1 < live && c1 - c0 < 65536 && (c1 == c0 || total + shape_cells(dev[c1]) <= kShapeChunkIds)) total += shape_cells(dev[c1++]);
-      std::fill(fill.begin(), fill.end(), 0u);
-      auto each_cell = [&](const dust::DevEditShape& d, auto&& f) {
-        for (uint32_t x = (d.lo & 255u) >> 4; x <= (d.hi & 255u) >> 4; ++x)
-          for (uint32_t y = ((d.lo >> 8) & 255u) >> 4; y <= ((d.hi >> 8) & 255u) >> 4; ++y)
-            for (uint32_t z = (d.lo >> 16) >> 4; z <= (d.hi >> 16) >> 4; ++z) f((x << 8) | (y << 4) | z);
-      };
-      for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ++fill[cell]; });
+      const size_t c1 = chunk_end(dev, c0);
       if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
-      cells.clear(); starts.clear();
-      uint32_t run = 0;
-      for (uint32_t cell = 0; cell < 4096; ++cell) {
-        const uint32_t k = fill[cell];
-        fill[cell] = run;  // where the cell's next id goes
-        if (k) { cells.push_back(cell); starts.push_back(run); run += k; }
-      }
-      starts.push_back(run);
-      ids.resize(run);
-      for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
-      if ((s = grow(m->ctx, es.shape_cells, cells.size() * 4)) != DUST_OK) return s;
-      if ((s = grow(m->ctx, es.shape_starts, starts.size() * 4)) != DUST_OK) return s;
-      if ((s = grow(m->ctx, es.shape_ids, ids.size() * 2)) != DUST_OK) return s;
-      HIP_TRY(hipMemcpyAsync(es.shape_cells.p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(es.shape_starts.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(es.shape_ids.p, ids.data(), ids.size() * 2, hipMemcpyHostToDevice, st));
+      lists.bin(dev, c0, c1);
+      if ((s = lists.upload(m->ctx, es)) != DUST_OK) return s;
       dust::EditShapeArgs a{};
       a.grid = static_cast<uint8_t*>(es.grid.p);
       a.shapes = static_cast<const dust::DevEditShape*>(es.shapes.p) + c0;
@@ -480,8 +506,145 @@ DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* s
       a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
       a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
       a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
-      a.n_cells = uint32_t(cells.size());
+      a.n_cells = uint32_t(lists.cells.size());
       HIP_TRY(dust::launch_edit_shapes(a, st));
+      c0 = c1;
+    }
+    if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
+    s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
+    if (s != DUST_OK) return s;
+    if (changed) {
+      std::fill(changed, changed + n, 0u);
+      for (size_t k = 0; k < live; ++k) changed[index[k]] = counts[k];
+    }
+    return DUST_OK;
+  });
+}
+
+// ---- model stamps (stamp.hip k_stamp)
+static_assert(sizeof(DustHipStamp) == 32 && sizeof(dust::DevStamp) == 32, "stamp records");
+namespace {
+bool valid_orient(uint32_t o) {
+  if (o >> 9) return false;
+  const uint32_t p0 = o & 3u, p1 = (o >> 2) & 3u, p2 = (o >> 4) & 3u;
+  return ((1u << p0) | (1u << p1) | (1u << p2)) == 7u;
+}
+// The caller's record -> the device's: the image box clipped to the tree, one affine map per destination axis, the operation as a
+// table. Everything in int64: any int32 offset is legal. false: the stamp covers nothing.
+bool device_stamp(const DustHipStamp& s, dust::DevStamp& d) {
+  for (int k = 0; k < 3; ++k)
+    if (s.src_lo[k] > s.src_hi[k]) return false;
+  uint32_t lo[3], hi[3];
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t p = (s.orient >> (2 * r)) & 3u;
+    const bool flip = (s.orient >> (6 + r)) & 1u;
+    const int64_t off = s.offset[r], first = std::max<int64_t>(off, 0), last = std::min<int64_t>(off + int64_t(s.src_hi[p] - s.src_lo[p]), 255);
+    if (first > last) return false;
+    lo[r] = uint32_t(first); hi[r] = uint32_t(last);
+    d.base[r] = int32_t(flip ? int64_t(s.src_hi[p]) + off : int64_t(s.src_lo[p]) - off);  // (|off| <= 255 here)
+  }
+  d.lo = lo[0] | (lo[1] << 8) | (lo[2] << 16);
+  d.hi = hi[0] | (hi[1] << 8) | (hi[2] << 16);
+  d.orient = s.orient;
+  // two bits per case (source solid) << 1 | (destination solid): keep the destination's byte, take the source's, or None
+  const uint32_t K = dust::kStampKeep, T = dust::kStampTake, N = dust::kStampClear;
+  auto table = [](uint32_t ee, uint32_t es, uint32_t se, uint32_t ss) { return ee | (es << 2) | (se << 4) | (ss << 6); };
+  switch (s.op) {
+    case DUST_HIP_STAMP_PLACE: d.table = table(K, K, T, K); break;
+    case DUST_HIP_STAMP_OVERWRITE: d.table = table(K, K, T, T); break;
+    case DUST_HIP_STAMP_REPLACE: d.table = table(T, T, T, T); break;
+    case DUST_HIP_STAMP_CARVE: d.table = table(K, K, K, N); break;
+    default: d.table = table(K, K, K, T); break;  // PAINT
+  }
+  d.pad = 0;
+  return true;
+}
+}  // namespace
+
+DustStatus dust_hip_model_stamp(DustHipModel* m, const DustHipModel* src, const DustHipStamp* stamps, uint32_t n, const uint8_t* palette_map,
+                                uint32_t* changed) {
+  if (!m || !src || (n && !stamps)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (n > DUST_HIP_MAX_STAMPS) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_STAMPS stamps in one call");
+  if (m->ctx != src->ctx) return fail(DUST_ERR_INVALID_ARGUMENT, "the source and the destination belong to different contexts");
+  DustStatus s = editable_kind(m);  // (before the stamps are looked at)
+  if (s == DUST_OK) s = editable_kind(src);
+  if (s != DUST_OK) return s;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!valid_orient(stamps[i].orient)) return fail(DUST_ERR_INVALID_ARGUMENT, "orient is not a signed axis permutation (p a permutation of 0, 1, 2; bits 9 and above zero)");
+    if (stamps[i].op > DUST_HIP_STAMP_PAINT) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown stamp op");
+  }
+  uint8_t map[256];  // grid byte (palette index + 1, 0 = None) -> grid byte
+  map[0] = 0;
+  for (uint32_t i = 0; i < 255; ++i) {
+    if (palette_map && palette_map[i] > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette_map entries must be 0..254");
+    map[i + 1] = uint8_t((palette_map ? palette_map[i] : i) + 1u);
+  }
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK || n == 0) return s;
+    EditState& es = *m->edit;
+    es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
+    hipStream_t st = ctx->stream;
+    // the stamps that cover something, in call order: `index` maps them back to the caller's
+    std::vector<dust::DevStamp> dev;
+    std::vector<uint32_t> index;
+    dev.reserve(n); index.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      dust::DevStamp d{};
+      if (device_stamp(stamps[i], d)) { dev.push_back(d); index.push_back(i); }
+    }
+    const size_t live = dev.size();
+    std::vector<uint32_t> counts(live, 0u);
+    const uint8_t* source = nullptr;
+    if (live) {
+      // The source as it stands now, as a grid: its own when it is editable (read in place), expanded into the context's scratch when it
+      // is not (the source itself is not touched), and a copy of the destination's when a model is stamped onto itself
+      const size_t grid_bytes = size_t(dust::kLattice) * 64;
+      if (src == m || !src->edit) {
+        if (!ctx->stamp_grid.p) {
+          const hipError_t e = ctx->stamp_grid.alloc(grid_bytes);
+          if (e != hipSuccess) { ctx->stamp_grid.release(); return hip_fail(e, "the stamp source grid (16 MiB)"); }
+        }
+        if (src == m) {
+          HIP_TRY(hipMemcpyAsync(ctx->stamp_grid.p, es.grid.p, grid_bytes, hipMemcpyDeviceToDevice, st));
+        } else {
+          HIP_TRY(hipMemsetAsync(ctx->stamp_grid.p, 0, grid_bytes, st));
+          dust::EditArgs e{};  // (expand only writes the grid)
+          e.grid = static_cast<uint8_t*>(ctx->stamp_grid.p);
+          HIP_TRY(dust::launch_edit_expand(e, static_cast<const DustHipBlock*>(src->blocks.p), static_cast<const uint8_t*>(src->materials.p), src->dev.n_blocks, st));
+        }
+        source = static_cast<const uint8_t*>(ctx->stamp_grid.p);
+      } else {
+        source = static_cast<const uint8_t*>(src->edit->grid.p);
+      }
+      if ((s = grow(ctx, es.shapes, live * sizeof(dust::DevStamp))) != DUST_OK) return s;
+      if ((s = grow(ctx, es.changed, live * 4)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_aux, sizeof(map))) != DUST_OK) return s;
+      HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), live * sizeof(dust::DevStamp), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
+      HIP_TRY(hipMemcpyAsync(ctx->stage_aux.p, map, sizeof(map), hipMemcpyHostToDevice, st));
+    }
+    // order-preserving chunks, each one launch, as dust_hip_model_edit_shapes cuts them
+    CellLists lists;
+    for (size_t c0 = 0; c0 < live;) {
+      const size_t c1 = chunk_end(dev, c0);
+      if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
+      lists.bin(dev, c0, c1);
+      if ((s = lists.upload(ctx, es)) != DUST_OK) return s;
+      dust::StampArgs a{};
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.src = source;
+      a.stamps = static_cast<const dust::DevStamp*>(es.shapes.p) + c0;
+      a.cells = static_cast<const uint32_t*>(es.shape_cells.p);
+      a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
+      a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
+      a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
+      a.palette_map = static_cast<const uint8_t*>(ctx->stage_aux.p);
+      a.n_cells = uint32_t(lists.cells.size());
+      HIP_TRY(dust::launch_stamp(a, st));
       c0 = c1;
     }
     if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));

@@ -320,6 +320,52 @@ DustStatus dust_hip_model_island_of(DustHipModel*, const uint32_t* xyz, uint32_t
 #define DUST_HIP_DETACH_KEEP_SOURCE 1u /* copy the islands into *out and leave the source as it is */
 DustStatus dust_hip_model_detach_islands(DustHipModel*, const uint32_t* keys, uint32_t n, uint32_t flags,
                                          DustHipModel** out /* may be NULL */);
+/* Model stamps: the constructive edit, and the inverse of detach_islands -- the voxels of one model pasted into another, rotated or
+ * mirrored, materials and all: a prefab (a tree, a wall segment, a door frame), a detached island that has come to rest, a copy of a
+ * region of the same model. edit_shapes writes one palette index per shape; a stamp carries a textured piece.
+ *
+ * Geometry: everything is integer, in the two models' tree coordinates (what set_voxels takes). A stamp names an inclusive sub-box
+ * [src_lo, src_hi] of the source, a signed axis permutation and where the image lands. p[r] = (orient >> 2r) & 3 is the source axis
+ * that destination axis r reads, g[r] = (orient >> (6 + r)) & 1 whether it runs backwards, for r = 0, 1, 2: {p[0], p[1], p[2]} must be
+ * a permutation of {0, 1, 2} and bits 9 and above must be 0 -- 48 orientations, the 24 mirrored ones included; orient == 0x24 is the
+ * identity. With e[k] = src_hi[k] - src_lo[k], the image box is offset[r] .. offset[r] + e[p[r]] on destination axis r. A destination
+ * voxel d that lies in the image box and inside the tree reads source voxel s: with u[r] = d[r] - offset[r],
+ *   s[p[r]] = src_lo[p[r]] + u[r]   when g[r] == 0,        s[p[r]] = src_hi[p[r]] - u[r]   when g[r] == 1.
+ * Any int32 offset is legal (nothing overflows); the image is clipped to the tree, and an image entirely outside it changes nothing.
+ * src_lo > src_hi on any axis covers nothing (changed[i] = 0, not an error, as the shapes' degenerate inputs).
+ * Values: v is the source voxel's value -- None, or palette_map[index] when a map is given (255 entries, one per palette index 0..254),
+ * otherwise the index itself; w is the destination voxel's. PLACE: v solid and w None -> v. OVERWRITE: v solid -> v. REPLACE: every
+ * voxel of the image box -> v, None included. CARVE: v solid -> None (the boolean difference). PAINT: v solid and w solid -> v. Every
+ * other voxel keeps w. The destination's palette is not touched: indices are copied (or mapped), colours are not.
+ * Order: the stamps of a call apply in array order, as n successive calls would. The source is read as it stood when the call began,
+ * also when src == dst: a model may be stamped onto itself, with overlapping images, without any memmove hazard. changed[i] is the
+ * number of voxels whose value after stamp i differs from their value before it; `changed` may be NULL. Deterministic: two runs give the
+ * same bytes and the same counts.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything changes: a null dst or src; null stamps with n > 0; n > DUST_HIP_MAX_STAMPS;
+ * models of different contexts; an invalid orient; an unknown op; a palette_map entry above 254. n == 0 is a no-op in the set_voxels
+ * sense (it may move dst into its editable form). DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that
+ * hold material byte 255), for dst and for src alike, before the stamps are looked at.
+ * Synchronous, like edit_shapes: the call returns with dst rebuilt -- the device arrays byte for byte what dust_hip_model_create builds
+ * from the resulting voxels -- and changed written. Scenes that instance dst must be committed again; dst's island labelling is
+ * invalidated when n > 0. The SOURCE is not modified in any way unless it is dst: it is not moved into editable form, its generation
+ * stays, and committed scenes that instance it stay valid (a source that is not editable is expanded into a 16 MiB scratch grid the
+ * context owns, allocated by the first call that needs it; nothing is cached from one call to the next). */
+#define DUST_HIP_STAMP_PLACE     0u  /* source solid, destination empty -> source's material              */
+#define DUST_HIP_STAMP_OVERWRITE 1u  /* source solid -> source's material, whatever was there              */
+#define DUST_HIP_STAMP_REPLACE   2u  /* every voxel of the image box takes the source's value, None too    */
+#define DUST_HIP_STAMP_CARVE     3u  /* source solid -> None (boolean difference)                          */
+#define DUST_HIP_STAMP_PAINT     4u  /* source solid and destination solid -> source's material            */
+#define DUST_HIP_MAX_STAMPS 65536u
+typedef struct DustHipStamp {        /* 32 bytes */
+  int32_t  offset[3];                /* where the lowest corner of the image box lands, destination tree coordinates */
+  uint32_t orient;                   /* signed axis permutation, above */
+  uint32_t op;
+  uint8_t  src_lo[3], pad0;          /* inclusive sub-box of the source, tree coordinates */
+  uint8_t  src_hi[3], pad1;
+  uint32_t reserved;                 /* ignored */
+} DustHipStamp;
+DustStatus dust_hip_model_stamp(DustHipModel* dst, const DustHipModel* src, const DustHipStamp* stamps, uint32_t n,
+                                const uint8_t* palette_map /* 255 entries, or NULL = identity */, uint32_t* changed /* n, may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

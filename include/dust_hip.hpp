@@ -176,6 +176,16 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return piece ? std::unique_ptr<VoxGeometry>(new VoxGeometry(piece)) : nullptr;
   }
+  // Model stamps (dust_hip_model_stamp): the voxels of `source` (which may be this geometry) pasted into this one, rotated or mirrored,
+  // in array order; palette_map, if given, renames the source's palette indices. Returns, per stamp, the voxels whose value it
+  // changed. The source is not modified; scenes that instance this geometry must commit() again.
+  std::vector<uint32_t> stamp(const VoxGeometry& source, const std::vector<DustHipStamp>& stamps, const std::array<uint8_t, 255>* palette_map = nullptr) {
+    std::vector<uint32_t> changed(stamps.size());
+    check(dust_hip_model_stamp(h_, source.h_, stamps.data(), uint32_t(stamps.size()), palette_map ? palette_map->data() : nullptr, changed.data()));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
   std::optional<uint8_t> get(UVec3 c) {
     int32_t v = -1;
     check(dust_hip_model_get_voxels(h_, c.data(), &v, 1));
