@@ -175,6 +175,22 @@ STAMP_PLACE, STAMP_OVERWRITE, STAMP_REPLACE, STAMP_CARVE, STAMP_PAINT = 0, 1, 2,
 MAX_STAMPS = 65536
 
 
+class FloodQuery(C.Structure):  # DustHipFloodQuery, 40 bytes: the medium a flood spreads through, its step limit and its inclusive region box
+    _fields_ = [("struct_size", C.c_uint32), ("medium", C.c_uint32), ("palette", C.c_int32), ("max_steps", C.c_uint32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3)]
+
+
+class FloodResult(C.Structure):  # DustHipFloodResult, 32 bytes: what a flood reached
+    _fields_ = [("reached", C.c_uint32), ("farthest", C.c_uint32), ("seeds_used", C.c_uint32), ("boundary", C.c_uint32),
+                ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("reserved", C.c_uint32 * 2)]
+
+
+FLOOD_EMPTY, FLOOD_SOLID, FLOOD_MATERIAL = 0, 1, 2
+FLOOD_UNREACHED = 0xFFFF
+FLOOD_MAX_STEPS = 65534
+MAX_FLOOD_SEEDS = 65536
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("rays", C.c_uint64), ("instances_tested", C.c_uint64),
                 ("upper_descents", C.c_uint64), ("mid_descents", C.c_uint64), ("bricks_tested", C.c_uint64),
@@ -235,6 +251,10 @@ SYMBOLS = {
     "dust_hip_model_island_of": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_detach_islands": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "dust_hip_model_stamp": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
+    "dust_hip_model_flood": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "dust_hip_model_flood_at": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "dust_hip_model_flood_paths": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "dust_hip_model_flood_apply": (C.c_int, [_P, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_scene_create": (C.c_int, [_P, C.POINTER(_P)]),

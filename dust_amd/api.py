@@ -38,6 +38,9 @@ EDIT_SHAPE_DTYPE = np.dtype([("a", "<f4", 3), ("kind", "<u4"), ("b", "<f4", 3), 
 STAMP_DTYPE = np.dtype([("offset", "<i4", 3), ("orient", "<u4"), ("op", "<u4"), ("src_lo", "u1", 3), ("pad0", "u1"), ("src_hi", "u1", 3), ("pad1", "u1"),
                         ("reserved", "<u4")])   # DustHipStamp
 ORIENT_IDENTITY = 0x24   # p = (0, 1, 2), no flips
+# DustHipFloodResult, 32 bytes: what a dust_hip_model_flood reached
+FLOOD_RESULT_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("seeds_used", "<u4"), ("boundary", "<u4"), ("lo", "u1", 3), ("pad0", "u1"),
+                               ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 2)])
 ISLAND_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("flags", "u1"), ("hi", "u1", 3), ("reserved", "u1"), ("sum", "<u8", 3)])
 FLT_MAX = float(np.finfo(np.float32).max)
 
@@ -406,6 +409,49 @@ class Model:
             assert len(pm) == 255
         L.check(self._lib.dust_hip_model_stamp(self._h, source._h, _ptr(stamps), len(stamps), None if pm is None else _ptr(pm), _ptr(changed)))
         return changed
+
+    def flood(self, seeds, medium=L.FLOOD_EMPTY, palette=0, max_steps=L.FLOOD_MAX_STEPS, region=None):
+        """Step distances from `seeds` (n, 3) through the passable voxels (dust_hip_model_flood): medium L.FLOOD_EMPTY (voxels holding
+        None), L.FLOOD_SOLID (solid voxels) or L.FLOOD_MATERIAL (solid voxels of palette index `palette`); steps go through shared faces,
+        at most max_steps of them, inside region = (lo, hi), an inclusive voxel box (None: the whole tree). Returns the result as a
+        FLOOD_RESULT_DTYPE record (reached, farthest, seeds_used, boundary, lo, hi). The field stays on the device for flood_at,
+        flood_paths and flood_apply until the next edit."""
+        seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1, 3)
+        q = L.FloodQuery(struct_size=C.sizeof(L.FloodQuery), medium=medium, palette=palette, max_steps=max_steps)
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        out = np.zeros(1, FLOOD_RESULT_DTYPE)
+        L.check(self._lib.dust_hip_model_flood(self._h, C.byref(q), _ptr(seeds) if len(seeds) else None, len(seeds), _ptr(out)))
+        return out[0]
+
+    def flood_at(self, xyz):
+        """steps of each voxel under the last flood (dust_hip_model_flood_at): uint16, L.FLOOD_UNREACHED where the flood did not get"""
+        xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
+        steps = np.zeros(len(xyz), np.uint16)
+        L.check(self._lib.dust_hip_model_flood_at(self._h, _ptr(xyz), _ptr(steps), len(steps)))
+        return steps
+
+    def flood_paths(self, starts, capacity, keys=None):
+        """Descend the last flood's field from each start to a seed (dust_hip_model_flood_paths). Returns (lengths, keys): lengths[i] the
+        voxels of path i (steps + 1; 0 for an unreached start), keys (n, capacity) its first min(lengths[i], capacity) voxels as
+        x << 16 | y << 8 | z, the start first (slots past them are left as they are: zero, or what the given `keys` array held).
+        capacity 2: the next step toward the goal."""
+        starts = np.ascontiguousarray(starts, np.uint32).reshape(-1, 3)
+        lengths = np.zeros(len(starts), np.uint32)
+        if keys is None:
+            keys = np.zeros((len(starts), capacity), np.uint32)
+        assert keys.dtype == np.uint32 and keys.flags.c_contiguous and keys.shape == (len(starts), capacity)
+        L.check(self._lib.dust_hip_model_flood_paths(self._h, _ptr(starts), len(starts), capacity, _ptr(keys) if capacity else None, _ptr(lengths)))
+        return lengths, keys
+
+    def flood_apply(self, value, max_steps=None):
+        """Every voxel the last flood reached within max_steps (None: all of them) takes `value`, a palette index or -1 for None
+        (dust_hip_model_flood_apply). Returns the number of voxels that changed. Scenes instancing the model must be committed again;
+        the field and the island labelling are invalid afterwards."""
+        changed = C.c_uint32()
+        L.check(self._lib.dust_hip_model_flood_apply(self._h, 0xFFFFFFFF if max_steps is None else int(max_steps), int(value), C.byref(changed)))
+        return changed.value
 
     def read(self):
         """(blocks, materials) as they stand on the device"""

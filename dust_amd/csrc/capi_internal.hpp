@@ -149,6 +149,9 @@ struct DustHipContext : RefCounted {
   // needs it) -- expanded from a source that is not editable, or the copy of a model stamped onto itself. Filled by every such call:
   // nothing is cached across calls
   DeviceBuffer stamp_grid;
+  // model floods (flood.hip): the worklists of a dust_hip_model_flood call -- two flag arrays and two brick lists that take turns, their
+  // lengths and the accumulator of the result (dust::kFloodWorkWords); 4 MiB, allocated by the first call
+  DeviceBuffer flood_work;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)
@@ -172,6 +175,12 @@ struct EditState {
   DeviceBuffer labels;
   bool labels_valid = false;
   uint32_t labels_corners = 0;  // the connectivity of that labelling
+  // model floods (dust_hip_model_flood): per voxel, brick-major like the grid, its step distance from the seeds (32 MiB, allocated by the
+  // first flood); valid until the next call that may change a voxel. flood_lo / flood_hi: the bounds of the reached voxels (what
+  // dust_hip_model_flood_apply visits), meaningful while flood_reached != 0
+  DeviceBuffer flood;
+  bool flood_valid = false;
+  uint32_t flood_reached = 0, flood_lo[3] = {0, 0, 0}, flood_hi[3] = {0, 0, 0};
 };
 
 struct DustHipModel : RefCounted {

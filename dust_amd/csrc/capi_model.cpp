@@ -1,5 +1,5 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the device hierarchy build, device-side voxel and shape
-// edits (edit.hip), model stamps (stamp.hip) and model islands (island.hip).
+// edits (edit.hip), model stamps (stamp.hip), model islands (island.hip) and model floods (flood.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -8,6 +8,7 @@
 #include "capi_internal.hpp"
 #include "vdb.hpp"
 #include "edit.hpp"
+#include "flood.hpp"
 #include "island.hpp"
 #include "stamp.hpp"
 
@@ -348,6 +349,7 @@ DustStatus dust_hip_model_set_voxels(DustHipModel* m, const uint32_t* xyz, const
     }
     const uint32_t un = uint32_t(uv.size());
     m->edit->labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
+    m->edit->flood_valid = false;   // (and so does dust_hip_model_flood's field)
     s = upload_batch(m, ux.data(), uv.data(), un, true);
     if (s != DUST_OK) return s;
     dust::EditArgs a = edit_args(m, *m->edit);
@@ -474,6 +476,7 @@ DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* s
     if (s != DUST_OK || n == 0) return s;
     EditState& es = *m->edit;
     es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
+    es.flood_valid = false;   // (and so does dust_hip_model_flood's field)
     hipStream_t st = m->ctx->stream;
     // the shapes that cover something, in call order: `index` maps them back to the caller's
     std::vector<dust::DevEditShape> dev;
@@ -587,6 +590,7 @@ DustStatus dust_hip_model_stamp(DustHipModel* m, const DustHipModel* src, const 
     if (s != DUST_OK || n == 0) return s;
     EditState& es = *m->edit;
     es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
+    es.flood_valid = false;   // (and so does dust_hip_model_flood's field)
     hipStream_t st = ctx->stream;
     // the stamps that cover something, in call order: `index` maps them back to the caller's
     std::vector<dust::DevStamp> dev;
@@ -817,12 +821,204 @@ DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, 
     if (!keep) {
       a.dst = nullptr;
       a.carve = 1u;
+      es.flood_valid = false;  // (dust_hip_model_flood's field describes the voxels as they were)
       HIP_TRY(dust::launch_island_detach(a, st));
       // (whole islands left: the labelling of the rest stands.) A failure in here is that of a shape edit's rebuild: the grid is
       // changed, the arrays are not; the new model is dropped with the error
       if ((s = rebuild_and_refresh(m, es)) != DUST_OK) { es.labels_valid = false; return s; }
     }
     if (out) *out = retain(fresh.m);  // the caller's reference (the guard drops the builder's)
+    return DUST_OK;
+  });
+}
+
+// ---- model floods (flood.hip): step distances from seeds through the empty or the solid voxels, kept on the device with the model
+static_assert(sizeof(DustHipFloodQuery) == 40 && sizeof(DustHipFloodResult) == 32, "flood records");
+namespace {
+DustStatus check_coordinates(const uint32_t* xyz, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i)
+    if (xyz[i * 3] >= 256u || xyz[i * 3 + 1] >= 256u || xyz[i * 3 + 2] >= 256u)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
+  return DUST_OK;
+}
+DustStatus no_field() { return fail(DUST_ERR_NOT_READY, "the model has no valid flood field: call dust_hip_model_flood (again after an edit)"); }
+}  // namespace
+
+DustStatus dust_hip_model_flood(DustHipModel* m, const DustHipFloodQuery* q, const uint32_t* seeds_xyz, uint32_t n_seeds, DustHipFloodResult* out) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);  // (before anything else is looked at)
+  if (s != DUST_OK) return s;
+  if (!q || (n_seeds && !seeds_xyz)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipFloodQuery");
+  if (q->medium > DUST_HIP_FLOOD_MATERIAL) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown flood medium");
+  if (q->medium == DUST_HIP_FLOOD_MATERIAL && (q->palette < 0 || q->palette > 254)) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254");
+  if (q->max_steps > DUST_HIP_FLOOD_MAX_STEPS) return fail(DUST_ERR_INVALID_ARGUMENT, "max_steps above DUST_HIP_FLOOD_MAX_STEPS");
+  if (n_seeds > DUST_HIP_MAX_FLOOD_SEEDS) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_FLOOD_SEEDS seeds in one call");
+  if ((s = check_coordinates(seeds_xyz, n_seeds)) != DUST_OK) return s;
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    es.flood_valid = false;  // until this field is complete
+    if (!es.flood.p) {
+      const hipError_t e = es.flood.alloc(size_t(dust::kLattice) * 64 * 2);
+      if (e != hipSuccess) { es.flood.release(); return hip_fail(e, "the flood field (32 MiB)"); }
+    }
+    const size_t L = dust::kLattice;
+    if ((s = grow(ctx, ctx->flood_work, (4 * L + dust::kFloodWorkWords) * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_in, size_t(n_seeds) * 12)) != DUST_OK) return s;
+    uint32_t* work = static_cast<uint32_t*>(ctx->flood_work.p);
+    uint32_t* flag[2] = {work + dust::kFloodFlag * L, work + (dust::kFloodFlag + 1) * L};
+    uint32_t* list[2] = {work + dust::kFloodList * L, work + (dust::kFloodList + 1) * L};
+    uint32_t* count = work + dust::kFloodCount * L;  // three, taking turns
+    dust::FloodArgs a{};
+    a.grid = static_cast<const uint8_t*>(es.grid.p);
+    a.field = static_cast<uint16_t*>(es.flood.p);
+    a.medium = q->medium;
+    a.byte = q->medium == DUST_HIP_FLOOD_MATERIAL ? uint32_t(q->palette) + 1u : 0u;
+    a.max_steps = q->max_steps;
+    bool nothing = false;  // lo > hi on an axis: nothing is passable
+    for (int r = 0; r < 3; ++r) {
+      a.lo[r] = q->lo[r];
+      a.hi[r] = std::min(q->hi[r], 255u);
+      nothing |= a.lo[r] > a.hi[r];
+    }
+    a.seeds = static_cast<const uint32_t*>(ctx->stage_in.p);
+    a.n_seeds = nothing ? 0u : n_seeds;
+    a.acc = count + dust::kFloodAcc;
+    // the flags (a flood that stopped at its ceiling leaves some set), the three counts and the accumulator
+    HIP_TRY(hipMemsetAsync(flag[0], 0, 2 * L * 4, st));
+    HIP_TRY(hipMemsetAsync(count, 0, dust::kFloodWorkWords * 4, st));
+    if (a.n_seeds) HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, seeds_xyz, size_t(n_seeds) * 12, hipMemcpyHostToDevice, st));
+    a.next_list = list[0]; a.next_flag = flag[0]; a.next_count = count;
+    HIP_TRY(dust::launch_flood_seed(a, st));
+    uint32_t acc[dust::kFloodAccWords] = {};
+    if (a.n_seeds) {
+      // Passes until one wakes no brick, in batches (a pass over an empty list exits at once), and never more than max_steps + 1: after
+      // pass p every voxel with steps < p is final, and no value is above max_steps
+      uint32_t listed = 0;
+      HIP_TRY(hipMemcpyAsync(&listed, count, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      const uint32_t ceiling = q->max_steps + 1u;
+      for (uint32_t pass = 0; listed != 0u && pass < ceiling;) {
+        const uint32_t batch = std::min(dust::kFloodBatch, ceiling - pass);
+        const uint32_t workgroups = std::min(2048u, std::max(32u, listed));  // (bricks / 4 would do for this pass; the next ones may list more)
+        for (uint32_t k = 0; k < batch; ++k, ++pass) {
+          a.list = list[pass & 1u]; a.flag = flag[pass & 1u]; a.count = count + pass % 3u;
+          a.next_list = list[(pass + 1u) & 1u]; a.next_flag = flag[(pass + 1u) & 1u]; a.next_count = count + (pass + 1u) % 3u;
+          a.zero_count = count + (pass + 2u) % 3u;
+          a.first = pass == 0u ? 1u : 0u;
+          HIP_TRY(dust::launch_flood_relax(a, workgroups, st));
+        }
+        HIP_TRY(hipMemcpyAsync(&listed, count + pass % 3u, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+      HIP_TRY(dust::launch_flood_result(a, st));
+      HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));  // (the seeds have left the caller's array)
+    DustHipFloodResult r{};
+    r.reached = acc[0];
+    if (r.reached) {
+      r.farthest = acc[1]; r.seeds_used = acc[2]; r.boundary = acc[3];
+      for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[4 + k]); r.hi[k] = uint8_t(acc[7 + k]); }
+    }
+    es.flood_reached = r.reached;
+    for (int k = 0; k < 3; ++k) { es.flood_lo[k] = r.lo[k]; es.flood_hi[k] = r.hi[k]; }
+    es.flood_valid = true;
+    if (out) *out = r;
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_flood_at(DustHipModel* m, const uint32_t* xyz, uint16_t* steps, uint32_t n) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (n && (!xyz || !steps)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if ((s = check_coordinates(xyz, n)) != DUST_OK) return s;
+  if (!m->edit || !m->edit->flood_valid) return no_field();
+  if (n == 0) return DUST_OK;
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((s = grow(ctx, ctx->stage_in, size_t(n) * 12)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_out, size_t(n) * 2)) != DUST_OK) return s;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(dust::launch_flood_lookup(static_cast<const uint16_t*>(m->edit->flood.p), static_cast<const uint32_t*>(ctx->stage_in.p),
+                                      static_cast<uint16_t*>(ctx->stage_out.p), n, st));
+    HIP_TRY(hipMemcpyAsync(steps, ctx->stage_out.p, size_t(n) * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_flood_paths(DustHipModel* m, const uint32_t* starts_xyz, uint32_t n, uint32_t capacity, uint32_t* keys, uint32_t* lengths) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (!lengths || (n && !starts_xyz) || (n && capacity && !keys)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if ((s = check_coordinates(starts_xyz, n)) != DUST_OK) return s;
+  if (!m->edit || !m->edit->flood_valid) return no_field();
+  if (n == 0) return DUST_OK;
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t slots = size_t(n) * capacity;
+    if ((s = grow(ctx, ctx->stage_in, size_t(n) * 12)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_out, slots * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_aux, size_t(n) * 4)) != DUST_OK) return s;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, starts_xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(dust::launch_flood_paths(static_cast<const uint16_t*>(m->edit->flood.p), static_cast<const uint32_t*>(ctx->stage_in.p), n, capacity,
+                                     static_cast<uint32_t*>(ctx->stage_out.p), static_cast<uint32_t*>(ctx->stage_aux.p), st));
+    // the slots past a path's end stay the caller's: the device rows come back beside them and only their written part is copied over
+    std::vector<uint32_t> rows(slots);
+    if (slots) HIP_TRY(hipMemcpyAsync(rows.data(), ctx->stage_out.p, slots * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(lengths, ctx->stage_aux.p, size_t(n) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t i = 0; i < n && capacity; ++i)
+      std::memcpy(keys + i * capacity, rows.data() + i * capacity, size_t(std::min(lengths[i], capacity)) * 4);
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_flood_apply(DustHipModel* m, uint32_t max_steps, int32_t value, uint32_t* changed) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (value > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxels)");
+  if (!m->edit || !m->edit->flood_valid) return no_field();
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    es.flood_valid = false;   // the field and the labelling describe the voxels as they were
+    es.labels_valid = false;
+    uint32_t n = 0;
+    if (es.flood_reached) {
+      if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;
+      dust::FloodApplyArgs a{};
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.field = static_cast<const uint16_t*>(es.flood.p);
+      a.max_steps = max_steps;
+      a.byte = value < 0 ? 0u : uint32_t(value) + 1u;
+      for (int k = 0; k < 3; ++k) { a.lo[k] = es.flood_lo[k]; a.hi[k] = es.flood_hi[k]; }
+      a.changed = static_cast<uint32_t*>(es.changed.p);
+      HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
+      HIP_TRY(dust::launch_flood_apply(a, st));
+      HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
+    }
+    s = rebuild_and_refresh(m, es);  // synchronises
+    if (s != DUST_OK) return s;
+    if (changed) *changed = n;
     return DUST_OK;
   });
 }

@@ -366,6 +366,73 @@ typedef struct DustHipStamp {        /* 32 bytes */
 } DustHipStamp;
 DustStatus dust_hip_model_stamp(DustHipModel* dst, const DustHipModel* src, const DustHipStamp* stamps, uint32_t n,
                                 const uint8_t* palette_map /* 255 entries, or NULL = identity */, uint32_t* changed /* n, may be NULL */);
+/* Model floods: questions about the space BETWEEN the solid voxels, and about connectivity with a distance attached -- where an agent can
+ * go after an edit and what its next step toward a goal is, whether a room is sealed, how far a gas or a fire gets in k steps, filling
+ * what a flood reaches with a material (water in a crater, a paint bucket, a vein of ore), the voxels within k steps of a blast through
+ * the structure itself. Coordinates are the model's tree coordinates (what set_voxels takes), on 256^3 models.
+ *
+ * A flood has a medium, which decides the voxels that are passable: DUST_HIP_FLOOD_EMPTY the voxels holding None, DUST_HIP_FLOOD_SOLID the
+ * solid voxels of any material, DUST_HIP_FLOOD_MATERIAL the solid voxels whose palette index equals query.palette. A voxel outside the
+ * query's inclusive region box [lo, hi] is never passable; the box is clipped to the tree, and lo > hi on any axis means nothing is
+ * passable. A step goes from a passable voxel to a passable voxel sharing a face (6 neighbours). steps(v) is the smallest number of steps
+ * from any seed to v; it is DUST_HIP_FLOOD_UNREACHED when v is not passable, not connected to a seed, or farther than query.max_steps
+ * (at most DUST_HIP_FLOOD_MAX_STEPS). Seeds that are not passable or lie outside the region are ignored (not an error); duplicates are
+ * harmless; n_seeds == 0 is legal and gives an all-unreached, valid field. Everything is integer and the field is a unique fixed point:
+ * two runs give the same bytes whatever the scheduling.
+ *
+ * dust_hip_model_flood computes the field and leaves it on the device with the model -- one uint16 per voxel, 32 MiB on top of the editable
+ * form, allocated by the first call and released with the model -- replacing the previous field. A model that is not yet editable is moved
+ * into its editable form first, exactly as find_islands does (scenes that instance it must then be committed again); on an editable model
+ * the call changes nothing a scene reads. The result record: reached, the voxels with steps != UNREACHED; farthest, the largest steps
+ * value; seeds_used, the voxels with steps == 0; boundary, the reached voxels that lie on a face of the clipped region (0: the flood is
+ * enclosed); lo / hi, the inclusive bounds of the reached voxels. With reached == 0 every member is 0.
+ * dust_hip_model_flood_at reads the field at coordinates, as island_of reads labels.
+ * dust_hip_model_flood_paths descends the field: for a reached start s with d = steps(s) the path is p_0 = s, ..., p_d, where p_(i+1) is
+ * the neighbour of p_i with steps == steps(p_i) - 1, the first such in the order -x, +x, -y, +y, -z, +z; p_d is a seed. lengths[i] = d + 1
+ * whatever the capacity; the first min(d + 1, capacity) voxels are written to keys[i * capacity ..] as x << 16 | y << 8 | z (the island key
+ * format) and the slots past them are left untouched. An unreached start has lengths[i] = 0 and writes nothing. capacity == 2 is "my
+ * next step toward the goal".
+ * dust_hip_model_flood_apply gives every voxel with steps != UNREACHED && steps <= max_steps the value `value` (a palette index 0..254, or
+ * negative for None; any uint32 is a legal max_steps). *changed is the number of voxels whose value differs afterwards. The model is
+ * rebuilt as after an edit -- its arrays byte for byte what dust_hip_model_create builds from the resulting voxels -- and its generation
+ * bumped: scenes must commit again.
+ * Validity: the field is invalidated by every set_voxels, edit_shapes, stamp (as destination) and carving detach_islands with n > 0, by
+ * flood_apply itself, and by a flood that fails. find_islands, island_of, KEEP_SOURCE detaches and being a stamp's source leave it
+ * standing. flood and flood_apply treat the island labelling as any edit would: flood leaves it, flood_apply invalidates it.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything changes: a null model, query or lengths; a struct_size below
+ * sizeof(DustHipFloodQuery); an unknown medium; palette outside 0..254 under MATERIAL; max_steps > DUST_HIP_FLOOD_MAX_STEPS in a query;
+ * null arrays with n > 0; n_seeds > DUST_HIP_MAX_FLOOD_SEEDS; a seed, start or lookup coordinate >= 256; null keys with capacity > 0 and
+ * n > 0; value > 254. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material byte 255), before
+ * anything but the model pointer is looked at. DUST_ERR_NOT_READY from flood_at, flood_paths and flood_apply without a standing field,
+ * also with n == 0. All four calls are synchronous.
+ * Out of scope: ground-walking agents (clearance, step height); 26-neighbour or weighted steps; floods across the instances of a scene,
+ * in world space; 4096^3 trees; an asynchronous form. */
+#define DUST_HIP_FLOOD_EMPTY    0u   /* passable: voxels holding None */
+#define DUST_HIP_FLOOD_SOLID    1u   /* passable: solid voxels of any material */
+#define DUST_HIP_FLOOD_MATERIAL 2u   /* passable: solid voxels whose palette index equals query.palette */
+#define DUST_HIP_FLOOD_UNREACHED 0xFFFFu
+#define DUST_HIP_FLOOD_MAX_STEPS 65534u
+#define DUST_HIP_MAX_FLOOD_SEEDS 65536u
+typedef struct DustHipFloodQuery {   /* 40 bytes */
+  uint32_t struct_size, medium;
+  int32_t  palette;                  /* read by DUST_HIP_FLOOD_MATERIAL only: 0..254 */
+  uint32_t max_steps;                /* 0..65534; larger values are refused */
+  uint32_t lo[3], hi[3];             /* inclusive region, clipped to the tree */
+} DustHipFloodQuery;
+typedef struct DustHipFloodResult {  /* 32 bytes */
+  uint32_t reached;                  /* voxels with steps != UNREACHED */
+  uint32_t farthest;                 /* the largest steps value (0 when reached == 0) */
+  uint32_t seeds_used;               /* voxels with steps == 0 */
+  uint32_t boundary;                 /* reached voxels on a face of the clipped region: 0 = the flood is enclosed */
+  uint8_t lo[3], pad0, hi[3], pad1;  /* inclusive bounds of the reached voxels; all 0 when reached == 0 */
+  uint32_t reserved[2];              /* 0 */
+} DustHipFloodResult;
+DustStatus dust_hip_model_flood(DustHipModel*, const DustHipFloodQuery*, const uint32_t* seeds_xyz, uint32_t n_seeds,
+                                DustHipFloodResult* out /* may be NULL */);
+DustStatus dust_hip_model_flood_at(DustHipModel*, const uint32_t* xyz, uint16_t* steps, uint32_t n);
+DustStatus dust_hip_model_flood_paths(DustHipModel*, const uint32_t* starts_xyz, uint32_t n, uint32_t capacity,
+                                      uint32_t* keys /* n * capacity, may be NULL when capacity == 0 */, uint32_t* lengths /* n */);
+DustStatus dust_hip_model_flood_apply(DustHipModel*, uint32_t max_steps, int32_t value, uint32_t* changed /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

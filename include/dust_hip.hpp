@@ -186,6 +186,44 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model floods (dust_hip_model_flood / flood_at / flood_paths / flood_apply): step distances from the seeds through the query's medium
+  // (empty voxels, solid voxels, or one material), kept on the device until the next edit; the distances at coordinates
+  // (DUST_HIP_FLOOD_UNREACHED where the flood did not get); per start, the first `capacity` voxels of its way down to a seed as
+  // x << 16 | y << 8 | z keys (empty for an unreached start; capacity 2: the next step); and every reached voxel within max_steps
+  // given a palette index (nullopt: None), after which scenes that instance this geometry must commit() again.
+  DustHipFloodResult flood(DustHipFloodQuery query, const std::vector<UVec3>& seeds) {
+    query.struct_size = sizeof(query);
+    std::vector<uint32_t> xyz;
+    for (const UVec3& c : seeds) xyz.insert(xyz.end(), c.begin(), c.end());
+    DustHipFloodResult result{};
+    check(dust_hip_model_flood(h_, &query, xyz.data(), uint32_t(seeds.size()), &result));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return result;
+  }
+  std::vector<uint16_t> flood_at(const std::vector<UVec3>& coords) {
+    std::vector<uint32_t> xyz;
+    std::vector<uint16_t> steps(coords.size());
+    for (const UVec3& c : coords) xyz.insert(xyz.end(), c.begin(), c.end());
+    check(dust_hip_model_flood_at(h_, xyz.data(), steps.data(), uint32_t(steps.size())));
+    return steps;
+  }
+  std::vector<std::vector<uint32_t>> flood_paths(const std::vector<UVec3>& starts, uint32_t capacity) {
+    std::vector<uint32_t> xyz, keys(starts.size() * size_t(capacity)), lengths(starts.size());
+    for (const UVec3& c : starts) xyz.insert(xyz.end(), c.begin(), c.end());
+    check(dust_hip_model_flood_paths(h_, xyz.data(), uint32_t(starts.size()), capacity, keys.data(), lengths.data()));
+    std::vector<std::vector<uint32_t>> paths(starts.size());
+    for (size_t i = 0; i < starts.size(); ++i)
+      paths[i].assign(keys.begin() + i * capacity, keys.begin() + i * capacity + (lengths[i] < capacity ? lengths[i] : capacity));
+    return paths;
+  }
+  uint32_t flood_apply(std::optional<uint8_t> palette_index, uint32_t max_steps = 0xFFFFFFFFu) {
+    uint32_t changed = 0;
+    check(dust_hip_model_flood_apply(h_, max_steps, palette_index ? int32_t(*palette_index) : -1, &changed));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
   std::optional<uint8_t> get(UVec3 c) {
     int32_t v = -1;
     check(dust_hip_model_get_voxels(h_, c.data(), &v, 1));
