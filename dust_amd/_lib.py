@@ -175,6 +175,23 @@ STAMP_PLACE, STAMP_OVERWRITE, STAMP_REPLACE, STAMP_CARVE, STAMP_PAINT = 0, 1, 2,
 MAX_STAMPS = 65536
 
 
+class Cast(C.Structure):  # DustHipCast, 48 bytes: a sub-box of a source model, its orientation and offset in the destination, a step and a step limit
+    _fields_ = [("offset", C.c_int32 * 3), ("orient", C.c_uint32), ("step", C.c_int32 * 3), ("max_steps", C.c_uint32), ("flags", C.c_uint32),
+                ("src_lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("src_hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+class CastHit(C.Structure):  # DustHipCastHit, 32 bytes: the free steps of a cast and what it touches first
+    _fields_ = [("steps", C.c_uint32), ("flags", C.c_uint32), ("contacts", C.c_uint32), ("voxels", C.c_uint32), ("contact", C.c_int32 * 3),
+                ("src_key", C.c_uint32)]
+
+
+CAST_WALLS = 1
+CAST_HIT, CAST_OVERLAP, CAST_HIT_WALL = 1, 2, 4
+CAST_MAX_STEPS = 65535
+MAX_CASTS = 65536
+CAST_NO_KEY = 0xFFFFFFFF
+
+
 class FloodQuery(C.Structure):  # DustHipFloodQuery, 40 bytes: the medium a flood spreads through, its step limit and its inclusive region box
     _fields_ = [("struct_size", C.c_uint32), ("medium", C.c_uint32), ("palette", C.c_int32), ("max_steps", C.c_uint32),
                 ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3)]
@@ -251,6 +268,7 @@ SYMBOLS = {
     "dust_hip_model_island_of": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_detach_islands": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "dust_hip_model_stamp": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
+    "dust_hip_model_cast": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_flood": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_flood_at": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_flood_paths": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),

@@ -38,6 +38,10 @@ EDIT_SHAPE_DTYPE = np.dtype([("a", "<f4", 3), ("kind", "<u4"), ("b", "<f4", 3), 
 STAMP_DTYPE = np.dtype([("offset", "<i4", 3), ("orient", "<u4"), ("op", "<u4"), ("src_lo", "u1", 3), ("pad0", "u1"), ("src_hi", "u1", 3), ("pad1", "u1"),
                         ("reserved", "<u4")])   # DustHipStamp
 ORIENT_IDENTITY = 0x24   # p = (0, 1, 2), no flips
+# DustHipCast, 48 bytes, and DustHipCastHit, 32 bytes: a cast of dust_hip_model_cast and its answer
+CAST_DTYPE = np.dtype([("offset", "<i4", 3), ("orient", "<u4"), ("step", "<i4", 3), ("max_steps", "<u4"), ("flags", "<u4"), ("src_lo", "u1", 3),
+                       ("pad0", "u1"), ("src_hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4")])
+CAST_HIT_DTYPE = np.dtype([("steps", "<u4"), ("flags", "<u4"), ("contacts", "<u4"), ("voxels", "<u4"), ("contact", "<i4", 3), ("src_key", "<u4")])
 # DustHipFloodResult, 32 bytes: what a dust_hip_model_flood reached
 FLOOD_RESULT_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("seeds_used", "<u4"), ("boundary", "<u4"), ("lo", "u1", 3), ("pad0", "u1"),
                                ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 2)])
@@ -410,6 +414,16 @@ class Model:
         L.check(self._lib.dust_hip_model_stamp(self._h, source._h, _ptr(stamps), len(stamps), None if pm is None else _ptr(pm), _ptr(changed)))
         return changed
 
+    def cast(self, source, casts):
+        """How far pieces of `source` (another Model of the same context, or this one) move inside this model before a voxel of them is
+        blocked (dust_hip_model_cast): `casts` a CAST_DTYPE array (see casts()), each independent of the others. Returns a CAST_HIT_DTYPE
+        array: steps (the free steps: the piece rests at offset + steps * step, ready for stamps()), flags (L.CAST_HIT, L.CAST_OVERLAP,
+        L.CAST_HIT_WALL), contacts, voxels, contact and src_key. Both models are only read."""
+        casts = np.ascontiguousarray(casts, CAST_DTYPE).reshape(-1)
+        hits = np.zeros(len(casts), CAST_HIT_DTYPE)
+        L.check(self._lib.dust_hip_model_cast(self._h, source._h, _ptr(casts) if len(casts) else None, len(casts), _ptr(hits) if len(casts) else None))
+        return hits
+
     def flood(self, seeds, medium=L.FLOOD_EMPTY, palette=0, max_steps=L.FLOOD_MAX_STEPS, region=None):
         """Step distances from `seeds` (n, 3) through the passable voxels (dust_hip_model_flood): medium L.FLOOD_EMPTY (voxels holding
         None), L.FLOOD_SOLID (solid voxels) or L.FLOOD_MATERIAL (solid voxels of palette index `palette`); steps go through shared faces,
@@ -635,6 +649,22 @@ def stamps(offset, orient=ORIENT_IDENTITY, op=L.STAMP_PLACE, src_lo=(0, 0, 0), s
     out["offset"] = offset
     out["orient"] = np.broadcast_to(np.asarray(orient, np.uint32), (len(offset),))
     out["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(offset),))
+    out["src_lo"] = np.broadcast_to(np.asarray(src_lo, np.uint8), (len(offset), 3))
+    out["src_hi"] = np.broadcast_to(np.asarray(src_hi, np.uint8), (len(offset), 3))
+    return out
+
+
+def casts(offset, step, max_steps, orient=ORIENT_IDENTITY, flags=0, src_lo=(0, 0, 0), src_hi=(255, 255, 255)):
+    """DustHipCast records (CAST_DTYPE) for Model.cast: offset (n, 3), where the lowest corner of each image box is at placement 0; step (3,)
+    or (n, 3), each component -1, 0 or 1; max_steps (0: a fit test), orient (see orientation()) and flags (L.CAST_WALLS) scalars or (n,);
+    src_lo / src_hi (3,) or (n, 3), the inclusive sub-box of the source."""
+    offset = np.asarray(offset, np.int32).reshape(-1, 3)
+    out = np.zeros(len(offset), CAST_DTYPE)
+    out["offset"] = offset
+    out["orient"] = np.broadcast_to(np.asarray(orient, np.uint32), (len(offset),))
+    out["step"] = np.broadcast_to(np.asarray(step, np.int32), (len(offset), 3))
+    out["max_steps"] = np.broadcast_to(np.asarray(max_steps, np.uint32), (len(offset),))
+    out["flags"] = np.broadcast_to(np.asarray(flags, np.uint32), (len(offset),))
     out["src_lo"] = np.broadcast_to(np.asarray(src_lo, np.uint8), (len(offset), 3))
     out["src_hi"] = np.broadcast_to(np.asarray(src_hi, np.uint8), (len(offset), 3))
     return out

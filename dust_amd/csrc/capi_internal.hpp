@@ -152,6 +152,9 @@ struct DustHipContext : RefCounted {
   // model floods (flood.hip): the worklists of a dust_hip_model_flood call -- two flag arrays and two brick lists that take turns, their
   // lengths and the accumulator of the result (dust::kFloodWorkWords); 4 MiB, allocated by the first call
   DeviceBuffer flood_work;
+  // model casts (cast.hip): the brick masks of a dust_hip_model_cast source that is not editable (2 MiB, EditArgs::brick_mask's layout),
+  // scattered from its blocks by every such call: nothing is cached across calls
+  DeviceBuffer cast_mask;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)

@@ -1,5 +1,5 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the device hierarchy build, device-side voxel and shape
-// edits (edit.hip), model stamps (stamp.hip), model islands (island.hip) and model floods (flood.hip).
+// edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip) and model floods (flood.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -7,6 +7,7 @@
 
 #include "capi_internal.hpp"
 #include "vdb.hpp"
+#include "cast.hpp"
 #include "edit.hpp"
 #include "flood.hpp"
 #include "island.hpp"
@@ -657,6 +658,175 @@ DustStatus dust_hip_model_stamp(DustHipModel* m, const DustHipModel* src, const 
     if (changed) {
       std::fill(changed, changed + n, 0u);
       for (size_t k = 0; k < live; ++k) changed[index[k]] = counts[k];
+    }
+    return DUST_OK;
+  });
+}
+
+// ---- model casts (cast.hip k_cast_walk / k_cast_count): both models are only read, through their brick masks
+static_assert(sizeof(DustHipCast) == 48 && sizeof(DustHipCastHit) == 32 && sizeof(dust::DevCast) == 48 && sizeof(dust::CastItem) == 8 &&
+              sizeof(dust::CastAcc) == 16, "cast records");
+namespace {
+constexpr size_t kCastChunkItems = size_t(1) << 20;  // work items (8 bytes) one launch carries; a whole-tree sub-box is 4096 of them
+
+// The caller's record -> the device's, everything in int64: any int32 offset is legal. Per destination axis the placements at which
+// the image box meets the tree are an interval; their intersection, cut to 0..max_steps, is all the device walks (under WALLS: from 0 to
+// one past the last placement the image is inside, or placement 0 alone when it begins outside). false: the sub-box is empty.
+bool device_cast(const DustHipCast& s, dust::DevCast& d) {
+  for (int k = 0; k < 3; ++k)
+    if (s.src_lo[k] > s.src_hi[k]) return false;
+  const bool walls = s.flags & DUST_HIP_CAST_WALLS;
+  const bool still = s.step[0] == 0 && s.step[1] == 0 && s.step[2] == 0;
+  const int64_t max_steps = still ? 0 : int64_t(s.max_steps);  // (every placement is placement 0)
+  const int64_t never = int64_t(1) << 40;                      // beyond any placement
+  int64_t first = -never, last = never;
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t p = (s.orient >> (2 * r)) & 3u;
+    const int64_t off = s.offset[r], ext = int64_t(s.src_hi[p]) - int64_t(s.src_lo[p]);
+    int64_t f, l;
+    if (s.step[r] == 0) {
+      const bool meets = off + ext >= 0 && off <= 255;
+      f = meets ? -never : 1; l = meets ? never : 0;
+    } else if (s.step[r] > 0) {
+      f = -(off + ext); l = 255 - off;
+    } else {
+      f = off - 255; l = off + ext;
+    }
+    first = std::max(first, f); last = std::min(last, l);
+    d.off[r] = int32_t(std::clamp<int64_t>(off, -dust::kCastOffsetLimit, dust::kCastOffsetLimit));
+    d.step[r] = s.step[r];
+  }
+  int64_t k_lo, k_hi;
+  if (walls) {
+    k_lo = 0;
+    k_hi = first <= 0 && last >= 0 ? std::min(max_steps, last + 1) : 0;
+  } else {
+    k_lo = std::max<int64_t>(first, 0);
+    k_hi = std::min(last, max_steps);
+  }
+  if (k_lo > k_hi) { k_lo = 1; k_hi = 0; }  // nothing to walk (the piece's voxels are still counted)
+  d.k_lo = uint32_t(k_lo); d.k_hi = uint32_t(k_hi);
+  d.max_steps = uint32_t(max_steps);
+  d.orient = s.orient | (walls ? dust::kCastWalls : 0u);
+  d.lo = s.src_lo[0] | (uint32_t(s.src_lo[1]) << 8) | (uint32_t(s.src_lo[2]) << 16);
+  d.hi = s.src_hi[0] | (uint32_t(s.src_hi[1]) << 8) | (uint32_t(s.src_hi[2]) << 16);
+  return true;
+}
+}  // namespace
+
+DustStatus dust_hip_model_cast(DustHipModel* m, const DustHipModel* src, const DustHipCast* casts, uint32_t n, DustHipCastHit* hits) {
+  if (!m || !src || (n && (!casts || !hits))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (n > DUST_HIP_MAX_CASTS) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_CASTS casts in one call");
+  if (m->ctx != src->ctx) return fail(DUST_ERR_INVALID_ARGUMENT, "the source and the destination belong to different contexts");
+  DustStatus s = editable_kind(m);  // (before the casts are looked at)
+  if (s == DUST_OK) s = editable_kind(src);
+  if (s != DUST_OK) return s;
+  for (uint32_t i = 0; i < n; ++i) {
+    const DustHipCast& c = casts[i];
+    if (!valid_orient(c.orient)) return fail(DUST_ERR_INVALID_ARGUMENT, "orient is not a signed axis permutation (p a permutation of 0, 1, 2; bits 9 and above zero)");
+    for (int r = 0; r < 3; ++r)
+      if (c.step[r] < -1 || c.step[r] > 1) return fail(DUST_ERR_INVALID_ARGUMENT, "a step component must be -1, 0 or 1");
+    if (c.max_steps > DUST_HIP_CAST_MAX_STEPS) return fail(DUST_ERR_INVALID_ARGUMENT, "max_steps above DUST_HIP_CAST_MAX_STEPS");
+    if (c.flags & ~DUST_HIP_CAST_WALLS) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown cast flags");
+  }
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));
+    DustStatus s = make_editable(m);
+    if (s != DUST_OK || n == 0) return s;
+    hipStream_t st = ctx->stream;
+    // the casts with a sub-box, in call order: `index` maps them back to the caller's
+    std::vector<dust::DevCast> dev;
+    std::vector<uint32_t> index;
+    dev.reserve(n); index.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      dust::DevCast d{};
+      if (device_cast(casts[i], d)) { dev.push_back(d); index.push_back(i); }
+    }
+    const size_t live = dev.size();
+    std::vector<unsigned long long> best(live, dust::kCastNoHit);
+    std::vector<dust::CastAcc> acc(live);
+    if (live) {
+      // The source's brick masks: its own when it is editable (dst itself included); otherwise its blocks' masks scattered into the
+      // context's scratch -- the source is not touched
+      const uint64_t* src_mask = nullptr;
+      if (src->edit) {
+        src_mask = static_cast<const uint64_t*>(src->edit->brick_mask.p);
+      } else {
+        const size_t bytes = size_t(dust::kLattice) * 8;
+        if (!ctx->cast_mask.p) {
+          const hipError_t e = ctx->cast_mask.alloc(bytes);
+          if (e != hipSuccess) { ctx->cast_mask.release(); return hip_fail(e, "the cast source masks (2 MiB)"); }
+        }
+        HIP_TRY(hipMemsetAsync(ctx->cast_mask.p, 0, bytes, st));
+        HIP_TRY(dust::launch_cast_masks(static_cast<uint64_t*>(ctx->cast_mask.p), static_cast<const DustHipBlock*>(src->blocks.p), src->dev.n_blocks, st));
+        src_mask = static_cast<const uint64_t*>(ctx->cast_mask.p);
+      }
+      auto cells_of = [](const dust::DevCast& d) {
+        size_t c = 1;
+        for (int r = 0; r < 3; ++r) c *= size_t((((d.hi >> (8 * r)) & 255u) >> 4) - (((d.lo >> (8 * r)) & 255u) >> 4) + 1u);
+        return c;
+      };
+      const size_t best_bytes = live * sizeof(unsigned long long);
+      if ((s = grow(ctx, ctx->stage_in, live * sizeof(dust::DevCast))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, best_bytes + live * sizeof(dust::CastAcc))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_aux, std::max(kCastChunkItems, size_t(4096)) * sizeof(dust::CastItem))) != DUST_OK) return s;
+      uint8_t* out = static_cast<uint8_t*>(ctx->stage_out.p);
+      HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, dev.data(), live * sizeof(dust::DevCast), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemsetAsync(out, 0xFF, best_bytes, st));                          // kCastNoHit
+      HIP_TRY(hipMemsetAsync(out + best_bytes, 0, live * sizeof(dust::CastAcc), st));
+      // chunks of casts, each one pair of launches: a chunk ends where its work items would pass kCastChunkItems
+      std::vector<dust::CastItem> items;
+      for (size_t c0 = 0; c0 < live;) {
+        size_t c1 = c0, total = 0;
+        while (c1 < live && (c1 == c0 || total + cells_of(dev[c1]) <= kCastChunkItems)) total += cells_of(dev[c1++]);
+        if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copy has left the host list
+        items.clear();
+        for (size_t i = c0; i < c1; ++i) {
+          const dust::DevCast& d = dev[i];
+          for (uint32_t x = (d.lo & 255u) >> 4; x <= (d.hi & 255u) >> 4; ++x)
+            for (uint32_t y = ((d.lo >> 8) & 255u) >> 4; y <= ((d.hi >> 8) & 255u) >> 4; ++y)
+              for (uint32_t z = (d.lo >> 16) >> 4; z <= (d.hi >> 16) >> 4; ++z) items.push_back({uint32_t(i - c0), (x << 8) | (y << 4) | z});
+        }
+        HIP_TRY(hipMemcpyAsync(ctx->stage_aux.p, items.data(), items.size() * sizeof(dust::CastItem), hipMemcpyHostToDevice, st));
+        dust::CastArgs a{};
+        a.src_mask = src_mask;
+        a.dst_mask = static_cast<const uint64_t*>(m->edit->brick_mask.p);
+        a.casts = static_cast<const dust::DevCast*>(ctx->stage_in.p) + c0;
+        a.items = static_cast<const dust::CastItem*>(ctx->stage_aux.p);
+        a.best = reinterpret_cast<unsigned long long*>(out) + c0;
+        a.acc = reinterpret_cast<dust::CastAcc*>(out + best_bytes) + c0;
+        a.n_items = uint32_t(items.size());
+        HIP_TRY(dust::launch_cast(a, st));
+        c0 = c1;
+      }
+      HIP_TRY(hipMemcpyAsync(best.data(), out, best_bytes, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(acc.data(), out + best_bytes, live * sizeof(dust::CastAcc), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));  // (the host vectors above stay alive until the copies are done)
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+      DustHipCastHit h{};
+      h.steps = casts[i].max_steps;
+      h.src_key = DUST_HIP_CAST_NO_KEY;
+      hits[i] = h;
+    }
+    for (size_t j = 0; j < live; ++j) {
+      const DustHipCast& c = casts[index[j]];
+      DustHipCastHit& h = hits[index[j]];
+      h.voxels = acc[j].voxels;
+      if (best[j] == dust::kCastNoHit) continue;
+      const uint32_t k = uint32_t(best[j] >> 24), key = uint32_t(best[j] & 0xFFFFFFu);
+      const uint32_t sv[3] = {key >> 16, (key >> 8) & 255u, key & 255u};
+      h.flags = DUST_HIP_CAST_HIT | (k == 0 ? DUST_HIP_CAST_OVERLAP : 0u) | (acc[j].wall ? DUST_HIP_CAST_HIT_WALL : 0u);
+      h.steps = k ? k - 1 : 0;
+      h.contacts = acc[j].contacts;
+      h.src_key = key;
+      for (int r = 0; r < 3; ++r) {
+        const uint32_t p = (c.orient >> (2 * r)) & 3u;
+        const int64_t u = ((c.orient >> (6 + r)) & 1u) ? int64_t(c.src_hi[p]) - int64_t(sv[p]) : int64_t(sv[p]) - int64_t(c.src_lo[p]);
+        h.contact[r] = int32_t(uint32_t(uint64_t(int64_t(c.offset[r]) + int64_t(k) * c.step[r] + u)));  // (the low 32 bits)
+      }
     }
     return DUST_OK;
   });

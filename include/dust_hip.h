@@ -366,6 +366,63 @@ typedef struct DustHipStamp {        /* 32 bytes */
 } DustHipStamp;
 DustStatus dust_hip_model_stamp(DustHipModel* dst, const DustHipModel* src, const DustHipStamp* stamps, uint32_t n,
                                 const uint8_t* palette_map /* 255 entries, or NULL = identity */, uint32_t* changed /* n, may be NULL */);
+/* Model casts: where a voxel piece comes to rest, and whether a prefab fits -- the voxel-against-voxel query between detach_islands
+ * ("debris that falls") and stamp ("a detached island that has come to rest"). sweep_boxes moves a box; a detached arch or a wall segment
+ * is not one. A cast takes a sub-box of a source model under one of the stamp's 48 orientations, puts it at an integer offset in the
+ * destination and moves it in integer steps along a direction: how many steps are free, and what does it touch first?
+ *
+ * Geometry: the stamp's definitions, word for word -- orient, p[r], g[r], e[k] and the image box offset[r] .. offset[r] + e[p[r]] as
+ * above. The piece is the set of solid source voxels s inside [src_lo, src_hi]. With u[r] = s[p[r]] - src_lo[p[r]] when g[r] == 0 and
+ * src_hi[p[r]] - s[p[r]] when g[r] == 1, voxel s stands at placement k = 0, 1, ... at
+ *   d_k(s)[r] = offset[r] + k * step[r] + u[r].
+ * A piece voxel is blocked at k when d_k lies inside the tree (0..255 on every axis) and the destination is solid there, or when d_k
+ * lies outside the tree and DUST_HIP_CAST_WALLS is set; without WALLS, voxels outside the tree touch nothing. Placement k is blocked
+ * when some piece voxel is.
+ * Result: let k* be the smallest blocked placement in 0..max_steps. If there is none: steps = max_steps, flags = 0, contacts = 0,
+ * contact = {0, 0, 0}, src_key = DUST_HIP_CAST_NO_KEY. Otherwise flags has HIT; steps = k* - 1, or 0 with OVERLAP when k* == 0; contacts
+ * is the number of piece voxels blocked at k*; HIT_WALL is set when one of them stands outside the tree; src_key = x << 16 | y << 8 | z
+ * of the blocked source voxel with the smallest such key, and contact = d_k*(that voxel) -- under WALLS it may lie outside 0..255 (it is
+ * computed in 64 bits and stored as its low 32: it can only wrap for an offset within 65 790 of the int32 limits). `voxels` is always the
+ * number of solid voxels in the source sub-box, whatever the clipping. The piece's resting place is offset + steps * step, ready to go
+ * into a DustHipStamp. A zero step is legal: every placement is then placement 0. src_lo > src_hi on any axis, or a piece with no solid
+ * voxel, gives no hit and voxels = 0. Any int32 offset is legal: nothing overflows, and the work does not grow with
+ * the offset or with max_steps -- no more placements are examined than the piece's image can spend inside the tree.
+ * State: both models are only read. dst is moved into its editable form first if it is not there yet, exactly as find_islands does
+ * (scenes that instance it must then be committed again); on an editable dst nothing a scene reads changes, and the island labelling
+ * and the flood field stay valid. src is treated as a stamp's source: not modified, not made editable, its generation stays. src == dst
+ * is allowed and not special: the piece meets its own voxels.
+ * The casts of a call are independent: hits[i] is what a call with casts[i] alone returns. Deterministic and exact: everything is integer.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything is written: a null dst or src; null casts or hits with n > 0;
+ * n > DUST_HIP_MAX_CASTS; models of different contexts; an invalid orient; a step component outside -1..1;
+ * max_steps > DUST_HIP_CAST_MAX_STEPS; flag bits other than WALLS. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees,
+ * models that hold material byte 255), for either model, before the records are looked at. n == 0 is a no-op in the find_islands sense
+ * (it may move dst into its editable form). Synchronous: the call returns with hits written.
+ * Out of scope: motion that is not an integer translation (rotation while moving, float offsets); casts against a scene's
+ * instances in world space; excluding an undetached island's own voxels (detach it first, or cast it from a KEEP_SOURCE copy
+ * against a carved destination); 4096^3 trees; an asynchronous form. */
+#define DUST_HIP_CAST_WALLS     1u   /* DustHipCast.flags: positions outside the tree block, as solid voxels do */
+#define DUST_HIP_CAST_HIT       1u   /* DustHipCastHit.flags: some placement 0..max_steps is blocked */
+#define DUST_HIP_CAST_OVERLAP   2u   /* ... and it is placement 0 */
+#define DUST_HIP_CAST_HIT_WALL  4u   /* ... and at least one contact lies outside the tree */
+#define DUST_HIP_CAST_MAX_STEPS 65535u
+#define DUST_HIP_MAX_CASTS      65536u
+#define DUST_HIP_CAST_NO_KEY    0xFFFFFFFFu
+typedef struct DustHipCast {        /* 48 bytes */
+  int32_t  offset[3];               /* where the image box's lowest corner is at placement 0 (stamp's offset) */
+  uint32_t orient;                  /* stamp's signed axis permutation */
+  int32_t  step[3];                 /* each -1, 0 or 1 */
+  uint32_t max_steps;               /* 0: a fit test */
+  uint32_t flags;
+  uint8_t  src_lo[3], pad0, src_hi[3], pad1;
+  uint32_t reserved;                /* ignored */
+} DustHipCast;
+typedef struct DustHipCastHit {     /* 32 bytes */
+  uint32_t steps, flags, contacts, voxels;
+  int32_t  contact[3];
+  uint32_t src_key;
+} DustHipCastHit;
+DustStatus dust_hip_model_cast(DustHipModel* dst, const DustHipModel* src, const DustHipCast* casts, uint32_t n,
+                               DustHipCastHit* hits /* n */);
 /* Model floods: questions about the space BETWEEN the solid voxels, and about connectivity with a distance attached -- where an agent can
  * go after an edit and what its next step toward a goal is, whether a room is sealed, how far a gas or a fire gets in k steps, filling
  * what a flood reaches with a material (water in a crater, a paint bucket, a vein of ore), the voxels within k steps of a blast through

@@ -186,6 +186,14 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model casts (dust_hip_model_cast): how far pieces of `source` (which may be this geometry) move inside this one before a voxel of
+  // them is blocked, each cast on its own: hits[i].steps free steps (the piece rests at offset + steps * step, ready for stamp()),
+  // flags, contacts and the first contact. Both geometries are only read (this one is moved into its editable form by the first call).
+  std::vector<DustHipCastHit> cast(const VoxGeometry& source, const std::vector<DustHipCast>& casts) {
+    std::vector<DustHipCastHit> hits(casts.size());
+    check(dust_hip_model_cast(h_, source.h_, casts.data(), uint32_t(casts.size()), hits.data()));
+    return hits;
+  }
   // Model floods (dust_hip_model_flood / flood_at / flood_paths / flood_apply): step distances from the seeds through the query's medium
   // (empty voxels, solid voxels, or one material), kept on the device until the next edit; the distances at coordinates
   // (DUST_HIP_FLOOD_UNREACHED where the flood did not get); per start, the first `capacity` voxels of its way down to a seed as
