@@ -1,5 +1,6 @@
 // capi_internal.hpp -- the host runtime's internal header (not part of the C ABI): the accessors comm.hip needs, and what the
 // runtime's translation units (capi.cpp, capi_model.cpp, capi_scene.cpp) share -- error helpers, DeviceBuffer, the handle structs.
+// (What the model calls compute without a device or a handle is model_records.hpp, which includes none of this.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/dust_hip.h"
@@ -76,6 +78,7 @@ struct DeviceBuffer {
   DeviceBuffer& operator=(const DeviceBuffer&) = delete;
   ~DeviceBuffer() { release(); }
   void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+  void swap(DeviceBuffer& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
   hipError_t alloc(size_t n) {
     if (p) { (void)hipFree(p); p = nullptr; }
     bytes = n;

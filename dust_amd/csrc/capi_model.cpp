@@ -1,5 +1,6 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the device hierarchy build, device-side voxel and shape
-// edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip) and model floods (flood.hip).
+// edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip) and model floods (flood.hip). The
+// arithmetic on the callers' records that needs no device (conversion, chunks, cell lists, cast hits) is model_records.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -7,11 +8,9 @@
 
 #include "capi_internal.hpp"
 #include "vdb.hpp"
-#include "cast.hpp"
-#include "edit.hpp"
 #include "flood.hpp"
 #include "island.hpp"
-#include "stamp.hpp"
+#include "model_records.hpp"
 
 // ------------------------------------------------------------------ device hierarchy build
 namespace {
@@ -297,10 +296,7 @@ DustStatus make_editable(DustHipModel* m, bool rebuild = true) {
   HIP_TRY(dust::launch_edit_expand(a, static_cast<const DustHipBlock*>(m->blocks.p), static_cast<const uint8_t*>(m->materials.p), m->dev.n_blocks, st));
   HIP_TRY(sync_stream(m->ctx));  // every launch that reads the old arrays is done (both streams of the context)
   auto swap_all = [&] {
-    std::swap(m->blocks.p, blocks.p); std::swap(m->blocks.bytes, blocks.bytes);
-    std::swap(m->materials.p, materials.p); std::swap(m->materials.bytes, materials.bytes);
-    std::swap(m->mid.p, mid.p); std::swap(m->mid.bytes, mid.bytes);
-    std::swap(m->dense_mask.p, dense_mask.p); std::swap(m->dense_mask.bytes, dense_mask.bytes);
+    m->blocks.swap(blocks); m->materials.swap(materials); m->mid.swap(mid); m->dense_mask.swap(dense_mask);
     m->dev.mid = static_cast<const dust::DevN4*>(m->mid.p);
     m->dev.dense_mask = static_cast<const uint64_t*>(m->dense_mask.p);
     m->dev.blocks = static_cast<const DustHipBlock*>(m->blocks.p);
@@ -313,6 +309,34 @@ DustStatus make_editable(DustHipModel* m, bool rebuild = true) {
   m->edit = std::move(e);
   return DUST_OK;
 }
+// what every call that works on the grid begins with
+DustStatus begin_edit(DustHipModel* m) {
+  HIP_TRY(hipSetDevice(m->ctx->device));
+  HIP_TRY(join_side(m->ctx));  // (a surfel pass on the second stream still traces the model as it is)
+  return make_editable(m);
+}
+// a call that may change a voxel is about to run
+void invalidate_derived(EditState& es) {
+  es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
+  es.flood_valid = false;   // (and so does dust_hip_model_flood's field)
+}
+// a buffer of one fixed size, allocated by the first call that needs it; out of device memory leaves it released
+DustStatus lazy_alloc(DeviceBuffer& b, size_t bytes, const char* what) {
+  if (b.p) return DUST_OK;
+  const hipError_t e = b.alloc(bytes);
+  if (e == hipSuccess) return DUST_OK;
+  b.release();
+  return hip_fail(e, what);
+}
+
+DustStatus check_coordinates(const uint32_t* xyz, uint32_t n, uint32_t extent = 256u) {
+  for (uint32_t i = 0; i < n; ++i)
+    if (xyz[i * 3] >= extent || xyz[i * 3 + 1] >= extent || xyz[i * 3 + 2] >= extent)
+      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
+  return DUST_OK;
+}
+DustStatus no_labelling() { return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)"); }
+DustStatus no_field() { return fail(DUST_ERR_NOT_READY, "the model has no valid flood field: call dust_hip_model_flood (again after an edit)"); }
 
 DustStatus upload_batch(DustHipModel* m, const uint32_t* xyz, const int32_t* values, uint32_t n, bool with_values) {
   EditState& e = *m->edit;
@@ -323,19 +347,86 @@ DustStatus upload_batch(DustHipModel* m, const uint32_t* xyz, const int32_t* val
   if (with_values) HIP_TRY(hipMemcpyAsync(e.values.p, values, size_t(n) * 4, hipMemcpyHostToDevice, m->ctx->stream));
   return DUST_OK;
 }
+
+extern "C++" {  // (templates: no C linkage)
+// dust_hip_model_island_of / dust_hip_model_flood_at: n coordinates up, one launch over them, n elements of type T back
+template <class T, class Launch>
+DustStatus lookup_call(DustHipModel* m, const uint32_t* xyz, T* out, uint32_t n, Launch&& launch) {
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DustStatus s;
+    if ((s = grow(ctx, ctx->stage_in, size_t(n) * 12)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_out, size_t(n) * sizeof(T))) != DUST_OK) return s;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
+    if ((s = launch(static_cast<const uint32_t*>(ctx->stage_in.p), static_cast<T*>(ctx->stage_out.p), st)) != DUST_OK) return s;
+    HIP_TRY(hipMemcpyAsync(out, ctx->stage_out.p, size_t(n) * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DUST_OK;
+  });
+}
+
+// The calls batched by root cell (shape edits, stamps), from the records that cover something (`dev`, in call order; index[k] is record
+// k's place among the caller's n) to the caller's `changed`. Order-preserving chunks, each one launch: its records binned into the 4096
+// root cells, an ascending list of u16 record ids per cell in CSR form, one workgroup per non-empty cell. `launch(c0, a)` gets the
+// chunk's first record and the arguments every such kernel takes (grid, cell lists, changed, n_cells); it adds its own and launches.
+template <class Args, class Rec, class Launch>
+DustStatus batched_edit(DustHipModel* m, const std::vector<Rec>& dev, const std::vector<uint32_t>& index, uint32_t n, uint32_t* changed, Launch&& launch) {
+  DustHipContext* ctx = m->ctx;
+  EditState& es = *m->edit;
+  hipStream_t st = ctx->stream;
+  const size_t live = dev.size();
+  std::vector<uint32_t> counts(live, 0u);
+  DustStatus s;
+  if (live) {
+    if ((s = grow(ctx, es.shapes, live * sizeof(Rec))) != DUST_OK) return s;
+    if ((s = grow(ctx, es.changed, live * 4)) != DUST_OK) return s;
+    HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), live * sizeof(Rec), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
+  }
+  dust::CellLists lists;
+  for (size_t c0 = 0; c0 < live;) {
+    const size_t c1 = dust::chunk_end(dev, c0, dust::kShapeChunkIds, dust::kShapeChunkRecords);
+    if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
+    lists.bin(dev, c0, c1);
+    if ((s = grow(ctx, es.shape_cells, lists.cells.size() * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, es.shape_starts, lists.starts.size() * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, es.shape_ids, lists.ids.size() * 2)) != DUST_OK) return s;
+    HIP_TRY(hipMemcpyAsync(es.shape_cells.p, lists.cells.data(), lists.cells.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(es.shape_starts.p, lists.starts.data(), lists.starts.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(es.shape_ids.p, lists.ids.data(), lists.ids.size() * 2, hipMemcpyHostToDevice, st));
+    Args a{};
+    a.grid = static_cast<uint8_t*>(es.grid.p);
+    a.cells = static_cast<const uint32_t*>(es.shape_cells.p);
+    a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
+    a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
+    a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
+    a.n_cells = uint32_t(lists.cells.size());
+    if ((s = launch(c0, a)) != DUST_OK) return s;
+    c0 = c1;
+  }
+  if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
+  s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
+  if (s != DUST_OK) return s;
+  if (changed) {
+    std::fill(changed, changed + n, 0u);
+    for (size_t k = 0; k < live; ++k) changed[index[k]] = counts[k];
+  }
+  return DUST_OK;
+}
+}  // extern "C++"
 }  // namespace
 
 DustStatus dust_hip_model_set_voxels(DustHipModel* m, const uint32_t* xyz, const int32_t* values, uint32_t n) {
   if (!m || (n && (!xyz || !values))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  for (uint32_t i = 0; i < n; ++i) {
-    if (xyz[i * 3] >= m->dev.extent || xyz[i * 3 + 1] >= m->dev.extent || xyz[i * 3 + 2] >= m->dev.extent)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
+  for (uint32_t i = 0; i < n; ++i) {  // (voxel by voxel: the first voxel that is wrong in either way is the one refused)
+    const DustStatus s = check_coordinates(xyz + size_t(i) * 3, 1, m->dev.extent);
+    if (s != DUST_OK) return s;
     if (values[i] > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxel)");
   }
   return guarded([&]() -> DustStatus {
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    HIP_TRY(join_side(m->ctx));  // (a surfel pass on the second stream still traces the model as it is)
-    DustStatus s = make_editable(m);
+    DustStatus s = begin_edit(m);
     if (s != DUST_OK || n == 0) return s;
     // a voxel named more than once takes its LAST value (what a sequence of set calls would leave): keep the last entry
     std::vector<uint32_t> ux;
@@ -349,8 +440,7 @@ DustStatus dust_hip_model_set_voxels(DustHipModel* m, const uint32_t* xyz, const
       uv.push_back(values[k]);
     }
     const uint32_t un = uint32_t(uv.size());
-    m->edit->labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
-    m->edit->flood_valid = false;   // (and so does dust_hip_model_flood's field)
+    invalidate_derived(*m->edit);
     s = upload_batch(m, ux.data(), uv.data(), un, true);
     if (s != DUST_OK) return s;
     dust::EditArgs a = edit_args(m, *m->edit);
@@ -363,104 +453,6 @@ DustStatus dust_hip_model_set_voxels(DustHipModel* m, const uint32_t* xyz, const
 }
 
 // ---- shape edits (edit.hip k_edit_shapes)
-namespace {
-constexpr size_t kShapeChunkIds = size_t(1) << 21;  // cell-list entries (u16) one launch carries: 4 MiB, 512 whole-tree shapes
-
-// The caller's record -> the device's: the two grid bytes of the operation and conservative voxel bounds -- the shape's extent
-// padded by more than a voxel (the float32 formulas stay within a small fraction of a voxel of the real distance for
-// coordinates up to 65 536), clipped to the tree. false: the shape covers nothing.
-bool device_shape(const DustHipEditShape& s, dust::DevEditShape& d) {
-  const bool box = s.kind == DUST_HIP_SHAPE_BOX, sphere = s.kind == DUST_HIP_SHAPE_SPHERE;
-  double lo[3], hi[3];
-  for (int r = 0; r < 3; ++r) {
-    if (!std::isfinite(s.a[r]) || (!sphere && !std::isfinite(s.b[r]))) return false;
-    if (box) {
-      if (s.a[r] > s.b[r]) return false;
-      lo[r] = s.a[r]; hi[r] = s.b[r];
-    } else {
-      if (!std::isfinite(s.radius) || s.radius < 0.0f || s.radius > 65536.0f) return false;
-      if (std::fabs(s.a[r]) > 65536.0f || (!sphere && std::fabs(s.b[r]) > 65536.0f)) return false;
-      const double p = s.a[r], q = sphere ? p : double(s.b[r]);
-      lo[r] = std::min(p, q) - double(s.radius); hi[r] = std::max(p, q) + double(s.radius);
-    }
-  }
-  uint32_t vlo[3], vhi[3];
-  for (int r = 0; r < 3; ++r) {  // voxel x is covered when lo <= x + 0.5 <= hi
-    const double l = std::floor(lo[r] - 0.5) - 1.0, h = std::ceil(hi[r] - 0.5) + 1.0;
-    if (l > 255.0 || h < 0.0) return false;
-    vlo[r] = l < 0.0 ? 0u : uint32_t(l);
-    vhi[r] = h > 255.0 ? 255u : uint32_t(h);
-  }
-  std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.b, s.b, sizeof(d.b));
-  d.kind = s.kind;
-  d.radius = box ? 0.0f : s.radius;
-  if (sphere) std::memcpy(d.b, s.a, sizeof(d.b));
-  const uint32_t byte = uint32_t(s.palette) + 1u;
-  switch (s.op) {
-    case DUST_HIP_EDIT_CARVE: d.solid_to = 0; d.empty_to = 0; break;
-    case DUST_HIP_EDIT_FILL: d.solid_to = byte; d.empty_to = byte; break;
-    case DUST_HIP_EDIT_PAINT: d.solid_to = byte; d.empty_to = 0; break;
-    default: d.solid_to = dust::kEditKeep; d.empty_to = byte; break;  // PLACE
-  }
-  d.lo = vlo[0] | (vlo[1] << 8) | (vlo[2] << 16);
-  d.hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
-  return true;
-}
-extern "C++" {  // (templates: no C linkage)
-// ---- the cell lists of a launch, shared by the shape edits and the stamps: a record's packed inclusive voxel bounds (lo, hi:
-// x | y << 8 | z << 16) binned into the 4096 root cells
-template <class Rec>
-inline size_t shape_cells(const Rec& d) {  // root cells (16^3 voxels) the bounds reach
-  size_t n = 1;
-  for (int r = 0; r < 3; ++r) n *= size_t((((d.hi >> (8 * r)) & 255u) >> 4) - (((d.lo >> (8 * r)) & 255u) >> 4) + 1u);
-  return n;
-}
-// where the order-preserving chunk that begins at record c0 ends: before its lists would pass kShapeChunkIds entries or its ids a u16
-template <class Rec>
-size_t chunk_end(const std::vector<Rec>& dev, size_t c0) {
-  size_t c1 = c0, total = 0;
-  while (c1 < dev.size() && c1 - c0 < 65536 && (c1 == c0 || total + shape_cells(dev[c1]) <= kShapeChunkIds)) total += shape_cells(dev[c1++]);
-  return c1;
-}
-// the chunk's lists on the host: the non-empty cells, and per cell an ascending list of u16 record ids (relative to c0) in CSR form
-struct CellLists {
-  std::vector<uint32_t> cells, starts, fill = std::vector<uint32_t>(4096);
-  std::vector<uint16_t> ids;
-  template <class Rec>
-  void bin(const std::vector<Rec>& dev, size_t c0, size_t c1) {
-    std::fill(fill.begin(), fill.end(), 0u);
-    auto each_cell = [&](const Rec& d, auto&& f) {
-      for (uint32_t x = (d.lo & 255u) >> 4; x <= (d.hi & 255u) >> 4; ++x)
-        for (uint32_t y = ((d.lo >> 8) & 255u) >> 4; y <= ((d.hi >> 8) & 255u) >> 4; ++y)
-          for (uint32_t z = (d.lo >> 16) >> 4; z <= (d.hi >> 16) >> 4; ++z) f((x << 8) | (y << 4) | z);
-    };
-    for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ++fill[cell]; });
-    cells.clear(); starts.clear();
-    uint32_t run = 0;
-    for (uint32_t cell = 0; cell < 4096; ++cell) {
-      const uint32_t k = fill[cell];
-      fill[cell] = run;  // where the cell's next id goes
-      if (k) { cells.push_back(cell); starts.push_back(run); run += k; }
-    }
-    starts.push_back(run);
-    ids.resize(run);
-    for (size_t i = c0; i < c1; ++i) each_cell(dev[i], [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
-  }
-  // into the model's staging buffers, on the context's stream (the host lists must stay as they are until the stream has been waited for)
-  DustStatus upload(DustHipContext* ctx, EditState& es) {
-    DustStatus s;
-    if ((s = grow(ctx, es.shape_cells, cells.size() * 4)) != DUST_OK) return s;
-    if ((s = grow(ctx, es.shape_starts, starts.size() * 4)) != DUST_OK) return s;
-    if ((s = grow(ctx, es.shape_ids, ids.size() * 2)) != DUST_OK) return s;
-    HIP_TRY(hipMemcpyAsync(es.shape_cells.p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(es.shape_starts.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(es.shape_ids.p, ids.data(), ids.size() * 2, hipMemcpyHostToDevice, ctx->stream));
-    return DUST_OK;
-  }
-};
-}  // extern "C++"
-}  // namespace
-
 DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* shapes, uint32_t n, uint32_t* changed) {
   if (!m || (n && !shapes)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
   if (n > DUST_HIP_MAX_EDIT_SHAPES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_EDIT_SHAPES shapes in one call");
@@ -471,97 +463,45 @@ DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* s
       return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254");
   }
   return guarded([&]() -> DustStatus {
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    HIP_TRY(join_side(m->ctx));
-    DustStatus s = make_editable(m);
+    DustStatus s = begin_edit(m);
     if (s != DUST_OK || n == 0) return s;
     EditState& es = *m->edit;
-    es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
-    es.flood_valid = false;   // (and so does dust_hip_model_flood's field)
-    hipStream_t st = m->ctx->stream;
-    // the shapes that cover something, in call order: `index` maps them back to the caller's
+    invalidate_derived(es);
     std::vector<dust::DevEditShape> dev;
     std::vector<uint32_t> index;
-    dev.reserve(n); index.reserve(n);
-    for (uint32_t i = 0; i < n; ++i) {
-      dust::DevEditShape d{};
-      if (device_shape(shapes[i], d)) { dev.push_back(d); index.push_back(i); }
-    }
-    const size_t live = dev.size();
-    std::vector<uint32_t> counts(live, 0u);
-    if (live) {
-      if ((s = grow(m->ctx, es.shapes, live * sizeof(dust::DevEditShape))) != DUST_OK) return s;
-      if ((s = grow(m->ctx, es.changed, live * 4)) != DUST_OK) return s;
-      HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), live * sizeof(dust::DevEditShape), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
-    }
-    // Order-preserving chunks, each one launch: its shapes binned into the 4096 root cells, an ascending list of u16 shape
-    // ids per cell in CSR form, one workgroup per non-empty cell. A chunk ends where its lists would pass kShapeChunkIds.
-    CellLists lists;
-    for (size_t c0 = 0; c0 < live;) {
-      const size_t c1 = chunk_end(dev, c0);
-      if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
-      lists.bin(dev, c0, c1);
-      if ((s = lists.upload(m->ctx, es)) != DUST_OK) return s;
-      dust::EditShapeArgs a{};
-      a.grid = static_cast<uint8_t*>(es.grid.p);
+    dust::live_records<dust::device_shape>(shapes, n, dev, index);
+    return batched_edit<dust::EditShapeArgs>(m, dev, index, n, changed, [&](size_t c0, dust::EditShapeArgs& a) -> DustStatus {
       a.shapes = static_cast<const dust::DevEditShape*>(es.shapes.p) + c0;
-      a.cells = static_cast<const uint32_t*>(es.shape_cells.p);
-      a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
-      a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
-      a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
-      a.n_cells = uint32_t(lists.cells.size());
-      HIP_TRY(dust::launch_edit_shapes(a, st));
-      c0 = c1;
-    }
-    if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
-    s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
-    if (s != DUST_OK) return s;
-    if (changed) {
-      std::fill(changed, changed + n, 0u);
-      for (size_t k = 0; k < live; ++k) changed[index[k]] = counts[k];
-    }
-    return DUST_OK;
+      HIP_TRY(dust::launch_edit_shapes(a, m->ctx->stream));
+      return DUST_OK;
+    });
   });
 }
 
 // ---- model stamps (stamp.hip k_stamp)
-static_assert(sizeof(DustHipStamp) == 32 && sizeof(dust::DevStamp) == 32, "stamp records");
 namespace {
-bool valid_orient(uint32_t o) {
-  if (o >> 9) return false;
-  const uint32_t p0 = o & 3u, p1 = (o >> 2) & 3u, p2 = (o >> 4) & 3u;
-  return ((1u << p0) | (1u << p1) | (1u << p2)) == 7u;
-}
-// The caller's record -> the device's: the image box clipped to the tree, one affine map per destination axis, the operation as a
-// table. Everything in int64: any int32 offset is legal. false: the stamp covers nothing.
-bool device_stamp(const DustHipStamp& s, dust::DevStamp& d) {
-  for (int k = 0; k < 3; ++k)
-    if (s.src_lo[k] > s.src_hi[k]) return false;
-  uint32_t lo[3], hi[3];
-  for (int r = 0; r < 3; ++r) {
-    const uint32_t p = (s.orient >> (2 * r)) & 3u;
-    const bool flip = (s.orient >> (6 + r)) & 1u;
-    const int64_t off = s.offset[r], first = std::max<int64_t>(off, 0), last = std::min<int64_t>(off + int64_t(s.src_hi[p] - s.src_lo[p]), 255);
-    if (first > last) return false;
-    lo[r] = uint32_t(first); hi[r] = uint32_t(last);
-    d.base[r] = int32_t(flip ? int64_t(s.src_hi[p]) + off : int64_t(s.src_lo[p]) - off);  // (|off| <= 255 here)
+// The source as it stands now, as a grid: its own when it is editable (read in place), expanded into the context's scratch when it
+// is not (the source itself is not touched), and a copy of the destination's when a model is stamped onto itself
+DustStatus stamp_source_grid(DustHipModel* m, const DustHipModel* src, const uint8_t** source) {
+  DustHipContext* ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  if (src != m && src->edit) {
+    *source = static_cast<const uint8_t*>(src->edit->grid.p);
+    return DUST_OK;
   }
-  d.lo = lo[0] | (lo[1] << 8) | (lo[2] << 16);
-  d.hi = hi[0] | (hi[1] << 8) | (hi[2] << 16);
-  d.orient = s.orient;
-  // two bits per case (source solid) << 1 | (destination solid): keep the destination's byte, take the source's, or None
-  const uint32_t K = dust::kStampKeep, T = dust::kStampTake, N = dust::kStampClear;
-  auto table = [](uint32_t ee, uint32_t es, uint32_t se, uint32_t ss) { return ee | (es << 2) | (se << 4) | (ss << 6); };
-  switch (s.op) {
-    case DUST_HIP_STAMP_PLACE: d.table = table(K, K, T, K); break;
-    case DUST_HIP_STAMP_OVERWRITE: d.table = table(K, K, T, T); break;
-    case DUST_HIP_STAMP_REPLACE: d.table = table(T, T, T, T); break;
-    case DUST_HIP_STAMP_CARVE: d.table = table(K, K, K, N); break;
-    default: d.table = table(K, K, K, T); break;  // PAINT
+  const size_t grid_bytes = size_t(dust::kLattice) * 64;
+  DustStatus s = lazy_alloc(ctx->stamp_grid, grid_bytes, "the stamp source grid (16 MiB)");
+  if (s != DUST_OK) return s;
+  if (src == m) {
+    HIP_TRY(hipMemcpyAsync(ctx->stamp_grid.p, m->edit->grid.p, grid_bytes, hipMemcpyDeviceToDevice, st));
+  } else {
+    HIP_TRY(hipMemsetAsync(ctx->stamp_grid.p, 0, grid_bytes, st));
+    dust::EditArgs e{};  // (expand only writes the grid)
+    e.grid = static_cast<uint8_t*>(ctx->stamp_grid.p);
+    HIP_TRY(dust::launch_edit_expand(e, static_cast<const DustHipBlock*>(src->blocks.p), static_cast<const uint8_t*>(src->materials.p), src->dev.n_blocks, st));
   }
-  d.pad = 0;
-  return true;
+  *source = static_cast<const uint8_t*>(ctx->stamp_grid.p);
+  return DUST_OK;
 }
 }  // namespace
 
@@ -574,7 +514,7 @@ DustStatus dust_hip_model_stamp(DustHipModel* m, const DustHipModel* src, const 
   if (s == DUST_OK) s = editable_kind(src);
   if (s != DUST_OK) return s;
   for (uint32_t i = 0; i < n; ++i) {
-    if (!valid_orient(stamps[i].orient)) return fail(DUST_ERR_INVALID_ARGUMENT, "orient is not a signed axis permutation (p a permutation of 0, 1, 2; bits 9 and above zero)");
+    if (!dust::valid_orient(stamps[i].orient)) return fail(DUST_ERR_INVALID_ARGUMENT, "orient is not a signed axis permutation (p a permutation of 0, 1, 2; bits 9 and above zero)");
     if (stamps[i].op > DUST_HIP_STAMP_PAINT) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown stamp op");
   }
   uint8_t map[256];  // grid byte (palette index + 1, 0 = None) -> grid byte
@@ -585,132 +525,45 @@ DustStatus dust_hip_model_stamp(DustHipModel* m, const DustHipModel* src, const 
   }
   return guarded([&]() -> DustStatus {
     DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(join_side(ctx));
-    DustStatus s = make_editable(m);
+    DustStatus s = begin_edit(m);
     if (s != DUST_OK || n == 0) return s;
     EditState& es = *m->edit;
-    es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
-    es.flood_valid = false;   // (and so does dust_hip_model_flood's field)
-    hipStream_t st = ctx->stream;
-    // the stamps that cover something, in call order: `index` maps them back to the caller's
+    invalidate_derived(es);
     std::vector<dust::DevStamp> dev;
     std::vector<uint32_t> index;
-    dev.reserve(n); index.reserve(n);
-    for (uint32_t i = 0; i < n; ++i) {
-      dust::DevStamp d{};
-      if (device_stamp(stamps[i], d)) { dev.push_back(d); index.push_back(i); }
-    }
-    const size_t live = dev.size();
-    std::vector<uint32_t> counts(live, 0u);
+    dust::live_records<dust::device_stamp>(stamps, n, dev, index);
     const uint8_t* source = nullptr;
-    if (live) {
-      // The source as it stands now, as a grid: its own when it is editable (read in place), expanded into the context's scratch when it
-      // is not (the source itself is not touched), and a copy of the destination's when a model is stamped onto itself
-      const size_t grid_bytes = size_t(dust::kLattice) * 64;
-      if (src == m || !src->edit) {
-        if (!ctx->stamp_grid.p) {
-          const hipError_t e = ctx->stamp_grid.alloc(grid_bytes);
-          if (e != hipSuccess) { ctx->stamp_grid.release(); return hip_fail(e, "the stamp source grid (16 MiB)"); }
-        }
-        if (src == m) {
-          HIP_TRY(hipMemcpyAsync(ctx->stamp_grid.p, es.grid.p, grid_bytes, hipMemcpyDeviceToDevice, st));
-        } else {
-          HIP_TRY(hipMemsetAsync(ctx->stamp_grid.p, 0, grid_bytes, st));
-          dust::EditArgs e{};  // (expand only writes the grid)
-          e.grid = static_cast<uint8_t*>(ctx->stamp_grid.p);
-          HIP_TRY(dust::launch_edit_expand(e, static_cast<const DustHipBlock*>(src->blocks.p), static_cast<const uint8_t*>(src->materials.p), src->dev.n_blocks, st));
-        }
-        source = static_cast<const uint8_t*>(ctx->stamp_grid.p);
-      } else {
-        source = static_cast<const uint8_t*>(src->edit->grid.p);
-      }
-      if ((s = grow(ctx, es.shapes, live * sizeof(dust::DevStamp))) != DUST_OK) return s;
-      if ((s = grow(ctx, es.changed, live * 4)) != DUST_OK) return s;
+    if (!dev.empty()) {
+      if ((s = stamp_source_grid(m, src, &source)) != DUST_OK) return s;
       if ((s = grow(ctx, ctx->stage_aux, sizeof(map))) != DUST_OK) return s;
-      HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), live * sizeof(dust::DevStamp), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
-      HIP_TRY(hipMemcpyAsync(ctx->stage_aux.p, map, sizeof(map), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(ctx->stage_aux.p, map, sizeof(map), hipMemcpyHostToDevice, ctx->stream));
     }
-    // order-preserving chunks, each one launch, as dust_hip_model_edit_shapes cuts them
-    CellLists lists;
-    for (size_t c0 = 0; c0 < live;) {
-      const size_t c1 = chunk_end(dev, c0);
-      if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
-      lists.bin(dev, c0, c1);
-      if ((s = lists.upload(ctx, es)) != DUST_OK) return s;
-      dust::StampArgs a{};
-      a.grid = static_cast<uint8_t*>(es.grid.p);
+    return batched_edit<dust::StampArgs>(m, dev, index, n, changed, [&](size_t c0, dust::StampArgs& a) -> DustStatus {
       a.src = source;
       a.stamps = static_cast<const dust::DevStamp*>(es.shapes.p) + c0;
-      a.cells = static_cast<const uint32_t*>(es.shape_cells.p);
-      a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
-      a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
-      a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
       a.palette_map = static_cast<const uint8_t*>(ctx->stage_aux.p);
-      a.n_cells = uint32_t(lists.cells.size());
-      HIP_TRY(dust::launch_stamp(a, st));
-      c0 = c1;
-    }
-    if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
-    s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
-    if (s != DUST_OK) return s;
-    if (changed) {
-      std::fill(changed, changed + n, 0u);
-      for (size_t k = 0; k < live; ++k) changed[index[k]] = counts[k];
-    }
-    return DUST_OK;
+      HIP_TRY(dust::launch_stamp(a, ctx->stream));
+      return DUST_OK;
+    });
   });
 }
 
 // ---- model casts (cast.hip k_cast_walk / k_cast_count): both models are only read, through their brick masks
-static_assert(sizeof(DustHipCast) == 48 && sizeof(DustHipCastHit) == 32 && sizeof(dust::DevCast) == 48 && sizeof(dust::CastItem) == 8 &&
-              sizeof(dust::CastAcc) == 16, "cast records");
 namespace {
-constexpr size_t kCastChunkItems = size_t(1) << 20;  // work items (8 bytes) one launch carries; a whole-tree sub-box is 4096 of them
-
-// The caller's record -> the device's, everything in int64: any int32 offset is legal. Per destination axis the placements at which
-// the image box meets the tree are an interval; their intersection, cut to 0..max_steps, is all the device walks (under WALLS: from 0 to
-// one past the last placement the image is inside, or placement 0 alone when it begins outside). false: the sub-box is empty.
-bool device_cast(const DustHipCast& s, dust::DevCast& d) {
-  for (int k = 0; k < 3; ++k)
-    if (s.src_lo[k] > s.src_hi[k]) return false;
-  const bool walls = s.flags & DUST_HIP_CAST_WALLS;
-  const bool still = s.step[0] == 0 && s.step[1] == 0 && s.step[2] == 0;
-  const int64_t max_steps = still ? 0 : int64_t(s.max_steps);  // (every placement is placement 0)
-  const int64_t never = int64_t(1) << 40;                      // beyond any placement
-  int64_t first = -never, last = never;
-  for (int r = 0; r < 3; ++r) {
-    const uint32_t p = (s.orient >> (2 * r)) & 3u;
-    const int64_t off = s.offset[r], ext = int64_t(s.src_hi[p]) - int64_t(s.src_lo[p]);
-    int64_t f, l;
-    if (s.step[r] == 0) {
-      const bool meets = off + ext >= 0 && off <= 255;
-      f = meets ? -never : 1; l = meets ? never : 0;
-    } else if (s.step[r] > 0) {
-      f = -(off + ext); l = 255 - off;
-    } else {
-      f = off - 255; l = off + ext;
-    }
-    first = std::max(first, f); last = std::min(last, l);
-    d.off[r] = int32_t(std::clamp<int64_t>(off, -dust::kCastOffsetLimit, dust::kCastOffsetLimit));
-    d.step[r] = s.step[r];
+// The source's brick masks: its own when it is editable (dst itself included); otherwise its blocks' masks scattered into the
+// context's scratch -- the source is not touched
+DustStatus cast_source_masks(DustHipContext* ctx, const DustHipModel* src, const uint64_t** src_mask) {
+  if (src->edit) {
+    *src_mask = static_cast<const uint64_t*>(src->edit->brick_mask.p);
+    return DUST_OK;
   }
-  int64_t k_lo, k_hi;
-  if (walls) {
-    k_lo = 0;
-    k_hi = first <= 0 && last >= 0 ? std::min(max_steps, last + 1) : 0;
-  } else {
-    k_lo = std::max<int64_t>(first, 0);
-    k_hi = std::min(last, max_steps);
-  }
-  if (k_lo > k_hi) { k_lo = 1; k_hi = 0; }  // nothing to walk (the piece's voxels are still counted)
-  d.k_lo = uint32_t(k_lo); d.k_hi = uint32_t(k_hi);
-  d.max_steps = uint32_t(max_steps);
-  d.orient = s.orient | (walls ? dust::kCastWalls : 0u);
-  d.lo = s.src_lo[0] | (uint32_t(s.src_lo[1]) << 8) | (uint32_t(s.src_lo[2]) << 16);
-  d.hi = s.src_hi[0] | (uint32_t(s.src_hi[1]) << 8) | (uint32_t(s.src_hi[2]) << 16);
-  return true;
+  const size_t bytes = size_t(dust::kLattice) * 8;
+  DustStatus s = lazy_alloc(ctx->cast_mask, bytes, "the cast source masks (2 MiB)");
+  if (s != DUST_OK) return s;
+  HIP_TRY(hipMemsetAsync(ctx->cast_mask.p, 0, bytes, ctx->stream));
+  HIP_TRY(dust::launch_cast_masks(static_cast<uint64_t*>(ctx->cast_mask.p), static_cast<const DustHipBlock*>(src->blocks.p), src->dev.n_blocks, ctx->stream));
+  *src_mask = static_cast<const uint64_t*>(ctx->cast_mask.p);
+  return DUST_OK;
 }
 }  // namespace
 
@@ -723,7 +576,7 @@ DustStatus dust_hip_model_cast(DustHipModel* m, const DustHipModel* src, const D
   if (s != DUST_OK) return s;
   for (uint32_t i = 0; i < n; ++i) {
     const DustHipCast& c = casts[i];
-    if (!valid_orient(c.orient)) return fail(DUST_ERR_INVALID_ARGUMENT, "orient is not a signed axis permutation (p a permutation of 0, 1, 2; bits 9 and above zero)");
+    if (!dust::valid_orient(c.orient)) return fail(DUST_ERR_INVALID_ARGUMENT, "orient is not a signed axis permutation (p a permutation of 0, 1, 2; bits 9 and above zero)");
     for (int r = 0; r < 3; ++r)
       if (c.step[r] < -1 || c.step[r] > 1) return fail(DUST_ERR_INVALID_ARGUMENT, "a step component must be -1, 0 or 1");
     if (c.max_steps > DUST_HIP_CAST_MAX_STEPS) return fail(DUST_ERR_INVALID_ARGUMENT, "max_steps above DUST_HIP_CAST_MAX_STEPS");
@@ -731,47 +584,22 @@ DustStatus dust_hip_model_cast(DustHipModel* m, const DustHipModel* src, const D
   }
   return guarded([&]() -> DustStatus {
     DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(join_side(ctx));
-    DustStatus s = make_editable(m);
+    DustStatus s = begin_edit(m);
     if (s != DUST_OK || n == 0) return s;
     hipStream_t st = ctx->stream;
-    // the casts with a sub-box, in call order: `index` maps them back to the caller's
-    std::vector<dust::DevCast> dev;
+    std::vector<dust::DevCast> dev;  // the casts with a sub-box
     std::vector<uint32_t> index;
-    dev.reserve(n); index.reserve(n);
-    for (uint32_t i = 0; i < n; ++i) {
-      dust::DevCast d{};
-      if (device_cast(casts[i], d)) { dev.push_back(d); index.push_back(i); }
-    }
+    dust::live_records<dust::device_cast>(casts, n, dev, index);
     const size_t live = dev.size();
     std::vector<unsigned long long> best(live, dust::kCastNoHit);
     std::vector<dust::CastAcc> acc(live);
     if (live) {
-      // The source's brick masks: its own when it is editable (dst itself included); otherwise its blocks' masks scattered into the
-      // context's scratch -- the source is not touched
       const uint64_t* src_mask = nullptr;
-      if (src->edit) {
-        src_mask = static_cast<const uint64_t*>(src->edit->brick_mask.p);
-      } else {
-        const size_t bytes = size_t(dust::kLattice) * 8;
-        if (!ctx->cast_mask.p) {
-          const hipError_t e = ctx->cast_mask.alloc(bytes);
-          if (e != hipSuccess) { ctx->cast_mask.release(); return hip_fail(e, "the cast source masks (2 MiB)"); }
-        }
-        HIP_TRY(hipMemsetAsync(ctx->cast_mask.p, 0, bytes, st));
-        HIP_TRY(dust::launch_cast_masks(static_cast<uint64_t*>(ctx->cast_mask.p), static_cast<const DustHipBlock*>(src->blocks.p), src->dev.n_blocks, st));
-        src_mask = static_cast<const uint64_t*>(ctx->cast_mask.p);
-      }
-      auto cells_of = [](const dust::DevCast& d) {
-        size_t c = 1;
-        for (int r = 0; r < 3; ++r) c *= size_t((((d.hi >> (8 * r)) & 255u) >> 4) - (((d.lo >> (8 * r)) & 255u) >> 4) + 1u);
-        return c;
-      };
+      if ((s = cast_source_masks(ctx, src, &src_mask)) != DUST_OK) return s;
       const size_t best_bytes = live * sizeof(unsigned long long);
       if ((s = grow(ctx, ctx->stage_in, live * sizeof(dust::DevCast))) != DUST_OK) return s;
       if ((s = grow(ctx, ctx->stage_out, best_bytes + live * sizeof(dust::CastAcc))) != DUST_OK) return s;
-      if ((s = grow(ctx, ctx->stage_aux, std::max(kCastChunkItems, size_t(4096)) * sizeof(dust::CastItem))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_aux, std::max(dust::kCastChunkItems, size_t(4096)) * sizeof(dust::CastItem))) != DUST_OK) return s;
       uint8_t* out = static_cast<uint8_t*>(ctx->stage_out.p);
       HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, dev.data(), live * sizeof(dust::DevCast), hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemsetAsync(out, 0xFF, best_bytes, st));                          // kCastNoHit
@@ -779,16 +607,9 @@ DustStatus dust_hip_model_cast(DustHipModel* m, const DustHipModel* src, const D
       // chunks of casts, each one pair of launches: a chunk ends where its work items would pass kCastChunkItems
       std::vector<dust::CastItem> items;
       for (size_t c0 = 0; c0 < live;) {
-        size_t c1 = c0, total = 0;
-        while (c1 < live && (c1 == c0 || total + cells_of(dev[c1]) <= kCastChunkItems)) total += cells_of(dev[c1++]);
+        const size_t c1 = dust::chunk_end(dev, c0, dust::kCastChunkItems, dust::kNoRecordCap);
         if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copy has left the host list
-        items.clear();
-        for (size_t i = c0; i < c1; ++i) {
-          const dust::DevCast& d = dev[i];
-          for (uint32_t x = (d.lo & 255u) >> 4; x <= (d.hi & 255u) >> 4; ++x)
-            for (uint32_t y = ((d.lo >> 8) & 255u) >> 4; y <= ((d.hi >> 8) & 255u) >> 4; ++y)
-              for (uint32_t z = (d.lo >> 16) >> 4; z <= (d.hi >> 16) >> 4; ++z) items.push_back({uint32_t(i - c0), (x << 8) | (y << 4) | z});
-        }
+        dust::cast_items(dev, c0, c1, items);
         HIP_TRY(hipMemcpyAsync(ctx->stage_aux.p, items.data(), items.size() * sizeof(dust::CastItem), hipMemcpyHostToDevice, st));
         dust::CastArgs a{};
         a.src_mask = src_mask;
@@ -805,42 +626,18 @@ DustStatus dust_hip_model_cast(DustHipModel* m, const DustHipModel* src, const D
       HIP_TRY(hipMemcpyAsync(acc.data(), out + best_bytes, live * sizeof(dust::CastAcc), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));  // (the host vectors above stay alive until the copies are done)
     }
-    for (uint32_t i = 0; i < n; ++i) {
-      DustHipCastHit h{};
-      h.steps = casts[i].max_steps;
-      h.src_key = DUST_HIP_CAST_NO_KEY;
-      hits[i] = h;
-    }
-    for (size_t j = 0; j < live; ++j) {
-      const DustHipCast& c = casts[index[j]];
-      DustHipCastHit& h = hits[index[j]];
-      h.voxels = acc[j].voxels;
-      if (best[j] == dust::kCastNoHit) continue;
-      const uint32_t k = uint32_t(best[j] >> 24), key = uint32_t(best[j] & 0xFFFFFFu);
-      const uint32_t sv[3] = {key >> 16, (key >> 8) & 255u, key & 255u};
-      h.flags = DUST_HIP_CAST_HIT | (k == 0 ? DUST_HIP_CAST_OVERLAP : 0u) | (acc[j].wall ? DUST_HIP_CAST_HIT_WALL : 0u);
-      h.steps = k ? k - 1 : 0;
-      h.contacts = acc[j].contacts;
-      h.src_key = key;
-      for (int r = 0; r < 3; ++r) {
-        const uint32_t p = (c.orient >> (2 * r)) & 3u;
-        const int64_t u = ((c.orient >> (6 + r)) & 1u) ? int64_t(c.src_hi[p]) - int64_t(sv[p]) : int64_t(sv[p]) - int64_t(c.src_lo[p]);
-        h.contact[r] = int32_t(uint32_t(uint64_t(int64_t(c.offset[r]) + int64_t(k) * c.step[r] + u)));  // (the low 32 bits)
-      }
-    }
+    for (uint32_t i = 0; i < n; ++i) hits[i] = dust::cast_hit(casts[i], dust::kCastNoHit, dust::CastAcc{});
+    for (size_t j = 0; j < live; ++j) hits[index[j]] = dust::cast_hit(casts[index[j]], best[j], acc[j]);
     return DUST_OK;
   });
 }
 
 DustStatus dust_hip_model_get_voxels(DustHipModel* m, const uint32_t* xyz, int32_t* values, uint32_t n) {
   if (!m || (n && (!xyz || !values))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  for (uint32_t i = 0; i < n; ++i)
-    if (xyz[i * 3] >= m->dev.extent || xyz[i * 3 + 1] >= m->dev.extent || xyz[i * 3 + 2] >= m->dev.extent)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
+  DustStatus s = check_coordinates(xyz, n, m->dev.extent);
+  if (s != DUST_OK) return s;
   return guarded([&]() -> DustStatus {
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    HIP_TRY(join_side(m->ctx));
-    DustStatus s = make_editable(m);
+    s = begin_edit(m);
     if (s != DUST_OK || n == 0) return s;
     s = upload_batch(m, xyz, nullptr, n, false);
     if (s != DUST_OK) return s;
@@ -864,9 +661,7 @@ DustStatus dust_hip_model_find_islands(DustHipModel* m, const DustHipIslandQuery
   if (q->connectivity > DUST_HIP_ISLANDS_CORNERS) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown island connectivity");
   return guarded([&]() -> DustStatus {
     DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(join_side(ctx));
-    DustStatus s = make_editable(m);
+    DustStatus s = begin_edit(m);
     if (s != DUST_OK) return s;
     EditState& es = *m->edit;
     hipStream_t st = ctx->stream;
@@ -875,10 +670,7 @@ DustStatus dust_hip_model_find_islands(DustHipModel* m, const DustHipIslandQuery
     // a call with room for every record labels once
     const bool relabel = !(es.labels_valid && es.labels_corners == corners);
     es.labels_valid = false;  // until this labelling is complete
-    if (!es.labels.p) {
-      const hipError_t e = es.labels.alloc(size_t(dust::kIslandKeys) * 4);
-      if (e != hipSuccess) { es.labels.release(); return hip_fail(e, "the island label array (64 MiB)"); }
-    }
+    if ((s = lazy_alloc(es.labels, size_t(dust::kIslandKeys) * 4, "the island label array (64 MiB)")) != DUST_OK) return s;
     if ((s = grow(ctx, ctx->island_mask, size_t(dust::kIslandRows) * 8)) != DUST_OK) return s;
     if ((s = grow(ctx, ctx->island_count, size_t(dust::kIslandRows) * 4)) != DUST_OK) return s;
     if ((s = grow(ctx, ctx->island_tmp, 260 * 4)) != DUST_OK) return s;
@@ -916,23 +708,11 @@ DustStatus dust_hip_model_island_of(DustHipModel* m, const uint32_t* xyz, uint32
   if (!m || (n && (!xyz || !keys))) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
   DustStatus s = editable_kind(m);
   if (s != DUST_OK) return s;
-  for (uint32_t i = 0; i < n; ++i)
-    if (xyz[i * 3] >= 256u || xyz[i * 3 + 1] >= 256u || xyz[i * 3 + 2] >= 256u)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
-  if (!m->edit || !m->edit->labels_valid)
-    return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)");
+  if ((s = check_coordinates(xyz, n)) != DUST_OK) return s;
+  if (!m->edit || !m->edit->labels_valid) return no_labelling();
   if (n == 0) return DUST_OK;
-  return guarded([&]() -> DustStatus {
-    DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if ((s = grow(ctx, ctx->stage_in, size_t(n) * 12)) != DUST_OK) return s;
-    if ((s = grow(ctx, ctx->stage_out, size_t(n) * 4)) != DUST_OK) return s;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
-    HIP_TRY(dust::launch_island_lookup(static_cast<const uint32_t*>(m->edit->labels.p), static_cast<const uint32_t*>(ctx->stage_in.p),
-                                       static_cast<uint32_t*>(ctx->stage_out.p), n, st));
-    HIP_TRY(hipMemcpyAsync(keys, ctx->stage_out.p, size_t(n) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+  return lookup_call(m, xyz, keys, n, [&](const uint32_t* in, uint32_t* out, hipStream_t st) -> DustStatus {
+    HIP_TRY(dust::launch_island_lookup(static_cast<const uint32_t*>(m->edit->labels.p), in, out, n, st));
     return DUST_OK;
   });
 }
@@ -945,8 +725,7 @@ DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, 
   DustStatus s = editable_kind(m);
   if (s != DUST_OK) return s;
   if (n == 0) { if (out) *out = nullptr; return DUST_OK; }
-  if (!m->edit || !m->edit->labels_valid)
-    return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)");
+  if (!m->edit || !m->edit->labels_valid) return no_labelling();
   return guarded([&]() -> DustStatus {
     DustHipContext* ctx = m->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1004,16 +783,6 @@ DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, 
 
 // ---- model floods (flood.hip): step distances from seeds through the empty or the solid voxels, kept on the device with the model
 static_assert(sizeof(DustHipFloodQuery) == 40 && sizeof(DustHipFloodResult) == 32, "flood records");
-namespace {
-DustStatus check_coordinates(const uint32_t* xyz, uint32_t n) {
-  for (uint32_t i = 0; i < n; ++i)
-    if (xyz[i * 3] >= 256u || xyz[i * 3 + 1] >= 256u || xyz[i * 3 + 2] >= 256u)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "voxel coordinate outside the tree extent");
-  return DUST_OK;
-}
-DustStatus no_field() { return fail(DUST_ERR_NOT_READY, "the model has no valid flood field: call dust_hip_model_flood (again after an edit)"); }
-}  // namespace
-
 DustStatus dust_hip_model_flood(DustHipModel* m, const DustHipFloodQuery* q, const uint32_t* seeds_xyz, uint32_t n_seeds, DustHipFloodResult* out) {
   if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
   DustStatus s = editable_kind(m);  // (before anything else is looked at)
@@ -1027,17 +796,12 @@ DustStatus dust_hip_model_flood(DustHipModel* m, const DustHipFloodQuery* q, con
   if ((s = check_coordinates(seeds_xyz, n_seeds)) != DUST_OK) return s;
   return guarded([&]() -> DustStatus {
     DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(join_side(ctx));
-    DustStatus s = make_editable(m);
+    DustStatus s = begin_edit(m);
     if (s != DUST_OK) return s;
     EditState& es = *m->edit;
     hipStream_t st = ctx->stream;
     es.flood_valid = false;  // until this field is complete
-    if (!es.flood.p) {
-      const hipError_t e = es.flood.alloc(size_t(dust::kLattice) * 64 * 2);
-      if (e != hipSuccess) { es.flood.release(); return hip_fail(e, "the flood field (32 MiB)"); }
-    }
+    if ((s = lazy_alloc(es.flood, size_t(dust::kLattice) * 64 * 2, "the flood field (32 MiB)")) != DUST_OK) return s;
     const size_t L = dust::kLattice;
     if ((s = grow(ctx, ctx->flood_work, (4 * L + dust::kFloodWorkWords) * 4)) != DUST_OK) return s;
     if ((s = grow(ctx, ctx->stage_in, size_t(n_seeds) * 12)) != DUST_OK) return s;
@@ -1113,17 +877,8 @@ DustStatus dust_hip_model_flood_at(DustHipModel* m, const uint32_t* xyz, uint16_
   if ((s = check_coordinates(xyz, n)) != DUST_OK) return s;
   if (!m->edit || !m->edit->flood_valid) return no_field();
   if (n == 0) return DUST_OK;
-  return guarded([&]() -> DustStatus {
-    DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if ((s = grow(ctx, ctx->stage_in, size_t(n) * 12)) != DUST_OK) return s;
-    if ((s = grow(ctx, ctx->stage_out, size_t(n) * 2)) != DUST_OK) return s;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
-    HIP_TRY(dust::launch_flood_lookup(static_cast<const uint16_t*>(m->edit->flood.p), static_cast<const uint32_t*>(ctx->stage_in.p),
-                                      static_cast<uint16_t*>(ctx->stage_out.p), n, st));
-    HIP_TRY(hipMemcpyAsync(steps, ctx->stage_out.p, size_t(n) * 2, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+  return lookup_call(m, xyz, steps, n, [&](const uint32_t* in, uint16_t* out, hipStream_t st) -> DustStatus {
+    HIP_TRY(dust::launch_flood_lookup(static_cast<const uint16_t*>(m->edit->flood.p), in, out, n, st));
     return DUST_OK;
   });
 }
@@ -1170,8 +925,7 @@ DustStatus dust_hip_model_flood_apply(DustHipModel* m, uint32_t max_steps, int32
     HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
     EditState& es = *m->edit;
     hipStream_t st = ctx->stream;
-    es.flood_valid = false;   // the field and the labelling describe the voxels as they were
-    es.labels_valid = false;
+    invalidate_derived(es);
     uint32_t n = 0;
     if (es.flood_reached) {
       if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;

@@ -1,0 +1,232 @@
+// model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp), cuts a call into chunks, bins a chunk's records into
+// root cells and decodes a cast's result. No HIP call, no handle, no error state: tests/cpp/model_records_test.cpp drives it on a CPU.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/dust_hip.h"
+#include "cast.hpp"
+#include "edit.hpp"
+#include "stamp.hpp"
+
+namespace dust {
+
+static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
+static_assert(sizeof(DustHipCast) == 48 && sizeof(DustHipCastHit) == 32 && sizeof(DevCast) == 48 && sizeof(CastItem) == 8 && sizeof(CastAcc) == 16,
+              "cast records");
+
+constexpr size_t kShapeChunkIds = size_t(1) << 21;   // cell-list entries (u16) one launch carries: 4 MiB, 512 whole-tree shapes
+constexpr size_t kShapeChunkRecords = 65536;         // ... and records: a cell lists them by u16 id
+constexpr size_t kCastChunkItems = size_t(1) << 20;  // work items (8 bytes) one launch carries; a whole-tree sub-box is 4096 of them
+constexpr size_t kNoRecordCap = ~size_t(0);          // (a cast's work items name their cast in 32 bits)
+
+// ---- the caller's record -> the device's. Each returns false for a record that covers nothing: it is never sent to the device
+inline bool valid_orient(uint32_t o) {
+  if (o >> 9) return false;
+  const uint32_t p0 = o & 3u, p1 = (o >> 2) & 3u, p2 = (o >> 4) & 3u;
+  return ((1u << p0) | (1u << p1) | (1u << p2)) == 7u;
+}
+
+// The two grid bytes of the operation and conservative voxel bounds -- the shape's extent padded by more than a voxel (the float32
+// formulas stay within a small fraction of a voxel of the real distance for coordinates up to 65 536), clipped to the tree.
+inline bool device_shape(const DustHipEditShape& s, DevEditShape& d) {
+  const bool box = s.kind == DUST_HIP_SHAPE_BOX, sphere = s.kind == DUST_HIP_SHAPE_SPHERE;
+  double lo[3], hi[3];
+  for (int r = 0; r < 3; ++r) {
+    if (!std::isfinite(s.a[r]) || (!sphere && !std::isfinite(s.b[r]))) return false;
+    if (box) {
+      if (s.a[r] > s.b[r]) return false;
+      lo[r] = s.a[r]; hi[r] = s.b[r];
+    } else {
+      if (!std::isfinite(s.radius) || s.radius < 0.0f || s.radius > 65536.0f) return false;
+      if (std::fabs(s.a[r]) > 65536.0f || (!sphere && std::fabs(s.b[r]) > 65536.0f)) return false;
+      const double p = s.a[r], q = sphere ? p : double(s.b[r]);
+      lo[r] = std::min(p, q) - double(s.radius); hi[r] = std::max(p, q) + double(s.radius);
+    }
+  }
+  uint32_t vlo[3], vhi[3];
+  for (int r = 0; r < 3; ++r) {  // voxel x is covered when lo <= x + 0.5 <= hi
+    const double l = std::floor(lo[r] - 0.5) - 1.0, h = std::ceil(hi[r] - 0.5) + 1.0;
+    if (l > 255.0 || h < 0.0) return false;
+    vlo[r] = l < 0.0 ? 0u : uint32_t(l);
+    vhi[r] = h > 255.0 ? 255u : uint32_t(h);
+  }
+  std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.b, s.b, sizeof(d.b));
+  d.kind = s.kind;
+  d.radius = box ? 0.0f : s.radius;
+  if (sphere) std::memcpy(d.b, s.a, sizeof(d.b));
+  const uint32_t byte = uint32_t(s.palette) + 1u;
+  switch (s.op) {
+    case DUST_HIP_EDIT_CARVE: d.solid_to = 0; d.empty_to = 0; break;
+    case DUST_HIP_EDIT_FILL: d.solid_to = byte; d.empty_to = byte; break;
+    case DUST_HIP_EDIT_PAINT: d.solid_to = byte; d.empty_to = 0; break;
+    default: d.solid_to = kEditKeep; d.empty_to = byte; break;  // PLACE
+  }
+  d.lo = vlo[0] | (vlo[1] << 8) | (vlo[2] << 16);
+  d.hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
+  return true;
+}
+
+// The image box clipped to the tree, one affine map per destination axis, the operation as a table. Everything in int64: any int32
+// offset is legal.
+inline bool device_stamp(const DustHipStamp& s, DevStamp& d) {
+  for (int k = 0; k < 3; ++k)
+    if (s.src_lo[k] > s.src_hi[k]) return false;
+  uint32_t lo[3], hi[3];
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t p = (s.orient >> (2 * r)) & 3u;
+    const bool flip = (s.orient >> (6 + r)) & 1u;
+    const int64_t off = s.offset[r], first = std::max<int64_t>(off, 0), last = std::min<int64_t>(off + int64_t(s.src_hi[p] - s.src_lo[p]), 255);
+    if (first > last) return false;
+    lo[r] = uint32_t(first); hi[r] = uint32_t(last);
+    d.base[r] = int32_t(flip ? int64_t(s.src_hi[p]) + off : int64_t(s.src_lo[p]) - off);  // (|off| <= 255 here)
+  }
+  d.lo = lo[0] | (lo[1] << 8) | (lo[2] << 16);
+  d.hi = hi[0] | (hi[1] << 8) | (hi[2] << 16);
+  d.orient = s.orient;
+  // two bits per case (source solid) << 1 | (destination solid): keep the destination's byte, take the source's, or None
+  const uint32_t K = kStampKeep, T = kStampTake, N = kStampClear;
+  auto table = [](uint32_t ee, uint32_t es, uint32_t se, uint32_t ss) { return ee | (es << 2) | (se << 4) | (ss << 6); };
+  switch (s.op) {
+    case DUST_HIP_STAMP_PLACE: d.table = table(K, K, T, K); break;
+    case DUST_HIP_STAMP_OVERWRITE: d.table = table(K, K, T, T); break;
+    case DUST_HIP_STAMP_REPLACE: d.table = table(T, T, T, T); break;
+    case DUST_HIP_STAMP_CARVE: d.table = table(K, K, K, N); break;
+    default: d.table = table(K, K, K, T); break;  // PAINT
+  }
+  d.pad = 0;
+  return true;
+}
+
+// Everything in int64: any int32 offset is legal. Per destination axis the placements at which the image box meets the tree are an
+// interval; their intersection, cut to 0..max_steps, is all the device walks (under WALLS: from 0 to one past the last placement the
+// image is inside, or placement 0 alone when it begins outside). false: the sub-box is empty.
+inline bool device_cast(const DustHipCast& s, DevCast& d) {
+  for (int k = 0; k < 3; ++k)
+    if (s.src_lo[k] > s.src_hi[k]) return false;
+  const bool walls = s.flags & DUST_HIP_CAST_WALLS;
+  const bool still = s.step[0] == 0 && s.step[1] == 0 && s.step[2] == 0;
+  const int64_t max_steps = still ? 0 : int64_t(s.max_steps);  // (every placement is placement 0)
+  const int64_t never = int64_t(1) << 40;                      // beyond any placement
+  int64_t first = -never, last = never;
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t p = (s.orient >> (2 * r)) & 3u;
+    const int64_t off = s.offset[r], ext = int64_t(s.src_hi[p]) - int64_t(s.src_lo[p]);
+    int64_t f, l;
+    if (s.step[r] == 0) {
+      const bool meets = off + ext >= 0 && off <= 255;
+      f = meets ? -never : 1; l = meets ? never : 0;
+    } else if (s.step[r] > 0) {
+      f = -(off + ext); l = 255 - off;
+    } else {
+      f = off - 255; l = off + ext;
+    }
+    first = std::max(first, f); last = std::min(last, l);
+    d.off[r] = int32_t(std::clamp<int64_t>(off, -kCastOffsetLimit, kCastOffsetLimit));
+    d.step[r] = s.step[r];
+  }
+  int64_t k_lo, k_hi;
+  if (walls) {
+    k_lo = 0;
+    k_hi = first <= 0 && last >= 0 ? std::min(max_steps, last + 1) : 0;
+  } else {
+    k_lo = std::max<int64_t>(first, 0);
+    k_hi = std::min(last, max_steps);
+  }
+  if (k_lo > k_hi) { k_lo = 1; k_hi = 0; }  // nothing to walk (the piece's voxels are still counted)
+  d.k_lo = uint32_t(k_lo); d.k_hi = uint32_t(k_hi);
+  d.max_steps = uint32_t(max_steps);
+  d.orient = s.orient | (walls ? kCastWalls : 0u);
+  d.lo = s.src_lo[0] | (uint32_t(s.src_lo[1]) << 8) | (uint32_t(s.src_lo[2]) << 16);
+  d.hi = s.src_hi[0] | (uint32_t(s.src_hi[1]) << 8) | (uint32_t(s.src_hi[2]) << 16);
+  return true;
+}
+
+// What a cast's caller gets: `best` is the device's minimum of (first blocked placement << 24 | source key), `acc` its counts. A cast
+// that never ran (no sub-box: kCastNoHit and a zero acc) or found nothing comes back with steps == max_steps and no key.
+inline DustHipCastHit cast_hit(const DustHipCast& c, unsigned long long best, const CastAcc& acc) {
+  DustHipCastHit h{};
+  h.steps = c.max_steps;
+  h.src_key = DUST_HIP_CAST_NO_KEY;
+  h.voxels = acc.voxels;
+  if (best == kCastNoHit) return h;
+  const uint32_t k = uint32_t(best >> 24), key = uint32_t(best & 0xFFFFFFu);
+  const uint32_t sv[3] = {key >> 16, (key >> 8) & 255u, key & 255u};
+  h.flags = DUST_HIP_CAST_HIT | (k == 0 ? DUST_HIP_CAST_OVERLAP : 0u) | (acc.wall ? DUST_HIP_CAST_HIT_WALL : 0u);
+  h.steps = k ? k - 1 : 0;
+  h.contacts = acc.contacts;
+  h.src_key = key;
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t p = (c.orient >> (2 * r)) & 3u;
+    const int64_t u = ((c.orient >> (6 + r)) & 1u) ? int64_t(c.src_hi[p]) - int64_t(sv[p]) : int64_t(sv[p]) - int64_t(c.src_lo[p]);
+    h.contact[r] = int32_t(uint32_t(uint64_t(int64_t(c.offset[r]) + int64_t(k) * c.step[r] + u)));  // (the low 32 bits)
+  }
+  return h;
+}
+
+// the records of a call that cover something, in call order: `index` maps them back to the caller's
+template <auto Convert, class In, class Rec>  // (the conversion as a template argument: called directly, as it was before this header)
+void live_records(const In* in, uint32_t n, std::vector<Rec>& dev, std::vector<uint32_t>& index) {
+  dev.reserve(n); index.reserve(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    Rec d{};
+    if (Convert(in[i], d)) { dev.push_back(d); index.push_back(i); }
+  }
+}
+
+// ---- root cells (16^3 voxels, x << 8 | y << 4 | z) that a record's packed inclusive voxel bounds (lo, hi: x | y << 8 | z << 16) reach
+inline size_t root_cell_count(uint32_t lo, uint32_t hi) {
+  size_t n = 1;
+  for (int r = 0; r < 3; ++r) n *= size_t((((hi >> (8 * r)) & 255u) >> 4) - (((lo >> (8 * r)) & 255u) >> 4) + 1u);
+  return n;
+}
+template <class F>
+inline __attribute__((always_inline)) void for_each_root_cell(uint32_t lo, uint32_t hi, F&& f) {  // x slowest
+  for (uint32_t x = (lo & 255u) >> 4; x <= (hi & 255u) >> 4; ++x)
+    for (uint32_t y = ((lo >> 8) & 255u) >> 4; y <= ((hi >> 8) & 255u) >> 4; ++y)
+      for (uint32_t z = ((lo >> 16) & 255u) >> 4; z <= ((hi >> 16) & 255u) >> 4; ++z) f((x << 8) | (y << 4) | z);
+}
+
+// where the order-preserving chunk that begins at record c0 ends: before its root cells would pass max_entries (a single record is
+// never cut) or its records max_records
+template <class Rec>
+size_t chunk_end(const std::vector<Rec>& dev, size_t c0, size_t max_entries, size_t max_records) {
+  size_t c1 = c0, total = 0;
+  while (c1 < dev.size() && c1 - c0 < max_records && (c1 == c0 || total + root_cell_count(dev[c1].lo, dev[c1].hi) <= max_entries)) {
+    total += root_cell_count(dev[c1].lo, dev[c1].hi);
+    ++c1;
+  }
+  return c1;
+}
+
+// a chunk of shapes or stamps on the host: the non-empty cells, and per cell an ascending list of u16 record ids (relative to c0) in CSR form
+struct CellLists {
+  std::vector<uint32_t> cells, starts, fill = std::vector<uint32_t>(4096);
+  std::vector<uint16_t> ids;
+  template <class Rec>
+  void bin(const std::vector<Rec>& dev, size_t c0, size_t c1) {
+    std::fill(fill.begin(), fill.end(), 0u);
+    for (size_t i = c0; i < c1; ++i) for_each_root_cell(dev[i].lo, dev[i].hi, [&](uint32_t cell) { ++fill[cell]; });
+    cells.clear(); starts.clear();
+    uint32_t run = 0;
+    for (uint32_t cell = 0; cell < 4096; ++cell) {
+      const uint32_t k = fill[cell];
+      fill[cell] = run;  // where the cell's next id goes
+      if (k) { cells.push_back(cell); starts.push_back(run); run += k; }
+    }
+    starts.push_back(run);
+    ids.resize(run);
+    for (size_t i = c0; i < c1; ++i) for_each_root_cell(dev[i].lo, dev[i].hi, [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
+  }
+};
+
+// a chunk of casts: one work item per cast (relative to c0) and source root cell its sub-box reaches, in cast order
+inline void cast_items(const std::vector<DevCast>& dev, size_t c0, size_t c1, std::vector<CastItem>& items) {
+  items.clear();
+  for (size_t i = c0; i < c1; ++i) for_each_root_cell(dev[i].lo, dev[i].hi, [&](uint32_t cell) { items.push_back({uint32_t(i - c0), cell}); });
+}
+
+}  // namespace dust

@@ -1,6 +1,6 @@
-"""The cast kernels' arithmetic without a device: a line-by-line Python port of the host's record (capi_model.cpp device_cast), of
-k_cast_walk and of k_cast_count (cast.hip) -- lanes as numpy arrays of 64, the wave-uniform values as Python integers, int32 sums checked
-for overflow -- run against tests/cast_witness.py on 256^3 grids. The work items run one after the other in a shuffled order against one
+"""The cast kernels' arithmetic without a device: a line-by-line Python port of the host's record (model_records.hpp device_cast;
+tests/test_model_records.py holds the native function to this port), of k_cast_walk and of k_cast_count (cast.hip) -- lanes as numpy
+arrays of 64, the wave-uniform values as Python integers, int32 sums checked for overflow -- run against tests/cast_witness.py on 256^3 grids. The work items run one after the other in a shuffled order against one
 shared `best`, so the relaxed read that prunes a walk sees anything from nothing to every other wave's result; every brick-mask index
 the port forms is checked against the lattice."""
 import numpy as np

@@ -159,7 +159,7 @@ def test_cpp_mirror_stamp_compiles(tmp_path):
                            os.path.join(ROOT, "tests", "cpp", "stamp_mirror.cpp"), "-o", str(tmp_path / "stamp_mirror.o")])
 
 
-# ---- the device path's arithmetic, ported line by line (dust_amd/csrc/stamp.hip k_stamp, capi_model.cpp device_stamp): no device runs
+# ---- the device path's arithmetic, ported line by line (dust_amd/csrc/stamp.hip k_stamp, model_records.hpp device_stamp): no device runs
 # here, but the per-axis scatter, the affine maps, the clipping and the op tables are plain integer code that Python can follow
 def _leaf_address(x, y, z):
     """edit.hpp leaf_code(x >> 2, y >> 2, z >> 2) * 64 + the voxel bit: where a voxel's byte lies in the brick-major grid"""
