@@ -1,5 +1,6 @@
 // capi.cpp -- the extern "C" boundary (include/dust_hip.h) and the host runtime behind it: the host-side wrappers, the context,
-// persistent pipeline buffers, pass scheduling. Models live in capi_model.cpp, scenes and scene queries in capi_scene.cpp.
+// persistent pipeline buffers, pass scheduling. Models live in capi_model.cpp, scenes and scene queries in capi_scene.cpp. What the frame
+// path computes without a device -- every launch's shape, the tile schedule's decisions -- is frame_plan.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -8,6 +9,7 @@
 #include <cstring>
 
 #include "capi_internal.hpp"
+#include "frame_plan.hpp"
 #include "vdb.hpp"
 #include "png.hpp"
 #include "sky.hpp"
@@ -39,7 +41,6 @@ hipError_t launch_accumulate(const FrameArgs& a, hipStream_t);
 hipError_t launch_tone_map(const uint16_t* src, const uint32_t* albedo, uint16_t* dst, uint32_t n_pixels, uint32_t* hist, float* avg,
                            float min_log, float log_range, float time_coeff, const float conv[9], uint32_t tf, hipStream_t s);
 hipError_t configure_kernels(size_t max_lds);
-constexpr uint32_t kTileOrderMaxBand = 65536;  // (kernels.hip)
 hipError_t launch_tile_order(const uint32_t* cost, uint32_t* order, uint32_t* cuts, bool reuse_cuts, uint32_t total, uint32_t per, hipStream_t s);
 hipError_t launch_cost_blend(const uint32_t* raw, uint32_t* smooth, uint32_t total, uint32_t keep_shift, hipStream_t s);
 hipError_t launch_cost_dilate(const uint32_t* in, uint32_t* out, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s);
@@ -175,8 +176,6 @@ struct Tuning {
   bool wide_share = false;         // WIDE_SHARE: two frames in flight on half of the slots each as 1024-thread workgroups, one per CU (experiment)
   bool no_stream_lds = false;   // NO_STREAM_LDS: the ray streams read grid, boxes and enter records from memory
   bool no_shared_view = false;  // NO_SHARED_VIEW: same-view frames of a launch each trace their own camera and sun rays (k_primary_ao_batch, never k_primary_ao_runs)
-  bool packet_gi() const { return gi_path != DUST_GI_PATH_STREAMS; }    // the GI passes a packet of 64 rays at a time (k_final_gather, k_surfel_trace)
-  bool packet_only() const { return gi_path == DUST_GI_PATH_PACKETS; }  // ... even where the streams are the default
   static uint32_t num(const char* name, uint32_t dflt) {
     const char* e = diag_env(name);
     return e ? uint32_t(std::strtoul(e, nullptr, 10)) : dflt;
@@ -224,19 +223,11 @@ struct DustHipPipeline {
   uint32_t counter_parity[4] = {0, 0, 0, 0};  // per pass kind: which of its two counter sets the next launch uses
   // per pass kind: cycles each tile took in the pass's last launch and the hand-out order made from them (k_tile_order);
   // valid for the tile grid they were recorded on
-  struct TileHistory {
+  struct TileHistory : dust::TileState {   // (the schedule's state and its step function: frame_plan.hpp)
     DeviceBuffer cost, order;
     DeviceBuffer spread;     // a moving view: each tile's estimate or its dearest neighbour's (k_cost_dilate)
     DeviceBuffer smooth;     // running mean of the measurements of each tile: what the order is made from (k_cost_blend)
     DeviceBuffer cuts;       // kRegions + 1 tile indices: the cost-balanced bands order[] was made for (FrameArgs::band_cuts)
-    uint32_t tiles_x = 0, tiles_y = 0, capacity = 0, age = 0;
-    uint32_t refresh = 8;    // launches between two measurements of a view that stands still (kOrderRefresh, doubling up to kOrderRefreshMax)
-    uint64_t view = 0;       // view_key() of the launch the costs / the order were taken under
-    bool recorded = false;   // cost[] holds the previous launch's measurements
-    bool ordered = false;    // order[] is a valid permutation of this tile grid
-    bool measured = false;   // cost[] holds a launch's measurements (maybe not the last launch's)
-    bool moving = false;     // the previous launch's view differed from the one before it
-    uint32_t cuts_age = 0;   // re-orderings since cuts[] was worked out
   } tile_history[4];
   uint64_t view_key = 0;     // this frame's camera + scene revision + sun + row band
   DeviceBuffer exposure;  // Histogram {u32 histogram[256]; f32 avg} (auto_exposure.playout)
@@ -611,70 +602,81 @@ DustStatus dust_hip_pipeline_set_noise(DustHipPipeline* p, uint32_t texture, con
 }
 
 extern "C" DustStatus dust_hip_pipeline_configure_gi(DustHipPipeline* p, uint32_t hash_capacity, uint32_t surfel_pool_size);
-// copies one launch descriptor into the next ring slot (pinned host -> device, on the launch stream)
+#define DUST_TRY(expr) do { const DustStatus s_ = (expr); if (s_ != DUST_OK) return s_; } while (0)
 
-// Work counters without a memset per launch: every pass kind owns two sets; a launch pulls tiles from one and its
-// first workgroup zeroes the other, which is the set the next launch of that kind (stream-ordered behind it) will use.
-// Cost-ordered hand-out for the launch about to be made (kernels.hip, k_tile_order): orders the tiles by what the pass's
-// previous launch measured, if that was on the same tile grid, and has this launch measure again.
-// While the view stands still (same camera, scene revision, sun and rows) the costs do too: the order is kept and re-measured
-// only every kOrderRefresh launches, which takes k_tile_order (~8 us) and the cost recording out of most frames; a moving view
-// measures and re-orders on every launch.
-// An order that a re-measurement of the same view has just confirmed is trusted for twice as long, up to 64 launches (the GI
-// kernels' costs drift as the hash fills: they keep being looked at).
-constexpr uint32_t kOrderRefresh = 8, kOrderRefreshMax = 64;
+// ---- what a pipeline contributes to a launch descriptor, wherever one is filled (frames, the GI exchange, a sharded surfel pass's second half)
+static void frame_size_args(const DustHipPipeline* p, dust::FrameArgs& a) {
+  a.width = p->width; a.height = p->height;
+  a.inv_width = 1.0f / float(p->width); a.inv_height = 1.0f / float(p->height); a.aspect = float(p->width) / float(p->height);
+}
+static void gi_args(const DustHipPipeline* p, dust::DevGI& gi) {
+  gi.hash = static_cast<uint32_t*>(p->gi_hash.p);
+  gi.hash_capacity = p->gi_capacity;
+  gi.pool = static_cast<dust::DevSurfel*>(p->gi_pool.p);
+  gi.pool_size = p->gi_pool_size;
+  gi.slot_owner = static_cast<uint32_t*>(p->gi_owner.p);
+  gi.pixel_surfel = static_cast<dust::DevSurfel*>(p->gi_pixel_surfel.p);
+  gi.requests = static_cast<dust::DevHashRequest*>(p->gi_requests.p);
+  gi.replacement = static_cast<dust::DevSurfel*>(p->gi_replacement.p);
+  gi.sun_payload = static_cast<float*>(p->gi_sun_payload.p);
+}
+// the radix sort's ping-pong pairs; the first pair is where a kernel leaves the keys and values to sort
+static void sort_args(const DustHipPipeline* p, dust::FrameArgs& b, uint32_t* sk[2], uint32_t* sv[2]) {
+  for (int k = 0; k < 2; ++k) { sk[k] = static_cast<uint32_t*>(p->gi_sort_keys[k].p); sv[k] = static_cast<uint32_t*>(p->gi_sort_vals[k].p); }
+  b.gi.sort_keys = sk[0];
+  b.gi.sort_vals = sv[0];
+}
+static void exchange_view(const DustHipPipeline* p, uint32_t padded_rows, DustHipGiExchange* out) {
+  out->pool_size = p->gi_pool_size;
+  out->width = p->width;
+  out->touched_rows = padded_rows;
+  out->slot_owner = p->gi_owner.p;
+  out->touched = p->gi_touched.p;
+  out->merged = p->gi_merged.p;
+}
+// the event pair around the launches of pass kind `kind`, in a timed frame
+static hipError_t ev_open(DustHipPipeline* p, int kind, hipStream_t st) { return p->timed_frame ? hipEventRecord(p->ev_begin(kind), st) : hipSuccess; }
+static hipError_t ev_close(DustHipPipeline* p, int kind, hipStream_t st) {
+  if (!p->timed_frame) return hipSuccess;
+  const hipError_t e = hipEventRecord(p->ev_end(kind), st);
+  if (e == hipSuccess) p->ev_valid[kind] = true;
+  return e;
+}
+
+// Cost-ordered hand-out for the launch about to be made: the decisions are dust::tile_step's (frame_plan.hpp), carried out here on the pass
+// kind's buffers. The history advances as far as the calls get: a failed one leaves the fields behind it as they were.
 static DustStatus order_tiles(DustHipPipeline* p, uint32_t kind, dust::FrameArgs& a, hipStream_t st) {
   a.tile_order = nullptr; a.tile_cost = nullptr; a.band_cuts = nullptr;
-  if (p->tune.no_tile_order) return DUST_OK;
   DustHipPipeline::TileHistory& h = p->tile_history[kind];
-  const uint32_t total = a.tiles_x * a.tiles_y;
-  const uint32_t per_band = (total + dust::kRegions - 1) / dust::kRegions;
-  if (per_band > dust::kTileOrderMaxBand) return DUST_OK;  // beyond 8K: screen order
-  if (total > h.capacity) {
+  const Tuning& t = p->tune;
+  dust::TileState next = h;
+  const dust::TileStep d = dust::tile_step(next, a.tiles_x, a.tiles_y, p->view_key,
+                                           {t.no_tile_order, t.equal_bands, t.dilate, t.force_moving, t.cuts_reuse, t.moving_refresh, t.still_refresh_max});
+  auto words = [](const DeviceBuffer& b) { return static_cast<uint32_t*>(b.p); };
+  if (d.allocate) {
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(h.cost.alloc(size_t(total) * 4)); HIP_TRY(h.order.alloc(size_t(total) * 4)); HIP_TRY(h.smooth.alloc(size_t(total) * 4)); HIP_TRY(h.spread.alloc(size_t(total) * 4));
+    for (DeviceBuffer* b : {&h.cost, &h.order, &h.smooth, &h.spread}) HIP_TRY(b->alloc(size_t(d.total) * 4));
     if (!h.cuts.p) HIP_TRY(h.cuts.alloc(size_t(dust::kRegions + 1) * 4));
-    h.capacity = total; h.tiles_x = h.tiles_y = 0;
+    h.capacity = d.total; h.tiles_x = h.tiles_y = 0;
   }
-  if (h.tiles_x != a.tiles_x || h.tiles_y != a.tiles_y) {  // a new grid: tiles nobody has timed count as free
+  if (d.reset) {
     h.recorded = false; h.ordered = false; h.measured = false; h.tiles_x = a.tiles_x; h.tiles_y = a.tiles_y;
-    HIP_TRY(hipMemsetAsync(h.cost.p, 0, size_t(total) * 4, st));
-    HIP_TRY(hipMemsetAsync(h.smooth.p, 0, size_t(total) * 4, st));
+    HIP_TRY(hipMemsetAsync(h.cost.p, 0, size_t(d.total) * 4, st));
+    HIP_TRY(hipMemsetAsync(h.smooth.p, 0, size_t(d.total) * 4, st));
   }
-  if (h.recorded) {
-    // (the cost-balanced cuts drift slowly: a view that moves keeps them for kCutsReuse re-orderings -- the scan for them is the longer half of the sorter)
-    const bool reuse = h.ordered && h.cuts_age + 1 < p->tune.cuts_reuse && h.moving;
-    HIP_TRY(dust::launch_cost_blend(static_cast<const uint32_t*>(h.cost.p), static_cast<uint32_t*>(h.smooth.p), total, p->tune.cost_keep_shift, st));
-    const bool spread = h.moving && p->tune.dilate && a.tiles_y > 1u;
-    if (spread) HIP_TRY(dust::launch_cost_dilate(static_cast<const uint32_t*>(h.smooth.p), static_cast<uint32_t*>(h.spread.p), a.tiles_x, a.tiles_y, st));
-    HIP_TRY(dust::launch_tile_order(static_cast<const uint32_t*>(spread ? h.spread.p : h.smooth.p), static_cast<uint32_t*>(h.order.p),
-                                    p->tune.equal_bands ? nullptr : static_cast<uint32_t*>(h.cuts.p), reuse, total, per_band, st));
-    h.cuts_age = reuse ? h.cuts_age + 1 : 0;
-    h.recorded = false; h.ordered = true; h.age = 0;
-  } else if (h.ordered) {
-    ++h.age;
+  if (d.blend) {
+    HIP_TRY(dust::launch_cost_blend(words(h.cost), words(h.smooth), d.total, t.cost_keep_shift, st));
+    if (d.dilate) HIP_TRY(dust::launch_cost_dilate(words(h.smooth), words(h.spread), a.tiles_x, a.tiles_y, st));
+    HIP_TRY(dust::launch_tile_order(words(d.dilate ? h.spread : h.smooth), words(h.order), t.equal_bands ? nullptr : words(h.cuts), d.reuse_cuts, d.total, d.per_band, st));
   }
-  if (h.ordered) {
-    a.tile_order = static_cast<const uint32_t*>(h.order.p);
-    if (!p->tune.equal_bands) a.band_cuts = static_cast<const uint32_t*>(h.cuts.p);
-  }
-  const bool still = h.ordered && h.view == p->view_key && !p->tune.force_moving;
-  if (!still) h.refresh = kOrderRefresh;
-  // A view that moves: tile costs shift by a fraction of a tile per frame, so the order of a few frames ago is still a good one -- it is
-  // re-measured (and the next launch re-ordered) every kMovingRefresh launches, not every launch: the sorter is a launch of its own
-  // between two frames (~10 us of a 230 us frame). The first launch after a standstill (a cut, a teleport) is measured at once.
-  const bool jumped = !still && !h.moving;
-  const uint32_t period = still ? std::min(h.refresh, p->tune.still_refresh_max) : p->tune.moving_refresh;
-  if (!h.ordered || jumped || h.age + 1 >= period) {  // measure this launch (each traced tile overwrites its cost): the next one re-orders
-    a.tile_cost = static_cast<uint32_t*>(h.cost.p);
-    h.recorded = true; h.measured = true;
-    if (still) h.refresh = std::min(kOrderRefreshMax, h.refresh * 2u);
-  }
-  h.moving = !still && h.measured && h.view != 0 && (h.view != p->view_key || p->tune.force_moving);  // (the first launch of a view that stands still is not a moving one;
-                                                                                                     //  DUST_HIP_FORCE_MOVING: a still view on a moving view's schedule)
-  h.view = p->view_key;
+  static_cast<dust::TileState&>(h) = next;
+  if (d.hand_order) a.tile_order = words(h.order);
+  if (d.hand_cuts) a.band_cuts = words(h.cuts);
+  if (d.measure) a.tile_cost = words(h.cost);
   return DUST_OK;
 }
+// Work counters without a memset per launch: every pass kind owns two sets; a launch pulls tiles from one and its
+// first workgroup zeroes the other, which is the set the next launch of that kind (stream-ordered behind it) will use.
 static void take_counters(DustHipPipeline* p, uint32_t kind, dust::FrameArgs& a) {
   uint32_t* base = static_cast<uint32_t*>(p->counters.p) + size_t(kind) * 2 * dust::kRegions * dust::kCounterStride;
   const uint32_t par = p->counter_parity[kind];
@@ -726,109 +728,92 @@ static DustStatus ensure_stream_buffers(DustHipPipeline* p, bool gather, bool su
   }
   return DUST_OK;
 }
-// The surfel pass of one frame (surfel.rgen + the spatial hash update) on stream `st`, on at most `resident` workgroup slots.
 // the recorded hash inserts, applied in surfel-index order (DUST_PASS_GI_ORDERED): in parallel over independent probe-window clusters (the serial
 // one-wavefront loop it is checked against stays reachable through DUST_HIP_DEBUG bit 16)
 static DustStatus apply_ordered(DustHipPipeline* p, dust::FrameArgs& b, hipStream_t st) {
-  uint32_t* sk[2] = {static_cast<uint32_t*>(p->gi_sort_keys[0].p), static_cast<uint32_t*>(p->gi_sort_keys[1].p)};
-  uint32_t* sv[2] = {static_cast<uint32_t*>(p->gi_sort_vals[0].p), static_cast<uint32_t*>(p->gi_sort_vals[1].p)};
+  uint32_t *sk[2], *sv[2];
   // keys -> sort by hash location -> marks (which requests the frame applies: k_surfel_apply_mark) -> the apply, parallel over clusters
   // or (DUST_HIP_DEBUG bit 16) the serial loop in surfel order it is checked against
-  b.gi.sort_keys = sk[0];
-  b.gi.sort_vals = sv[0];
+  sort_args(p, b, sk, sv);
   b.apply_alive = static_cast<unsigned long long*>(p->gi_apply_alive.p);
   b.apply_dead = static_cast<uint8_t*>(p->gi_apply_dead.p);
   b.apply_words = (p->gi_pool_size + 63u) / 64u;
   b.apply_starts = b.apply_alive + b.apply_words + 1;
   HIP_TRY(dust::launch_surfel_apply(b, 2, st));
-  uint32_t bits = 1;
-  while ((1ull << bits) <= uint64_t(p->gi_capacity)) ++bits;  // locations 0 .. capacity (capacity itself = "no insert")
   bool in_b = false;
-  HIP_TRY(dust::radix_sort_pairs(p->gi_sort_scratch.p, sk[0], sv[0], sk[1], sv[1], p->gi_pool_size, bits, &in_b, st));
+  HIP_TRY(dust::radix_sort_pairs(p->gi_sort_scratch.p, sk[0], sv[0], sk[1], sv[1], p->gi_pool_size, dust::apply_key_bits(p->gi_capacity), &in_b, st));
   b.gi.apply_keys = sk[in_b ? 1 : 0];
   b.gi.apply_vals = sv[in_b ? 1 : 0];
   HIP_TRY(dust::launch_surfel_apply(b, 4, st));
   HIP_TRY(dust::launch_surfel_apply(b, (p->tune.debug & 16u) ? 1 : 3, st));
   return DUST_OK;
 }
+// The surfel pass of one frame (surfel.rgen + the spatial hash update) on stream `st`, on at most `resident` workgroup slots.
 // shard_world >= 1: the trace of rank shard_rank's share of the ordered pool only, records staged in slot order, nothing applied
 // (dust_hip_gi_surfel_exchange_run completes the pass)
 static DustStatus run_surfel_pass(DustHipPipeline* p, const dust::FrameArgs& a, uint32_t passes, bool count, hipStream_t st, uint32_t resident,
-                                  uint32_t shard_rank = 0, uint32_t shard_world = 0) {
-  DustHipContext* ctx = p->ctx;
+                                  bool as_stream, uint32_t shard_rank = 0, uint32_t shard_world = 0) {
   const Tuning& tune = p->tune;
-  const uint32_t block = tune.block;
-    dust::FrameArgs b = a;  // 64 consecutive surfels x one ray kind per wavefront: one row of "tiles", cosine items then sun items
-    // on the second stream the pass is the longer of the two sides that share the SIMDs: its waves win the issue arbitration
-    if (st != ctx->stream) b.prio_floor = tune.side_prio;
-    b.tiles_x = 2 * ((p->gi_pool_size + 63) / 64);
-    b.tiles_y = 1;
-    b.stats = static_cast<dust::DevStats*>(p->stats.p) + 4;
-    uint32_t* sk[2] = {static_cast<uint32_t*>(p->gi_sort_keys[0].p), static_cast<uint32_t*>(p->gi_sort_keys[1].p)};
-    uint32_t* sv[2] = {static_cast<uint32_t*>(p->gi_sort_vals[0].p), static_cast<uint32_t*>(p->gi_sort_vals[1].p)};
-    b.gi.sort_keys = sk[0];
-    b.gi.sort_vals = sv[0];
-    if (p->timed_frame) HIP_TRY(hipEventRecord(p->ev_begin(3), st));
-    if (!tune.no_surfel_sort) {  // phase 0: 16-bit space-filling-curve keys + radix sort -> gi.perm
-      HIP_TRY(dust::launch_surfel_keys(b, st));
-      bool in_b = false;
-      HIP_TRY(dust::radix_sort_pairs(p->gi_sort_scratch.p, sk[0], sv[0], sk[1], sv[1], p->gi_pool_size, 16, &in_b, st));
-      b.gi.perm = sv[in_b ? 1 : 0];
+  dust::FrameArgs b = a;  // 64 consecutive surfels x one ray kind per wavefront: one row of "tiles", cosine items then sun items
+  // on the second stream the pass is the longer of the two sides that share the SIMDs: its waves win the issue arbitration
+  if (st != p->ctx->stream) b.prio_floor = tune.side_prio;
+  b.tiles_x = 2 * ((p->gi_pool_size + 63) / 64);
+  b.tiles_y = 1;
+  b.stats = static_cast<dust::DevStats*>(p->stats.p) + 4;
+  uint32_t *sk[2], *sv[2];
+  sort_args(p, b, sk, sv);
+  HIP_TRY(ev_open(p, 3, st));
+  if (!tune.no_surfel_sort) {  // phase 0: 16-bit space-filling-curve keys + radix sort -> gi.perm
+    HIP_TRY(dust::launch_surfel_keys(b, st));
+    bool in_b = false;
+    HIP_TRY(dust::radix_sort_pairs(p->gi_sort_scratch.p, sk[0], sv[0], sk[1], sv[1], p->gi_pool_size, 16, &in_b, st));
+    b.gi.perm = sv[in_b ? 1 : 0];
+  }
+  const bool staged = shard_world >= 1;
+  if (staged) {
+    const dust::ShardRange r = dust::shard_range(p->gi_pool_size, shard_rank, shard_world);
+    if (p->gi_stage_slots < r.cap) {   // (made for the pool size of the frame that needs them: the slots of every rank's share index all three)
+      HIP_TRY(hipStreamSynchronize(st));
+      p->gi_stage_slots = 0;
+      HIP_TRY(p->gi_stage_req.alloc(r.cap * sizeof(dust::DevHashRequest)));
+      HIP_TRY(p->gi_stage_repl.alloc(r.cap * 16));
+      HIP_TRY(p->gi_stage_sun.alloc(r.cap * 16));
+      HIP_TRY(hipMemsetAsync(p->gi_stage_req.p, 0, r.cap * sizeof(dust::DevHashRequest), st));
+      HIP_TRY(hipMemsetAsync(p->gi_stage_repl.p, 0xFF, r.cap * 16, st));   // direction 0xFFFFFFFF: "keep"
+      HIP_TRY(hipMemsetAsync(p->gi_stage_sun.p, 0, r.cap * 16, st));
+      p->gi_stage_slots = r.cap;
     }
-    const bool staged = shard_world >= 1;
-    if (staged) {
-      const uint32_t groups = (p->gi_pool_size + 63u) / 64u, per = (groups + shard_world - 1u) / shard_world;
-      const size_t cap = size_t(groups + 64u) * 64u;   // room for any world up to 64: a rank's share ends on a group boundary
-      if (p->gi_stage_slots < cap) {   // (made for the pool size of the frame that needs them: the slots of every rank's share index all three)
-        HIP_TRY(hipStreamSynchronize(st));
-        p->gi_stage_slots = 0;
-        HIP_TRY(p->gi_stage_req.alloc(cap * sizeof(dust::DevHashRequest)));
-        HIP_TRY(p->gi_stage_repl.alloc(cap * 16));
-        HIP_TRY(p->gi_stage_sun.alloc(cap * 16));
-        HIP_TRY(hipMemsetAsync(p->gi_stage_req.p, 0, cap * sizeof(dust::DevHashRequest), st));
-        HIP_TRY(hipMemsetAsync(p->gi_stage_repl.p, 0xFF, cap * 16, st));   // direction 0xFFFFFFFF: "keep"
-        HIP_TRY(hipMemsetAsync(p->gi_stage_sun.p, 0, cap * 16, st));
-        p->gi_stage_slots = cap;
-      }
-      b.sf_stage_req = static_cast<dust::DevHashRequest*>(p->gi_stage_req.p);
-      b.sf_stage_repl = static_cast<dust::DevSurfel*>(p->gi_stage_repl.p);
-      b.sf_stage_sun = static_cast<float*>(p->gi_stage_sun.p);
-      b.sf_group_begin = std::min(groups, shard_rank * per);
-      b.sf_group_count = std::min(per, groups - b.sf_group_begin);
-      b.tiles_x = 2 * b.sf_group_count;   // (a rank past the end of the pool traces nothing)
-      p->sf_shard.pending = true; p->sf_shard.perm = b.gi.perm; p->sf_shard.rank = shard_rank; p->sf_shard.world = shard_world;
-      p->sf_shard.slots_per_rank = per * 64u;
-    }
-    if (tune.packet_gi() || !b.grid.cells || staged) {   // (a sharded trace runs as packets: the stream's shading kernel writes by surfel index)
-      if (b.tiles_x) {   // (a rank past the end of the pool traces nothing)
-        take_counters(p, 3, b);
-        { DustStatus os = order_tiles(p, 3, b, st); if (os != DUST_OK) return os; }
-        const uint32_t sgrid = std::max(8u, std::min<uint32_t>(resident, (b.tiles_x + 7) / 8));
-        HIP_TRY(dust::launch_surfel_trace(b, sgrid, block, count, st));
-      }
-    } else {
-      // phase 1 as a ray stream (gi.hip): the pool's rays, compacted -> one ray per lane, lanes refilled -> the hash lookups over the hit records
-      stream_args(p, 1, b, 0.1f, 10000.0f);  // surfel.rgen:33-62
+    b.sf_stage_req = static_cast<dust::DevHashRequest*>(p->gi_stage_req.p);
+    b.sf_stage_repl = static_cast<dust::DevSurfel*>(p->gi_stage_repl.p);
+    b.sf_stage_sun = static_cast<float*>(p->gi_stage_sun.p);
+    b.sf_group_begin = r.group_begin;
+    b.sf_group_count = r.group_count;
+    b.tiles_x = 2 * b.sf_group_count;   // (a rank past the end of the pool traces nothing)
+    p->sf_shard.pending = true; p->sf_shard.perm = b.gi.perm; p->sf_shard.rank = shard_rank; p->sf_shard.world = shard_world;
+    p->sf_shard.slots_per_rank = r.slots_per_rank;
+  }
+  if (!as_stream || staged) {   // (a sharded trace runs as packets: the stream's shading kernel writes by surfel index)
+    if (b.tiles_x) {   // (a rank past the end of the pool traces nothing)
       take_counters(p, 3, b);
-      b.stream.count_unbinned = count ? 1u : 0u;
-      if (count) HIP_TRY(hipMemsetAsync(b.stream.unbinned, 0, 2 * 4, st));
-      HIP_TRY(dust::launch_surfel_rays(b, st));
-      // (one 1024-thread workgroup per CU: sixteen waves share one staged copy of the top-level data)
-      const uint32_t want = (p->gi_pool_size * 2u + 1023u) / 1024u;
-      const uint32_t sgrid = std::max(8u, std::min<uint32_t>((resident * block / 1024u) & ~7u, (want + 7u) & ~7u));
-      HIP_TRY(dust::launch_ray_walk(b, 3, sgrid, 1024, count, st));
-      HIP_TRY(dust::launch_surfel_shade(b, st));
+      DUST_TRY(order_tiles(p, 3, b, st));
+      HIP_TRY(dust::launch_surfel_trace(b, dust::packet_grid(resident, b.tiles_x), tune.block, count, st));
     }
-    // phase 2: apply the recorded inserts. Default: concurrently, like the reference's shaders. DUST_PASS_GI_ORDERED: the
-    // result of applying them in surfel-index order (apply_ordered). A sharded trace stops here: its records are not complete yet.
-    if (staged) {
-    } else if (!(passes & DUST_PASS_GI_ORDERED)) {
-      HIP_TRY(dust::launch_surfel_apply(b, 0, st));
-    } else {
-      DustStatus as = apply_ordered(p, b, st);
-      if (as != DUST_OK) return as;
-    }
-    if (p->timed_frame) { HIP_TRY(hipEventRecord(p->ev_end(3), st)); p->ev_valid[3] = true; }
+  } else {
+    // phase 1 as a ray stream (gi.hip): the pool's rays, compacted -> one ray per lane, lanes refilled -> the hash lookups over the hit records
+    stream_args(p, 1, b, 0.1f, 10000.0f);  // surfel.rgen:33-62
+    take_counters(p, 3, b);
+    b.stream.count_unbinned = count ? 1u : 0u;
+    if (count) HIP_TRY(hipMemsetAsync(b.stream.unbinned, 0, 2 * 4, st));
+    HIP_TRY(dust::launch_surfel_rays(b, st));
+    const uint32_t want = (p->gi_pool_size * 2u + 1023u) / 1024u;
+    HIP_TRY(dust::launch_ray_walk(b, 3, dust::ray_walk_grid(resident, tune.block, want), 1024, count, st));
+    HIP_TRY(dust::launch_surfel_shade(b, st));
+  }
+  // phase 2: apply the recorded inserts. Default: concurrently, like the reference's shaders. DUST_PASS_GI_ORDERED: the
+  // result of applying them in surfel-index order (apply_ordered). A sharded trace stops here: its records are not complete yet.
+  if (!staged && !(passes & DUST_PASS_GI_ORDERED)) HIP_TRY(dust::launch_surfel_apply(b, 0, st));
+  else if (!staged) DUST_TRY(apply_ordered(p, b, st));
+  HIP_TRY(ev_close(p, 3, st));
   return DUST_OK;
 }
 // Several frames in one persistent launch (dust_hip_render_frames): the frames are PREPARED in order -- the scene as each of them sees it, its
@@ -861,7 +846,7 @@ static DustStatus check_frame(DustHipPipeline* p, const DustHipScene* s, const D
   std::memcpy(&fp_copy, fp_in, std::min<size_t>(fp_in->struct_size, sizeof fp_copy));
   const DustHipFrameParams* fp = &fp_copy;
   if (p->ctx != s->ctx) return fail(DUST_ERR_INVALID_ARGUMENT, "pipeline and scene belong to different contexts");
-  { DustStatus rs = check_scene_ready(s); if (rs != DUST_OK) return rs; }
+  DUST_TRY(check_scene_ready(s));
   const uint32_t need5 = DUST_PASS_AMBIENT_OCCLUSION | DUST_PASS_FINAL_GATHER | DUST_PASS_SURFEL;
   if ((fp->passes & need5) && !p->noise5.p)
     return fail(DUST_ERR_NOT_READY, "blue-noise texture 5 (unitvec3_cosine) not loaded");  // standard.rs:254
@@ -890,46 +875,36 @@ static DustStatus check_frame(DustHipPipeline* p, const DustHipScene* s, const D
   }
   return DUST_OK;
 }
-static DustStatus render_frame_impl(DustHipPipeline* p, const DustHipScene* s, const DustHipCamera* cam, const DustHipSky* sky,
-                                    const DustHipFrameParams* fp_in, FrameRole role, BatchJoin* join) {
-  DustHipFrameParams fp_copy{};
-  { DustStatus cs = check_frame(p, s, cam, sky, fp_in, fp_copy); if (cs != DUST_OK) return cs; }
-  const DustHipFrameParams* fp = &fp_copy;
-  const bool sharded = (fp->passes & DUST_PASS_GI_SHARDED) != 0;
-  if ((fp->passes & (DUST_PASS_FINAL_GATHER | DUST_PASS_SURFEL)) && !p->gi_hash.p) {
-    DustStatus gs = dust_hip_pipeline_configure_gi(p, dust::kSpatialHashCapacity, dust::kSurfelPoolSize);
-    if (gs != DUST_OK) return gs;
+
+// ---- one frame. What its passes share: the handles, the frame's flags and its plan (frame_plan.hpp). The descriptor `a` goes from pass to pass
+// as each one left it (statistics slot, work counters, tile order, start sequence number): a later pass's copy holds exactly what it always held.
+struct Frame {
+  DustHipPipeline* p; DustHipContext* ctx; const DustHipScene* s; const DustHipFrameParams* fp; hipStream_t st;
+  bool count = false, sharded = false;
+  bool fg_stream = false, sf_stream = false;   // the GI passes that run as ray streams (gather_as_stream, surfel_as_stream)
+  bool calibrate = false;                      // the frame runs its surfel pass in place, timed (side_share)
+  uint32_t share = 0;                          // the surfel pass's percent of the slots on the second stream
+  dust::SlotInputs si; dust::SlotPlan plan;
+  // the frame's first traversal launch tells the host that the frame has started (DustHipContext::started; dust_hip_scene_commit)
+  bool start_said = false;
+  void say_start(dust::FrameArgs& x) {
+    if (start_said || !ctx->started) return;
+    start_said = true;
+    x.started_word = const_cast<uint32_t*>(ctx->started);
+    x.started_seq = ++ctx->frame_seq;
+    s->slots[s->current].last_seq = x.started_seq;
   }
-  DustHipContext* ctx = p->ctx;
-  HIP_TRY(hipSetDevice(ctx->device));
-  dust::FrameArgs a{};
-  s->touch();
+};
+// the frame's descriptor: what the scene, the pipeline, the camera and the sky contribute (a pass adds its own: counters, tile order, stream)
+static void frame_args(const DustHipPipeline* p, const DustHipScene* s, const DustHipCamera* cam, const DustHipSky* sky, const DustHipFrameParams* fp,
+                       dust::FrameArgs& a) {
+  const Tuning& tune = p->tune;
   scene_args(s, a);
-  a.stream_refill = p->tune.stream_refill; a.stream_top_iters = p->tune.stream_top_iters;
-  {  // what the ray-stream kernels stage in LDS, as far as it goes. The ray-making kernels (256 threads, many workgroups per CU): grid cells,
-     // items and instance boxes within 40 KB; k_ray_walk (one 1024-thread workgroup per CU): the enter records behind its roots.
-    auto layout = [&](size_t budget, bool bin) {
-      dust::DevStreamLds l;
-      size_t at = 0;
-      auto place = [&](size_t bytes) -> uint32_t {
-        bytes = (bytes + 15) & ~size_t(15);
-        if (p->tune.no_stream_lds || at + bytes > budget) return 0xFFFFFFFFu;
-        const uint32_t off = uint32_t(at);
-        at += bytes;
-        return off;
-      };
-      const size_t n_cells = size_t(a.grid.dim[0]) * a.grid.dim[1] * a.grid.dim[2];
-      l.cells = bin ? place(n_cells * 4) : 0xFFFFFFFFu;
-      l.items = bin ? place(size_t(a.grid.n_items) * 2) : 0xFFFFFFFFu;
-      l.boxes = bin ? place(size_t(a.n_instances) * 32) : 0xFFFFFFFFu;
-      l.enters = bin ? 0xFFFFFFFFu : place(size_t(a.n_instances) * sizeof(dust::DevEnter));
-      l.total = uint32_t(at);
-      return l;
-    };
-    a.sl_bin = layout(40 * 1024, true);
-    a.sl_walk = layout(p->ctx->max_lds - std::min<size_t>(p->ctx->max_lds, size_t(a.n_lds_models) * dust::kN16LdsBytes), false);
-  }
   for (int k = 0; k < 3; ++k) { a.world_min[k] = s->world_min[k]; a.world_max[k] = s->world_max[k]; }
+  for (const DustHipModel* m : s->models) a.deep |= m->dev.n_levels == 3 ? 1u : 0u;
+  a.stream_refill = tune.stream_refill; a.stream_top_iters = tune.stream_top_iters;
+  a.sl_bin = dust::stream_lds(dust::kStreamBinBudget, true, a.grid.dim, a.grid.n_items, a.n_instances, tune.no_stream_lds);
+  a.sl_walk = dust::stream_lds(dust::stream_walk_budget(p->ctx->max_lds, a.n_lds_models), false, a.grid.dim, a.grid.n_items, a.n_instances, tune.no_stream_lds);
   std::memcpy(a.cam.col0, cam->view_col0, 12); std::memcpy(a.cam.col1, cam->view_col1, 12);
   std::memcpy(a.cam.col2, cam->view_col2, 12); std::memcpy(a.cam.pos, cam->position, 12);
   a.cam.tan_half_fov = cam->tan_half_fov; a.cam.far_ = cam->far_; a.cam.near_ = cam->near_;
@@ -943,11 +918,9 @@ static DustStatus render_frame_impl(DustHipPipeline* p, const DustHipScene* s, c
   a.g.motion = static_cast<uint16_t*>(p->plane(DUST_PLANE_MOTION));
   a.g.voxel_id = static_cast<uint32_t*>(p->plane(DUST_PLANE_VOXEL_ID));
   a.g.accum = static_cast<float*>(p->plane(DUST_PLANE_ACCUM));
-  a.width = p->width; a.height = p->height;
-  a.inv_width = 1.0f / float(p->width); a.inv_height = 1.0f / float(p->height); a.aspect = float(p->width) / float(p->height);
+  frame_size_args(p, a);
   a.row_begin = fp->row_begin;
-  a.row_end = fp->row_end ? fp->row_end : p->height;
-  if (a.row_begin >= a.row_end || a.row_end > p->height) return fail(DUST_ERR_INVALID_ARGUMENT, "bad row range");
+  a.row_end = fp->row_end ? fp->row_end : p->height;   // (check_frame has seen the range)
   a.tiles_x = (p->width + dust::kTileW - 1) / dust::kTileW;
   a.tiles_y = (a.row_end - a.row_begin + dust::kTileH - 1) / dust::kTileH;
   a.rand = fp->rand; a.frame_index = fp->frame_index;
@@ -955,338 +928,312 @@ static DustStatus render_frame_impl(DustHipPipeline* p, const DustHipScene* s, c
   if (p->noise5.p) a.noise5 = static_cast<const uint8_t*>(p->noise5.p) + size_t(fp->frame_index % p->noise5_layers) * 128 * 128 * 4;  // noise.rs:50
   a.stats = static_cast<dust::DevStats*>(p->stats.p);
   a.accum_count = p->accum_count;
-  const Tuning& tune = p->tune;
   a.debug = tune.debug;
   a.static_rounds_request = tune.static_rounds;
-  for (const DustHipModel* m : s->models) a.deep |= m->dev.n_levels == 3 ? 1u : 0u;
-  {  // which GI passes of this frame run as ray streams (decided once, here: the launches below ask the same questions)
-    const bool fg_stream = (fp->passes & DUST_PASS_FINAL_GATHER) && a.grid.cells &&
-                           (!tune.packet_gi() || (a.deep && !tune.packet_only() && !(tune.debug & 12u) && !tune.no_gather_order));
-    const bool sf_stream = (fp->passes & DUST_PASS_SURFEL) && a.grid.cells && !tune.packet_gi();
-    if (fg_stream || sf_stream) { DustStatus es = ensure_stream_buffers(p, fg_stream, sf_stream); if (es != DUST_OK) return es; }
+  gi_args(p, a.gi);
+}
+static dust::SlotInputs slot_inputs(const DustHipPipeline* p, const dust::FrameArgs& a) {   // (the share is the caller's to add)
+  const Tuning& t = p->tune;
+  dust::SlotInputs in;
+  in.num_cus = uint32_t(p->ctx->num_cus); in.max_lds = p->ctx->max_lds;
+  in.block = t.block; in.blocks_per_cu = t.blocks_per_cu;
+  in.n_lds_models = a.n_lds_models; in.n_instances = a.n_instances; in.n_groups = a.n_groups;
+  in.no_lds_boxes = t.no_lds_boxes;
+  in.reserve_request = t.reserve_blocks; in.in_collective = p->in_collective; in.side_busy = p->ctx->side_busy;
+  in.frames_in_flight = p->frames_in_flight; in.in_flight_slots = t.in_flight_slots; in.in_flight_oversub = t.in_flight_oversub;
+  in.total_tiles = a.tiles_x * a.tiles_y;
+  return in;
+}
+// The surfel pass's share of the slots for this frame, and whether the frame calibrates it: the configured share, or the calibrated one
+// once the pipeline has it (DustHipPipeline::side_cal), or the guess from the ray counts.
+static DustStatus side_share(Frame& f, const dust::FrameArgs& a) {
+  DustHipPipeline* p = f.p;
+  const Tuning& tune = p->tune;
+  f.share = tune.side_share;
+  if (f.share) return DUST_OK;
+  auto& cal = p->side_cal;
+  if (cal.state == 1 && hipEventQuery(cal.q1) == hipSuccess) {
+    float P = 0.0f, Q = 0.0f;
+    if (hipEventElapsedTime(&P, cal.p0, cal.p1) == hipSuccess && hipEventElapsedTime(&Q, cal.q0, cal.q1) == hipSuccess && P > 0.0f && Q > 0.0f)
+      cal.share = dust::calibrated_share(P, Q, a.deep != 0);
+    cal.state = 2;
   }
-  const bool count = fp->passes & DUST_PASS_COUNT_STATS;
-  const uint32_t block = tune.block;
-  uint32_t bpc = tune.blocks_per_cu;
-  size_t lds = size_t(a.n_lds_models) * dust::kN16LdsBytes + (block / 64) * (dust::kMaxCand * 8 + 8) + 16;
-  if (lds > ctx->max_lds) return fail(DUST_ERR_INVALID_ARGUMENT, "staged roots and candidate lists exceed the device's LDS");
-  // the instance boxes ride along when the workgroups of a CU still fit side by side (the packet cull reads all of them, per packet)
-  a.n_lds_boxes = 0;
-  const uint32_t cull_boxes = a.n_groups ? a.n_groups : a.n_instances;  // (a large scene stages the boxes of its groups of 64)
-  if (!tune.no_lds_boxes && (lds + size_t(cull_boxes) * 32) * bpc <= 160 * 1024 && lds + size_t(cull_boxes) * 32 <= ctx->max_lds) {
-    a.n_lds_boxes = cull_boxes;
-    lds += size_t(cull_boxes) * 32;
+  (void)hipGetLastError();  // (hipEventQuery's "not ready" is not an error of this call)
+  const bool gi_frame = (f.fp->passes & DUST_PASS_PRIMARY) && (f.fp->passes & DUST_PASS_SURFEL);
+  // (not the pipeline's first GI frames: they touch the hash and the pool for the first time -- 400 MB of first-touch page faults inside the
+  //  timed pass; one deep-tree run in five calibrated a share half as large again from it: 4.66 ms per frame against 4.27-4.30)
+  if (gi_frame && cal.state == 0) ++cal.gi_frames;
+  f.calibrate = cal.state == 0 && cal.gi_frames >= 3u && gi_frame && !tune.no_side_stream && !f.count && !f.sharded && !(tune.debug & 16u);
+  if (f.calibrate) HIP_TRY(join_side(f.ctx));   // (the timed frame runs its passes one after the other, behind the previous frame's surfel pass)
+  if (f.calibrate && !cal.p0)
+    for (hipEvent_t* e : {&cal.p0, &cal.p1, &cal.q0, &cal.q1}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableSystemFence));
+  f.share = cal.share ? cal.share : dust::guessed_share(p->gi_pool_size, p->width, a.row_end - a.row_begin);
+  return DUST_OK;
+}
+
+// The Lead's launch of all the frames of a BatchJoin, `a.started_seq` and the view runs filled in
+static DustStatus launch_batch(Frame& f, BatchJoin* join, const dust::FusedShape& shape) {
+  const DustHipScene* s = f.s;
+  f.say_start(join->frames[0]);   // (the kernel's first descriptor says it)
+  for (uint32_t i = 0; i < join->n; ++i) {
+    // Every scene image a frame of the launch reads is in use from NOW until the launch is done. dust_hip_scene_commit recycles an image by
+    // `epoch` (has anybody waited for the stream since a frame reading it was enqueued?) and `last_seq`: both were stamped when the frame
+    // was PREPARED (touch()), and a commit between then and now may have waited for the stream -- the image would pass for idle
+    // (found by tools/stress_host.py frames: 17 to 19 frames per call with moves, the third launch's commits landing on the second's images).
+    s->slots[join->image_of[i]].epoch = f.ctx->sync_epoch;
+    s->slots[join->image_of[i]].last_seq = join->frames[0].started_seq;
+    // the boxes staged in LDS are frame 0's image's: a frame of another image (an instance moved in between) reads its own from memory
+    if (join->image_of[i] != join->image_of[0]) join->frames[i].n_lds_boxes = 0;
   }
-  while (bpc > 1 && lds * bpc > 160 * 1024) --bpc;
-  const uint32_t total_tiles = a.tiles_x * a.tiles_y;
-  // Workgroups per persistent launch: every slot of every CU, minus what the caller asks to be left free. The traversal
-  // kernels hold all VGPRs of the SIMDs they run on, so a kernel of another queue (an RCCL send/receive moving the previous
-  // frame to another GPU) can only become resident next to them where a workgroup slot was left empty.
-  uint32_t resident = uint32_t(ctx->num_cus) * bpc;
-  // (DUST_RESERVE_AUTO: nothing until the pipeline has been seen in a collective of world > 1 -- comm.hip says so --, 32 from then on: without
-  //  them RCCL's kernels wait 36 us - 0.2 ms behind a persistent launch, with them under 10 us; they cost the traversal 5 %)
-  const uint32_t reserve_blocks = (tune.reserve_blocks == DUST_RESERVE_AUTO ? (p->in_collective ? 32u : 0u) : tune.reserve_blocks) & ~7u;
-  if (reserve_blocks && reserve_blocks + 8u <= resident) resident -= reserve_blocks;
-  hipStream_t st = ctx->stream;
+  uint32_t runs[dust::kMaxBatch];
+  dust::view_runs(join->continues, join->n, runs);
+  for (uint32_t i = 0; i < join->n; ++i) join->frames[i].view_run = runs[i];
+  join->launched = true;
+  if ((f.p->tune.debug & 32u) || dust::launch_primary_ao_batch(join->frames, join->n, shape.fgrid, shape.fblock, f.st) != hipSuccess) {   // (DUST_HIP_DEBUG bit 32: as if refused)
+    // (the launch carries 8.5 KB of kernel arguments -- probed on this runtime, which takes 16 KB. Should a runtime refuse it: the prepared
+    //  frames one launch each, the same results)
+    (void)hipGetLastError();
+    for (uint32_t i = 0; i < join->n; ++i) HIP_TRY(dust::launch_primary_ao(join->frames[i], shape.fgrid, shape.fblock, false, f.st));
+  }
+  return DUST_OK;
+}
+// The fused pixel pass: primary + AO in one launch. Single: this frame's own launch. Follower: the frame is prepared and left in the join.
+// Lead: prepared likewise, then all of the join's frames are launched.
+static DustStatus fused_pass(Frame& f, dust::FrameArgs& a, const DustHipCamera* cam, const DustHipSky* sky, FrameRole role, BatchJoin* join) {
+  DustHipPipeline* p = f.p;
+  const Tuning& tune = p->tune;
+  take_counters(p, 0, a);
+  bool continues = false;
+  if (role != FrameRole::Single) {
+    const uint32_t i = join->slot;
+    join->took_counters[i] = true;
+    join->cams[i] = cam; join->skies[i] = sky;
+    continues = i > 0 && !tune.no_shared_view && join->image_of[i - 1] == uint32_t(f.s->current) &&
+                std::memcmp(cam, join->cams[i - 1], sizeof *cam) == 0 && std::memcmp(sky, join->skies[i - 1], sizeof *sky) == 0;
+    join->continues[i] = continues;
+  }
+  if (continues) {
+    // a follower of a view run: the launch hands out the run's tiles by its leader's order and writes the leader's cost buffer. This pipeline's tile
+    // history is left as it stands -- nothing of it is read, nothing is measured for it --, valid for its next launch, alone or grouped differently.
+    a.tile_order = nullptr; a.tile_cost = nullptr; a.band_cuts = nullptr;
+  } else {
+    DUST_TRY(order_tiles(p, 0, a, f.st));
+  }
+  a.stats = static_cast<dust::DevStats*>(p->stats.p);
+  if (role != FrameRole::Single) {   // a frame of a launch of several: prepared; the last one launches them all
+    join->frames[join->slot] = a;
+    join->image_of[join->slot] = f.s->current;
+    if (join->slot == 0) join->timer = p;
+    if (role == FrameRole::Follower) return DUST_OK;
+  }
+  DustHipPipeline* tp = role == FrameRole::Lead ? join->timer : p;   // whose event pair brackets the launch
+  HIP_TRY(ev_open(tp, 0, f.st));
+  const dust::FusedShape shape = dust::fused_shape(f.si, f.plan, tune.wide_fused, tune.wide_share, role == FrameRole::Lead ? join->n : 1u);
+  if (shape.too_big) return fail(DUST_ERR_INVALID_ARGUMENT, "staged roots and candidate lists exceed the device's LDS");
+  if (role == FrameRole::Lead) {
+    DUST_TRY(launch_batch(f, join, shape));
+  } else {
+    f.say_start(a);
+    HIP_TRY(dust::launch_primary_ao(a, shape.fgrid, shape.fblock, f.count, f.st));
+  }
+  a.started_word = nullptr;
+  HIP_TRY(ev_close(tp, 0, f.st));
+  if (tp->timed_frame) tp->ev_valid[1] = false;
+  return DUST_OK;
+}
+// The unfused pixel passes (DUST_HIP_NO_FUSE=1 keeps the reference's one-launch-per-pass shape), kind 0: primary, 1: AO
+static DustStatus pixel_pass(Frame& f, dust::FrameArgs& a, int kind) {
+  DustHipPipeline* p = f.p;
+  take_counters(p, kind, a);
+  DUST_TRY(order_tiles(p, kind, a, f.st));
+  a.stats = static_cast<dust::DevStats*>(p->stats.p) + kind;
+  HIP_TRY(ev_open(p, kind, f.st));
+  f.say_start(a);
+  HIP_TRY(kind == 0 ? dust::launch_primary(a, f.plan.grid, p->tune.block, f.count, f.st) : dust::launch_ambient_occlusion(a, f.plan.grid, p->tune.block, f.count, f.st));
+  a.started_word = nullptr;
+  HIP_TRY(ev_close(p, kind, f.st));
+  return DUST_OK;
+}
+// The final gather as a ray stream (gi.hip): make and bin the band's gather rays (a thread per pixel) -> walk them one per lane, lanes refilled
+// (k_ray_walk) -> shade the hit records (a thread per pixel). Behind the previous frame's surfel pass, like the packet kernel: rays and
+// hit records touch no GI state and COULD run beside that pass, but two persistent launches sharing the slots both get slower
+// (the 4096^3 tree's GI frame: 5.40 ms beside it, 4.56 behind it).
+static DustStatus gather_stream_pass(Frame& f, const dust::FrameArgs& a) {
+  DustHipPipeline* p = f.p;
+  const hipStream_t st = f.st;
+  HIP_TRY(join_side(f.ctx));
+  dust::FrameArgs g = a;
+  stream_args(p, 0, g, 8.0f, a.cam.far_);  // final_gather.rgen:47-50
+  g.gi.fg_hits = g.stream.ray_hits;
+  take_counters(p, 2, g);
+  g.stream.count_unbinned = f.count ? 1u : 0u;
+  if (f.count) HIP_TRY(hipMemsetAsync(g.stream.unbinned, 0, 2 * 4, st));
+  HIP_TRY(ev_open(p, 2, st));
+  HIP_TRY(dust::launch_gather_rays(g, st));
+  const uint32_t want = uint32_t((size_t(p->width) * (a.row_end - a.row_begin) + 1023u) / 1024u);
+  HIP_TRY(dust::launch_ray_walk(g, 2, dust::ray_walk_grid(f.plan.resident, p->tune.block, want), 1024, f.count, st));
+  dust::FrameArgs sh = a;   // (pixel order over the band)
+  sh.gi.fg_hits = g.gi.fg_hits;
+  HIP_TRY(dust::launch_final_gather_shade(sh, !f.sharded, st));
+  HIP_TRY(ev_close(p, 2, st));
+  return DUST_OK;
+}
+// The final gather as packets of 64 rays (k_final_gather)
+// (Round 4 also built the gather as a trace-only kernel beside the previous frame's surfel pass + a shading pass over hit records, and
+//  round 3 as refilled ray lanes inside the packet kernel: both measured slower and were removed in round 6 -- docs/EXPERIMENTS.md.)
+static DustStatus gather_packet_pass(Frame& f, const dust::FrameArgs& a) {
+  DustHipPipeline* p = f.p;
+  const hipStream_t st = f.st;
+  dust::FrameArgs g = a;
+  if (!p->tune.no_gather_order) {  // pre-pass: regroup the band's live pixels by ray-direction octant
+    const uint32_t otx = (p->width + 63) / 64, oty = (a.row_end - a.row_begin + 63) / 64;
+    g.gi.order = static_cast<uint32_t*>(p->gi_order.p);
+    g.gi.order_count = static_cast<uint32_t*>(p->gi_order_count.p);
+    g.gi.order_tiles_x = otx;
+    HIP_TRY(dust::launch_gather_order(g, otx * oty, st));
+    // work items: 64 packets of 64 per tile, the empty ones skipped by the kernel
+    g.tiles_x = otx * oty * 64u;
+    g.tiles_y = 1;
+  }
+  HIP_TRY(join_side(f.ctx));  // the previous frame's surfel pass has written the hash and the pool this gather reads
+  take_counters(p, 2, g);
+  DUST_TRY(order_tiles(p, 2, g, st));
+  HIP_TRY(ev_open(p, 2, st));  // (behind the regrouping pre-pass: the gather kernel)
+  HIP_TRY(dust::launch_final_gather(g, dust::packet_grid(f.plan.resident, g.tiles_x * g.tiles_y), p->tune.block, f.count, !f.sharded, st));
+  HIP_TRY(ev_close(p, 2, st));
+  return DUST_OK;
+}
+// The surfel pass: on the context's second stream, behind this frame's final gather (see DustHipContext::side): the pass is a handful of
+// latency-bound launches around a trace that is as long as its longest ray, and nothing of THIS frame waits for it. In place -- on the
+// main stream, on all the slots -- in a counting, sharded or calibrating frame.
+static DustStatus surfel_pass(Frame& f, const dust::FrameArgs& a) {
+  DustHipPipeline* p = f.p;
+  DustHipContext* ctx = f.ctx;
+  const Tuning& tune = p->tune;
+  const bool aside = !tune.no_side_stream && !f.count && !f.sharded && !(tune.debug & 16u) && !f.calibrate;
+  if (aside) HIP_TRY(fork_side(ctx));
+  else HIP_TRY(join_side(ctx));
+  if (f.calibrate) HIP_TRY(hipEventRecord(p->side_cal.q0, f.st));
+  DustStatus rs = run_surfel_pass(p, a, f.fp->passes, f.count, aside ? ctx->side : f.st, aside ? dust::side_resident(f.plan.resident, f.share) : f.plan.resident,
+                                  f.sf_stream, f.fp->surfel_rank, f.fp->surfel_world);
+  // (whatever of the pass was enqueued -- all of it, or what came before a failed launch -- is waited for by the next user of the GI state)
+  if (aside) { ctx->side_busy = true; const hipError_t re = hipEventRecord(ctx->ev_side_done, ctx->side); if (rs == DUST_OK && re != hipSuccess) rs = hip_fail(re, "hipEventRecord(ev_side_done)"); }
+  if (rs != DUST_OK) return rs;
+  if (f.calibrate) { HIP_TRY(hipEventRecord(p->side_cal.q1, f.st)); p->side_cal.state = 1; }
+  return DUST_OK;
+}
+static DustStatus accumulate_pass(Frame& f, const dust::FrameArgs& a) {
+  f.p->have_history = false;  // the plane now holds an N-frame mean, not the denoiser's history
+  HIP_TRY(dust::launch_accumulate(a, f.st));
+  f.p->accum_count += 1;
+  return DUST_OK;
+}
+static DustStatus denoise_pass(Frame& f, const dust::FrameArgs& a) {
+  DustHipPipeline* p = f.p;
+  const size_t px = size_t(p->width) * p->height;
+  if (!p->hist_accum[0].p) {
+    for (int k = 0; k < 2; ++k) {
+      HIP_TRY(p->hist_accum[k].alloc(px * 16)); HIP_TRY(p->hist_geo[k].alloc(px * 16));
+    }
+    p->have_history = false;
+  }
+  dust::DenoiseArgs d{};
+  d.illuminance = a.g.illuminance; d.denoised = a.g.denoised; d.normal = a.g.normal; d.depth = a.g.depth;
+  d.motion = a.g.motion; d.voxel_id = a.g.voxel_id;
+  const uint32_t in = p->hist_parity, out = in ^ 1u;
+  // The radiance history lives in DUST_PLANE_ACCUM itself (it is what that plane shows while the denoiser runs): this frame
+  // reads the plane's buffer and writes the spare one, and the two then trade places -- no copy. A caller-bound plane cannot
+  // trade: it takes part as one side of an ordinary pair and receives a copy.
+  const bool trade = p->bound[DUST_PLANE_ACCUM] == nullptr;
+  d.hist_in_accum = static_cast<const float*>(trade ? p->planes[DUST_PLANE_ACCUM].p : p->hist_accum[in].p);
+  d.hist_out_accum = static_cast<float*>(trade ? p->hist_accum[0].p : p->hist_accum[out].p);
+  d.hist_in_geo = static_cast<const uint32_t*>(p->hist_geo[in].p);
+  d.hist_out_geo = static_cast<uint32_t*>(p->hist_geo[out].p);
+  if (trade != p->hist_traded) p->have_history = false;  // the plane was bound or released since the last frame: start over
+  p->hist_traded = trade;
+  d.cam = a.cam; d.prev = p->prev_cam;
+  d.have_history = p->have_history ? 1u : 0u;
+  d.width = p->width; d.height = p->height; d.frame_index = f.fp->frame_index;
+  d.aspect = a.aspect;
+  d.max_frames = float(std::max(1u, p->denoise.max_accumulated_frames));
+  d.disocclusion = p->denoise.disocclusion_threshold;
+  d.antilag_sigma = p->denoise.antilag_sigma_scale;
+  d.antilag_power = p->denoise.antilag_power;
+  d.max_radius = p->denoise.max_blur_radius;
+  HIP_TRY(dust::launch_denoise(d, f.st));
+  // DUST_PLANE_ACCUM shows the temporal accumulation (rgb + frame count) of the frame just filtered
+  if (trade) { std::swap(p->planes[DUST_PLANE_ACCUM].p, p->hist_accum[0].p); std::swap(p->planes[DUST_PLANE_ACCUM].bytes, p->hist_accum[0].bytes); }
+  else HIP_TRY(hipMemcpyAsync(p->plane(DUST_PLANE_ACCUM), d.hist_out_accum, px * 16, hipMemcpyDeviceToDevice, f.st));
+  p->hist_parity = out;
+  p->have_history = true;
+  p->prev_cam = a.cam;
+  return DUST_OK;
+}
+
+// One frame: its descriptor, its plan, then its passes in order, each a function above.
+static DustStatus render_frame_impl(DustHipPipeline* p, const DustHipScene* s, const DustHipCamera* cam, const DustHipSky* sky,
+                                    const DustHipFrameParams* fp_in, FrameRole role, BatchJoin* join) {
+  DustHipFrameParams fp_copy{};
+  DUST_TRY(check_frame(p, s, cam, sky, fp_in, fp_copy));
+  const DustHipFrameParams* fp = &fp_copy;
+  if ((fp->passes & (DUST_PASS_FINAL_GATHER | DUST_PASS_SURFEL)) && !p->gi_hash.p)
+    DUST_TRY(dust_hip_pipeline_configure_gi(p, dust::kSpatialHashCapacity, dust::kSurfelPoolSize));
+  DustHipContext* ctx = p->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const Tuning& tune = p->tune;
+  const bool batched = role != FrameRole::Single;
+  // ---- 1. the descriptor
+  dust::FrameArgs a{};
+  s->touch();
+  frame_args(p, s, cam, sky, fp, a);
+  Frame f{p, ctx, s, fp, ctx->stream};
+  const hipStream_t st = f.st;
+  f.count = fp->passes & DUST_PASS_COUNT_STATS;
+  f.sharded = (fp->passes & DUST_PASS_GI_SHARDED) != 0;
+  f.fg_stream = dust::gather_as_stream(fp->passes, a.grid.cells != nullptr, tune.gi_path, a.deep != 0, tune.debug, tune.no_gather_order);
+  f.sf_stream = dust::surfel_as_stream(fp->passes, a.grid.cells != nullptr, tune.gi_path);
+  if (f.fg_stream || f.sf_stream) DUST_TRY(ensure_stream_buffers(p, f.fg_stream, f.sf_stream));
+  // ---- 2. the plan (frame_plan.hpp). Whether the roots and lists fit does not depend on the share: asked first, before anything of the pipeline changes
+  f.si = slot_inputs(p, a);
+  if (dust::slot_plan(f.si).too_big) return fail(DUST_ERR_INVALID_ARGUMENT, "staged roots and candidate lists exceed the device's LDS");
   p->stats_valid = false;
-  // An event pair around a launch costs the stream ~6 us per record (a marker packet the next dispatch waits behind): 5 % of a
-  // 0.23 ms frame. A context that only wants averages over a run of frames (bench.py) times every 4th frame's launches.
   // (the further frames of a batched launch have no launch of their own to time: frame 0's pair brackets the launch of all of them)
-  // -- at the same rate PER FRAME as single launches are: a launch of n frames counts as n of the stride
-  const uint32_t stride = role != FrameRole::Single ? std::max(1u, ctx->timing_stride / join->n) : ctx->timing_stride;
-  const bool times_launch = role == FrameRole::Single || join->slot == 0;   // (a launch of several frames: frame 0's pipeline)
-  p->timed_frame = times_launch && ctx->timing && (p->frame_counter++ % stride) == 0;
+  const uint32_t stride = dust::timing_stride(ctx->timing_stride, batched, batched ? join->n : 1u);
+  const bool times_launch = !batched || join->slot == 0;   // (a launch of several frames: frame 0's pipeline)
+  p->timed_frame = times_launch && ctx->timing && dust::launch_timed(p->frame_counter++, stride);
   // (a frame that is not timed has no times: dust_hip_pipeline_pass_stats must not hand out an earlier frame's)
   if (!p->timed_frame) for (bool& v : p->ev_valid) v = false;
-  // while a surfel pass may be running on the second stream, the primary / AO kernels leave it its share of the slots (persistent
-  // launches hold what they get: whichever came first would otherwise own the GPU until it is done)
-  // The share: the pass's rays against the pixel passes' (pool x 18 surfel-ray costs to 3 rays per pixel, which puts the castle at
-  // 50 % at 1080p and 20 % at 4K -- where round 2's feedback loop settled, without its calibration frame, event probes and waits)
-  uint32_t share = tune.side_share;
-  bool calibrate = false;
-  if (!share) {
-    auto& cal = p->side_cal;
-    if (cal.state == 1 && hipEventQuery(cal.q1) == hipSuccess) {
-      float P = 0.0f, Q = 0.0f;
-      if (hipEventElapsedTime(&P, cal.p0, cal.p1) == hipSuccess && hipEventElapsedTime(&Q, cal.q0, cal.q1) == hipSuccess && P > 0.0f && Q > 0.0f)
-        {
-        // (a scene of many instances: the pass in place is as long as its longest items, 0.19 ms for 0.10 ms of work per wave, so it needs
-        // fewer slots than its time says -- share sweeps of round 5's last session: 39 % at 1080p and 16 % at 4K where 1.05 gave 47 and 21,
-        // GI frame 0.691 -> 0.667 ms. The 4096^3 tree's pass, one instance and long walks, is as long as its work: 1.05 stays there.)
-        const float k = a.deep ? 1.05f : 1.4f;
-        cal.share = uint32_t(std::min(65.0f, std::max(10.0f, 100.0f * Q / (Q + k * P) - 3.0f)));
-      }
-      cal.state = 2;
-    }
-    (void)hipGetLastError();  // (hipEventQuery's "not ready" is not an error of this call)
-    const bool gi_frame = (fp->passes & DUST_PASS_PRIMARY) && (fp->passes & DUST_PASS_SURFEL);
-    // (not the pipeline's first GI frames: they touch the hash and the pool for the first time -- 400 MB of first-touch page faults inside the
-    //  timed pass; one deep-tree run in five calibrated a share half as large again from it: 4.66 ms per frame against 4.27-4.30)
-    if (gi_frame && cal.state == 0) ++cal.gi_frames;
-    calibrate = cal.state == 0 && cal.gi_frames >= 3u && gi_frame && !tune.no_side_stream && !count && !sharded && !(tune.debug & 16u);
-    if (calibrate) HIP_TRY(join_side(ctx));   // (the timed frame runs its passes one after the other, behind the previous frame's surfel pass)
-    if (calibrate && !cal.p0)
-      for (hipEvent_t* e : {&cal.p0, &cal.p1, &cal.q0, &cal.q1}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableSystemFence));
-    if (cal.share) share = cal.share;
-    else {
-      const double surfel = double(p->gi_pool_size) * 18.0, pixel = 3.0 * double(p->width) * double(a.row_end - a.row_begin);
-      share = uint32_t(std::min(60.0, std::max(15.0, 100.0 * surfel / (surfel + pixel))));
-    }
-  }
-  const uint32_t side_slots = ctx->side_busy ? std::max(8u, (resident * share / 100u) & ~7u) : 0u;
-  const uint32_t main_resident = std::max(8u, resident - std::min(resident - 8u, side_slots));
-  // (a caller with several frames in flight, each on a pipeline of its own: this launch takes its share of the slots -- whole
-  // rounds over the 8 XCDs -- and leaves the rest to the others, dust_hip_pipeline_set_frames_in_flight)
-  // (DUST_IN_FLIGHT_ALL: every launch asks for all of them -- whole frames one behind the other on two or three streams: the next frame's
-  //  workgroups become resident on the CUs the previous frame's last tiles have left)
-  const bool share_slots = p->frames_in_flight > 1 && tune.in_flight_slots == DUST_IN_FLIGHT_SHARE;
-  // (diagnostic IN_FLIGHT_OVERSUB = percent: each of the n launches asks for that much more than its 1/n -- the extra workgroups wait for a slot)
-  const uint32_t frame_slots = share_slots ? std::min(main_resident, std::max(8u, ((main_resident / p->frames_in_flight) * (100u + tune.in_flight_oversub) / 100u) & ~7u)) : main_resident;
-  const uint32_t grid = std::max(8u, std::min<uint32_t>(frame_slots, (total_tiles + 7) / 8));
-  {  // FNV-1a over what decides a tile's cost
-    uint64_t k = 1469598103934665603ull;
-    auto mix = [&k](const void* data, size_t n) { const uint8_t* b = static_cast<const uint8_t*>(data); for (size_t i = 0; i < n; ++i) { k ^= b[i]; k *= 1099511628211ull; } };
-    mix(cam, sizeof *cam); mix(&s, sizeof s); mix(&s->revision, sizeof s->revision); mix(sky->state, sizeof sky->state);
-    mix(&a.row_begin, sizeof a.row_begin); mix(&a.row_end, sizeof a.row_end);
-    p->view_key = k;
-  }
-  a.gi.hash = static_cast<uint32_t*>(p->gi_hash.p);
-  a.gi.hash_capacity = p->gi_capacity;
-  a.gi.pool = static_cast<dust::DevSurfel*>(p->gi_pool.p);
-  a.gi.pool_size = p->gi_pool_size;
-  a.gi.slot_owner = static_cast<uint32_t*>(p->gi_owner.p);
-  a.gi.pixel_surfel = static_cast<dust::DevSurfel*>(p->gi_pixel_surfel.p);
-  a.gi.requests = static_cast<dust::DevHashRequest*>(p->gi_requests.p);
-  a.gi.replacement = static_cast<dust::DevSurfel*>(p->gi_replacement.p);
-  a.gi.sun_payload = static_cast<float*>(p->gi_sun_payload.p);
-  if (count) HIP_TRY(hipMemsetAsync(p->stats.p, 0, 8 * sizeof(dust::DevStats), st));
-  // primary + AO in one launch unless told otherwise (DUST_HIP_NO_FUSE=1 keeps the reference's one-launch-per-pass shape)
+  DUST_TRY(side_share(f, a));
+  f.si.share = f.share;
+  f.plan = dust::slot_plan(f.si);
+  a.n_lds_boxes = f.plan.n_lds_boxes;
+  p->view_key = dust::view_key(*cam, s, s->revision, *sky, a.row_begin, a.row_end);
+  if (f.count) HIP_TRY(hipMemsetAsync(p->stats.p, 0, 8 * sizeof(dust::DevStats), st));
+  // ---- 3. the passes. Primary + AO in one launch unless told otherwise (DUST_HIP_NO_FUSE=1 keeps the reference's one-launch-per-pass shape)
   const bool fuse = (fp->passes & DUST_PASS_PRIMARY) && (fp->passes & DUST_PASS_AMBIENT_OCCLUSION) && !tune.no_fuse;
   p->fused_last = fuse;
-  // the frame's first traversal launch tells the host that the frame has started (DustHipContext::started; dust_hip_scene_commit)
-  bool start_said = false;
-  auto say_start = [&](dust::FrameArgs& x) {
-    if (start_said || !ctx->started) return;
-    start_said = true;
-    x.started_word = const_cast<uint32_t*>(ctx->started);
-    x.started_seq = ++ctx->frame_seq;
-    s->slots[s->current].last_seq = x.started_seq;
-  };
-  if (calibrate) HIP_TRY(hipEventRecord(p->side_cal.p0, st));
-  if (role != FrameRole::Single && (!fuse || count)) return fail(DUST_ERR_INVALID_ARGUMENT, "a batched frame must be a fused primary + AO frame");  // (dust_hip_render_frames checks)
+  if (f.calibrate) HIP_TRY(hipEventRecord(p->side_cal.p0, st));
+  if (batched && (!fuse || f.count)) return fail(DUST_ERR_INVALID_ARGUMENT, "a batched frame must be a fused primary + AO frame");  // (dust_hip_render_frames checks)
   if (fuse) {
-    take_counters(p, 0, a);
-    bool continues = false;
-    if (role != FrameRole::Single) {
-      const uint32_t i = join->slot;
-      join->took_counters[i] = true;
-      join->cams[i] = cam; join->skies[i] = sky;
-      continues = i > 0 && !tune.no_shared_view && join->image_of[i - 1] == s->current &&
-                  std::memcmp(cam, join->cams[i - 1], sizeof *cam) == 0 && std::memcmp(sky, join->skies[i - 1], sizeof *sky) == 0;
-      join->continues[i] = continues;
-    }
-    if (continues) {
-      // a follower of a view run: the launch hands out the run's tiles by its leader's order and writes the leader's cost buffer. This pipeline's tile
-      // history is left as it stands -- nothing of it is read, nothing is measured for it --, valid for its next launch, alone or grouped differently.
-      a.tile_order = nullptr; a.tile_cost = nullptr; a.band_cuts = nullptr;
-    } else {
-      DustStatus os = order_tiles(p, 0, a, st);
-      if (os != DUST_OK) return os;
-    }
-    a.stats = static_cast<dust::DevStats*>(p->stats.p);
-    if (role != FrameRole::Single) {   // a frame of a launch of several: prepared; the last one launches them all
-      join->frames[join->slot] = a;
-      join->image_of[join->slot] = s->current;
-      if (join->slot == 0) join->timer = p;
-      if (role == FrameRole::Follower) return DUST_OK;
-    }
-    DustHipPipeline* tp = role == FrameRole::Lead ? join->timer : p;   // whose event pair brackets the launch
-    if (tp->timed_frame) HIP_TRY(hipEventRecord(tp->ev_begin(0), st));
-    // One 1024-thread workgroup per CU when the kernel has the device to itself (no surfel pass beside it, one frame in flight,
-    // no slots reserved, the default block size): the roots are staged once per CU and sixteen waves share a tile queue
-    uint32_t fblock = block, fgrid = grid;
-    const size_t batch_lds = role == FrameRole::Lead ? 16u * (join->n - 1u) : 0u;   // a tile queue per further frame
-    if (lds + batch_lds > ctx->max_lds) return fail(DUST_ERR_INVALID_ARGUMENT, "staged roots and candidate lists exceed the device's LDS");
-    const size_t lds_wide = size_t(a.n_lds_models) * dust::kN16LdsBytes + 16u * (dust::kMaxCand * 8 + 8) + 16 + size_t(a.n_lds_boxes) * 32 + batch_lds;
-    if (tune.wide_fused && block == 512 && bpc == 2 && !ctx->side_busy && !share_slots && !reserve_blocks && lds_wide <= ctx->max_lds &&
-        grid == resident) {
-      fblock = 1024;
-      fgrid = std::max(8u, std::min<uint32_t>(uint32_t(ctx->num_cus), (total_tiles + 7) / 8));
-    } else if (tune.wide_fused && tune.wide_share && block == 512 && bpc == 2 && !ctx->side_busy && share_slots && p->frames_in_flight == 2 && !reserve_blocks &&
-               lds_wide <= ctx->max_lds && grid == frame_slots && frame_slots * 2u == resident) {
-      // two whole frames in flight, each on half of the slots: half of the CUs each, one 1024-thread workgroup per CU
-      fblock = 1024;
-      fgrid = std::max(8u, (frame_slots / 2u) & ~7u);
-    }
-    if (role == FrameRole::Lead) {
-      say_start(join->frames[0]);   // (the kernel's first descriptor says it)
-      for (uint32_t i = 0; i < join->n; ++i) {
-        // Every scene image a frame of the launch reads is in use from NOW until the launch is done. dust_hip_scene_commit recycles an image by
-        // `epoch` (has anybody waited for the stream since a frame reading it was enqueued?) and `last_seq`: both were stamped when the frame
-        // was PREPARED (touch()), and a commit between then and now may have waited for the stream -- the image would pass for idle
-        // (found by tools/stress_host.py frames: 17 to 19 frames per call with moves, the third launch's commits landing on the second's images).
-        s->slots[join->image_of[i]].epoch = ctx->sync_epoch;
-        s->slots[join->image_of[i]].last_seq = join->frames[0].started_seq;
-        // the boxes staged in LDS are frame 0's image's: a frame of another image (an instance moved in between) reads its own from memory
-        if (join->image_of[i] != join->image_of[0]) join->frames[i].n_lds_boxes = 0;
-      }
-      for (uint32_t i = 0; i < join->n;) {   // view runs: the leader says how many frames follow it with the same view, a follower says 0
-        uint32_t run = 1;
-        while (i + run < join->n && join->continues[i + run]) ++run;
-        join->frames[i].view_run = run;
-        for (uint32_t m = 1; m < run; ++m) join->frames[i + m].view_run = 0;
-        i += run;
-      }
-      join->launched = true;
-      if ((tune.debug & 32u) || dust::launch_primary_ao_batch(join->frames, join->n, fgrid, fblock, st) != hipSuccess) {   // (DUST_HIP_DEBUG bit 32: as if refused)
-        // (the launch carries 8.5 KB of kernel arguments -- probed on this runtime, which takes 16 KB. Should a runtime refuse it: the prepared
-        //  frames one launch each, the same results)
-        (void)hipGetLastError();
-        for (uint32_t i = 0; i < join->n; ++i) HIP_TRY(dust::launch_primary_ao(join->frames[i], fgrid, fblock, false, st));
-      }
-    } else {
-      say_start(a);
-      HIP_TRY(dust::launch_primary_ao(a, fgrid, fblock, count, st));
-    }
-    a.started_word = nullptr;
-    if (tp->timed_frame) { HIP_TRY(hipEventRecord(tp->ev_end(0), st)); tp->ev_valid[0] = true; tp->ev_valid[1] = false; }
+    DUST_TRY(fused_pass(f, a, cam, sky, role, join));
+    if (role == FrameRole::Follower) return DUST_OK;   // (prepared: the Lead launches it)
   }
-  if (!fuse && (fp->passes & DUST_PASS_PRIMARY)) {
-    take_counters(p, 0, a);
-    { DustStatus os = order_tiles(p, 0, a, st); if (os != DUST_OK) return os; }
-    a.stats = static_cast<dust::DevStats*>(p->stats.p);
-    if (p->timed_frame) HIP_TRY(hipEventRecord(p->ev_begin(0), st));
-    say_start(a);
-    HIP_TRY(dust::launch_primary(a, grid, block, count, st));
-    a.started_word = nullptr;
-    if (p->timed_frame) { HIP_TRY(hipEventRecord(p->ev_end(0), st)); p->ev_valid[0] = true; }
-  }
-  if (!fuse && (fp->passes & DUST_PASS_AMBIENT_OCCLUSION)) {
-    take_counters(p, 1, a);
-    { DustStatus os = order_tiles(p, 1, a, st); if (os != DUST_OK) return os; }
-    a.stats = static_cast<dust::DevStats*>(p->stats.p) + 1;
-    if (p->timed_frame) HIP_TRY(hipEventRecord(p->ev_begin(1), st));
-    say_start(a);
-    HIP_TRY(dust::launch_ambient_occlusion(a, grid, block, count, st));
-    a.started_word = nullptr;
-    if (p->timed_frame) { HIP_TRY(hipEventRecord(p->ev_end(1), st)); p->ev_valid[1] = true; }
-  }
-  if (calibrate) HIP_TRY(hipEventRecord(p->side_cal.p1, st));
+  if (!fuse && (fp->passes & DUST_PASS_PRIMARY)) DUST_TRY(pixel_pass(f, a, 0));
+  if (!fuse && (fp->passes & DUST_PASS_AMBIENT_OCCLUSION)) DUST_TRY(pixel_pass(f, a, 1));
+  if (f.calibrate) HIP_TRY(hipEventRecord(p->side_cal.p1, st));
   if (fp->passes & DUST_PASS_FINAL_GATHER) {
-    if (sharded) {  // pixels that stamp nothing must read 0 after the all-gather
+    if (f.sharded) {  // pixels that stamp nothing must read 0 after the all-gather
       a.gi.touched = static_cast<uint32_t*>(p->gi_touched.p);
       a.gi.merged = static_cast<dust::DevSurfel*>(p->gi_merged.p);
       HIP_TRY(hipMemsetAsync(a.gi.touched + size_t(a.row_begin) * p->width, 0, size_t(a.row_end - a.row_begin) * p->width * 4, st));
     }
     a.stats = static_cast<dust::DevStats*>(p->stats.p) + 3;
-    // (a 4096^3 tree: long walks through one instance -- the one workload where a lane of its own per ray pays: 1.66 against 1.82 ms)
-    if (a.grid.cells && (!tune.packet_gi() || (a.deep && !tune.packet_only() && !(tune.debug & 12u) && !tune.no_gather_order))) {
-      // The pass as a ray stream (gi.hip): make and bin the band's gather rays (a thread per pixel) -> walk them one per lane, lanes refilled
-      // (k_ray_walk) -> shade the hit records (a thread per pixel). Behind the previous frame's surfel pass, like the packet kernel: rays and
-      // hit records touch no GI state and COULD run beside that pass, but two persistent launches sharing the slots both get slower
-      // (the 4096^3 tree's GI frame: 5.40 ms beside it, 4.56 behind it).
-      HIP_TRY(join_side(ctx));
-      dust::FrameArgs g = a;
-      stream_args(p, 0, g, 8.0f, a.cam.far_);  // final_gather.rgen:47-50
-      g.gi.fg_hits = g.stream.ray_hits;
-      take_counters(p, 2, g);
-      g.stream.count_unbinned = count ? 1u : 0u;
-      if (count) HIP_TRY(hipMemsetAsync(g.stream.unbinned, 0, 2 * 4, st));
-      if (p->timed_frame) HIP_TRY(hipEventRecord(p->ev_begin(2), st));
-      HIP_TRY(dust::launch_gather_rays(g, st));
-      const uint32_t want = uint32_t((size_t(p->width) * (a.row_end - a.row_begin) + 1023u) / 1024u);
-      const uint32_t slots = resident;
-      const uint32_t ggrid = std::max(8u, std::min<uint32_t>((slots * block / 1024u) & ~7u, (want + 7u) & ~7u));
-      HIP_TRY(dust::launch_ray_walk(g, 2, ggrid, 1024, count, st));
-      dust::FrameArgs sh = a;   // (pixel order over the band)
-      sh.gi.fg_hits = g.gi.fg_hits;
-      HIP_TRY(dust::launch_final_gather_shade(sh, !sharded, st));
-      if (p->timed_frame) { HIP_TRY(hipEventRecord(p->ev_end(2), st)); p->ev_valid[2] = true; }
-    } else {
-    dust::FrameArgs g = a;
-    uint32_t ggrid = std::max(8u, std::min<uint32_t>(resident, (total_tiles + 7) / 8));
-    if (!tune.no_gather_order) {  // pre-pass: regroup the band's live pixels by ray-direction octant
-      const uint32_t otx = (p->width + 63) / 64, oty = (a.row_end - a.row_begin + 63) / 64;
-      g.gi.order = static_cast<uint32_t*>(p->gi_order.p);
-      g.gi.order_count = static_cast<uint32_t*>(p->gi_order_count.p);
-      g.gi.order_tiles_x = otx;
-      HIP_TRY(dust::launch_gather_order(g, otx * oty, st));
-      // work items: 64 packets of 64 per tile, the empty ones skipped by the kernel
-      g.tiles_x = otx * oty * 64u;
-      g.tiles_y = 1;
-      ggrid = std::max(8u, std::min<uint32_t>(resident, (g.tiles_x + 7) / 8));
-    }
-    // (Round 4 also built the gather as a trace-only kernel beside the previous frame's surfel pass + a shading pass over hit records, and
-    //  round 3 as refilled ray lanes inside the packet kernel: both measured slower and were removed in round 6 -- docs/EXPERIMENTS.md.)
-    HIP_TRY(join_side(ctx));  // the previous frame's surfel pass has written the hash and the pool this gather reads
-    take_counters(p, 2, g);
-    { DustStatus os = order_tiles(p, 2, g, st); if (os != DUST_OK) return os; }
-    if (p->timed_frame) HIP_TRY(hipEventRecord(p->ev_begin(2), st));  // (behind the regrouping pre-pass: the gather kernel)
-    HIP_TRY(dust::launch_final_gather(g, ggrid, block, count, !sharded, st));
-    if (p->timed_frame) { HIP_TRY(hipEventRecord(p->ev_end(2), st)); p->ev_valid[2] = true; }
-      }
+    DUST_TRY(f.fg_stream ? gather_stream_pass(f, a) : gather_packet_pass(f, a));
   }
-  if (fp->passes & DUST_PASS_SURFEL) {
-    // On the context's second stream, behind this frame's final gather (see DustHipContext::side): the pass is a handful of
-    // latency-bound launches around a trace that is as long as its longest ray, and nothing of THIS frame waits for it.
-    const bool aside = !tune.no_side_stream && !count && !sharded && !(tune.debug & 16u) && !calibrate;
-    if (aside) HIP_TRY(fork_side(ctx));
-    else HIP_TRY(join_side(ctx));
-    if (calibrate) HIP_TRY(hipEventRecord(p->side_cal.q0, st));
-    // beside the next frame's kernels it takes a share of the workgroup slots (both are persistent launches: with all slots
-    // taken by the first, the second would simply run after it)
-    const uint32_t side_resident = std::max(8u, (resident * share / 100u) & ~7u);
-    DustStatus rs = run_surfel_pass(p, a, fp->passes, count, aside ? ctx->side : st, aside ? side_resident : resident, fp->surfel_rank, fp->surfel_world);
-    // (whatever of the pass was enqueued -- all of it, or what came before a failed launch -- is waited for by the next user of the GI state)
-    if (aside) { ctx->side_busy = true; const hipError_t re = hipEventRecord(ctx->ev_side_done, ctx->side); if (rs == DUST_OK && re != hipSuccess) rs = hip_fail(re, "hipEventRecord(ev_side_done)"); }
-    if (rs != DUST_OK) return rs;
-    if (calibrate) { HIP_TRY(hipEventRecord(p->side_cal.q1, st)); p->side_cal.state = 1; }
-  }
-  if (fp->passes & DUST_PASS_ACCUMULATE) {
-    p->have_history = false;  // the plane now holds an N-frame mean, not the denoiser's history
-    HIP_TRY(dust::launch_accumulate(a, st));
-    p->accum_count += 1;
-  }
-  if (fp->passes & DUST_PASS_DENOISE) {
-    const size_t px = size_t(p->width) * p->height;
-    if (!p->hist_accum[0].p) {
-      for (int k = 0; k < 2; ++k) {
-        HIP_TRY(p->hist_accum[k].alloc(px * 16)); HIP_TRY(p->hist_geo[k].alloc(px * 16));
-      }
-      p->have_history = false;
-    }
-    dust::DenoiseArgs d{};
-    d.illuminance = a.g.illuminance; d.denoised = a.g.denoised; d.normal = a.g.normal; d.depth = a.g.depth;
-    d.motion = a.g.motion; d.voxel_id = a.g.voxel_id;
-    const uint32_t in = p->hist_parity, out = in ^ 1u;
-    // The radiance history lives in DUST_PLANE_ACCUM itself (it is what that plane shows while the denoiser runs): this frame
-    // reads the plane's buffer and writes the spare one, and the two then trade places -- no copy. A caller-bound plane cannot
-    // trade: it takes part as one side of an ordinary pair and receives a copy.
-    const bool trade = p->bound[DUST_PLANE_ACCUM] == nullptr;
-    d.hist_in_accum = static_cast<const float*>(trade ? p->planes[DUST_PLANE_ACCUM].p : p->hist_accum[in].p);
-    d.hist_out_accum = static_cast<float*>(trade ? p->hist_accum[0].p : p->hist_accum[out].p);
-    d.hist_in_geo = static_cast<const uint32_t*>(p->hist_geo[in].p);
-    d.hist_out_geo = static_cast<uint32_t*>(p->hist_geo[out].p);
-    if (trade != p->hist_traded) p->have_history = false;  // the plane was bound or released since the last frame: start over
-    p->hist_traded = trade;
-    d.cam = a.cam; d.prev = p->prev_cam;
-    d.have_history = p->have_history ? 1u : 0u;
-    d.width = p->width; d.height = p->height; d.frame_index = fp->frame_index;
-    d.aspect = a.aspect;
-    d.max_frames = float(std::max(1u, p->denoise.max_accumulated_frames));
-    d.disocclusion = p->denoise.disocclusion_threshold;
-    d.antilag_sigma = p->denoise.antilag_sigma_scale;
-    d.antilag_power = p->denoise.antilag_power;
-    d.max_radius = p->denoise.max_blur_radius;
-    HIP_TRY(dust::launch_denoise(d, st));
-    // DUST_PLANE_ACCUM shows the temporal accumulation (rgb + frame count) of the frame just filtered
-    if (trade) { std::swap(p->planes[DUST_PLANE_ACCUM].p, p->hist_accum[0].p); std::swap(p->planes[DUST_PLANE_ACCUM].bytes, p->hist_accum[0].bytes); }
-    else HIP_TRY(hipMemcpyAsync(p->plane(DUST_PLANE_ACCUM), d.hist_out_accum, px * 16, hipMemcpyDeviceToDevice, st));
-    p->hist_parity = out;
-    p->have_history = true;
-    p->prev_cam = a.cam;
-  }
-  if (count) {
+  if (fp->passes & DUST_PASS_SURFEL) DUST_TRY(surfel_pass(f, a));
+  if (fp->passes & DUST_PASS_ACCUMULATE) DUST_TRY(accumulate_pass(f, a));
+  if (fp->passes & DUST_PASS_DENOISE) DUST_TRY(denoise_pass(f, a));
+  if (f.count) {
     HIP_TRY(hipMemcpyAsync(p->host_stats, p->stats.p, 8 * sizeof(dust::DevStats), hipMemcpyDeviceToHost, st));
     p->stats_valid = true;
   }
@@ -1507,12 +1454,7 @@ DustStatus dust_hip_pipeline_gi_exchange(DustHipPipeline* p, uint32_t padded_row
     HIP_TRY(hipMemsetAsync(p->gi_merged.p, 0, size_t(p->gi_pool_size) * 16, p->ctx->stream));
     p->gi_touched_rows = padded_rows;
   }
-  out->pool_size = p->gi_pool_size;
-  out->width = p->width;
-  out->touched_rows = padded_rows;
-  out->slot_owner = p->gi_owner.p;
-  out->touched = p->gi_touched.p;
-  out->merged = p->gi_merged.p;
+  exchange_view(p, padded_rows, out);
   return DUST_OK;
 }
 static DustStatus gi_exchange_launch(DustHipPipeline* p, uint32_t row_begin, uint32_t row_end, uint32_t frame_index, bool import) {
@@ -1523,16 +1465,10 @@ static DustStatus gi_exchange_launch(DustHipPipeline* p, uint32_t row_begin, uin
   HIP_TRY(hipSetDevice(p->ctx->device));
   HIP_TRY(join_side(p->ctx));
   dust::FrameArgs a{};
-  a.width = p->width; a.height = p->height;
-  a.inv_width = 1.0f / float(p->width); a.inv_height = 1.0f / float(p->height); a.aspect = float(p->width) / float(p->height);
+  frame_size_args(p, a);
   a.row_begin = row_begin; a.row_end = row_end;
   a.frame_index = frame_index;
-  a.gi.hash = static_cast<uint32_t*>(p->gi_hash.p);
-  a.gi.hash_capacity = p->gi_capacity;
-  a.gi.pool = static_cast<dust::DevSurfel*>(p->gi_pool.p);
-  a.gi.pool_size = p->gi_pool_size;
-  a.gi.slot_owner = static_cast<uint32_t*>(p->gi_owner.p);
-  a.gi.pixel_surfel = static_cast<dust::DevSurfel*>(p->gi_pixel_surfel.p);
+  gi_args(p, a.gi);
   a.gi.touched = static_cast<uint32_t*>(p->gi_touched.p);
   a.gi.merged = static_cast<dust::DevSurfel*>(p->gi_merged.p);
   HIP_TRY(import ? dust::launch_gi_import(a, p->ctx->stream) : dust::launch_gi_export(a, p->ctx->stream));
@@ -1729,12 +1665,7 @@ DustStatus gi_exchange_view(DustHipPipeline* p, uint32_t padded_rows, DustHipGiE
   if (!p->gi_touched.p || p->gi_touched_rows != padded_rows)
     return fail(DUST_ERR_NOT_READY, "the GI exchange buffers were not prepared for this world x band_rows: call dust_hip_pipeline_gi_exchange(p, world * band_rows) "
                                     "BEFORE the frame's final gather (a later call would re-create them and drop the frame's stamps)");
-  out->pool_size = p->gi_pool_size;
-  out->width = p->width;
-  out->touched_rows = padded_rows;
-  out->slot_owner = p->gi_owner.p;
-  out->touched = p->gi_touched.p;
-  out->merged = p->gi_merged.p;
+  exchange_view(p, padded_rows, out);
   return DUST_OK;
 }
 void pipeline_note_collective(DustHipPipeline* p) { p->in_collective = true; }
@@ -1750,13 +1681,7 @@ DustStatus surfel_finish(DustHipPipeline* p, uint32_t frame_index) {
   HIP_TRY(hipSetDevice(p->ctx->device));
   dust::FrameArgs a{};
   a.frame_index = frame_index;
-  a.gi.hash = static_cast<uint32_t*>(p->gi_hash.p);
-  a.gi.hash_capacity = p->gi_capacity;
-  a.gi.pool = static_cast<dust::DevSurfel*>(p->gi_pool.p);
-  a.gi.pool_size = p->gi_pool_size;
-  a.gi.requests = static_cast<dust::DevHashRequest*>(p->gi_requests.p);
-  a.gi.replacement = static_cast<dust::DevSurfel*>(p->gi_replacement.p);
-  a.gi.sun_payload = static_cast<float*>(p->gi_sun_payload.p);
+  gi_args(p, a.gi);
   a.gi.perm = p->sf_shard.perm;
   a.sf_stage_req = static_cast<dust::DevHashRequest*>(p->gi_stage_req.p);
   a.sf_stage_repl = static_cast<dust::DevSurfel*>(p->gi_stage_repl.p);

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- the host runtime's internal header (not part of the C ABI): the accessors comm.hip needs, and what the
 // runtime's translation units (capi.cpp, capi_model.cpp, capi_scene.cpp) share -- error helpers, DeviceBuffer, the handle structs.
-// (What the model calls compute without a device or a handle is model_records.hpp, which includes none of this.)
+// (What the model calls and the frame path compute without a device or a handle is model_records.hpp and frame_plan.hpp, which include none of this.)
 #pragma once
 #include <hip/hip_runtime.h>
 
