@@ -736,7 +736,7 @@ __global__ void k_surfel_apply_racy(const FrameArgs) {
 //      others are written to the pass's stream, compacted inside their group (a 16 x 16 pixel tile / 256 surfels): no atomics,
 //      the same order in every run;
 //   2. k_ray_walk, persistent: a wavefront is 64 LANES that each carry one ray of the stream through its candidates: enter the
-//      next one (walk_begin), walk it (walk_step: trace_instance's loop body, verbatim), until the candidates are used up or
+//      next one (walk_begin), walk it (walk_step: trace_instance's cell steps, walk_cell.hpp), until the candidates are used up or
 //      the ray is settled; the hit record is stored and the lane takes the stream's next ray. A trip of the wave's loop steps
 //      every walking lane; when enough lanes are NOT walking they are set up together. This is north_star's "compaction of
 //      active rays": a lane never waits for the longest ray of a packet, only for the phase its neighbours are in;

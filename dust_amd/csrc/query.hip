@@ -3,7 +3,7 @@
 //
 // One ray per LANE, as k_ray_walk carries the GI passes' rays (gi.hip): a lane takes the next ray of the launch, walks the top-level grid
 // (top_begin / top_next, top.hpp) to the next instance whose box the ray meets in front of its hit so far, enters it (walk_begin) and
-// walks it cell by cell (walk_step: trace_instance's loop body, verbatim), until the grid has nothing more in front of the hit; then the
+// walks it cell by cell (walk_step: trace_instance's cell steps, walk_cell.hpp), until the grid has nothing more in front of the hit; then the
 // 32-byte hit record is written and the lane takes another ray. A trip of the wave's loop advances every lane by one phase, whatever
 // phase its neighbours are in. Every ray is a primary-type ray (RT 0, hit.rint): the same brick tests on a superset of the bricks that
 // can be accepted and the same tie rule as the frame's camera rays and the CPU oracle's single-ray trace -- results are bit-identical by

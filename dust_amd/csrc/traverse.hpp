@@ -27,6 +27,7 @@
 #define DUST_DEVICE_ADDRESS_SPACES 1
 #include "dust_dev.h"
 #include "exact_div.hpp"
+#include "walk_cell.hpp"
 
 #ifdef DUST_PLAIN_STORES
 #define DUST_NT_STORE(v, p) (*(p) = (v))
@@ -138,10 +139,6 @@ __device__ __forceinline__ V3 div3(V3 v, float b) {  // v / b
   return mk(div_by(v.x, b, y, sp), div_by(v.y, b, y, sp), div_by(v.z, b, y, sp));
 }
 __device__ __forceinline__ V3 normalize3(V3 v) { return div3(v, sqrtf(dot3(v, v))); }
-__device__ __forceinline__ int f2i_clamp(float f, int lo, int hi) {  // clamp(int(floor-ed f)) with NaN -> lo side of 0
-  float c = fminf(fmaxf(f, (float)lo), (float)hi);                   // fmaxf(NaN, lo) == lo
-  return (int)c;
-}
 __device__ __forceinline__ int f2i_trunc(float f) {  // ivec3(float): toward zero; NaN -> 0, saturating (v_cvt_i32_f32)
   if (f != f) return 0;
   if (f >= 2147483648.0f) return 2147483647;
@@ -708,42 +705,16 @@ __device__ void trace_instance(ModelRef m, uint32_t inst, V3 o, V3 d, float tmin
   PROF_ENTER(P_CAND);
   const int E = (int)m.extent;
   const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z}, inv[3] = {inv_d.x, inv_d.y, inv_d.z};
-  float t = fmaxf(te, 0.0f);
-  if (RT >= 2) t = fmaxf(t, tmin * (1.0f - 1e-6f));
+  float t, near_tol, tx_stop;
   int ijk[3];
-  // Near-plane screen (see the loop): |p/4 - rint(p/4)| <= near_tol flags an entry point that may lie within
-  // delta = 1e-6 (|o_a| + |p_a| + 16) of a brick plane. One tolerance for the whole visit: 3e-7 (20 % above delta / 4,
-  // which covers evaluating p at the step's exit time instead of the clamped t) times the largest |o_a| + |p_a| the
-  // walk can meet (p is linear in t, so the ends of [te, tx] bound it).
-  float reach = 0.0f;
-  bool screen = false;  // does the CURRENT cell's entry point need the exact near-plane test?
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    // the cell the ray is moving into: floor for d >= 0, ceil - 1 for d < 0 (differs only on a cell plane), kept inside
-    // the tight bounds: the start point is the origin inside them or the entry point on them, and an entry point that
-    // rounding left a hair outside would otherwise start the walk one (empty) cell early, next to the plane, every time
-    const float p = oo[a] + dd[a] * t;
-    ijk[a] = f2i_clamp(dd[a] < 0.0f ? ceilf(p) - 1.0f : floorf(p), (int)m.bmin[a], (int)m.bmax[a] - 1);
-    reach = fmaxf(reach, fabsf(oo[a]) + fmaxf(fabsf(p), fabsf(oo[a] + dd[a] * tx)));
-  }
-  const float near_tol = 3.0e-7f * (reach + 16.0f);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    // The first cell gets the exact test's own shape with the looser tolerance, because it can tell what the cheap
-    // distance-to-a-multiple-of-4 cannot: a walk that starts on the model's bounds (every visit from outside does:
-    // the bounds are brick planes) is "near a plane" there by construction, but no brick exists beyond it, and that
-    // is not worth a call. (A plane only matters if bricks can exist on its far side.)
-    const int b0 = ijk[a] & ~3, blo = (int)m.bmin[a], bhi = (int)m.bmax[a] - 1;
-    const float q = (oo[a] + dd[a] * t) - (float)b0;
-    screen = screen | ((q <= 4.0f * near_tol) & (b0 - 1 >= blo)) | ((q >= 4.0f - 4.0f * near_tol) & (b0 + 4 <= bhi));
-  }
+  bool screen;  // does the CURRENT cell's entry point need the exact near-plane test?
+  walk_enter<RT>(oo, dd, m.bmin, m.bmax, te, tx, tmin, t, ijk, near_tol, screen, tx_stop);
   uint32_t stepped = 0;   // bit a: axis a crossed a plane on the last step
   uint32_t cl_main = 2;
   MidCache mc;
   midcache_reset(mc);
   const bool zero_axis = DEEP && __any(d.x == 0.0f || d.y == 0.0f || d.z == 0.0f);  // (of the lanes in this visit)
   bool prev_whole = false;  // DEEP: the cell the walk has just left was a whole 16-cell (or larger) with nothing untested in it
-  const float tx_stop = tx * (1.0f + 1e-5f) + 1e-5f;
   PROF_LEAVE(P_CAND);
   for (int guard = 0; guard < 200000; ++guard) {
     PROF_COUNT(P_N_STEPS, 1);
@@ -778,76 +749,16 @@ __device__ void trace_instance(ModelRef m, uint32_t inst, V3 o, V3 d, float tmin
     if (DEEP && (cl_main & kDirectCell)) { cl_main = 4; direct = true; cell_mid = key; cell_mask = mask; mask = 0; }
     PROF_LEAVE(P_FIND);
     // DEEP, screen raised, and the cell is a whole 16-cell with nothing untested in it (empty, missed, or about to be tested brick
-    // by brick): the bricks inside it need no neighbour visit -- but a brick ACROSS the face the ray came in through does, whatever
-    // plane its other axes are near (round 2's kernels looked again at 16-plane granularity only and lost one such brick in 4 000
-    // random deep scenes: tools/stress_parity.py STRESS_DEEP=1, seed 20833). That brick lies in the 16-cell the walk has just
-    // left: if that was itself a whole cell with nothing untested (prev_whole, below) there is nothing to do; else its child mask
-    // is what the cache holds, and the call is made only if the mask has a brick there -- or for the rarer shapes (ties, two
-    // near planes, a near 16-plane).
-    if (DEEP && __builtin_expect(screen, 0) && cl_main >= 4u) {
-      bool near16 = false, across_needed = true, sided = true;
-      uint32_t near4 = 0;
-      int c[3] = {ijk[0], ijk[1], ijk[2]};
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        if (stepped & (1u << a)) {
-          c[a] = dd[a] > 0.0f ? (ijk[a] & ~15) - 1 : (ijk[a] & ~15) + 16;  // back across the face
-        } else {
-          const float pa = oo[a] + dd[a] * t;
-          const float r4 = pa * 0.25f;
-          if (fabsf(r4 - rintf(r4)) <= near_tol) {
-            near4 += 1u;
-            const int b0 = ijk[a] & ~3;
-            const float q = pa - (float)b0;
-            // (a near plane that is a 16-cell's face has neighbours outside the cell on its own: the exact code looks)
-            if (q <= 8.0f * near_tol) { c[a] = b0 - 1; near16 = near16 | ((b0 & 15) == 0); }
-            else if (q >= 4.0f - 8.0f * near_tol) { c[a] = b0 + 4; near16 = near16 | (((b0 + 4) & 15) == 0); }
-            else sided = false;  // (the integer cell and the point disagree about the side: let the exact code look)
-          }
-        }
-      }
-      if (stepped == 0u || near4 == 0u) across_needed = false;  // nothing lies across an entered face and near another plane
-      else if (__popc(stepped) == 1 && near4 == 1u && sided) {
-        const int kd = ((c[0] >> 4) << 16) | ((c[1] >> 4) << 8) | (c[2] >> 4);
-        const uint32_t bd = ((uint32_t)((c[0] >> 2) & 3) << 4) | ((uint32_t)((c[1] >> 2) & 3) << 2) | (uint32_t)((c[2] >> 2) & 3);
-        if (prev_whole || (kd == mc.key && !((mc.mask4 >> bd) & 1ull))) across_needed = false;
-      }
-      screen = (__popc(stepped) > 1) | near16 | !sided | across_needed;
-    }
+    // by brick): only a brick ACROSS the face the ray came in through can still need the neighbour visit (whole_cell_screen)
+    if (DEEP && __builtin_expect(screen, 0) && cl_main >= 4u) screen = whole_cell_screen(oo, dd, t, ijk, stepped, near_tol, prev_whole, mc.key, mc.mask4);
     // leave the cell of size 2^cl_main that contains ijk
     PROF_ENTER(P_ADVANCE);
-    const int S = 1 << cl_main;
-    float ta[3], tn = INFINITY;
-    int cc[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      cc[a] = ijk[a] & ~(S - 1);
-      if (dd[a] != 0.0f) {
-        const float plane = (float)(dd[a] > 0.0f ? cc[a] + S : cc[a]);
-        ta[a] = (plane - oo[a]) * inv[a];
-      } else {
-        ta[a] = INFINITY;
-      }
-      tn = fminf(tn, ta[a]);
-    }
-    const bool stuck = !(tn < INFINITY);
-    uint32_t next_stepped = 0;
+    float tn;
+    bool stuck;
+    uint32_t next_stepped;
     int next_ijk[3];
-    bool outside = false, next_screen = false;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      if (ta[a] == tn) {
-        next_stepped |= 1u << a;
-        next_ijk[a] = dd[a] > 0.0f ? cc[a] + S : cc[a] - 1;
-        if (next_ijk[a] < 0 || next_ijk[a] >= E) outside = true;
-      } else {
-        const float p = oo[a] + dd[a] * tn;  // the next cell's entry point on an axis that does not cross a plane
-        next_ijk[a] = f2i_clamp(floorf(p), cc[a], cc[a] + S - 1);
-        const float r = p * 0.25f;
-        next_screen = next_screen | (fabsf(r - rintf(r)) <= near_tol);
-      }
-    }
-    next_screen = next_screen | (__popc(next_stepped) > 1);
+    bool outside, next_screen;
+    cell_exit(oo, dd, inv, ijk, cl_main, E, near_tol, tn, next_ijk, next_stepped, stuck, outside, next_screen);
     PROF_LEAVE(P_ADVANCE);
     {
       const bool have = mask != 0;
@@ -1231,8 +1142,9 @@ __device__ void trace_ray(ArgsRef a_in, bool active, V3 o, V3 d, float tmin, flo
 }
 
 // ------------------------------------------------------------------ one ray per lane: a visit as a state a lane carries (k_ray_walk, gi.hip)
-// walk_begin + walk_step are trace_instance's prologue and loop body, verbatim: what a ray computes is what trace_ray / trace_instance
-// compute for it; only which rays share a wavefront when changes -- never a result.
+// walk_begin + walk_step are trace_instance's prologue and loop body as a state: both call walk_cell.hpp for where a visit starts, the whole-cell
+// refinement of `screen` and the step out of a cell, so what a ray computes is what trace_ray / trace_instance compute for it; only which
+// rays share a wavefront when changes -- never a result.
 struct WalkState {          // one lane's visit of one instance
   V3 o, d, inv;             // object-space ray, inv = 1 / d (IEEE division: the intersection shader's reciprocal)
   float t, tx_stop, near_tol;
@@ -1257,7 +1169,7 @@ struct ModelLite {  // the two-level part of a DevModel, as find_brick reads it
   DUST_RO(uint8_t) l2;
   DUST_RO(DevL2Cell) l2_cells;
 };
-// trace_instance's prologue: false when the ray misses the model's bounds
+// trace_instance's prologue (walk_enter): false when the ray misses the model's bounds
 // (Model: a DevModel record, or any view with its bmin / bmax / lds_slot / extent / root / dense_mask members: EnterView)
 struct EnterView {
   float bmin[3], bmax[3];
@@ -1275,29 +1187,12 @@ __device__ __forceinline__ bool walk_begin(WalkState& w, const Model& m, uint32_
   if (!slab_box(o, d, w.inv, m.bmin, m.bmax, te, tx)) return false;
   if (in_brick_plane<RT>(o, d)) return false;
   const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
-  float t = fmaxf(te, 0.0f);
-  if (RT >= 2) t = fmaxf(t, tmin * (1.0f - 1e-6f));
-  float reach = 0.0f;
-  bool screen = false;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float p = oo[a] + dd[a] * t;
-    w.ijk[a] = f2i_clamp(dd[a] < 0.0f ? ceilf(p) - 1.0f : floorf(p), (int)m.bmin[a], (int)m.bmax[a] - 1);
-    reach = fmaxf(reach, fabsf(oo[a]) + fmaxf(fabsf(p), fabsf(oo[a] + dd[a] * tx)));
-  }
-  w.near_tol = 3.0e-7f * (reach + 16.0f);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int b0 = w.ijk[a] & ~3, blo = (int)m.bmin[a], bhi = (int)m.bmax[a] - 1;
-    const float q = (oo[a] + dd[a] * t) - (float)b0;
-    screen = screen | ((q <= 4.0f * w.near_tol) & (b0 - 1 >= blo)) | ((q >= 4.0f - 4.0f * w.near_tol) & (b0 + 4 <= bhi));
-  }
-  w.t = t; w.screen = screen; w.stepped = 0; w.cl_main = 2; w.steps = 0; w.prev_whole = false;
+  walk_enter<RT>(oo, dd, m.bmin, m.bmax, te, tx, tmin, w.t, w.ijk, w.near_tol, w.screen, w.tx_stop);
+  w.stepped = 0; w.cl_main = 2; w.steps = 0; w.prev_whole = false;
   midcache_reset(w.mc);
-  w.tx_stop = tx * (1.0f + 1e-5f) + 1e-5f;
   return true;
 }
-// trace_instance's loop body: one cell. Returns true when the visit is over.
+// trace_instance's loop body (whole_cell_screen, cell_exit): one cell, its bricks tested at once. Returns true when the visit is over.
 template <int RT, int MODE>
 __device__ __forceinline__ bool walk_step(WalkState& w, const DUST_CONST_AS DevModel* mp, float tmin, float tmax, bool any_hit, Hit& best, LaneStats& st) {
   {
@@ -1307,7 +1202,6 @@ __device__ __forceinline__ bool walk_step(WalkState& w, const DUST_CONST_AS DevM
     if (++w.steps > 200000u) return true;
   }
   const float oo[3] = {w.o.x, w.o.y, w.o.z}, dd[3] = {w.d.x, w.d.y, w.d.z}, inv[3] = {w.inv.x, w.inv.y, w.inv.z};
-  const int E = (int)w.extent;
   uint32_t key;
   uint64_t mask;
   if (DEEP) {
@@ -1322,70 +1216,16 @@ __device__ __forceinline__ bool walk_step(WalkState& w, const DUST_CONST_AS DevM
     lm.root = w.root; lm.dense_mask = w.dense_mask; lm.lds_slot = w.lds_slot; lm.l2 = nullptr; lm.l2_cells = nullptr;
     mask = find_brick<MODE>(lm, w.ijk[0], w.ijk[1], w.ijk[2], w.cl_main, key, w.mc, st, true, w.o, w.d, w.inv);
   }
-  // (trace_instance's refinement of `screen` for a whole 16-cell with nothing untested in it, verbatim: only a brick ACROSS the entered face
-  //  can need the neighbour visit -- without it the camera, sun and AO rays of a 4096^3 tree, which take sparse cells whole, made the call on
-  //  most of the trips whose entry point lies near a brick plane)
-  if (DEEP && __builtin_expect(w.screen, 0) && w.cl_main >= 4u) {
-    bool near16 = false, across_needed = true, sided = true;
-    uint32_t near4 = 0;
-    int c[3] = {w.ijk[0], w.ijk[1], w.ijk[2]};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      if (w.stepped & (1u << a)) {
-        c[a] = dd[a] > 0.0f ? (w.ijk[a] & ~15) - 1 : (w.ijk[a] & ~15) + 16;  // back across the face
-      } else {
-        const float pa = oo[a] + dd[a] * w.t;
-        const float r4 = pa * 0.25f;
-        if (fabsf(r4 - rintf(r4)) <= w.near_tol) {
-          near4 += 1u;
-          const int b0 = w.ijk[a] & ~3;
-          const float q = pa - (float)b0;
-          if (q <= 8.0f * w.near_tol) { c[a] = b0 - 1; near16 = near16 | ((b0 & 15) == 0); }
-          else if (q >= 4.0f - 8.0f * w.near_tol) { c[a] = b0 + 4; near16 = near16 | (((b0 + 4) & 15) == 0); }
-          else sided = false;
-        }
-      }
-    }
-    if (w.stepped == 0u || near4 == 0u) across_needed = false;
-    else if (__popc(w.stepped) == 1 && near4 == 1u && sided) {
-      const int kd = ((c[0] >> 4) << 16) | ((c[1] >> 4) << 8) | (c[2] >> 4);
-      const uint32_t bd = ((uint32_t)((c[0] >> 2) & 3) << 4) | ((uint32_t)((c[1] >> 2) & 3) << 2) | (uint32_t)((c[2] >> 2) & 3);
-      if (w.prev_whole || (kd == w.mc.key && !((w.mc.mask4 >> bd) & 1ull))) across_needed = false;
-    }
-    w.screen = (__popc(w.stepped) > 1) | near16 | !sided | across_needed;
-  }
-  const int S = 1 << w.cl_main;
-  float ta[3], tn = INFINITY;
-  int cc[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    cc[a] = w.ijk[a] & ~(S - 1);
-    if (dd[a] != 0.0f) {
-      const float plane = (float)(dd[a] > 0.0f ? cc[a] + S : cc[a]);
-      ta[a] = (plane - oo[a]) * inv[a];
-    } else {
-      ta[a] = INFINITY;
-    }
-    tn = fminf(tn, ta[a]);
-  }
-  const bool stuck = !(tn < INFINITY);
-  uint32_t next_stepped = 0;
+  // (only a brick ACROSS the entered face can need the neighbour visit -- without this the camera, sun and AO rays of a 4096^3 tree, which
+  //  take sparse cells whole, made the call on most of the trips whose entry point lies near a brick plane)
+  if (DEEP && __builtin_expect(w.screen, 0) && w.cl_main >= 4u)
+    w.screen = whole_cell_screen(oo, dd, w.t, w.ijk, w.stepped, w.near_tol, w.prev_whole, w.mc.key, w.mc.mask4);
+  float tn;
+  bool stuck;
+  uint32_t next_stepped;
   int next_ijk[3];
-  bool outside = false, next_screen = false;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (ta[a] == tn) {
-      next_stepped |= 1u << a;
-      next_ijk[a] = dd[a] > 0.0f ? cc[a] + S : cc[a] - 1;
-      if (next_ijk[a] < 0 || next_ijk[a] >= E) outside = true;
-    } else {
-      const float p = oo[a] + dd[a] * tn;
-      next_ijk[a] = f2i_clamp(floorf(p), cc[a], cc[a] + S - 1);
-      const float r = p * 0.25f;
-      next_screen = next_screen | (fabsf(r - rintf(r)) <= w.near_tol);
-    }
-  }
-  next_screen = next_screen | (__popc(next_stepped) > 1);
+  bool outside, next_screen;
+  cell_exit(oo, dd, inv, w.ijk, w.cl_main, (int)w.extent, w.near_tol, tn, next_ijk, next_stepped, stuck, outside, next_screen);
   if (mask != 0) test_brick<RT, MODE>(mask, w.inst, key, w.ijk[0] & ~3, w.ijk[1] & ~3, w.ijk[2] & ~3, w.o, w.d, w.inv, tmin, tmax, best, st);
   if (__builtin_expect(w.screen, 0)) {
     const u32x8 nv = visit_neighbours<RT, MODE>(mp, w.inst, w.o.x, w.o.y, w.o.z, w.d.x, w.d.y, w.d.z, w.inv.x, w.inv.y, w.inv.z, tmin, tmax, w.t,
