@@ -208,6 +208,24 @@ FLOOD_MAX_STEPS = 65534
 MAX_FLOOD_SEEDS = 65536
 
 
+class DistanceQuery(C.Structure):  # DustHipDistanceQuery, 32 bytes: the targets a distance field measures to, its metric and its radius
+    _fields_ = [("struct_size", C.c_uint32), ("target", C.c_uint32), ("metric", C.c_uint32), ("flags", C.c_uint32),
+                ("palette", C.c_int32), ("max_radius", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class DistanceResult(C.Structure):  # DustHipDistanceResult, 32 bytes: the counts of a distance field and where its largest value is
+    _fields_ = [("targets", C.c_uint32), ("near", C.c_uint32), ("far", C.c_uint32), ("largest", C.c_uint32),
+                ("largest_key", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+DISTANCE_TO_SOLID, DISTANCE_TO_EMPTY, DISTANCE_TO_MATERIAL = 0, 1, 2
+DISTANCE_EUCLIDEAN, DISTANCE_CHEBYSHEV = 0, 1
+DISTANCE_WALLS = 1
+DISTANCE_FAR = 0xFFFF
+DISTANCE_MAX_RADIUS = 255
+DISTANCE_NO_KEY = 0xFFFFFFFF
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("rays", C.c_uint64), ("instances_tested", C.c_uint64),
                 ("upper_descents", C.c_uint64), ("mid_descents", C.c_uint64), ("bricks_tested", C.c_uint64),
@@ -273,6 +291,9 @@ SYMBOLS = {
     "dust_hip_model_flood_at": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_flood_paths": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "dust_hip_model_flood_apply": (C.c_int, [_P, C.c_uint32, C.c_int32, _u32p]),
+    "dust_hip_model_distance": (C.c_int, [_P, _P, _P]),
+    "dust_hip_model_distance_at": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "dust_hip_model_distance_apply": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_scene_create": (C.c_int, [_P, C.POINTER(_P)]),

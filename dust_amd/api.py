@@ -45,6 +45,8 @@ CAST_HIT_DTYPE = np.dtype([("steps", "<u4"), ("flags", "<u4"), ("contacts", "<u4
 # DustHipFloodResult, 32 bytes: what a dust_hip_model_flood reached
 FLOOD_RESULT_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("seeds_used", "<u4"), ("boundary", "<u4"), ("lo", "u1", 3), ("pad0", "u1"),
                                ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 2)])
+# DustHipDistanceResult, 32 bytes: the counts of a dust_hip_model_distance field and where its largest value is
+DISTANCE_RESULT_DTYPE = np.dtype([("targets", "<u4"), ("near", "<u4"), ("far", "<u4"), ("largest", "<u4"), ("largest_key", "<u4"), ("reserved", "<u4", 3)])
 ISLAND_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("flags", "u1"), ("hi", "u1", 3), ("reserved", "u1"), ("sum", "<u8", 3)])
 FLT_MAX = float(np.finfo(np.float32).max)
 
@@ -465,6 +467,35 @@ class Model:
         the field and the island labelling are invalid afterwards."""
         changed = C.c_uint32()
         L.check(self._lib.dust_hip_model_flood_apply(self._h, 0xFFFFFFFF if max_steps is None else int(max_steps), int(value), C.byref(changed)))
+        return changed.value
+
+    def distance(self, target=L.DISTANCE_TO_SOLID, metric=L.DISTANCE_EUCLIDEAN, max_radius=L.DISTANCE_MAX_RADIUS, walls=False, palette=0):
+        """The exact distance from every voxel to the nearest target (dust_hip_model_distance): target L.DISTANCE_TO_SOLID (the solid
+        voxels), L.DISTANCE_TO_EMPTY (the voxels holding None) or L.DISTANCE_TO_MATERIAL (the solid voxels of palette index `palette`);
+        metric L.DISTANCE_EUCLIDEAN (the SQUARED distance dx^2 + dy^2 + dz^2) or L.DISTANCE_CHEBYSHEV (max(|dx|, |dy|, |dz|)); values
+        above max_radius^2 (max_radius under CHEBYSHEV) are L.DISTANCE_FAR; walls: the voxels outside the tree are targets too. Returns
+        the result as a DISTANCE_RESULT_DTYPE record (targets, near, far, largest, largest_key). The field stays on the device for
+        distance_at and distance_apply until the next edit."""
+        q = L.DistanceQuery(struct_size=C.sizeof(L.DistanceQuery), target=target, metric=metric, flags=L.DISTANCE_WALLS if walls else 0,
+                            palette=palette, max_radius=max_radius)
+        out = np.zeros(1, DISTANCE_RESULT_DTYPE)
+        L.check(self._lib.dust_hip_model_distance(self._h, C.byref(q), _ptr(out)))
+        return out[0]
+
+    def distance_at(self, xyz):
+        """the value of each voxel in the last distance field (dust_hip_model_distance_at): uint16, L.DISTANCE_FAR beyond the radius"""
+        xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
+        values = np.zeros(len(xyz), np.uint16)
+        L.check(self._lib.dust_hip_model_distance_at(self._h, _ptr(xyz), _ptr(values), len(values)))
+        return values
+
+    def distance_apply(self, value, lo=1, hi=0xFFFFFFFF):
+        """Every voxel whose value in the last distance field is not FAR and lies in lo..hi (the field's units: squared under EUCLIDEAN)
+        takes `value`, a palette index or -1 for None (dust_hip_model_distance_apply). Returns the number of voxels that changed.
+        Scenes instancing the model must be committed again; the distance field, the flood field and the island labelling are invalid
+        afterwards."""
+        changed = C.c_uint32()
+        L.check(self._lib.dust_hip_model_distance_apply(self._h, int(lo), int(hi), int(value), C.byref(changed)))
         return changed.value
 
     def read(self):

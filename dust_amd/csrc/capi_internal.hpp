@@ -187,6 +187,12 @@ struct EditState {
   DeviceBuffer flood;
   bool flood_valid = false;
   uint32_t flood_reached = 0, flood_lo[3] = {0, 0, 0}, flood_hi[3] = {0, 0, 0};
+  // model distances (dust_hip_model_distance): per voxel, brick-major like the grid, its distance to the nearest target (32 MiB of its
+  // own, allocated by the first call); valid under the flood field's rules. distance_finite: the voxels with a value other than FAR
+  // (0: dust_hip_model_distance_apply has nothing to visit)
+  DeviceBuffer distance;
+  bool distance_valid = false;
+  uint32_t distance_finite = 0;
 };
 
 struct DustHipModel : RefCounted {

@@ -8,6 +8,7 @@
 
 #include "capi_internal.hpp"
 #include "vdb.hpp"
+#include "distance.hpp"
 #include "flood.hpp"
 #include "island.hpp"
 #include "model_records.hpp"
@@ -319,6 +320,7 @@ DustStatus begin_edit(DustHipModel* m) {
 void invalidate_derived(EditState& es) {
   es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
   es.flood_valid = false;   // (and so does dust_hip_model_flood's field)
+  es.distance_valid = false;  // (and dust_hip_model_distance's)
 }
 // a buffer of one fixed size, allocated by the first call that needs it; out of device memory leaves it released
 DustStatus lazy_alloc(DeviceBuffer& b, size_t bytes, const char* what) {
@@ -336,6 +338,7 @@ DustStatus check_coordinates(const uint32_t* xyz, uint32_t n, uint32_t extent = 
   return DUST_OK;
 }
 DustStatus no_labelling() { return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)"); }
+DustStatus no_distance() { return fail(DUST_ERR_NOT_READY, "the model has no valid distance field: call dust_hip_model_distance (again after an edit)"); }
 DustStatus no_field() { return fail(DUST_ERR_NOT_READY, "the model has no valid flood field: call dust_hip_model_flood (again after an edit)"); }
 
 DustStatus upload_batch(DustHipModel* m, const uint32_t* xyz, const int32_t* values, uint32_t n, bool with_values) {
@@ -771,6 +774,7 @@ DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, 
       a.dst = nullptr;
       a.carve = 1u;
       es.flood_valid = false;  // (dust_hip_model_flood's field describes the voxels as they were)
+      es.distance_valid = false;  // (and so does dust_hip_model_distance's)
       HIP_TRY(dust::launch_island_detach(a, st));
       // (whole islands left: the labelling of the rest stands.) A failure in here is that of a shape edit's rebuild: the grid is
       // changed, the arrays are not; the new model is dropped with the error
@@ -938,6 +942,94 @@ DustStatus dust_hip_model_flood_apply(DustHipModel* m, uint32_t max_steps, int32
       a.changed = static_cast<uint32_t*>(es.changed.p);
       HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
       HIP_TRY(dust::launch_flood_apply(a, st));
+      HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
+    }
+    s = rebuild_and_refresh(m, es);  // synchronises
+    if (s != DUST_OK) return s;
+    if (changed) *changed = n;
+    return DUST_OK;
+  });
+}
+
+// ---- model distances (distance.hip): the exact distance from every voxel to the nearest target voxel, kept on the device with the model
+static_assert(sizeof(DustHipDistanceQuery) == 32 && sizeof(DustHipDistanceResult) == 32 && sizeof(dust::DistanceAcc) == 16, "distance records");
+DustStatus dust_hip_model_distance(DustHipModel* m, const DustHipDistanceQuery* q, DustHipDistanceResult* out) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);  // (before anything else is looked at)
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipDistanceQuery");
+  if (q->target > DUST_HIP_DISTANCE_TO_MATERIAL) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown distance target");
+  if (q->metric > DUST_HIP_DISTANCE_CHEBYSHEV) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown distance metric");
+  if (q->flags & ~DUST_HIP_DISTANCE_WALLS) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown distance flag");
+  if (q->target == DUST_HIP_DISTANCE_TO_MATERIAL && (q->palette < 0 || q->palette > 254)) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254");
+  if (q->max_radius == 0 || q->max_radius > DUST_HIP_DISTANCE_MAX_RADIUS) return fail(DUST_ERR_INVALID_ARGUMENT, "max_radius must be 1..DUST_HIP_DISTANCE_MAX_RADIUS");
+  dust::DistanceArgs a{};
+  if (!dust::device_distance(*q, a)) return fail(DUST_ERR_INVALID_ARGUMENT, "invalid distance query");
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    DustStatus s = begin_edit(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    es.distance_valid = false;  // until this field is complete
+    if ((s = lazy_alloc(es.distance, size_t(dust::kLattice) * 64 * 2, "the distance field (32 MiB)")) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_aux, sizeof(dust::DistanceAcc))) != DUST_OK) return s;
+    a.grid = static_cast<const uint8_t*>(es.grid.p);
+    a.brick_mask = static_cast<const uint64_t*>(es.brick_mask.p);
+    a.field = static_cast<uint16_t*>(es.distance.p);
+    a.acc = static_cast<dust::DistanceAcc*>(ctx->stage_aux.p);
+    HIP_TRY(hipMemsetAsync(a.acc, 0, sizeof(dust::DistanceAcc), st));
+    HIP_TRY(dust::launch_distance_field(a, st));
+    dust::DistanceAcc acc{};
+    HIP_TRY(hipMemcpyAsync(&acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const DustHipDistanceResult r = dust::distance_result(acc);
+    es.distance_finite = r.targets + r.near;
+    es.distance_valid = true;
+    if (out) *out = r;
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_distance_at(DustHipModel* m, const uint32_t* xyz, uint16_t* values, uint32_t n) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (n && (!xyz || !values)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if ((s = check_coordinates(xyz, n)) != DUST_OK) return s;
+  if (!m->edit || !m->edit->distance_valid) return no_distance();
+  if (n == 0) return DUST_OK;
+  return lookup_call(m, xyz, values, n, [&](const uint32_t* in, uint16_t* out, hipStream_t st) -> DustStatus {
+    HIP_TRY(dust::launch_distance_lookup(static_cast<const uint16_t*>(m->edit->distance.p), in, out, n, st));
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_distance_apply(DustHipModel* m, uint32_t lo, uint32_t hi, int32_t value, uint32_t* changed) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (value > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxels)");
+  if (!m->edit || !m->edit->distance_valid) return no_distance();
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    invalidate_derived(es);
+    uint32_t n = 0;
+    if (es.distance_finite && lo <= hi) {
+      if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;
+      dust::DistanceApplyArgs a{};
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.field = static_cast<const uint16_t*>(es.distance.p);
+      a.lo = lo; a.hi = hi;
+      a.byte = value < 0 ? 0u : uint32_t(value) + 1u;
+      a.changed = static_cast<uint32_t*>(es.changed.p);
+      HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
+      HIP_TRY(dust::launch_distance_apply(a, st));
       HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
     }
     s = rebuild_and_refresh(m, es);  // synchronises

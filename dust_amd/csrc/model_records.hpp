@@ -1,5 +1,5 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells and decodes a cast's result. No HIP call, no handle, no error state: tests/cpp/model_records_test.cpp drives it on a CPU.
 #pragma once
 #include <algorithm>
@@ -9,6 +9,7 @@
 
 #include "../../include/dust_hip.h"
 #include "cast.hpp"
+#include "distance.hpp"
 #include "edit.hpp"
 #include "stamp.hpp"
 
@@ -165,6 +166,34 @@ inline DustHipCastHit cast_hit(const DustHipCast& c, unsigned long long best, co
     h.contact[r] = int32_t(uint32_t(uint64_t(int64_t(c.offset[r]) + int64_t(k) * c.step[r] + u)));  // (the low 32 bits)
   }
   return h;
+}
+
+// A distance query as the kernels read it: the target byte, the radius no pass looks beyond and the limit in the field's own units
+// (squared under EUCLIDEAN). The pointers and the accumulator are the caller's. false: a query the call refuses.
+inline bool device_distance(const DustHipDistanceQuery& q, DistanceArgs& d) {
+  if (q.target > DUST_HIP_DISTANCE_TO_MATERIAL || q.metric > DUST_HIP_DISTANCE_CHEBYSHEV || (q.flags & ~DUST_HIP_DISTANCE_WALLS) != 0u) return false;
+  if (q.target == DUST_HIP_DISTANCE_TO_MATERIAL && (q.palette < 0 || q.palette > 254)) return false;
+  if (q.max_radius == 0u || q.max_radius > DUST_HIP_DISTANCE_MAX_RADIUS) return false;
+  d.target = q.target;
+  d.metric = q.metric;
+  d.byte = q.target == DUST_HIP_DISTANCE_TO_MATERIAL ? uint32_t(q.palette) + 1u : 0u;
+  d.radius = q.max_radius;
+  d.limit = q.metric == DUST_HIP_DISTANCE_EUCLIDEAN ? q.max_radius * q.max_radius : q.max_radius;
+  d.walls = (q.flags & DUST_HIP_DISTANCE_WALLS) ? 1u : 0u;
+  return true;
+}
+// What a distance call's caller gets from the reduction's accumulator (2^24 voxels in all).
+inline DustHipDistanceResult distance_result(const DistanceAcc& acc) {
+  DustHipDistanceResult r{};
+  r.targets = acc.targets;
+  r.far = acc.far;
+  r.near = (1u << 24) - acc.targets - acc.far;
+  r.largest_key = DUST_HIP_DISTANCE_NO_KEY;
+  if (r.targets + r.near != 0u) {
+    r.largest = uint32_t(acc.best >> 32);
+    r.largest_key = 0xFFFFFFu - uint32_t(acc.best & 0xFFFFFFu);
+  }
+  return r;
 }
 
 // the records of a call that cover something, in call order: `index` maps them back to the caller's

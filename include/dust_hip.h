@@ -490,6 +490,77 @@ DustStatus dust_hip_model_flood_at(DustHipModel*, const uint32_t* xyz, uint16_t*
 DustStatus dust_hip_model_flood_paths(DustHipModel*, const uint32_t* starts_xyz, uint32_t n, uint32_t capacity,
                                       uint32_t* keys /* n * capacity, may be NULL when capacity == 0 */, uint32_t* lengths /* n */);
 DustStatus dust_hip_model_flood_apply(DustHipModel*, uint32_t max_steps, int32_t value, uint32_t* changed /* may be NULL */);
+/* Model distances: how much ROOM there is. Rays, boxes, islands, floods and casts answer which voxels are solid, or count unit steps
+ * through faces; a distance field answers whether a sphere of radius r fits at a voxel, how thick a wall is here, where the roomiest
+ * spot is, and which voxels lie within r of the surface -- growing terrain by r (snow, moss, armour), eroding it by r (melt,
+ * weathering), painting the outer k voxels of a solid (scorch, rust). Coordinates are the model's tree coordinates, on 256^3 models.
+ *
+ * A query has a target set: DUST_HIP_DISTANCE_TO_SOLID the solid voxels, DUST_HIP_DISTANCE_TO_EMPTY the voxels holding None,
+ * DUST_HIP_DISTANCE_TO_MATERIAL the solid voxels whose palette index equals query.palette. value(v) is the minimum over all targets t of
+ * the metric between the voxel coordinates of v and t: under DUST_HIP_DISTANCE_EUCLIDEAN dx^2 + dy^2 + dz^2, the SQUARED distance (an
+ * integer; take the root on the host if you need it), under DUST_HIP_DISTANCE_CHEBYSHEV max(|dx|, |dy|, |dz|), the clearance of a cube.
+ * A target itself holds 0. With R = query.max_radius (1..DUST_HIP_DISTANCE_MAX_RADIUS) the limit is R^2 under EUCLIDEAN and R under
+ * CHEBYSHEV: a value above the limit, or no target at all, is reported as DUST_HIP_DISTANCE_FAR; a value at or below it is exact.
+ * With R = 255 and one target at (0, 0, 0), voxel (255, 0, 0) holds 65025 and voxel (255, 1, 0) holds FAR. Under the flag
+ * DUST_HIP_DISTANCE_WALLS every voxel outside the tree (coordinate -1 or 256 on an axis, and beyond) is a target too; the nearest of
+ * them lies straight across the nearest face, so the value is min(value, w^2) under EUCLIDEAN and min(value, w) under CHEBYSHEV with
+ * w = min over the axes of min(c + 1, 256 - c), under the same limit. Everything is integer: two runs give the same bytes.
+ * Three identities: a ball of radius r around a voxel's centre holds no target centre iff the EUCLIDEAN value is above r^2; a cube of
+ * half-width k (2 k + 1 voxels wide) around a voxel holds no target iff the CHEBYSHEV value is above k; TO_EMPTY with WALLS is "how deep
+ * inside the solid" (wall thickness on the solid side), and the maximum of a TO_SOLID field is the roomiest spot on the empty side.
+ *
+ * dust_hip_model_distance computes the field and leaves it on the device with the model -- one uint16 per voxel, brick-major like the
+ * editable grid, 32 MiB of its own next to the flood field and the island labelling, allocated by the first call and released with the
+ * model -- replacing the previous distance field. A model that is not yet editable is moved into its editable form first, exactly as
+ * flood does (scenes that instance it must then be committed again); on an editable model the call changes nothing a scene reads. The
+ * result record: targets, the voxels with value 0; near, the voxels with 0 < value != FAR; far, the voxels with value FAR (the three sum
+ * to 2^24); largest, the largest value != FAR (0 when there is none); largest_key, x << 16 | y << 8 | z of the LOWEST-keyed voxel that
+ * holds it, DUST_HIP_DISTANCE_NO_KEY when targets + near == 0.
+ * dust_hip_model_distance_at reads the field at coordinates, as flood_at reads steps.
+ * dust_hip_model_distance_apply gives every voxel with value != FAR && lo <= value <= hi the value `value` (a palette index 0..254, or
+ * negative for None). lo and hi are in the field's own units -- squared under EUCLIDEAN --, any uint32 is legal and lo > hi matches
+ * nothing. *changed is the number of voxels whose value differs afterwards. The model is rebuilt as after flood_apply -- its arrays
+ * byte for byte what dust_hip_model_create builds from the resulting voxels -- and its generation bumped: scenes must commit again.
+ * With r = 2 under EUCLIDEAN (r^2 = 4): a TO_SOLID field, range 1..4 and a palette index grow the solid by 2; a TO_EMPTY field, range
+ * 1..4 and None erode it by 2; a TO_EMPTY field, range 1..4 and a palette index paint its two-voxel skin.
+ * Validity: the distance field stands under exactly the rules of the flood field. It is invalidated by every set_voxels, edit_shapes,
+ * stamp (as destination) and carving detach_islands with n > 0, by flood_apply, by distance_apply itself, and by a distance call that
+ * fails. find_islands, island_of, flood, flood_at, flood_paths, KEEP_SOURCE detaches and being a stamp's or a cast's source leave it
+ * standing. distance leaves the flood field and the island labelling standing; distance_apply invalidates all three, as any edit does.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything changes: a null model or query; a struct_size below
+ * sizeof(DustHipDistanceQuery); an unknown target, metric or flag bit; palette outside 0..254 under TO_MATERIAL; max_radius of 0 or above
+ * DUST_HIP_DISTANCE_MAX_RADIUS; null arrays with n > 0; a coordinate >= 256; value > 254. DUST_ERR_UNSUPPORTED exactly where set_voxels
+ * returns it (4096^3 trees, models that hold material byte 255), before anything but the model pointer is looked at.
+ * DUST_ERR_NOT_READY from distance_at and distance_apply without a standing field, also with n == 0. All three calls are synchronous.
+ * Out of scope: a flood restricted by clearance (what agent-sized paths need: an entry point of its own, DustHipFloodQuery stays as it
+ * is); listing the voxels above a value; Manhattan distance; distances across the instances of a scene, in world space; 4096^3 trees; an
+ * asynchronous form. */
+#define DUST_HIP_DISTANCE_TO_SOLID    0u  /* targets: the solid voxels */
+#define DUST_HIP_DISTANCE_TO_EMPTY    1u  /* targets: the voxels holding None */
+#define DUST_HIP_DISTANCE_TO_MATERIAL 2u  /* targets: the solid voxels whose palette index equals query.palette */
+#define DUST_HIP_DISTANCE_EUCLIDEAN   0u  /* value = dx^2 + dy^2 + dz^2 between voxel coordinates (the SQUARED distance) */
+#define DUST_HIP_DISTANCE_CHEBYSHEV   1u  /* value = max(|dx|, |dy|, |dz|): the clearance of a cube */
+#define DUST_HIP_DISTANCE_WALLS       1u  /* flags: every voxel outside the tree is a target too */
+#define DUST_HIP_DISTANCE_FAR         0xFFFFu
+#define DUST_HIP_DISTANCE_MAX_RADIUS  255u
+#define DUST_HIP_DISTANCE_NO_KEY      0xFFFFFFFFu
+typedef struct DustHipDistanceQuery {   /* 32 bytes */
+  uint32_t struct_size, target, metric, flags;
+  int32_t  palette;                     /* read under TO_MATERIAL only: 0..254 */
+  uint32_t max_radius;                  /* 1..255 */
+  uint32_t reserved[2];                 /* 0 */
+} DustHipDistanceQuery;
+typedef struct DustHipDistanceResult {  /* 32 bytes */
+  uint32_t targets;                     /* voxels with value 0 */
+  uint32_t near;                        /* voxels with 0 < value != FAR */
+  uint32_t far;                         /* voxels with value FAR; targets + near + far == 2^24 */
+  uint32_t largest;                     /* the largest value != FAR (0 when there is none) */
+  uint32_t largest_key;                 /* x << 16 | y << 8 | z of the LOWEST-keyed voxel holding it; NO_KEY when targets + near == 0 */
+  uint32_t reserved[3];                 /* 0 */
+} DustHipDistanceResult;
+DustStatus dust_hip_model_distance(DustHipModel*, const DustHipDistanceQuery*, DustHipDistanceResult* out /* may be NULL */);
+DustStatus dust_hip_model_distance_at(DustHipModel*, const uint32_t* xyz, uint16_t* values, uint32_t n);
+DustStatus dust_hip_model_distance_apply(DustHipModel*, uint32_t lo, uint32_t hi, int32_t value, uint32_t* changed /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

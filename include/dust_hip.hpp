@@ -232,6 +232,32 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model distances (dust_hip_model_distance / distance_at / distance_apply): the exact distance from every voxel to the nearest
+  // target of the query (solid voxels, empty voxels, or one material) -- squared under DUST_HIP_DISTANCE_EUCLIDEAN --, kept on the
+  // device until the next edit; the values at coordinates (DUST_HIP_DISTANCE_FAR beyond the radius); and every voxel whose value lies
+  // in lo..hi given a palette index (nullopt: None), after which scenes that instance this geometry must commit() again.
+  DustHipDistanceResult distance(DustHipDistanceQuery query) {
+    query.struct_size = sizeof(query);
+    DustHipDistanceResult result{};
+    check(dust_hip_model_distance(h_, &query, &result));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return result;
+  }
+  std::vector<uint16_t> distance_at(const std::vector<UVec3>& coords) {
+    std::vector<uint32_t> xyz;
+    std::vector<uint16_t> values(coords.size());
+    for (const UVec3& c : coords) xyz.insert(xyz.end(), c.begin(), c.end());
+    check(dust_hip_model_distance_at(h_, xyz.data(), values.data(), uint32_t(values.size())));
+    return values;
+  }
+  uint32_t distance_apply(std::optional<uint8_t> palette_index, uint32_t lo = 1, uint32_t hi = 0xFFFFFFFFu) {
+    uint32_t changed = 0;
+    check(dust_hip_model_distance_apply(h_, lo, hi, palette_index ? int32_t(*palette_index) : -1, &changed));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
   std::optional<uint8_t> get(UVec3 c) {
     int32_t v = -1;
     check(dust_hip_model_get_voxels(h_, c.data(), &v, 1));
