@@ -226,6 +226,14 @@ DISTANCE_MAX_RADIUS = 255
 DISTANCE_NO_KEY = 0xFFFFFFFF
 
 
+class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
+    _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
+                ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
+
+
+N16_BYTES, N16_ROOT_BYTES = 656, 640
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("rays", C.c_uint64), ("instances_tested", C.c_uint64),
                 ("upper_descents", C.c_uint64), ("mid_descents", C.c_uint64), ("bricks_tested", C.c_uint64),
@@ -296,6 +304,7 @@ SYMBOLS = {
     "dust_hip_model_distance_apply": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
+    "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_scene_create": (C.c_int, [_P, C.POINTER(_P)]),
     "dust_hip_scene_destroy": (None, [_P]),
     "dust_hip_scene_add_instance": (C.c_int, [_P, _P, _f32p, _f32p, _u32p]),

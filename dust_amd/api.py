@@ -47,6 +47,9 @@ FLOOD_RESULT_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("seeds_
                                ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 2)])
 # DustHipDistanceResult, 32 bytes: the counts of a dust_hip_model_distance field and where its largest value is
 DISTANCE_RESULT_DTYPE = np.dtype([("targets", "<u4"), ("near", "<u4"), ("far", "<u4"), ("largest", "<u4"), ("largest_key", "<u4"), ("reserved", "<u4", 3)])
+# DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
+MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
+L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
 ISLAND_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("flags", "u1"), ("hi", "u1", 3), ("reserved", "u1"), ("sum", "<u8", 3)])
 FLT_MAX = float(np.finfo(np.float32).max)
 
@@ -506,6 +509,24 @@ class Model:
         mats = np.zeros(max(nm.value, 1), np.uint8)
         L.check(self._lib.dust_hip_model_read(self._h, _ptr(blocks), len(blocks), _ptr(mats), len(mats)))
         return blocks[: nb.value], mats[: nm.value]
+
+    def read_hierarchy(self):
+        """The upper levels as they stand on the device (dust_hip_model_read_hierarchy), as a dict of numpy arrays: extent_log2, n_mid,
+        n_l2, bmin / bmax (float32, 3), root (uint8, 656), host_root (uint8, 640: the copy a scene commit uses), mid (MID_NODE_DTYPE,
+        n_mid), dense_mask (uint64, n_mid * 64), and for 4096^3 trees l2 (uint8, n_l2 * 656) and l2_cells (L2_CELL_DTYPE, n_l2 * 4096)."""
+        info = L.HierarchyInfo(struct_size=C.sizeof(L.HierarchyInfo))
+        L.check(self._lib.dust_hip_model_read_hierarchy(self._h, C.byref(info), None, 0, None, 0, None, None, None, 0, None, 0))
+        n_mid, n_l2 = info.n_mid, info.n_l2
+        mid = np.zeros(max(n_mid, 1), MID_NODE_DTYPE)
+        dense = np.zeros(max(n_mid, 1) * 64, np.uint64)
+        root, host_root = np.zeros(L.N16_BYTES, np.uint8), np.zeros(L.N16_ROOT_BYTES, np.uint8)
+        l2 = np.zeros(max(n_l2, 1) * L.N16_BYTES, np.uint8)
+        cells = np.zeros(max(n_l2, 1) * 4096, L2_CELL_DTYPE)
+        L.check(self._lib.dust_hip_model_read_hierarchy(self._h, C.byref(info), _ptr(mid), len(mid), _ptr(dense), len(dense), _ptr(root), _ptr(host_root),
+                                                        _ptr(l2), max(n_l2, 1), _ptr(cells), len(cells)))
+        assert (info.n_mid, info.n_l2) == (n_mid, n_l2)
+        return dict(extent_log2=info.extent_log2, n_mid=n_mid, n_l2=n_l2, bmin=np.array(info.bmin, np.float32), bmax=np.array(info.bmax, np.float32),
+                    root=root, host_root=host_root, mid=mid[:n_mid], dense_mask=dense[: n_mid * 64], l2=l2[: n_l2 * L.N16_BYTES], l2_cells=cells[: n_l2 * 4096])
 
 
 class Scene:

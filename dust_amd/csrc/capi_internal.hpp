@@ -202,6 +202,7 @@ struct DustHipModel : RefCounted {
   dust::DevModel dev{};
   uint32_t id = 0;
   uint64_t n_materials = 0;
+  uint32_t n_mid = 0, n_l2 = 0;  // mid nodes and l2 nodes in use (an editable model's mid / dense_mask buffers hold room for 4096)
   uint32_t generation = 0;  // bumped by every edit: scenes record it at commit and refuse to render a stale copy
   bool has_material_255 = false;  // the edit grid stores palette index + 1 in a byte: such a model cannot become editable
   std::unique_ptr<EditState> edit;

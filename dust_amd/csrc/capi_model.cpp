@@ -1,6 +1,7 @@
-// capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the device hierarchy build, device-side voxel and shape
-// edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip) and model floods (flood.hip). The
-// arithmetic on the callers' records that needs no device (conversion, chunks, cell lists, cast hits) is model_records.hpp.
+// capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
+// edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip) and model floods (flood.hip). What
+// needs no device is in two headers: the hierarchy build itself (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp,
+// the arithmetic on the callers' records (conversion, chunks, cell lists, cast hits) in model_records.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -10,114 +11,9 @@
 #include "vdb.hpp"
 #include "distance.hpp"
 #include "flood.hpp"
+#include "hierarchy.hpp"
 #include "island.hpp"
 #include "model_records.hpp"
-
-// ------------------------------------------------------------------ device hierarchy build
-namespace {
-
-struct N16Builder {
-  std::vector<uint8_t> bytes;  // kN16Bytes per node
-  uint8_t* node(size_t i) { return bytes.data() + i * dust::kN16Bytes; }
-  size_t add() {
-    bytes.resize(bytes.size() + dust::kN16Bytes, 0);
-    return bytes.size() / dust::kN16Bytes - 1;
-  }
-  void finish(size_t i, uint32_t child_base) {  // rank prefix per 64-bit word + base of the first child
-    uint64_t* mask = reinterpret_cast<uint64_t*>(node(i));
-    uint16_t* pre = reinterpret_cast<uint16_t*>(node(i) + 512);
-    uint32_t run = 0;
-    for (int w = 0; w < 64; ++w) {
-      pre[w] = static_cast<uint16_t>(run);
-      run += static_cast<uint32_t>(__builtin_popcountll(mask[w]));
-    }
-    std::memcpy(node(i) + 640, &child_base, 4);
-  }
-};
-
-// Builds root / l2 / mid arrays from blocks given in Tree::iter_leaf order (depth-first, ascending bits).
-DustStatus build_hierarchy(const DustHipBlock* blocks, uint32_t n, uint32_t extent_log2, N16Builder& root,
-                           N16Builder& l2, std::vector<dust::DevN4>& mid, std::vector<uint64_t>& dense_mask,
-                           float bmin[3], float bmax[3]) {
-  const bool deep = extent_log2 == 12;
-  const uint32_t extent = 1u << extent_log2;
-  root.add();
-  uint64_t prev_key = 0;
-  int64_t cur_l2 = -1, cur_mid = -1;
-  uint32_t cur_l2_cell = 0xFFFFFFFFu, cur_mid_cell = 0xFFFFFFFFu;
-  for (int a = 0; a < 3; ++a) { bmin[a] = 1e30f; bmax[a] = -1e30f; }
-  auto idx16 = [](uint32_t x, uint32_t y, uint32_t z) { return (x << 8) | (y << 4) | z; };
-  for (uint32_t i = 0; i < n; ++i) {
-    const DustHipBlock& b = blocks[i];
-    if ((b.x & 3) || (b.y & 3) || (b.z & 3) || b.x >= extent || b.y >= extent || b.z >= extent)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "block position is not a 4-aligned coordinate inside the tree extent");
-    if (b.mask == 0) return fail(DUST_ERR_INVALID_ARGUMENT, "block with empty occupancy mask");
-    // depth-first order key: per level, x slowest (node/internal.rs:78-81)
-    uint64_t key = 0;
-    const uint32_t shifts_deep[3] = {8, 4, 2}, bits_deep[3] = {4, 4, 2};
-    const uint32_t shifts_std[2] = {4, 2}, bits_std[2] = {4, 2};
-    const uint32_t* sh = deep ? shifts_deep : shifts_std;
-    const uint32_t* bt = deep ? bits_deep : bits_std;
-    const int nl = deep ? 3 : 2;
-    for (int l = 0; l < nl; ++l) {
-      const uint32_t m = (1u << bt[l]) - 1;
-      key = (key << (3 * bt[l])) | (uint64_t(((b.x >> sh[l]) & m)) << (2 * bt[l])) | (uint64_t((b.y >> sh[l]) & m) << bt[l]) |
-            uint64_t((b.z >> sh[l]) & m);
-    }
-    if (i > 0 && key <= prev_key)
-      return fail(DUST_ERR_INVALID_ARGUMENT, "blocks are not in Tree::iter_leaf order (depth-first, ascending child bits)");
-    prev_key = key;
-    const float p[3] = {float(b.x), float(b.y), float(b.z)};
-    for (int a = 0; a < 3; ++a) {
-      bmin[a] = std::min(bmin[a], p[a]);
-      bmax[a] = std::max(bmax[a], p[a] + 4.0f);
-    }
-    // descend, creating nodes on first touch (children of a node are contiguous because of the order)
-    size_t n16 = 0;           // node holding the 16-cell bit
-    N16Builder* holder = &root;
-    if (deep) {
-      const uint32_t cell = idx16(b.x >> 8, b.y >> 8, b.z >> 8);
-      if (cell != cur_l2_cell) {
-        cur_l2 = int64_t(l2.add());
-        cur_l2_cell = cell;
-        dust::vdb::bit_set(reinterpret_cast<uint64_t*>(root.node(0)), cell, true);
-        cur_mid_cell = 0xFFFFFFFFu;
-      }
-      holder = &l2;
-      n16 = size_t(cur_l2);
-    }
-    const uint32_t cell16 = idx16((b.x >> 4) & 15, (b.y >> 4) & 15, (b.z >> 4) & 15);
-    const uint32_t mid_cell_key = deep ? uint32_t(cur_l2) * 4096u + cell16 : cell16;
-    if (mid_cell_key != cur_mid_cell) {
-      dust::vdb::bit_set(reinterpret_cast<uint64_t*>(holder->node(n16)), cell16, true);
-      dust::DevN4 nd{0, 0, i, 0};
-      mid.push_back(nd);
-      cur_mid = int64_t(mid.size()) - 1;
-      cur_mid_cell = mid_cell_key;
-    }
-    const uint32_t bit = (((b.x >> 2) & 3) << 4) | (((b.y >> 2) & 3) << 2) | ((b.z >> 2) & 3);
-    if (bit < 32) mid[size_t(cur_mid)].mask_lo |= 1u << bit;
-    else mid[size_t(cur_mid)].mask_hi |= 1u << (bit - 32);
-    if (dense_mask.size() < mid.size() * 64) dense_mask.resize(mid.size() * 64, 0);
-    dense_mask[size_t(cur_mid) * 64 + bit] = b.mask;
-  }
-  // prefixes and child bases: children were appended in order, so base = running count
-  if (deep) {
-    root.finish(0, 0);
-    uint32_t run = 0;
-    for (size_t i = 0; i < l2.bytes.size() / dust::kN16Bytes; ++i) {
-      l2.finish(i, run);
-      const uint64_t* mask = reinterpret_cast<const uint64_t*>(l2.node(i));
-      for (int w = 0; w < 64; ++w) run += uint32_t(__builtin_popcountll(mask[w]));
-    }
-  } else {
-    root.finish(0, 0);
-  }
-  if (n == 0) { for (int a = 0; a < 3; ++a) { bmin[a] = 0.0f; bmax[a] = 0.0f; } }
-  return DUST_OK;
-}
-
-}  // namespace
 
 void release(const DustHipModel* cm) {
   DustHipModel* m = const_cast<DustHipModel*>(cm);
@@ -139,12 +35,14 @@ DustStatus dust_hip_model_create(DustHipContext* ctx, const DustHipBlock* blocks
   if (tree_extent_log2 != 8 && tree_extent_log2 != 12)
     return fail(DUST_ERR_INVALID_ARGUMENT, "tree_extent_log2 must be 8 (hierarchy 4,2,2) or 12 (hierarchy 4,4,2,2)");
   return guarded([&]() -> DustStatus {
-    N16Builder root, l2;
-    std::vector<dust::DevN4> mid;
-    std::vector<uint64_t> dense_mask;
-    float bmin[3], bmax[3];
-    DustStatus s = build_hierarchy(blocks, n_blocks, tree_extent_log2, root, l2, mid, dense_mask, bmin, bmax);
-    if (s != DUST_OK) return s;
+    dust::Hierarchy h;
+    const char* refusal = nullptr;
+    const DustStatus s = dust::build_hierarchy(blocks, n_blocks, tree_extent_log2, h, &refusal);
+    if (s != DUST_OK) return fail(s, refusal);
+    dust::N16Builder& root = h.root;
+    dust::N16Builder& l2 = h.l2;
+    const std::vector<dust::DevN4>& mid = h.mid;
+    const std::vector<uint64_t>& dense_mask = h.dense_mask;
     for (uint32_t i = 0; i < n_blocks; ++i) {
       const uint64_t need = uint64_t(blocks[i].material_ptr) + uint64_t(__builtin_popcountll(blocks[i].mask));
       if (need > n_materials) return fail(DUST_ERR_INVALID_ARGUMENT, "block material_ptr runs past the material buffer");
@@ -159,28 +57,8 @@ DustStatus dust_hip_model_create(DustHipContext* ctx, const DustHipBlock* blocks
     m->host_root.assign(root.bytes.begin(), root.bytes.begin() + dust::kN16LdsBytes);
     HIP_TRY(m->l2.upload(l2.bytes.data(), l2.bytes.size(), up));
     if (tree_extent_log2 == 12) {  // the per-cell table the DEEP kernel variants look 16-cells up in: {mid index, child mask} per cell
-      const size_t n_l2 = l2.bytes.size() / dust::kN16Bytes;
-      std::vector<dust::DevL2Cell> cells(n_l2 * 4096, dust::DevL2Cell{0xFFFFFFFFu, 0u, 0ull});
-      for (size_t i = 0; i < n_l2; ++i) {
-        const uint64_t* mask = reinterpret_cast<const uint64_t*>(l2.node(i));
-        uint32_t base;
-        std::memcpy(&base, l2.node(i) + 640, 4);
-        uint32_t run = base;  // children of a node are contiguous, in ascending bit order
-        for (uint32_t w = 0; w < 64; ++w)
-          for (uint64_t bits = mask[w]; bits; bits &= bits - 1) {
-            dust::DevL2Cell& c = cells[i * 4096 + w * 64 + uint32_t(__builtin_ctzll(bits))];
-            c.mid = run;
-            c.child_mask = (uint64_t(mid[run].mask_hi) << 32) | mid[run].mask_lo;
-            uint32_t lo[3] = {3, 3, 3}, hi[3] = {0, 0, 0};
-            for (uint64_t cm = c.child_mask; cm; cm &= cm - 1) {
-              const uint32_t b = uint32_t(__builtin_ctzll(cm)), xyz[3] = {b >> 4, (b >> 2) & 3u, b & 3u};
-              for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], xyz[k]); hi[k] = std::max(hi[k], xyz[k]); }
-            }
-            c.bounds = lo[0] | (lo[1] << 2) | (lo[2] << 4) | (hi[0] << 6) | (hi[1] << 8) | (hi[2] << 10);
-            ++run;
-          }
-      }
-      HIP_TRY(m->l2_cells.upload(cells.data(), cells.size() * sizeof(dust::DevL2Cell), up));
+      dust::build_l2_cells(h);
+      HIP_TRY(m->l2_cells.upload(h.l2_cells.data(), h.l2_cells.size() * sizeof(dust::DevL2Cell), up));
     }
     HIP_TRY(m->mid.upload(mid.data(), mid.size() * sizeof(dust::DevN4), up));
     HIP_TRY(m->dense_mask.upload(dense_mask.data(), dense_mask.size() * 8, up));
@@ -200,13 +78,15 @@ DustStatus dust_hip_model_create(DustHipContext* ctx, const DustHipBlock* blocks
     d.blocks = static_cast<const DustHipBlock*>(m->blocks.p);
     d.materials = static_cast<const uint8_t*>(m->materials.p);
     d.palette = static_cast<const uint32_t*>(m->palette.p);
-    std::memcpy(d.bmin, bmin, sizeof(bmin));
-    std::memcpy(d.bmax, bmax, sizeof(bmax));
+    std::memcpy(d.bmin, h.bmin, sizeof(h.bmin));
+    std::memcpy(d.bmax, h.bmax, sizeof(h.bmax));
     d.extent = 1u << tree_extent_log2;
     d.n_levels = tree_extent_log2 == 12 ? 3 : 2;
     d.n_blocks = n_blocks;
     d.lds_slot = -1;
     m->n_materials = n_materials;
+    m->n_mid = uint32_t(mid.size());
+    m->n_l2 = uint32_t(l2.count());
     *out = retain(m);  // the caller's reference (the guard drops the builder's)
     return DUST_OK;
   });
@@ -258,6 +138,7 @@ DustStatus rebuild_and_refresh(DustHipModel* m, EditState& es) {
   HIP_TRY(hipStreamSynchronize(st));
   m->dev.n_blocks = h.n_blocks;
   m->n_materials = h.n_materials;
+  m->n_mid = h.n_mid;
   std::memcpy(m->dev.bmin, h.bmin, sizeof(h.bmin));
   std::memcpy(m->dev.bmax, h.bmax, sizeof(h.bmax));
   m->generation += 1;
@@ -1055,6 +936,36 @@ DustStatus dust_hip_model_read(const DustHipModel* m, DustHipBlock* blocks, uint
   if (blocks && m->dev.n_blocks) HIP_TRY(hipMemcpyAsync(blocks, m->blocks.p, size_t(m->dev.n_blocks) * sizeof(DustHipBlock), hipMemcpyDeviceToHost, st));
   if (materials && m->n_materials) HIP_TRY(hipMemcpyAsync(materials, m->materials.p, size_t(m->n_materials), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return DUST_OK;
+}
+
+// ---- the upper levels as they stand on the device (what tests/test_gpu_hierarchy.py holds to the host build and to a witness)
+static_assert(sizeof(DustHipHierarchyInfo) == 48 && sizeof(DustHipMidNode) == sizeof(dust::DevN4) && sizeof(DustHipL2Cell) == sizeof(dust::DevL2Cell) &&
+              DUST_HIP_N16_BYTES == dust::kN16Bytes && DUST_HIP_N16_ROOT_BYTES == dust::kN16LdsBytes, "hierarchy records");
+DustStatus dust_hip_model_read_hierarchy(const DustHipModel* m, DustHipHierarchyInfo* info, DustHipMidNode* mid, uint32_t mid_capacity,
+                                         uint64_t* dense_mask, uint64_t dense_mask_capacity, uint8_t* root, uint8_t* host_root,
+                                         uint8_t* l2, uint32_t l2_capacity, DustHipL2Cell* l2_cells, uint64_t l2_cell_capacity) {
+  if (!m || !info) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(info, "DustHipHierarchyInfo");
+  const uint32_t n_mid = m->n_mid, n_l2 = m->n_l2;
+  if ((mid && mid_capacity < n_mid) || (dense_mask && dense_mask_capacity < uint64_t(n_mid) * 64) || (l2 && l2_capacity < n_l2) ||
+      (l2_cells && l2_cell_capacity < uint64_t(n_l2) * 4096))
+    return fail(DUST_ERR_INVALID_ARGUMENT, "destination too small (call with the info record alone for the sizes)");
+  HIP_TRY(hipSetDevice(m->ctx->device));
+  const hipStream_t st = m->ctx->stream;
+  if (mid && n_mid) HIP_TRY(hipMemcpyAsync(mid, m->mid.p, size_t(n_mid) * sizeof(dust::DevN4), hipMemcpyDeviceToHost, st));
+  if (dense_mask && n_mid) HIP_TRY(hipMemcpyAsync(dense_mask, m->dense_mask.p, size_t(n_mid) * 64 * 8, hipMemcpyDeviceToHost, st));
+  if (root) HIP_TRY(hipMemcpyAsync(root, m->root.p, dust::kN16Bytes, hipMemcpyDeviceToHost, st));
+  if (l2 && n_l2) HIP_TRY(hipMemcpyAsync(l2, m->l2.p, size_t(n_l2) * dust::kN16Bytes, hipMemcpyDeviceToHost, st));
+  if (l2_cells && n_l2) HIP_TRY(hipMemcpyAsync(l2_cells, m->l2_cells.p, size_t(n_l2) * 4096 * sizeof(dust::DevL2Cell), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host_root) std::memcpy(host_root, m->host_root.data(), dust::kN16LdsBytes);
+  info->extent_log2 = m->dev.extent == 256 ? 8u : 12u;
+  info->n_mid = n_mid;
+  info->n_l2 = n_l2;
+  std::memcpy(info->bmin, m->dev.bmin, sizeof(info->bmin));
+  std::memcpy(info->bmax, m->dev.bmax, sizeof(info->bmax));
+  info->reserved[0] = info->reserved[1] = 0;
   return DUST_OK;
 }
 

@@ -13,7 +13,9 @@
 //   k_edit_emit_blocks   Block records (position, mask, material_ptr, avg_albedo) + the compacted material stream
 //   k_edit_upper_levels  root mask / rank prefixes, mid nodes, dense_mask, tight bounds, counts (one workgroup)
 // The result is, array for array, what dust_hip_model_create builds on the host from the same voxels
-// (loader.rs:244-274 + collector.rs + geometry.rs:68-128 + capi_model.cpp build_hierarchy): tests compare them byte for byte.
+// (loader.rs:244-274 + collector.rs + geometry.rs:68-128 + hierarchy.hpp build_hierarchy): tests compare them byte for byte -- the
+// Block records and the material stream in tests/test_gpu_edit.py and the tests of the later edit calls, everything
+// k_edit_upper_levels writes (root, mid nodes, dense_mask, n_mid, bounds) in tests/test_gpu_hierarchy.py.
 // avg_albedo's linear->sRGB curve is a table the HOST evaluates (the same powf the host-side flatten calls), indexed by
 // (voxel count, colour sum): the device only adds and looks up, so not one bit depends on a device transcendental.
 #include <hip/hip_runtime.h>
@@ -221,7 +223,7 @@ __global__ void __launch_bounds__(256) k_edit_emit_blocks(EditArgs e) {
   e.blocks[index] = b;
 }
 
-// root node, mid nodes, dense_mask, bounds: one workgroup of 1024 threads, four root cells each (capi_model.cpp build_hierarchy)
+// root node, mid nodes, dense_mask, bounds: one workgroup of 1024 threads, four root cells each (hierarchy.hpp build_hierarchy)
 __global__ void __launch_bounds__(1024) k_edit_upper_levels(EditArgs e) {
   __shared__ uint32_t part[1024];
   __shared__ uint64_t root_mask[64];

@@ -198,7 +198,9 @@ void dust_hip_model_destroy(DustHipModel*);
  * (what Tree::set_value takes), < 256 each; a voxel named twice takes its last value. The first edit of a model moves it into
  * an editable form (a dense voxel grid on the device, ~44 MB); every batch then rewrites root, mid nodes, brick masks, Block
  * records (material_ptr, avg_albedo) and the material stream on the GPU with scans over the brick lattice -- afterwards the
- * device arrays are byte for byte what dust_hip_model_create builds from the same voxels. Asynchronous edits are not
+ * device arrays are byte for byte what dust_hip_model_create builds from the same voxels (held by tests/test_gpu_edit.py and
+ * its siblings for the Block records and the material stream, and by tests/test_gpu_hierarchy.py, through
+ * dust_hip_model_read_hierarchy, for the root, the mid nodes, the dense masks, their count and the bounds). Asynchronous edits are not
  * offered: the call returns when the model is rebuilt (it reads sizes and bounds back). Scenes that instance the model must
  * be committed again (dust_hip_scene_commit) before they render: bounds and the staged root may have changed.
  * DUST_ERR_UNSUPPORTED for 4096^3 models. */
@@ -564,6 +566,49 @@ DustStatus dust_hip_model_distance_apply(DustHipModel*, uint32_t lo, uint32_t hi
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);
+/* The upper levels of a model as they stand on the device -- what the traversal descends through before it reaches a Block --, and a
+ * synchronous copy of them to the host: a check of the device-side rebuild (set_voxels and every later edit call) against
+ * dust_hip_model_create, array for array. Layouts:
+ *   N16 node (root; l2 nodes of 4096^3 trees), DUST_HIP_N16_BYTES: 64 x u64 child mask, bit (x << 8 | y << 4 | z) of the node's 16^3
+ *     cells; 64 x u16 rank prefix, the number of children in the mask words before this one; u32 child_base; 12 bytes of zero. A child's
+ *     index is child_base + prefix[word] + popcount(mask[word] below the bit): into the l2 nodes from a 4096^3 tree's root, into the
+ *     mid nodes otherwise.
+ *   DustHipMidNode: the 64-bit mask of a 16^3 cell's 4^3 bricks (bit x << 4 | y << 2 | z), and the Block index of its first brick;
+ *     brick `bit` is Block first_block + popcount(mask below the bit).
+ *   dense_mask: 64 x u64 per mid node, the occupancy mask of brick `bit` at [mid * 64 + bit], 0 where there is none.
+ *   DustHipL2Cell (4096^3 trees): per l2 node and 16^3 cell, [l2 * 4096 + cell]: its mid node, or 0xFFFFFFFF with bounds and
+ *     child_mask 0 for an empty cell; the mid node's mask; the box of its occupied bricks, lo.x | lo.y << 2 | lo.z << 4 | hi.x << 6 |
+ *     hi.y << 8 | hi.z << 10.
+ * info (struct_size set by the caller) receives extent_log2 (8 or 12), n_mid, n_l2 (0 for 256^3 trees) and the tight bounds bmin /
+ * bmax of the bricks (all 0 for an empty model). Every array is optional (NULL: not copied): mid takes n_mid records, dense_mask
+ * n_mid * 64 words, root DUST_HIP_N16_BYTES, l2 n_l2 * DUST_HIP_N16_BYTES, l2_cells n_l2 * 4096 records; host_root takes the
+ * DUST_HIP_N16_ROOT_BYTES (masks and prefixes) the library keeps on the host, the copy dust_hip_scene_commit puts into the scene image.
+ * The capacities are counted in records (mid, l2, l2_cells) and words (dense_mask); a call with info alone reports the sizes. What lies
+ * past n_mid in an editable model's buffers is not part of any contract and is not copied.
+ * DUST_ERR_INVALID_ARGUMENT, before anything is written: a null model or info; a struct_size below sizeof(DustHipHierarchyInfo); a
+ * capacity below what its array takes. Synchronous, like dust_hip_model_read: it waits for the context's stream. */
+#define DUST_HIP_N16_BYTES      656u
+#define DUST_HIP_N16_ROOT_BYTES 640u
+typedef struct DustHipHierarchyInfo {   /* 48 bytes */
+  uint32_t struct_size;
+  uint32_t extent_log2;                 /* 8 or 12 */
+  uint32_t n_mid, n_l2;
+  float bmin[3], bmax[3];
+  uint32_t reserved[2];                 /* 0 */
+} DustHipHierarchyInfo;
+typedef struct DustHipMidNode {         /* 16 bytes */
+  uint32_t mask_lo, mask_hi;
+  uint32_t first_block;
+  uint32_t pad;                         /* 0 */
+} DustHipMidNode;
+typedef struct DustHipL2Cell {          /* 16 bytes */
+  uint32_t mid;
+  uint32_t bounds;
+  uint64_t child_mask;
+} DustHipL2Cell;
+DustStatus dust_hip_model_read_hierarchy(const DustHipModel*, DustHipHierarchyInfo* info, DustHipMidNode* mid, uint32_t mid_capacity,
+                                         uint64_t* dense_mask, uint64_t dense_mask_capacity, uint8_t* root, uint8_t* host_root,
+                                         uint8_t* l2, uint32_t l2_capacity, DustHipL2Cell* l2_cells, uint64_t l2_cell_capacity);
 /* Lifetimes: a scene keeps the models it instances alive, every model / scene / pipeline its context; destroying a scene or
  * pipeline first waits for the frames in flight on the context's stream. After *_destroy the CALLER must not use the handle
  * again, whatever else still holds the object. Calls on one context are not thread-safe against each other;
