@@ -13,6 +13,7 @@
 
 #include "../../include/dust_hip.h"
 #include "dust_dev.h"
+#include "grid.hpp"
 #include "vox.hpp"
 
 namespace dust_internal {
@@ -170,6 +171,15 @@ DustStatus grow(DustHipContext* ctx, DeviceBuffer& b, size_t bytes);
 const char* diag_env(const char* name);  // "NO_FUSE" -> $DUST_HIP_NO_FUSE: the library's one environment lookup (capi.cpp)
 void release(DustHipContext* c);
 
+// a uint16 per voxel of an editable model (field.hpp). `count`: the voxels that hold a value (0: an apply call has nothing to visit);
+// `box`: the root cells that hold them -- the flood's reached voxels' bounds while count != 0, every cell for a distance field
+struct VoxelField {
+  DeviceBuffer values;
+  bool valid = false;
+  uint32_t count = 0;
+  dust::CellBox box{};
+};
+
 // device-side voxel edits (edit.hip): the dense voxel grid and the scratch tables of the rebuild, created on a model's first edit
 struct EditState {
   DeviceBuffer grid, brick_mask, flag_leaf, count_major, scan_tmp, header;
@@ -181,18 +191,10 @@ struct EditState {
   DeviceBuffer labels;
   bool labels_valid = false;
   uint32_t labels_corners = 0;  // the connectivity of that labelling
-  // model floods (dust_hip_model_flood): per voxel, brick-major like the grid, its step distance from the seeds (32 MiB, allocated by the
-  // first flood); valid until the next call that may change a voxel. flood_lo / flood_hi: the bounds of the reached voxels (what
-  // dust_hip_model_flood_apply visits), meaningful while flood_reached != 0
-  DeviceBuffer flood;
-  bool flood_valid = false;
-  uint32_t flood_reached = 0, flood_lo[3] = {0, 0, 0}, flood_hi[3] = {0, 0, 0};
-  // model distances (dust_hip_model_distance): per voxel, brick-major like the grid, its distance to the nearest target (32 MiB of its
-  // own, allocated by the first call); valid under the flood field's rules. distance_finite: the voxels with a value other than FAR
-  // (0: dust_hip_model_distance_apply has nothing to visit)
-  DeviceBuffer distance;
-  bool distance_valid = false;
-  uint32_t distance_finite = 0;
+  // model floods and model distances (dust_hip_model_flood, dust_hip_model_distance): per voxel, brick-major like the grid, its step
+  // distance from the seeds / its distance to the nearest target (32 MiB each, allocated by the first call); valid until the next call
+  // that may change a voxel
+  VoxelField flood, distance;
 };
 
 struct DustHipModel : RefCounted {

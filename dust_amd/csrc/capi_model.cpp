@@ -10,6 +10,7 @@
 #include "capi_internal.hpp"
 #include "vdb.hpp"
 #include "distance.hpp"
+#include "field.hpp"
 #include "flood.hpp"
 #include "hierarchy.hpp"
 #include "island.hpp"
@@ -197,11 +198,11 @@ DustStatus begin_edit(DustHipModel* m) {
   HIP_TRY(join_side(m->ctx));  // (a surfel pass on the second stream still traces the model as it is)
   return make_editable(m);
 }
+void invalidate_fields(EditState& es) { es.flood.valid = es.distance.valid = false; }  // (the fields describe the voxels as they were)
 // a call that may change a voxel is about to run
 void invalidate_derived(EditState& es) {
   es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
-  es.flood_valid = false;   // (and so does dust_hip_model_flood's field)
-  es.distance_valid = false;  // (and dust_hip_model_distance's)
+  invalidate_fields(es);
 }
 // a buffer of one fixed size, allocated by the first call that needs it; out of device memory leaves it released
 DustStatus lazy_alloc(DeviceBuffer& b, size_t bytes, const char* what) {
@@ -233,7 +234,7 @@ DustStatus upload_batch(DustHipModel* m, const uint32_t* xyz, const int32_t* val
 }
 
 extern "C++" {  // (templates: no C linkage)
-// dust_hip_model_island_of / dust_hip_model_flood_at: n coordinates up, one launch over them, n elements of type T back
+// dust_hip_model_island_of / field_at: n coordinates up, one launch over them, n elements of type T back
 template <class T, class Launch>
 DustStatus lookup_call(DustHipModel* m, const uint32_t* xyz, T* out, uint32_t n, Launch&& launch) {
   return guarded([&]() -> DustStatus {
@@ -247,6 +248,57 @@ DustStatus lookup_call(DustHipModel* m, const uint32_t* xyz, T* out, uint32_t n,
     if ((s = launch(static_cast<const uint32_t*>(ctx->stage_in.p), static_cast<T*>(ctx->stage_out.p), st)) != DUST_OK) return s;
     HIP_TRY(hipMemcpyAsync(out, ctx->stage_out.p, size_t(n) * sizeof(T), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return DUST_OK;
+  });
+}
+
+// dust_hip_model_flood_at / _distance_at: the values of field `which` at n coordinates; `none`: the refusal while it is not valid
+DustStatus field_at(DustHipModel* m, VoxelField EditState::*which, DustStatus (*none)(), const uint32_t* xyz, uint16_t* out, uint32_t n) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (n && (!xyz || !out)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if ((s = check_coordinates(xyz, n)) != DUST_OK) return s;
+  if (!m->edit || !(*m->edit.*which).valid) return none();
+  if (n == 0) return DUST_OK;
+  return lookup_call(m, xyz, out, n, [&](const uint32_t* in, uint16_t* values, hipStream_t st) -> DustStatus {
+    HIP_TRY(dust::launch_lookup(static_cast<const uint16_t*>((*m->edit.*which).values.p), in, values, n, st));
+    return DUST_OK;
+  });
+}
+
+// dust_hip_model_flood_apply / _distance_apply: the voxels whose value in field `which` lies in lo..hi take `value`; then the rebuild
+DustStatus field_apply(DustHipModel* m, VoxelField EditState::*which, DustStatus (*none)(), uint32_t lo, uint32_t hi, int32_t value, uint32_t* changed) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (value > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxels)");
+  if (!m->edit || !(*m->edit.*which).valid) return none();
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
+    EditState& es = *m->edit;
+    const VoxelField& f = es.*which;
+    hipStream_t st = ctx->stream;
+    invalidate_derived(es);
+    uint32_t n = 0;
+    if (f.count && lo <= hi) {
+      if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;
+      dust::FieldApplyArgs a{};
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.field = static_cast<const uint16_t*>(f.values.p);
+      a.lo = lo; a.hi = hi;
+      a.byte = value < 0 ? 0u : uint32_t(value) + 1u;
+      a.box = f.box;
+      a.changed = static_cast<uint32_t*>(es.changed.p);
+      HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
+      HIP_TRY(dust::launch_field_apply(a, st));
+      HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
+    }
+    s = rebuild_and_refresh(m, es);  // synchronises
+    if (s != DUST_OK) return s;
+    if (changed) *changed = n;
     return DUST_OK;
   });
 }
@@ -596,7 +648,7 @@ DustStatus dust_hip_model_island_of(DustHipModel* m, const uint32_t* xyz, uint32
   if (!m->edit || !m->edit->labels_valid) return no_labelling();
   if (n == 0) return DUST_OK;
   return lookup_call(m, xyz, keys, n, [&](const uint32_t* in, uint32_t* out, hipStream_t st) -> DustStatus {
-    HIP_TRY(dust::launch_island_lookup(static_cast<const uint32_t*>(m->edit->labels.p), in, out, n, st));
+    HIP_TRY(dust::launch_lookup(static_cast<const uint32_t*>(m->edit->labels.p), in, out, n, st));
     return DUST_OK;
   });
 }
@@ -654,8 +706,7 @@ DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, 
     if (!keep) {
       a.dst = nullptr;
       a.carve = 1u;
-      es.flood_valid = false;  // (dust_hip_model_flood's field describes the voxels as they were)
-      es.distance_valid = false;  // (and so does dust_hip_model_distance's)
+      invalidate_fields(es);
       HIP_TRY(dust::launch_island_detach(a, st));
       // (whole islands left: the labelling of the rest stands.) A failure in here is that of a shape edit's rebuild: the grid is
       // changed, the arrays are not; the new model is dropped with the error
@@ -668,6 +719,7 @@ DustStatus dust_hip_model_detach_islands(DustHipModel* m, const uint32_t* keys, 
 
 // ---- model floods (flood.hip): step distances from seeds through the empty or the solid voxels, kept on the device with the model
 static_assert(sizeof(DustHipFloodQuery) == 40 && sizeof(DustHipFloodResult) == 32, "flood records");
+static_assert(dust::kFieldNone == DUST_HIP_FLOOD_UNREACHED && dust::kFieldNone == DUST_HIP_DISTANCE_FAR, "one value means none in both fields");
 DustStatus dust_hip_model_flood(DustHipModel* m, const DustHipFloodQuery* q, const uint32_t* seeds_xyz, uint32_t n_seeds, DustHipFloodResult* out) {
   if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
   DustStatus s = editable_kind(m);  // (before anything else is looked at)
@@ -685,8 +737,8 @@ DustStatus dust_hip_model_flood(DustHipModel* m, const DustHipFloodQuery* q, con
     if (s != DUST_OK) return s;
     EditState& es = *m->edit;
     hipStream_t st = ctx->stream;
-    es.flood_valid = false;  // until this field is complete
-    if ((s = lazy_alloc(es.flood, size_t(dust::kLattice) * 64 * 2, "the flood field (32 MiB)")) != DUST_OK) return s;
+    es.flood.valid = false;  // until this field is complete
+    if ((s = lazy_alloc(es.flood.values, size_t(dust::kLattice) * 64 * 2, "the flood field (32 MiB)")) != DUST_OK) return s;
     const size_t L = dust::kLattice;
     if ((s = grow(ctx, ctx->flood_work, (4 * L + dust::kFloodWorkWords) * 4)) != DUST_OK) return s;
     if ((s = grow(ctx, ctx->stage_in, size_t(n_seeds) * 12)) != DUST_OK) return s;
@@ -696,7 +748,7 @@ DustStatus dust_hip_model_flood(DustHipModel* m, const DustHipFloodQuery* q, con
     uint32_t* count = work + dust::kFloodCount * L;  // three, taking turns
     dust::FloodArgs a{};
     a.grid = static_cast<const uint8_t*>(es.grid.p);
-    a.field = static_cast<uint16_t*>(es.flood.p);
+    a.field = static_cast<uint16_t*>(es.flood.values.p);
     a.medium = q->medium;
     a.byte = q->medium == DUST_HIP_FLOOD_MATERIAL ? uint32_t(q->palette) + 1u : 0u;
     a.max_steps = q->max_steps;
@@ -746,26 +798,16 @@ DustStatus dust_hip_model_flood(DustHipModel* m, const DustHipFloodQuery* q, con
       r.farthest = acc[1]; r.seeds_used = acc[2]; r.boundary = acc[3];
       for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[4 + k]); r.hi[k] = uint8_t(acc[7 + k]); }
     }
-    es.flood_reached = r.reached;
-    for (int k = 0; k < 3; ++k) { es.flood_lo[k] = r.lo[k]; es.flood_hi[k] = r.hi[k]; }
-    es.flood_valid = true;
+    es.flood.count = r.reached;
+    for (int k = 0; k < 3; ++k) { es.flood.box.lo[k] = r.lo[k] >> 4; es.flood.box.hi[k] = r.hi[k] >> 4; }
+    es.flood.valid = true;
     if (out) *out = r;
     return DUST_OK;
   });
 }
 
 DustStatus dust_hip_model_flood_at(DustHipModel* m, const uint32_t* xyz, uint16_t* steps, uint32_t n) {
-  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
-  DustStatus s = editable_kind(m);
-  if (s != DUST_OK) return s;
-  if (n && (!xyz || !steps)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  if ((s = check_coordinates(xyz, n)) != DUST_OK) return s;
-  if (!m->edit || !m->edit->flood_valid) return no_field();
-  if (n == 0) return DUST_OK;
-  return lookup_call(m, xyz, steps, n, [&](const uint32_t* in, uint16_t* out, hipStream_t st) -> DustStatus {
-    HIP_TRY(dust::launch_flood_lookup(static_cast<const uint16_t*>(m->edit->flood.p), in, out, n, st));
-    return DUST_OK;
-  });
+  return field_at(m, &EditState::flood, no_field, xyz, steps, n);
 }
 
 DustStatus dust_hip_model_flood_paths(DustHipModel* m, const uint32_t* starts_xyz, uint32_t n, uint32_t capacity, uint32_t* keys, uint32_t* lengths) {
@@ -774,7 +816,7 @@ DustStatus dust_hip_model_flood_paths(DustHipModel* m, const uint32_t* starts_xy
   if (s != DUST_OK) return s;
   if (!lengths || (n && !starts_xyz) || (n && capacity && !keys)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
   if ((s = check_coordinates(starts_xyz, n)) != DUST_OK) return s;
-  if (!m->edit || !m->edit->flood_valid) return no_field();
+  if (!m->edit || !m->edit->flood.valid) return no_field();
   if (n == 0) return DUST_OK;
   return guarded([&]() -> DustStatus {
     DustHipContext* ctx = m->ctx;
@@ -785,7 +827,7 @@ DustStatus dust_hip_model_flood_paths(DustHipModel* m, const uint32_t* starts_xy
     if ((s = grow(ctx, ctx->stage_aux, size_t(n) * 4)) != DUST_OK) return s;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, starts_xyz, size_t(n) * 12, hipMemcpyHostToDevice, st));
-    HIP_TRY(dust::launch_flood_paths(static_cast<const uint16_t*>(m->edit->flood.p), static_cast<const uint32_t*>(ctx->stage_in.p), n, capacity,
+    HIP_TRY(dust::launch_flood_paths(static_cast<const uint16_t*>(m->edit->flood.values.p), static_cast<const uint32_t*>(ctx->stage_in.p), n, capacity,
                                      static_cast<uint32_t*>(ctx->stage_out.p), static_cast<uint32_t*>(ctx->stage_aux.p), st));
     // the slots past a path's end stay the caller's: the device rows come back beside them and only their written part is copied over
     std::vector<uint32_t> rows(slots);
@@ -799,37 +841,7 @@ DustStatus dust_hip_model_flood_paths(DustHipModel* m, const uint32_t* starts_xy
 }
 
 DustStatus dust_hip_model_flood_apply(DustHipModel* m, uint32_t max_steps, int32_t value, uint32_t* changed) {
-  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
-  DustStatus s = editable_kind(m);
-  if (s != DUST_OK) return s;
-  if (value > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxels)");
-  if (!m->edit || !m->edit->flood_valid) return no_field();
-  return guarded([&]() -> DustStatus {
-    DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
-    EditState& es = *m->edit;
-    hipStream_t st = ctx->stream;
-    invalidate_derived(es);
-    uint32_t n = 0;
-    if (es.flood_reached) {
-      if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;
-      dust::FloodApplyArgs a{};
-      a.grid = static_cast<uint8_t*>(es.grid.p);
-      a.field = static_cast<const uint16_t*>(es.flood.p);
-      a.max_steps = max_steps;
-      a.byte = value < 0 ? 0u : uint32_t(value) + 1u;
-      for (int k = 0; k < 3; ++k) { a.lo[k] = es.flood_lo[k]; a.hi[k] = es.flood_hi[k]; }
-      a.changed = static_cast<uint32_t*>(es.changed.p);
-      HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
-      HIP_TRY(dust::launch_flood_apply(a, st));
-      HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
-    }
-    s = rebuild_and_refresh(m, es);  // synchronises
-    if (s != DUST_OK) return s;
-    if (changed) *changed = n;
-    return DUST_OK;
-  });
+  return field_apply(m, &EditState::flood, no_field, 0u, max_steps, value, changed);
 }
 
 // ---- model distances (distance.hip): the exact distance from every voxel to the nearest target voxel, kept on the device with the model
@@ -853,12 +865,12 @@ DustStatus dust_hip_model_distance(DustHipModel* m, const DustHipDistanceQuery* 
     if (s != DUST_OK) return s;
     EditState& es = *m->edit;
     hipStream_t st = ctx->stream;
-    es.distance_valid = false;  // until this field is complete
-    if ((s = lazy_alloc(es.distance, size_t(dust::kLattice) * 64 * 2, "the distance field (32 MiB)")) != DUST_OK) return s;
+    es.distance.valid = false;  // until this field is complete
+    if ((s = lazy_alloc(es.distance.values, size_t(dust::kLattice) * 64 * 2, "the distance field (32 MiB)")) != DUST_OK) return s;
     if ((s = grow(ctx, ctx->stage_aux, sizeof(dust::DistanceAcc))) != DUST_OK) return s;
     a.grid = static_cast<const uint8_t*>(es.grid.p);
     a.brick_mask = static_cast<const uint64_t*>(es.brick_mask.p);
-    a.field = static_cast<uint16_t*>(es.distance.p);
+    a.field = static_cast<uint16_t*>(es.distance.values.p);
     a.acc = static_cast<dust::DistanceAcc*>(ctx->stage_aux.p);
     HIP_TRY(hipMemsetAsync(a.acc, 0, sizeof(dust::DistanceAcc), st));
     HIP_TRY(dust::launch_distance_field(a, st));
@@ -866,58 +878,20 @@ DustStatus dust_hip_model_distance(DustHipModel* m, const DustHipDistanceQuery* 
     HIP_TRY(hipMemcpyAsync(&acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const DustHipDistanceResult r = dust::distance_result(acc);
-    es.distance_finite = r.targets + r.near;
-    es.distance_valid = true;
+    es.distance.count = r.targets + r.near;
+    es.distance.box = dust::CellBox{{0, 0, 0}, {15, 15, 15}};  // (the field keeps no bounds)
+    es.distance.valid = true;
     if (out) *out = r;
     return DUST_OK;
   });
 }
 
 DustStatus dust_hip_model_distance_at(DustHipModel* m, const uint32_t* xyz, uint16_t* values, uint32_t n) {
-  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
-  DustStatus s = editable_kind(m);
-  if (s != DUST_OK) return s;
-  if (n && (!xyz || !values)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
-  if ((s = check_coordinates(xyz, n)) != DUST_OK) return s;
-  if (!m->edit || !m->edit->distance_valid) return no_distance();
-  if (n == 0) return DUST_OK;
-  return lookup_call(m, xyz, values, n, [&](const uint32_t* in, uint16_t* out, hipStream_t st) -> DustStatus {
-    HIP_TRY(dust::launch_distance_lookup(static_cast<const uint16_t*>(m->edit->distance.p), in, out, n, st));
-    return DUST_OK;
-  });
+  return field_at(m, &EditState::distance, no_distance, xyz, values, n);
 }
 
 DustStatus dust_hip_model_distance_apply(DustHipModel* m, uint32_t lo, uint32_t hi, int32_t value, uint32_t* changed) {
-  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
-  DustStatus s = editable_kind(m);
-  if (s != DUST_OK) return s;
-  if (value > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxels)");
-  if (!m->edit || !m->edit->distance_valid) return no_distance();
-  return guarded([&]() -> DustStatus {
-    DustHipContext* ctx = m->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
-    EditState& es = *m->edit;
-    hipStream_t st = ctx->stream;
-    invalidate_derived(es);
-    uint32_t n = 0;
-    if (es.distance_finite && lo <= hi) {
-      if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;
-      dust::DistanceApplyArgs a{};
-      a.grid = static_cast<uint8_t*>(es.grid.p);
-      a.field = static_cast<const uint16_t*>(es.distance.p);
-      a.lo = lo; a.hi = hi;
-      a.byte = value < 0 ? 0u : uint32_t(value) + 1u;
-      a.changed = static_cast<uint32_t*>(es.changed.p);
-      HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
-      HIP_TRY(dust::launch_distance_apply(a, st));
-      HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
-    }
-    s = rebuild_and_refresh(m, es);  // synchronises
-    if (s != DUST_OK) return s;
-    if (changed) *changed = n;
-    return DUST_OK;
-  });
+  return field_apply(m, &EditState::distance, no_distance, lo, hi, value, changed);
 }
 
 DustStatus dust_hip_model_info(const DustHipModel* m, uint32_t* n_blocks, uint64_t* n_materials) {

@@ -30,7 +30,6 @@ namespace dust {
 
 namespace {
 
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ int32_t pick(int32_t x, int32_t y, int32_t z, uint32_t axis) { return axis == 0u ? x : axis == 1u ? y : z; }
 
 // what both kernels know of a cast's source brick: per lane, where its voxel stands at placement 0, whether it belongs to the piece, its key
@@ -56,8 +55,9 @@ struct CastView {
   }
   // the mask of the cell's brick `lane`, clipped to the sub-box
   __device__ __forceinline__ uint64_t clipped(const uint64_t* src_mask, uint32_t cell, uint32_t lane) const {
-    const int32_t x0 = (int32_t)((((cell >> 8) << 2) | (lane >> 4)) * 4u), y0 = (int32_t)(((((cell >> 4) & 15u) << 2) | ((lane >> 2) & 3u)) * 4u),
-                  z0 = (int32_t)((((cell & 15u) << 2) | (lane & 3u)) * 4u);
+    uint32_t bx, by, bz;
+    cell_brick(cell, lane, bx, by, bz);
+    const int32_t x0 = (int32_t)(bx * 4u), y0 = (int32_t)(by * 4u), z0 = (int32_t)(bz * 4u);  // the brick's first voxel
     uint64_t mx = 0, my = 0, mz = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -69,13 +69,14 @@ struct CastView {
   }
   // brick b (0..63, wave-uniform) of the cell, whose mask is bm: this lane's voxel
   __device__ __forceinline__ BrickView brick(uint32_t cell, uint32_t b, uint64_t bm, uint32_t lane, int32_t s0[3]) const {
-    s0[0] = (int32_t)((((cell >> 8) << 2) | (b >> 4)) * 4u);
-    s0[1] = (int32_t)(((((cell >> 4) & 15u) << 2) | ((b >> 2) & 3u)) * 4u);
-    s0[2] = (int32_t)((((cell & 15u) << 2) | (b & 3u)) * 4u);
-    const int32_t sx = s0[0] + (int32_t)(lane >> 4), sy = s0[1] + (int32_t)((lane >> 2) & 3u), sz = s0[2] + (int32_t)(lane & 3u);
+    uint32_t bx, by, bz;
+    cell_brick(cell, b, bx, by, bz);
+    const Voxel mine = brick_voxel(bx, by, bz, lane);
+    s0[0] = (int32_t)(bx * 4u); s0[1] = (int32_t)(by * 4u); s0[2] = (int32_t)(bz * 4u);
+    const int32_t sx = (int32_t)mine.x, sy = (int32_t)mine.y, sz = (int32_t)mine.z;
     BrickView v;
     v.solid = (bm >> lane) & 1ull;
-    v.key = ((uint32_t)sx << 16) | ((uint32_t)sy << 8) | (uint32_t)sz;
+    v.key = mine.key();
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       const int32_t sp = pick(sx, sy, sz, p[r]), lp = pick(lo[0], lo[1], lo[2], p[r]), hp = pick(hi[0], hi[1], hi[2], p[r]);
@@ -91,7 +92,7 @@ struct CastView {
     if (!v.solid) return false;
     if (!inside) return walls;
     const uint64_t w = dst_mask[leaf_code((uint32_t)dx >> 2, (uint32_t)dy >> 2, (uint32_t)dz >> 2)];  // (all three < 64: inside the lattice)
-    return (w >> ((((uint32_t)dx & 3u) << 4) | (((uint32_t)dy & 3u) << 2) | ((uint32_t)dz & 3u))) & 1ull;
+    return (w >> voxel_bit((uint32_t)dx, (uint32_t)dy, (uint32_t)dz)) & 1ull;
   }
 };
 

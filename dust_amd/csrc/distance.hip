@@ -16,7 +16,7 @@
 //                      wave vote. Values above the limit become FAR after every pass (a nearest target within R has every per-axis
 //                      offset within R). The last pass folds WALLS into its store
 //   k_distance_result  a wave per 16 bricks: ballots for the counts, one 64-bit maximum of value << 32 | (0xFFFFFF - key) per wave
-//   k_distance_lookup  a thread per coordinate;  k_distance_apply  a wave per 16 bricks: the grid bytes of the voxels in a value range
+// (dust_hip_model_distance_at and _distance_apply: field.hip)
 // A workgroup reads and writes only its own column, so nothing is ordered between workgroups: no fences, no spins, and everything is
 // integer -- two runs give the same bytes.
 #include <hip/hip_runtime.h>
@@ -26,6 +26,7 @@
 
 #include "distance.hpp"
 #include "edit.hpp"
+#include "field.hpp"
 
 namespace dust {
 
@@ -34,9 +35,6 @@ namespace {
 constexpr uint32_t kPad = 256;                 // FAR values on either side of a line in LDS: line[i +- k] needs no bounds check (k <= 255)
 constexpr uint32_t kStride = 256 + 2 * kPad + 4;  // uint16 per line; 386 dwords: the 16 lines of a brick row fall into 32 different banks
 constexpr uint32_t kNoBit = 1024;              // farther than any bit of a line
-
-__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 // brick b of the column (u, v) along `axis`: u, v are the brick coordinates on the other two axes, in x, y, z order
 __device__ __forceinline__ uint32_t column_brick(uint32_t axis, uint32_t b, uint32_t u, uint32_t v) {
@@ -47,9 +45,6 @@ __device__ __forceinline__ uint32_t bit_along(uint32_t axis, uint32_t bit) { ret
 __device__ __forceinline__ uint32_t bit_line(uint32_t axis, uint32_t bit) {
   const uint32_t s = 4u - 2u * axis;
   return ((bit >> (s + 2u)) << s) | (bit & ((1u << s) - 1u));
-}
-__device__ __forceinline__ uint32_t voxel_index(uint32_t x, uint32_t y, uint32_t z) {  // into the grid and the field
-  return leaf_code(x >> 2, y >> 2, z >> 2) * 64u + (((x & 3u) << 4) | ((y & 3u) << 2) | (z & 3u));
 }
 
 // the column's 64 brick rows, LDS -> field: wave w takes bricks w, w + 4, ...; lane = voxel bit
@@ -102,7 +97,7 @@ __global__ void __launch_bounds__(256) k_distance_bits(DistanceArgs a) {
       if (below != 0ull) d_lo = lane - 63u + (uint32_t)__builtin_clzll(below);
       if (above != 0ull) d_hi = (uint32_t)__builtin_ctzll(above);
       const uint32_t d = umin(d_lo, d_hi);
-      const uint32_t value = d > a.radius ? kDistanceFar : a.metric == kDistanceEuclidean ? d * d : d;
+      const uint32_t value = d > a.radius ? kFieldNone : a.metric == kDistanceEuclidean ? d * d : d;
       col[line * kStride + kPad + (uint32_t)p * 64u + lane] = (uint16_t)value;
     }
   }
@@ -117,7 +112,7 @@ __global__ void __launch_bounds__(256) k_distance_scan(DistanceArgs a, uint32_t 
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   for (uint32_t t = threadIdx.x; t < 16u * 2u * kPad; t += 256u) {  // the pads of the 16 lines
     const uint32_t r = t & (2u * kPad - 1u);
-    col[(t / (2u * kPad)) * kStride + (r < kPad ? r : r + 256u)] = (uint16_t)kDistanceFar;
+    col[(t / (2u * kPad)) * kStride + (r < kPad ? r : r + 256u)] = (uint16_t)kFieldNone;
   }
   {
     const uint32_t at = bit_line(axis, lane) * kStride + kPad + bit_along(axis, lane);
@@ -134,7 +129,7 @@ __global__ void __launch_bounds__(256) k_distance_scan(DistanceArgs a, uint32_t 
     uint32_t out[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) out[p] = line[(uint32_t)p * 64u + lane];
-    const bool finite = out[0] != kDistanceFar || out[1] != kDistanceFar || out[2] != kDistanceFar || out[3] != kDistanceFar;
+    const bool finite = out[0] != kFieldNone || out[1] != kFieldNone || out[2] != kFieldNone || out[3] != kFieldNone;
     if (__any(finite)) {  // (a line of FAR stays FAR)
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
@@ -152,7 +147,7 @@ __global__ void __launch_bounds__(256) k_distance_scan(DistanceArgs a, uint32_t 
             best = umin(best, umax(umin(at[-(int)k], at[k]), k));
           }
         }
-        out[p] = best > limit ? kDistanceFar : best;
+        out[p] = best > limit ? kFieldNone : best;
       }
     }
     if (last != 0u && a.walls != 0u) {
@@ -163,7 +158,7 @@ __global__ void __launch_bounds__(256) k_distance_scan(DistanceArgs a, uint32_t 
       for (int p = 0; p < 4; ++p) {
         const uint32_t i = (uint32_t)p * 64u + lane;
         const uint32_t w = umin(w12, umin(i + 1u, 256u - i));
-        const uint32_t value = w > radius ? kDistanceFar : a.metric == kDistanceEuclidean ? w * w : w;
+        const uint32_t value = w > radius ? kFieldNone : a.metric == kDistanceEuclidean ? w * w : w;
         out[p] = umin(out[p], value);
       }
     }
@@ -186,11 +181,9 @@ __global__ void __launch_bounds__(256) k_distance_result(DistanceArgs a) {
     const uint32_t code = blockIdx.x * 64u + wave * 16u + k;
     const uint32_t value = a.field[(size_t)code * 64u + lane];
     targets += (uint32_t)__popcll(__ballot(value == 0u));
-    far += (uint32_t)__popcll(__ballot(value == kDistanceFar));
-    if (value != kDistanceFar) {
-      uint32_t bx, by, bz;
-      leaf_decode(code, bx, by, bz);
-      const uint32_t key = ((bx * 4u + (lane >> 4)) << 16) | ((by * 4u + ((lane >> 2) & 3u)) << 8) | (bz * 4u + (lane & 3u));
+    far += (uint32_t)__popcll(__ballot(value == kFieldNone));
+    if (value != kFieldNone) {
+      const uint32_t key = code_voxel(code, lane).key();
       const unsigned long long packed = ((unsigned long long)value << 32) | (unsigned long long)(0xFFFFFFu - key);
       best = packed > best ? packed : best;
     }
@@ -214,26 +207,6 @@ __global__ void __launch_bounds__(256) k_distance_result(DistanceArgs a) {
   }
 }
 
-__global__ void __launch_bounds__(256) k_distance_lookup(const uint16_t* field, const uint32_t* xyz, uint16_t* values, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  values[i] = field[voxel_index(xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2])];  // (the host has checked the coordinates)
-}
-
-// a workgroup per root cell, a wave per 16 bricks
-__global__ void __launch_bounds__(256) k_distance_apply(DistanceApplyArgs a) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t n = 0;
-  for (uint32_t k = 0; k < 16u; ++k) {
-    const size_t at = ((size_t)blockIdx.x * 64u + wave * 16u + k) * 64u + lane;
-    const uint32_t value = a.field[at];
-    const bool differs = value != kDistanceFar && value >= a.lo && value <= a.hi && a.grid[at] != a.byte;
-    if (differs) a.grid[at] = (uint8_t)a.byte;
-    n += (uint32_t)__popcll(__ballot(differs));
-  }
-  if (n && lane == 0u) atomicAdd(a.changed, n);
-}
-
 // ------------------------------------------------------------------ launchers (capi_model.cpp)
 hipError_t launch_distance_field(const DistanceArgs& a, hipStream_t s) {
   const dim3 columns(64 * 64), cells(kLattice / 64), block(256);
@@ -241,14 +214,6 @@ hipError_t launch_distance_field(const DistanceArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_distance_scan, columns, block, 0, s, a, 1u, 0u);
   hipLaunchKernelGGL(k_distance_scan, columns, block, 0, s, a, 2u, 1u);
   hipLaunchKernelGGL(k_distance_result, cells, block, 0, s, a);
-  return hipGetLastError();
-}
-hipError_t launch_distance_lookup(const uint16_t* field, const uint32_t* xyz, uint16_t* values, uint32_t n, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_distance_lookup, dim3((n + 255u) / 256u), dim3(256), 0, s, field, xyz, values, n);
-  return hipGetLastError();
-}
-hipError_t launch_distance_apply(const DistanceApplyArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_distance_apply, dim3(kLattice / 64), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

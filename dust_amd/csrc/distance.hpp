@@ -7,7 +7,6 @@
 
 namespace dust {
 
-constexpr uint32_t kDistanceFar = 0xFFFFu;  // DUST_HIP_DISTANCE_FAR
 constexpr uint32_t kDistanceToSolid = 0, kDistanceToEmpty = 1, kDistanceToMaterial = 2;  // DUST_HIP_DISTANCE_TO_*
 constexpr uint32_t kDistanceEuclidean = 0, kDistanceChebyshev = 1;                       // DUST_HIP_DISTANCE_EUCLIDEAN, _CHEBYSHEV
 
@@ -30,16 +29,7 @@ struct DistanceArgs {
   DistanceAcc* acc;
 };
 
-struct DistanceApplyArgs {
-  uint8_t* grid;
-  const uint16_t* field;
-  uint32_t lo, hi, byte;  // every voxel with value != FAR and lo <= value <= hi takes the grid byte (0 = None)
-  uint32_t* changed;      // one word, zeroed by the caller
-};
-
 // the three passes (x, y, z) and the result reduction; afterwards a.field is complete and a.acc holds the counts
 hipError_t launch_distance_field(const DistanceArgs& a, hipStream_t s);
-hipError_t launch_distance_lookup(const uint16_t* field, const uint32_t* xyz, uint16_t* values, uint32_t n, hipStream_t s);
-hipError_t launch_distance_apply(const DistanceApplyArgs& a, hipStream_t s);
 
 }  // namespace dust

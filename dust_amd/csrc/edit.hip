@@ -9,7 +9,7 @@
 //   k_edit_shapes        (dust_hip_model_edit_shapes) boxes, spheres and capsules written into the grid, a wavefront per brick
 //   k_edit_brick_masks   one thread per 4^3 brick of the lattice: occupancy mask + voxel count, in both orders that matter
 //                        (iter_leaf order for block indices, the collector's block-major order for material_ptr)
-//   scan                 exclusive prefix sums of the two 262 144-entry tables
+//   scan                 exclusive prefix sums of the two 262 144-entry tables (scan.hpp: k_table_scan_local, k_table_scan_sums)
 //   k_edit_emit_blocks   Block records (position, mask, material_ptr, avg_albedo) + the compacted material stream
 //   k_edit_upper_levels  root mask / rank prefixes, mid nodes, dense_mask, tight bounds, counts (one workgroup)
 // The result is, array for array, what dust_hip_model_create builds on the host from the same voxels
@@ -23,7 +23,9 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "cell_records.hpp"
 #include "edit.hpp"
+#include "scan.hpp"
 
 namespace dust {
 
@@ -31,7 +33,7 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// (leaf_code / leaf_decode, the brick code in Tree::iter_leaf order: edit.hpp)
+// (leaf_code / leaf_decode, the brick code in Tree::iter_leaf order: grid.hpp)
 // collector.rs:25-27: block_index = bx + 64 by + 4096 bz -- the order the material stream is compacted in
 __device__ __forceinline__ uint32_t major_code(uint32_t bx, uint32_t by, uint32_t bz) { return bx + 64u * by + 4096u * bz; }
 
@@ -54,48 +56,32 @@ __global__ void k_edit_apply(EditArgs e) {
   if (i >= e.n_edits) return;
   const uint32_t x = e.xyz[i * 3], y = e.xyz[i * 3 + 1], z = e.xyz[i * 3 + 2];
   const int32_t v = e.values[i];
-  e.grid[(size_t)leaf_code(x >> 2, y >> 2, z >> 2) * 64 + (((x & 3u) << 4) | ((y & 3u) << 2) | (z & 3u))] = v < 0 ? 0u : (uint8_t)(v + 1);
+  e.grid[voxel_index(x, y, z)] = v < 0 ? 0u : (uint8_t)(v + 1);
 }
 // VoxGeometry::get
 __global__ void k_edit_read(EditArgs e) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= e.n_edits) return;
   const uint32_t x = e.xyz[i * 3], y = e.xyz[i * 3 + 1], z = e.xyz[i * 3 + 2];
-  e.values_out[i] = (int32_t)e.grid[(size_t)leaf_code(x >> 2, y >> 2, z >> 2) * 64 + (((x & 3u) << 4) | ((y & 3u) << 2) | (z & 3u))] - 1;
+  e.values_out[i] = (int32_t)e.grid[voxel_index(x, y, z)] - 1;
 }
 
-// dust_hip_model_edit_shapes: carve / fill / paint / place boxes, spheres and capsules straight into the grid. One workgroup per
-// root cell (16^3 voxels) that some shape's bounds reach, four waves of 16 bricks each: wave w owns the cell's child bits
-// 16 w .. 16 w + 15 (one x slice of bricks), lane = voxel bit x<<4 | y<<2 | z, so a brick's 64 grid bytes are one coalesced
-// load. A lane keeps its 16 voxels in registers and walks the cell's shape list ONCE, in call order; every shape record is
-// wave-uniform (loaded by a uniform index), rejected by its integer brick bounds before any per-voxel arithmetic, and
-// counted per wave: one ordinary vector atomic add of the ballots' popcounts (integer adds: the counts do not depend on
-// the order the waves arrive in). Bricks are written back once, and only those in which some lane changed.
-// Membership is the header's float32 contract, operation for operation (-ffp-contract=off; `/` is the IEEE division).
+// dust_hip_model_edit_shapes: carve / fill / paint / place boxes, spheres and capsules straight into the grid, on the skeleton of
+// cell_records.hpp: a workgroup per root cell that some shape's bounds reach, the cell's shape list walked once in call order. Every
+// shape record is wave-uniform and rejected by its integer brick bounds before any per-voxel arithmetic. Membership is the header's float32 contract, operation for operation (-ffp-contract=off; `/` is the IEEE division).
 namespace {
 __device__ __forceinline__ float dot3(float u0, float u1, float u2, float v0, float v1, float v2) { return (u0 * v0 + u1 * v1) + u2 * v2; }
 }  // namespace
 
 __global__ void __launch_bounds__(256) k_edit_shapes(EditShapeArgs a) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t cell = a.cells[blockIdx.x];
-  const uint32_t first = a.cell_start[blockIdx.x], last = a.cell_start[blockIdx.x + 1];
-  const uint32_t bx = ((cell >> 8) << 2) | wave, by0 = ((cell >> 4) & 15u) << 2, bz0 = (cell & 15u) << 2;  // brick coordinates
-  uint8_t* mine = a.grid + ((size_t)cell * 64u + wave * 16u) * 64u + lane;
-  // voxel centres: small integers + 0.5, exact in float32
-  const float cx = (float)(bx * 4u + (lane >> 4)) + 0.5f;
-  const float cy0 = (float)(by0 * 4u + ((lane >> 2) & 3u)) + 0.5f, cz0 = (float)(bz0 * 4u + (lane & 3u)) + 0.5f;
-  uint32_t v[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) v[k] = mine[k * 64];
-  uint32_t dirty = 0;
-  for (uint32_t j = first; j < last; ++j) {
-    const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.ids[j]);
+  walk_cell_records(a, [&](CellBricks& c, uint32_t id) -> uint32_t {
     const DevEditShape s = a.shapes[id];
     const uint32_t lo_x = (s.lo & 255u) >> 2, lo_y = ((s.lo >> 8) & 255u) >> 2, lo_z = (s.lo >> 16) >> 2;
     const uint32_t hi_x = (s.hi & 255u) >> 2, hi_y = ((s.hi >> 8) & 255u) >> 2, hi_z = (s.hi >> 16) >> 2;
-    if (bx < lo_x || bx > hi_x) continue;
+    if (c.bx < lo_x || c.bx > hi_x) return 0u;
+    // voxel centres: small integers + 0.5, exact in float32
+    const Voxel p = brick_voxel(c.bx, c.by0, c.bz0, c.lane);
+    const float cx = (float)p.x + 0.5f, cy0 = (float)p.y + 0.5f, cz0 = (float)p.z + 0.5f;
     const float rr = s.radius * s.radius;
     const float ab0 = s.b[0] - s.a[0], ab1 = s.b[1] - s.a[1], ab2 = s.b[2] - s.a[2];
     const float l = dot3(ab0, ab1, ab2, ab0, ab1, ab2);
@@ -103,7 +89,7 @@ __global__ void __launch_bounds__(256) k_edit_shapes(EditShapeArgs a) {
     uint32_t n = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      const uint32_t by = by0 + (uint32_t)(k >> 2), bz = bz0 + (uint32_t)(k & 3);
+      const uint32_t by = c.by0 + (uint32_t)(k >> 2), bz = c.bz0 + (uint32_t)(k & 3);
       if (by < lo_y || by > hi_y || bz < lo_z || bz > hi_z) continue;
       const float cy = cy0 + (float)((k >> 2) * 4), cz = cz0 + (float)((k & 3) * 4);  // exact
       bool in;
@@ -119,19 +105,12 @@ __global__ void __launch_bounds__(256) k_edit_shapes(EditShapeArgs a) {
           in = dot3(q0, q1, q2, q0, q1, q2) <= rr;
         }
       }
-      const uint32_t g = v[k];
+      const uint32_t g = c.v[k];
       const uint32_t to = g ? (s.solid_to == kEditKeep ? g : s.solid_to) : s.empty_to;
-      const bool differs = in && to != g;
-      const uint64_t m = __ballot(differs);
-      if (differs) v[k] = to;
-      n += (uint32_t)__popcll(m);
-      dirty |= (m != 0ull ? 1u : 0u) << k;
+      n += c.set(k, in && to != g, to);
     }
-    if (n && lane == 0) atomicAdd(&a.changed[id], n);
-  }
-#pragma unroll
-  for (int k = 0; k < 16; ++k)
-    if ((dirty >> k) & 1u) mine[k * 64] = (uint8_t)v[k];
+    return n;
+  });
 }
 
 __global__ void __launch_bounds__(256) k_edit_brick_masks(EditArgs e) {
@@ -153,44 +132,23 @@ __global__ void __launch_bounds__(256) k_edit_brick_masks(EditArgs e) {
   e.count_major[major_code(bx, by, bz)] = (uint32_t)__popcll(mask);
 }
 
-// exclusive scan of kLattice counters, 1024 per workgroup: (1) local scan + block sum, (2) scan of the 256 sums, (3) add back.
-// `which`: 0 = flag_leaf, 1 = count_major
-__global__ void __launch_bounds__(256) k_edit_scan_local(EditArgs e) {
+// the exclusive scan of scan.hpp: (1) local scan of 1024 entries per workgroup + block sum, (2) scan of a table's 256 sums
+__global__ void __launch_bounds__(256) k_table_scan_local(TableScan t) {
   __shared__ uint32_t sums[256];
-  const uint32_t which = blockIdx.y;
-  uint32_t* v = which ? e.count_major : e.flag_leaf;
+  uint32_t* v = t.table[blockIdx.y];
   const uint32_t base = blockIdx.x * 1024u + threadIdx.x * 4u;
   const uint32_t a0 = v[base], a1 = v[base + 1], a2 = v[base + 2], a3 = v[base + 3];
   const uint32_t s = a0 + a1 + a2 + a3;
-  sums[threadIdx.x] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256u; d <<= 1) {
-    const uint32_t x = threadIdx.x >= d ? sums[threadIdx.x - d] : 0u;
-    __syncthreads();
-    sums[threadIdx.x] += x;
-    __syncthreads();
-  }
-  const uint32_t before = sums[threadIdx.x] - s;
+  const uint32_t before = block_scan_inclusive<256>(sums, s) - s;
   v[base] = before; v[base + 1] = before + a0; v[base + 2] = before + a0 + a1; v[base + 3] = before + a0 + a1 + a2;
-  if (threadIdx.x == 255) e.scan_tmp[which * 256 + blockIdx.x] = sums[255];
+  if (threadIdx.x == 255) t.tmp[blockIdx.y * 256 + blockIdx.x] = sums[255];
 }
-__global__ void __launch_bounds__(256) k_edit_scan_sums(EditArgs e) {
+__global__ void __launch_bounds__(256) k_table_scan_sums(TableScan t) {
   __shared__ uint32_t sums[256];
-  uint32_t* t = e.scan_tmp + blockIdx.x * 256;
-  const uint32_t s = t[threadIdx.x];
-  sums[threadIdx.x] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256u; d <<= 1) {
-    const uint32_t x = threadIdx.x >= d ? sums[threadIdx.x - d] : 0u;
-    __syncthreads();
-    sums[threadIdx.x] += x;
-    __syncthreads();
-  }
-  t[threadIdx.x] = sums[threadIdx.x] - s;
-  if (threadIdx.x == 255) {
-    if (blockIdx.x == 0) e.header->n_blocks = sums[255];
-    else e.header->n_materials = sums[255];
-  }
+  uint32_t* b = t.tmp + blockIdx.x * 256;
+  const uint32_t s = b[threadIdx.x];
+  b[threadIdx.x] = block_scan_inclusive<256>(sums, s) - s;
+  if (threadIdx.x == 255) *t.total[blockIdx.x] = sums[255];
 }
 
 // Block records + material stream (geometry.rs:68-128, collector.rs:50-60): one thread per brick of the lattice
@@ -249,15 +207,7 @@ __global__ void __launch_bounds__(1024) k_edit_upper_levels(EditArgs e) {
       }
     }
   }
-  part[threadIdx.x] = mine;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024u; d <<= 1) {
-    const uint32_t x = threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += x;
-    __syncthreads();
-  }
-  uint32_t mi = part[threadIdx.x] - mine;  // mid nodes are stored in root-child order == depth first
+  uint32_t mi = block_scan_inclusive<1024>(part, mine) - mine;  // mid nodes are stored in root-child order == depth first
   for (int k = 0; k < 4; ++k) {
     if (!child[k]) continue;
     const uint32_t cell = threadIdx.x * 4u + k;
@@ -299,10 +249,15 @@ hipError_t launch_edit_shapes(const EditShapeArgs& a, hipStream_t s) {
   if (a.n_cells) hipLaunchKernelGGL(k_edit_shapes, dim3(a.n_cells), dim3(256), 0, s, a);
   return hipGetLastError();
 }
+hipError_t launch_table_scan(const TableScan& t, uint32_t n_tables, hipStream_t s) {
+  hipLaunchKernelGGL(k_table_scan_local, dim3(kLattice / 1024, n_tables), dim3(256), 0, s, t);
+  hipLaunchKernelGGL(k_table_scan_sums, dim3(n_tables), dim3(256), 0, s, t);
+  return hipGetLastError();
+}
 hipError_t launch_edit_rebuild(const EditArgs& e, hipStream_t s) {
   hipLaunchKernelGGL(k_edit_brick_masks, dim3(kLattice / 256), dim3(256), 0, s, e);
-  hipLaunchKernelGGL(k_edit_scan_local, dim3(256, 2), dim3(256), 0, s, e);
-  hipLaunchKernelGGL(k_edit_scan_sums, dim3(2), dim3(256), 0, s, e);
+  const hipError_t err = launch_table_scan(TableScan{{e.flag_leaf, e.count_major}, {&e.header->n_blocks, &e.header->n_materials}, e.scan_tmp}, 2, s);
+  if (err != hipSuccess) return err;
   hipLaunchKernelGGL(k_edit_emit_blocks, dim3(kLattice / 256), dim3(256), 0, s, e);
   hipLaunchKernelGGL(k_edit_upper_levels, dim3(1), dim3(1024), 0, s, e);
   return hipGetLastError();

@@ -6,28 +6,15 @@
 #include <cstdint>
 
 #include "dust_dev.h"
+#include "grid.hpp"  // the grid's brick order (leaf_code, kLattice): every kernel file of the model calls reads it from there
 
 namespace dust {
 
-constexpr uint32_t kLattice = 64 * 64 * 64;  // bricks of a 256^3 model
 constexpr uint32_t kSrgbRow = 64 * 255 + 1;  // colour sums 0 .. 64 * 255 per voxel count
-
-// the grid's brick order, shared by edit.hip and island.hip
-// brick code in Tree::iter_leaf order: root child index (x>>4)<<8 | (y>>4)<<4 | (z>>4) (node/internal.rs:78-81), then the
-// mid node's child bit ((x>>2)&3)<<4 | ((y>>2)&3)<<2 | ((z>>2)&3); bx, by, bz are brick coordinates (voxel >> 2)
-__device__ __forceinline__ uint32_t leaf_code(uint32_t bx, uint32_t by, uint32_t bz) {
-  return ((((bx >> 2) << 8) | ((by >> 2) << 4) | (bz >> 2)) << 6) | ((bx & 3u) << 4) | ((by & 3u) << 2) | (bz & 3u);
-}
-__device__ __forceinline__ void leaf_decode(uint32_t code, uint32_t& bx, uint32_t& by, uint32_t& bz) {
-  const uint32_t r = code >> 6, c = code & 63u;
-  bx = ((r >> 8) << 2) | (c >> 4);
-  by = (((r >> 4) & 15u) << 2) | ((c >> 2) & 3u);
-  bz = ((r & 15u) << 2) | (c & 3u);
-}
 
 struct EditHeader {  // what the host reads back after a rebuild
   uint32_t n_blocks, n_mid;
-  unsigned long long n_materials;
+  uint32_t n_materials, pad;  // (at most 2^24: a byte per voxel)
   float bmin[3], bmax[3];
 };
 

@@ -11,8 +11,7 @@
 //                   that changed is written back, and for every face on which some lane's value dropped below what the facing voxel
 //                   could make of its own the neighbour brick is put on the NEXT pass's worklist (a flag per brick keeps it there once; the list's length is one atomic counter)
 //   k_flood_result  a workgroup per root cell of the region: count, maximum, zeros, region-face count and bounds of the reached voxels
-//   k_flood_lookup  a thread per coordinate;  k_flood_paths  a thread per start, descending the field;  k_flood_apply  a wavefront per
-//                   16 bricks of the root cells that hold reached voxels: the grid bytes of the voxels within max_steps
+//   k_flood_paths   a thread per start, descending the field  (dust_hip_model_flood_at and _flood_apply: field.hip)
 // A pass is one launch; the host launches passes until one leaves an empty worklist (capi_model.cpp). An empty pass exits at once, and
 // work per pass follows the listed bricks, not the lattice.
 //
@@ -27,6 +26,7 @@
 #include <cstdint>
 
 #include "edit.hpp"
+#include "field.hpp"
 #include "flood.hpp"
 
 namespace dust {
@@ -39,14 +39,14 @@ __device__ __forceinline__ bool passable(const FloodArgs& a, uint32_t g, uint32_
   const bool medium = a.medium == kEmptyMedium ? g == 0u : a.medium == kSolidMedium ? g != 0u : g == a.byte;
   return medium && x >= a.lo[0] && x <= a.hi[0] && y >= a.lo[1] && y <= a.hi[1] && z >= a.lo[2] && z <= a.hi[2];
 }
-__device__ __forceinline__ uint32_t voxel_index(uint32_t x, uint32_t y, uint32_t z) {  // into the grid and the field
-  return leaf_code(x >> 2, y >> 2, z >> 2) * 64u + (((x & 3u) << 4) | ((y & 3u) << 2) | (z & 3u));
+// the root cells the region reaches
+__host__ __device__ inline CellBox region_cells(const FloodArgs& a) {
+  return {{a.lo[0] >> 4, a.lo[1] >> 4, a.lo[2] >> 4}, {a.hi[0] >> 4, a.hi[1] >> 4, a.hi[2] >> 4}};
 }
 // put brick `code` on a worklist unless it is there already (at most kLattice entries: one per flag)
 __device__ __forceinline__ void wake(uint32_t* flag, uint32_t* list, uint32_t* count, uint32_t code) {
   if (atomicExch(flag + code, 1u) == 0u) list[atomicAdd(count, 1u)] = code;
 }
-__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 }  // namespace
 
@@ -62,22 +62,24 @@ __global__ void __launch_bounds__(256) k_flood_seed(FloodArgs a) {
 
 __global__ void __launch_bounds__(256) k_flood_relax(FloodArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  const uint32_t wave = uniform(blockIdx.x * 4u + (threadIdx.x >> 6));
   const uint32_t n_waves = gridDim.x * 4u;
   if (wave == 0u && lane == 0u) *a.zero_count = 0u;  // (nobody reads or appends to that one during this pass)
   const uint32_t n = *a.count;
-  const uint32_t lx = lane >> 4, ly = (lane >> 2) & 3u, lz = lane & 3u;
+  const Voxel in_brick = brick_voxel(0u, 0u, 0u, lane);
+  const uint32_t lx = in_brick.x, ly = in_brick.y, lz = in_brick.z;
   for (uint32_t i = wave; i < n; i += n_waves) {
-    const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.list[i]);
+    const uint32_t code = uniform(a.list[i]);
     if (lane == 0u) a.flag[code] = 0u;  // (this pass wakes bricks on the OTHER flag array)
     uint32_t bx, by, bz;
     leaf_decode(code, bx, by, bz);
     const size_t at = (size_t)code * 64u + lane;
-    const bool open = passable(a, a.grid[at], bx * 4u + lx, by * 4u + ly, bz * 4u + lz);
-    const uint32_t v0 = open ? (uint32_t)a.field[at] : kFloodUnreached;
+    const Voxel p = brick_voxel(bx, by, bz, lane);
+    const bool open = passable(a, a.grid[at], p.x, p.y, p.z);
+    const uint32_t v0 = open ? (uint32_t)a.field[at] : kFieldNone;
     // the facing voxels of the neighbour bricks, once (a stale value is harmless: see the head of the file). An impassable voxel holds
-    // kFloodUnreached, so its passability need not be looked at
-    uint32_t ext_x = kFloodUnreached, ext_y = kFloodUnreached, ext_z = kFloodUnreached;  // (a lane has at most one such neighbour per axis)
+    // kFieldNone, so its passability need not be looked at
+    uint32_t ext_x = kFieldNone, ext_y = kFieldNone, ext_z = kFieldNone;  // (a lane has at most one such neighbour per axis)
     if (open) {
       if (lx == 0u && bx > 0u) ext_x = a.field[(size_t)leaf_code(bx - 1u, by, bz) * 64u + lane + 48u];
       if (lx == 3u && bx < 63u) ext_x = a.field[(size_t)leaf_code(bx + 1u, by, bz) * 64u + lane - 48u];
@@ -88,10 +90,10 @@ __global__ void __launch_bounds__(256) k_flood_relax(FloodArgs a) {
     }
     const uint32_t ext = umin(ext_x, umin(ext_y, ext_z));
     uint32_t v = v0;
-    if (open && ext + 1u <= a.max_steps) v = umin(v, ext + 1u);  // (kFloodUnreached + 1 is above every max_steps)
+    if (open && ext + 1u <= a.max_steps) v = umin(v, ext + 1u);  // (kFieldNone + 1 is above every max_steps)
     // an entry from outside and at most 63 edges inside: after 63 rounds every lane is final, the 64th only confirms it
     for (int round = 0; round < 64; ++round) {
-      uint32_t m = kFloodUnreached;
+      uint32_t m = kFieldNone;
       const uint32_t zm = (uint32_t)__shfl((int)v, (int)((lane - 1u) & 63u)), zp = (uint32_t)__shfl((int)v, (int)((lane + 1u) & 63u));
       const uint32_t ym = (uint32_t)__shfl((int)v, (int)((lane - 4u) & 63u)), yp = (uint32_t)__shfl((int)v, (int)((lane + 4u) & 63u));
       const uint32_t xm = (uint32_t)__shfl((int)v, (int)((lane - 16u) & 63u)), xp = (uint32_t)__shfl((int)v, (int)((lane + 16u) & 63u));
@@ -109,8 +111,8 @@ __global__ void __launch_bounds__(256) k_flood_relax(FloodArgs a) {
     if (dropped) a.field[at] = (uint16_t)v;
     // Whom to wake: the brick behind a face on which some lane's value dropped AND would lower the facing voxel as it was read above.
     // (That read may be stale, but the voxel's value only decreases: if v + 1 does not beat what was read, it does not beat what is
-    // there now. A facing voxel that is impassable reads kFloodUnreached and wakes its brick for nothing, once.)
-    const bool news = (dropped || (a.first != 0u && v != kFloodUnreached)) && v + 1u <= a.max_steps;
+    // there now. A facing voxel that is impassable reads kFieldNone and wakes its brick for nothing, once.)
+    const bool news = (dropped || (a.first != 0u && v != kFieldNone)) && v + 1u <= a.max_steps;
     const uint64_t news_x = __ballot(news && v + 1u < ext_x), news_y = __ballot(news && v + 1u < ext_y), news_z = __ballot(news && v + 1u < ext_z);
     if ((news_x | news_y | news_z) != 0ull && lane < 6u) {  // lane f looks after face f: -x, +x, -y, +y, -z, +z
       const uint64_t x_face = 0xFFFFull, y_face = 0x000F000F000F000Full, z_face = 0x1111111111111111ull;
@@ -133,18 +135,15 @@ __global__ void __launch_bounds__(256) k_flood_result(FloodArgs a) {
   __shared__ uint32_t sum[kFloodAccWords];
   if (threadIdx.x < kFloodAccWords) sum[threadIdx.x] = 0u;
   __syncthreads();
-  const uint32_t c_lo[3] = {a.lo[0] >> 4, a.lo[1] >> 4, a.lo[2] >> 4}, c_n[2] = {(a.hi[1] >> 4) - c_lo[1] + 1u, (a.hi[2] >> 4) - c_lo[2] + 1u};
-  const uint32_t cx = c_lo[0] + blockIdx.x / (c_n[0] * c_n[1]), cy = c_lo[1] + (blockIdx.x / c_n[1]) % c_n[0], cz = c_lo[2] + blockIdx.x % c_n[1];
-  const uint32_t cell = (cx << 8) | (cy << 4) | cz;
+  const uint32_t cell = region_cells(a).cell(blockIdx.x);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint32_t reached = 0, farthest = 0, zeros = 0, boundary = 0, inv_lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
   for (uint32_t k = 0; k < 16u; ++k) {
     const uint32_t code = cell * 64u + wave * 16u + k;
     const uint32_t v = a.field[(size_t)code * 64u + lane];
-    if (v == kFloodUnreached) continue;
-    uint32_t bx, by, bz;
-    leaf_decode(code, bx, by, bz);
-    const uint32_t p[3] = {bx * 4u + (lane >> 4), by * 4u + ((lane >> 2) & 3u), bz * 4u + (lane & 3u)};
+    if (v == kFieldNone) continue;
+    const Voxel at = code_voxel(code, lane);
+    const uint32_t p[3] = {at.x, at.y, at.z};
     reached += 1u;
     farthest = v > farthest ? v : farthest;
     zeros += v == 0u ? 1u : 0u;
@@ -168,24 +167,18 @@ __global__ void __launch_bounds__(256) k_flood_result(FloodArgs a) {
   else if (threadIdx.x < 10u) atomicMax(&a.acc[threadIdx.x], sum[threadIdx.x]);                                      // the order does not matter
 }
 
-__global__ void __launch_bounds__(256) k_flood_lookup(const uint16_t* field, const uint32_t* xyz, uint16_t* steps, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  steps[i] = field[voxel_index(xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2])];  // (the host has checked the coordinates)
-}
-
 // a thread per start: the first neighbour one step closer, in the order -x, +x, -y, +y, -z, +z, until a seed or the capacity
 __global__ void __launch_bounds__(256) k_flood_paths(const uint16_t* field, const uint32_t* starts, uint32_t n, uint32_t capacity, uint32_t* keys, uint32_t* lengths) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   uint32_t x = starts[i * 3], y = starts[i * 3 + 1], z = starts[i * 3 + 2];  // (the host has checked the coordinates)
   uint32_t d = field[voxel_index(x, y, z)];
-  lengths[i] = d == kFloodUnreached ? 0u : d + 1u;
-  if (d == kFloodUnreached) return;
+  lengths[i] = d == kFieldNone ? 0u : d + 1u;
+  if (d == kFieldNone) return;
   const uint32_t count = d + 1u < capacity ? d + 1u : capacity;
   uint32_t* out = keys + (size_t)i * capacity;
   for (uint32_t k = 0; k < count; ++k) {
-    out[k] = (x << 16) | (y << 8) | z;
+    out[k] = Voxel{x, y, z}.key();
     if (k + 1u == count) break;
     const uint32_t want = d - 1u;  // (d >= 1 here: k + 1 < count <= d + 1)
     if (x > 0u && field[voxel_index(x - 1u, y, z)] == want) x -= 1u;
@@ -199,32 +192,7 @@ __global__ void __launch_bounds__(256) k_flood_paths(const uint16_t* field, cons
   }
 }
 
-// a workgroup per root cell of the reached voxels' cell box, a wave per 16 bricks
-__global__ void __launch_bounds__(256) k_flood_apply(FloodApplyArgs a) {
-  const uint32_t c_lo[3] = {a.lo[0] >> 4, a.lo[1] >> 4, a.lo[2] >> 4}, c_n[2] = {(a.hi[1] >> 4) - c_lo[1] + 1u, (a.hi[2] >> 4) - c_lo[2] + 1u};
-  const uint32_t cx = c_lo[0] + blockIdx.x / (c_n[0] * c_n[1]), cy = c_lo[1] + (blockIdx.x / c_n[1]) % c_n[0], cz = c_lo[2] + blockIdx.x % c_n[1];
-  const uint32_t cell = (cx << 8) | (cy << 4) | cz;
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t n = 0;
-  for (uint32_t k = 0; k < 16u; ++k) {
-    const size_t at = ((size_t)cell * 64u + wave * 16u + k) * 64u + lane;
-    const uint32_t v = a.field[at];
-    const bool differs = v != kFloodUnreached && v <= a.max_steps && a.grid[at] != a.byte;
-    if (differs) a.grid[at] = (uint8_t)a.byte;
-    n += (uint32_t)__popcll(__ballot(differs));
-  }
-  if (n && lane == 0u) atomicAdd(a.changed, n);
-}
-
 // ------------------------------------------------------------------ launchers (capi_model.cpp)
-namespace {
-uint32_t cell_count(const uint32_t lo[3], const uint32_t hi[3]) {
-  uint32_t n = 1;
-  for (int r = 0; r < 3; ++r) n *= (hi[r] >> 4) - (lo[r] >> 4) + 1u;
-  return n;
-}
-}  // namespace
-
 hipError_t launch_flood_seed(const FloodArgs& a, hipStream_t s) {
   hipError_t e = hipMemsetAsync(a.field, 0xFF, (size_t)kLattice * 64u * 2u, s);
   if (e != hipSuccess) return e;
@@ -236,19 +204,11 @@ hipError_t launch_flood_relax(const FloodArgs& a, uint32_t workgroups, hipStream
   return hipGetLastError();
 }
 hipError_t launch_flood_result(const FloodArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_flood_result, dim3(cell_count(a.lo, a.hi)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-hipError_t launch_flood_lookup(const uint16_t* field, const uint32_t* xyz, uint16_t* steps, uint32_t n, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_flood_lookup, dim3((n + 255u) / 256u), dim3(256), 0, s, field, xyz, steps, n);
+  hipLaunchKernelGGL(k_flood_result, dim3(region_cells(a).count()), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_flood_paths(const uint16_t* field, const uint32_t* starts, uint32_t n, uint32_t capacity, uint32_t* keys, uint32_t* lengths, hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_flood_paths, dim3((n + 255u) / 256u), dim3(256), 0, s, field, starts, n, capacity, keys, lengths);
-  return hipGetLastError();
-}
-hipError_t launch_flood_apply(const FloodApplyArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_flood_apply, dim3(cell_count(a.lo, a.hi)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -7,7 +7,6 @@
 
 namespace dust {
 
-constexpr uint32_t kFloodUnreached = 0xFFFFu;  // DUST_HIP_FLOOD_UNREACHED
 constexpr uint32_t kFloodBatch = 8;            // relaxation passes launched per read-back of the worklist's length
 
 // the context's flood scratch, in 32-bit words (L = kLattice): two flag arrays and two worklists that take turns, three worklist lengths
@@ -38,21 +37,11 @@ struct FloodArgs {
   uint32_t* acc;          // kFloodAccWords, zeroed by the caller
 };
 
-struct FloodApplyArgs {
-  uint8_t* grid;
-  const uint16_t* field;
-  uint32_t max_steps, byte;  // every voxel with steps <= max_steps takes the grid byte (0 = None)
-  uint32_t lo[3], hi[3];     // the bounds of the reached voxels
-  uint32_t* changed;         // one word, zeroed by the caller
-};
-
 // memset + seeds: afterwards list 0 names the seeded bricks (the scratch's flags and counts zeroed by the caller)
 hipError_t launch_flood_seed(const FloodArgs& a, hipStream_t s);
 // one relaxation pass over a.list with `workgroups` workgroups (any number >= 1 is correct: the list is walked with a stride)
 hipError_t launch_flood_relax(const FloodArgs& a, uint32_t workgroups, hipStream_t s);
 hipError_t launch_flood_result(const FloodArgs& a, hipStream_t s);
-hipError_t launch_flood_lookup(const uint16_t* field, const uint32_t* xyz, uint16_t* steps, uint32_t n, hipStream_t s);
 hipError_t launch_flood_paths(const uint16_t* field, const uint32_t* starts, uint32_t n, uint32_t capacity, uint32_t* keys, uint32_t* lengths, hipStream_t s);
-hipError_t launch_flood_apply(const FloodApplyArgs& a, hipStream_t s);
 
 }  // namespace dust

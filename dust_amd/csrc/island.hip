@@ -9,7 +9,7 @@
 //   k_island_join     a wavefront per brick: every voxel pair across a brick boundary (the "forward" half of the 6 or 26 directions)
 //                     is united in a lock-free union-find on the labels -- atomicMin only, a parent is always a smaller key
 //   k_island_flatten  a thread per key: label = root; the roots of 64 consecutive keys are one ballot (root_mask, root_count)
-//   scan              exclusive prefix sums of the 262 144 root counts: an island's rank in key order, and the number of islands
+//   scan              (scan.hpp) exclusive prefix sums of the 262 144 root counts: an island's rank in key order, and the number of islands
 //   k_island_stats    a wavefront per 16 rows of 64 keys: voxels that share an island are reduced in the wave (one x, one y, z = lane)
 //                     and across its rows before one lane adds them to the island's accumulator with integer atomics
 //   k_island_emit     accumulator -> the 40-byte record
@@ -22,15 +22,11 @@
 
 #include "edit.hpp"
 #include "island.hpp"
+#include "scan.hpp"
 
 namespace dust {
 
 namespace {
-
-// key of the voxel `bit` of brick (bx, by, bz)
-__device__ __forceinline__ uint32_t voxel_key(uint32_t bx, uint32_t by, uint32_t bz, uint32_t bit) {
-  return ((bx * 4u + (bit >> 4)) << 16) | ((by * 4u + ((bit >> 2) & 3u)) << 8) | (bz * 4u + (bit & 3u));
-}
 
 constexpr uint64_t kZ0 = 0x1111111111111111ull, kZ3 = 0x8888888888888888ull;  // voxel bits with z == 0 / z == 3
 constexpr uint64_t kY0 = 0x000F000F000F000Full, kY3 = 0xF000F000F000F000ull;  // ... y == 0 / y == 3
@@ -113,7 +109,7 @@ __global__ void __launch_bounds__(256) k_island_join(IslandArgs a) {
     const bool inside = (unsigned)nx < 256u && (unsigned)ny < 256u && (unsigned)nz < 256u;
     const bool other_brick = (nx >> 2) != (x >> 2) || (ny >> 2) != (y >> 2) || (nz >> 2) != (z >> 2);  // (the same brick is k_island_local's)
     uint32_t theirs = kNoIsland;
-    if (mine != kNoIsland && inside && other_brick) theirs = a.label[((uint32_t)nx << 16) | ((uint32_t)ny << 8) | (uint32_t)nz];
+    if (mine != kNoIsland && inside && other_brick) theirs = a.label[Voxel{(uint32_t)nx, (uint32_t)ny, (uint32_t)nz}.key()];
     bool todo = theirs != kNoIsland;
     // lanes that would unite the same two brick components (a whole face of a solid brick) leave it to the lowest of them
     const unsigned long long pair = ((unsigned long long)mine << 32) | theirs;
@@ -144,40 +140,6 @@ __global__ void __launch_bounds__(256) k_island_flatten(IslandArgs a) {
     a.root_mask[key >> 6] = m;
     a.root_count[key >> 6] = (uint32_t)__popcll(m);
   }
-}
-
-// exclusive scan of the kIslandRows root counts, 1024 per workgroup (edit.hip's scheme): local scan + block sums, then the 256 sums
-__global__ void __launch_bounds__(256) k_island_scan_local(IslandArgs a) {
-  __shared__ uint32_t sums[256];
-  uint32_t* v = a.root_count;
-  const uint32_t base = blockIdx.x * 1024u + threadIdx.x * 4u;
-  const uint32_t a0 = v[base], a1 = v[base + 1], a2 = v[base + 2], a3 = v[base + 3];
-  const uint32_t s = a0 + a1 + a2 + a3;
-  sums[threadIdx.x] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256u; d <<= 1) {
-    const uint32_t x = threadIdx.x >= d ? sums[threadIdx.x - d] : 0u;
-    __syncthreads();
-    sums[threadIdx.x] += x;
-    __syncthreads();
-  }
-  const uint32_t before = sums[threadIdx.x] - s;
-  v[base] = before; v[base + 1] = before + a0; v[base + 2] = before + a0 + a1; v[base + 3] = before + a0 + a1 + a2;
-  if (threadIdx.x == 255) a.scan_tmp[blockIdx.x] = sums[255];
-}
-__global__ void __launch_bounds__(256) k_island_scan_sums(IslandArgs a) {
-  __shared__ uint32_t sums[256];
-  const uint32_t s = a.scan_tmp[threadIdx.x];
-  sums[threadIdx.x] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256u; d <<= 1) {
-    const uint32_t x = threadIdx.x >= d ? sums[threadIdx.x - d] : 0u;
-    __syncthreads();
-    sums[threadIdx.x] += x;
-    __syncthreads();
-  }
-  a.scan_tmp[threadIdx.x] = sums[threadIdx.x] - s;
-  if (threadIdx.x == 255) a.scan_tmp[256] = sums[255];
 }
 
 namespace {
@@ -213,7 +175,7 @@ constexpr uint32_t kStatsRows = 16;  // rows of 64 keys per wave: four y values,
 
 __global__ void __launch_bounds__(256) k_island_stats(IslandArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  const uint32_t wave = uniform(blockIdx.x * 4u + (threadIdx.x >> 6));
   Held h{};
   for (uint32_t k = 0; k < kStatsRows; ++k) {
     const uint32_t row = wave * kStatsRows + k;  // x << 10 | y << 2 | z >> 6
@@ -256,12 +218,6 @@ __global__ void __launch_bounds__(256) k_island_emit(IslandArgs a) {
   a.records[i] = r;
 }
 
-__global__ void __launch_bounds__(256) k_island_lookup(const uint32_t* label, const uint32_t* xyz, uint32_t* keys, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  keys[i] = label[(xyz[i * 3] << 16) | (xyz[i * 3 + 1] << 8) | xyz[i * 3 + 2]];  // (the host has checked the coordinates)
-}
-
 __global__ void __launch_bounds__(256) k_island_select(const uint32_t* label, const uint32_t* keys, uint32_t n, uint64_t* selected, uint32_t* bad) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
@@ -300,18 +256,13 @@ hipError_t launch_island_label(const IslandArgs& a, bool relabel, hipStream_t s)
     hipLaunchKernelGGL(k_island_join, dim3(kLattice / 4), dim3(256), 0, s, a);
   }
   hipLaunchKernelGGL(k_island_flatten, dim3(kIslandKeys / 256), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_island_scan_local, dim3(kIslandRows / 1024), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_island_scan_sums, dim3(1), dim3(256), 0, s, a);
-  return hipGetLastError();
+  static_assert(kIslandRows == kLattice, "the root counts are a table of scan.hpp");
+  return launch_table_scan(TableScan{{a.root_count, nullptr}, {a.scan_tmp + 256, nullptr}, a.scan_tmp}, 1, s);
 }
 hipError_t launch_island_records(const IslandArgs& a, hipStream_t s) {
   if (a.capacity == 0) return hipSuccess;
   hipLaunchKernelGGL(k_island_stats, dim3(kIslandRows / kStatsRows / 4), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_island_emit, dim3((a.capacity + 255u) / 256u), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-hipError_t launch_island_lookup(const uint32_t* label, const uint32_t* xyz, uint32_t* keys, uint32_t n, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_island_lookup, dim3((n + 255u) / 256u), dim3(256), 0, s, label, xyz, keys, n);
   return hipGetLastError();
 }
 hipError_t launch_island_select(const uint32_t* label, const uint32_t* keys, uint32_t n, uint64_t* selected, uint32_t* bad, hipStream_t s) {

@@ -53,8 +53,7 @@ struct IslandDetachArgs {
 hipError_t launch_island_label(const IslandArgs& a, bool relabel, hipStream_t s);
 // the first a.capacity records in key order (a.acc zeroed by the caller)
 hipError_t launch_island_records(const IslandArgs& a, hipStream_t s);
-// keys[i] = label of voxel xyz[3 i ..]
-hipError_t launch_island_lookup(const uint32_t* label, const uint32_t* xyz, uint32_t* keys, uint32_t n, hipStream_t s);
+// (dust_hip_model_island_of: the lookup of field.hpp, by key)
 // selected (zeroed by the caller) gets a bit per key that names an island; *bad counts the keys that do not (zeroed by the caller)
 hipError_t launch_island_select(const uint32_t* label, const uint32_t* keys, uint32_t n, uint64_t* selected, uint32_t* bad, hipStream_t s);
 hipError_t launch_island_detach(const IslandDetachArgs& a, hipStream_t s);

@@ -131,7 +131,7 @@ def test_set_voxels_sequence(ctx):
     1 empty (created empty, made editable by clearing an already empty voxel); 2 the single voxel (0, 0, 0); 3 the single voxel
     (255, 255, 255); 4 one voxel in each of the 4096 root cells (n_mid == the capacity of the mid buffer); 5 back down to three voxels, in
     root cells 0, 2047 and 4095; 6 empty again; 7 one root cell fully solid, single bricks at mid bits 0, 31, 32 and 63 around it; 8 a
-    random model over the whole tree plus a slab of full bricks, its bricks straddling many 1024-code chunks of k_edit_scan_local."""
+    random model over the whole tree plus a slab of full bricks, its bricks straddling many 1024-code chunks of k_table_scan_local."""
     model = host_model(ctx, empty_grid())
     assert model.read_hierarchy()["n_mid"] == 0
     model.set_voxels(np.array([[17, 200, 3]], np.uint32), np.array([-1], np.int32))
@@ -144,7 +144,7 @@ def test_set_voxels_sequence(ctx):
     assert (n_mid[2], n_mid[3], n_mid[4], n_mid[5], n_mid[6], n_mid[7]) == (1, 1, 4096, 3, 0, 7)
     assert sorted(np.flatnonzero(np.unpackbits(model_root_mask(state(5)), bitorder="little")).tolist()) == [0, 2047, 4095]
     chunks = np.unique(leaf_codes(state(8)) >> 10)
-    assert len(chunks) > 200 and chunks.min() < 8 and chunks.max() > 247, "state 8 must straddle the scan chunks of k_edit_scan_local"
+    assert len(chunks) > 200 and chunks.min() < 8 and chunks.max() > 247, "state 8 must straddle the scan chunks of k_table_scan_local"
     assert 3000 < int(np.count_nonzero(state(8))) < 8000 and np.count_nonzero(np.array(list(HW.bricks_of_grid(state(8)).values()), np.uint64) == np.uint64((1 << 64) - 1)) == 64
 
 

@@ -36,7 +36,7 @@ SPECIAL = [I32_MIN, I32_MIN + 1, -256, -1, 0, 255, 256, I32_MAX - 1, I32_MAX]
 def exe():
     """built once, again when the program or a header it includes is newer (as tests/test_cpp_mirror.py caches its binary)"""
     os.makedirs(os.path.dirname(EXE), exist_ok=True)
-    deps = [SRC, os.path.join(ROOT, "include", "dust_hip.h")] + [os.path.join(CSRC, h) for h in ("model_records.hpp", "cast.hpp", "stamp.hpp", "edit.hpp", "dust_dev.h")]
+    deps = [SRC, os.path.join(ROOT, "include", "dust_hip.h")] + [os.path.join(CSRC, h) for h in ("model_records.hpp", "cast.hpp", "stamp.hpp", "edit.hpp", "grid.hpp", "dust_dev.h")]
     if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-Wall", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                                "-static-libasan", "-static-libubsan",   # (the runtimes inside the program: nothing to load first)
