@@ -13,8 +13,7 @@
 // Work distribution: persistent workgroups (about one per CU) take chunks of kQueryChunk rays from a device counter -- the workgroup
 // stages the scene's root nodes in LDS once (walk_step reads them through lds_slot), so the launch must not be n / 256 short-lived
 // workgroups. A picking query of a few rays is one workgroup.
-#include "top.hpp"
-#include "query.hpp"
+#include "box_query.hpp"  // palette_index, next_chunk, launch_by_mode
 
 namespace dust {
 namespace {
@@ -44,10 +43,7 @@ __device__ __forceinline__ void put_hit(ArgsRef a, const QueryArgs& q, uint32_t 
     const uint32_t vx = h.voxel >> 4, vy = (h.voxel >> 2) & 3u, vz = h.voxel & 3u;
     const V3 ctr = mk(((float)b.x + (float)vx) + 0.5f, ((float)b.y + (float)vy) + 0.5f, ((float)b.z + (float)vz) + 0.5f);
     const uint32_t face = normal2faceid(cubed_normalize(mk(hpo.x - ctr.x, hpo.y - ctr.y, hpo.z - ctr.z)));
-    const uint32_t m1 = (uint32_t)b.mask, m2 = (uint32_t)(b.mask >> 32);
-    const uint32_t ma = h.voxel < 32u ? (m1 & ((1u << (h.voxel & 31u)) - 1u)) : m1;
-    const uint32_t mb = h.voxel >= 32u ? (m2 & ((1u << ((h.voxel - 32u) & 31u)) - 1u)) : 0u;
-    const uint32_t pal = m.materials[b.material_ptr + (uint32_t)__popc(ma) + (uint32_t)__popc(mb)];
+    const uint32_t pal = palette_index(b, m.materials, h.voxel);
     r0.x = __float_as_uint(h.t); r0.y = h.inst; r0.z = block; r0.w = h.voxel;
     r1.x = (uint32_t)b.x + vx; r1.y = (uint32_t)b.y + vy; r1.z = (uint32_t)b.z + vz; r1.w = (face & 0xFFu) | ((pal & 0xFFu) << 8);
   }
@@ -58,7 +54,7 @@ __device__ __forceinline__ void put_hit(ArgsRef a, const QueryArgs& q, uint32_t 
 
 }  // namespace
 
-// MODE: bit 1 = DEEP (the scene holds a 4096^3 model), bit 2 = LARGE (more than kFlatCullMax instances: the group boxes exist)
+// MODE: launch_by_mode (box_query.hpp)
 template <int MODE>
 __global__ void __launch_bounds__(1024, 4) k_ray_query(const FrameArgs, const QueryArgs q) {
   ArgsRef a0 = launch_args();
@@ -91,10 +87,7 @@ __global__ void __launch_bounds__(1024, 4) k_ray_query(const FrameArgs, const Qu
       const uint64_t b_empty = __ballot(state == Q_EMPTY);
       if (b_empty != 0ull && !dry) {
         if (win_next == win_end) {  // the wave's chunk is used up
-          unsigned long long k = 0;
-          if (lane == 0) k = atomicAdd(q.counter, (unsigned long long)kQueryChunk);
-          k = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(k >> 32)) << 32) |
-              (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k);
+          const unsigned long long k = next_chunk(q.counter, kQueryChunk, lane);
           if (k >= q.n) dry = true;
           else { win_next = (uint32_t)k; win_end = (uint32_t)min((unsigned long long)q.n, k + kQueryChunk); }
         }
@@ -168,13 +161,7 @@ __global__ void __launch_bounds__(1024, 4) k_ray_query(const FrameArgs, const Qu
 // grid, block: the host's choice (capi_scene.cpp trace_rays_impl); the dynamic LDS is the staged roots
 hipError_t launch_ray_query(const FrameArgs& a, const QueryArgs& q, uint32_t grid, uint32_t block, hipStream_t s) {
   const size_t lds = (size_t)a.n_lds_models * kN16LdsBytes;
-  switch ((a.deep ? 2 : 0) | (a.n_groups ? 4 : 0)) {
-    case 0: hipLaunchKernelGGL(k_ray_query<0>, dim3(grid), dim3(block), lds, s, a, q); break;
-    case 2: hipLaunchKernelGGL(k_ray_query<2>, dim3(grid), dim3(block), lds, s, a, q); break;
-    case 4: hipLaunchKernelGGL(k_ray_query<4>, dim3(grid), dim3(block), lds, s, a, q); break;
-    default: hipLaunchKernelGGL(k_ray_query<6>, dim3(grid), dim3(block), lds, s, a, q); break;
-  }
-  return hipGetLastError();
+  return launch_by_mode(a, [&](auto mode) { hipLaunchKernelGGL(k_ray_query<decltype(mode)::value>, dim3(grid), dim3(block), lds, s, a, q); });
 }
 hipError_t configure_query_kernels(size_t max_lds) {  // (as configure_gi_kernels: dynamic LDS beyond 64 KiB must be asked for)
   const void* fns[] = {(const void*)k_ray_query<0>, (const void*)k_ray_query<2>, (const void*)k_ray_query<4>, (const void*)k_ray_query<6>};

@@ -3,17 +3,18 @@
 // thrown props, camera spring arms. The moving counterpart of overlap.hip's boxes; the contract is in include/dust_hip.h.
 //
 // One query per WAVE, as overlap.hip: persistent workgroups of kSweepWaves waves take kSweepChunk queries at a time from the ray
-// queries' device counter (same stream, same protocol). A query:
-//  1. lists the instances whose conservative world box (DevBox) meets the swept box (the union of the box at t = 0 and t = 1): the grid
-//     cells it covers, the group boxes or every box in id order, as overlap.hip does (a copy: moving that code into a header both
-//     kernels include raised k_overlap_boxes' VGPRs). Each listed instance gets the time the box enters
-//     its DevBox (the contract's slab times; the DevBox grown by 2^-22 |translation| so that it encloses the float32 voxel corners,
-//     whose rounding grows with the translation) and the list is ranked by (entry, id) in LDS. Instances are visited in that order
-//     until the next entry is strictly later than the best t (an equal entry with a lower id can still win).
-//  2. per instance: the swept box through w2o gives a voxel range; its 256-cells (4096^3 trees) and 16-cells are tested a lane per
-//     cell by their own entry times, and only the cells the box enters before the best t have their mid node looked up; the occupied
-//     ones are visited in ascending (entry, child) order, and a cell is skipped once its entry is later than the best t.
-//     Each mid node is tested a lane per BRICK:
+// queries' device counter (same stream, same protocol). The listing of instances (here: those the SWEPT box meets, the union of the
+// box at t = 0 and t = 1), the per-instance voxel range (of the swept box), the separating axes, the float32 formulas and the tree
+// steps are box_query.hpp's, shared with overlap.hip (sharing them left the registers where they were: here 256 VGPRs, 84 B scratch
+// per lane, 12-14 SGPR spills, one wave per SIMD; k_overlap_boxes 185-191 VGPRs, no scratch, two waves -- docs/EXPERIMENTS.md,
+// "Scene box kernels"). What this file owns:
+//  1. the order of the visit: each listed instance gets the time the box enters its DevBox (the contract's slab times; the DevBox
+//     grown by 2^-22 |translation| so that it encloses the float32 voxel corners, whose rounding grows with the translation) and the
+//     list is ranked by (entry, id) in LDS. Instances are visited in that order until the next entry is strictly later than the best
+//     t (an equal entry with a lower id can still win). A query that could not be listed tests every instance box in id order.
+//  2. per instance: its 256-cells (4096^3 trees) and 16-cells are tested a lane per cell by their own entry times, and only the cells
+//     the box enters before the best t have their mid node looked up; the occupied ones are visited in ascending (entry, child) order,
+//     and a cell is skipped once its entry is later than the best t. Each mid node is tested a lane per BRICK:
 //       Axis-aligned instances: per world axis, the 5 planes of the brick's voxels by the box queries' corner formula; the brick's
 //       slab first, then the 4 voxel slabs' entry / exit times; a voxel's T_in / T_out are a max / min of three. The times of an
 //       enclosing slab (brick, cell, DevBox) come from the same planes through the same monotone float32 operations, so they enter no
@@ -26,34 +27,23 @@
 // Quotients: RN(x / d) as div_by with the query's three reciprocals (exact_div.hpp); the plain IEEE division where d_r is outside
 // [2^-100, 2^100] (wave-uniform per query: a subnormal d_r's reciprocal overflows) or where a quotient or numerator leaves the range in
 // which the three-operation sequence is exact.
-#include "top.hpp"
-#include "query.hpp"
+#include "box_query.hpp"
 #include "exact_div.hpp"
 
 namespace dust {
 namespace {
 
-constexpr uint32_t kSweepCand = 256;       // a wave's candidate list in LDS (and as many slots to rank it into)
-constexpr uint32_t kSweepGridCells = 512;  // grid cells a swept box may cover for the grid path; more: the group boxes / the id-order scan
-constexpr uint32_t kNoMid = 0xFFFFFFFFu;
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;   // a lane with nothing to offer to a wave minimum
 
 struct SweepLds {
-  uint32_t cand[2 * kSweepCand];  // [0, kSweepCand): as found; [kSweepCand, 2 kSweepCand): ranked by (entry, id)
-  float entry[2 * kSweepCand];    // ... and when the box enters each one's DevBox (+inf: never in [0, 1))
-  f32x4 axis[16];                 // general instances: the 15 separating axes {L, support of a unit voxel on L}
-  f32x4 axis_m[16];               // ... {L . delta, support of the box on L, |L.x| + |L.y| + |L.z|, 1 / |L|}
-  float axis_r[16];               // ... 1 / (L . delta)
+  uint32_t cand[2 * kBoxCand];  // [0, kBoxCand): as found; [kBoxCand, 2 kBoxCand): ranked by (entry, id)
+  float entry[2 * kBoxCand];    // ... and when the box enters each one's DevBox (+inf: never in [0, 1))
+  f32x4 axis[16];               // general instances: the 15 separating axes {L, support of a unit voxel on L}
+  f32x4 axis_m[16];             // ... {L . delta, support of the box on L, |L.x| + |L.y| + |L.z|, 1 / |L|}
+  float axis_r[16];             // ... 1 / (L . delta)
 };
 __shared__ SweepLds g_sweep[kSweepWaves];
 
-__device__ __forceinline__ void wave_sync_lds() {  // LDS written by some lanes of the wave, read by others
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ float uniform_f(float v) { return __uint_as_float(uniform(__float_as_uint(v))); }
-__device__ __forceinline__ bool finite(float v) { return __builtin_isfinite(v); }
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
@@ -82,11 +72,6 @@ __device__ __forceinline__ float qdiv(float a, const Sweep& q, int r) {
   return v;
 }
 
-// the box queries' per-axis rule: v_lo < hi && lo < v_hi; lo == hi: v_lo <= lo < v_hi
-__device__ __forceinline__ bool slab_overlap(float vlo, float vhi, float lo, float hi) {
-  return lo < hi ? (vlo < hi && lo < vhi) : (vlo <= lo && lo < vhi);
-}
-
 // the contract's entry / exit times of the world slab [a, b] on axis r; a resting axis: (-inf, +inf) in contact, else (+inf, -inf)
 __device__ __forceinline__ void slab_times(float a, float b, const Sweep& q, int r, float& e, float& x) {
   if ((q.moving >> r) & 1u) {
@@ -105,26 +90,9 @@ __device__ __forceinline__ float entry_of(float tin, float tout) {
   return (tin < tout && tin < 1.0f && tout > 0.0f) ? fmaxf(tin, 0.0f) : INFINITY;
 }
 
-// axis-aligned instance: world coordinate r of a point whose model coordinate c is p (the others 0: their products are +-0, which
-// changes at most the sign of a zero result -- the box queries' corner formula, as overlap.hip's aligned_mask)
-__device__ __forceinline__ float plane(DUST_RO(float) o2w, int r, int c, float p) {
-  const float px = c == 0 ? p : 0.0f, py = c == 1 ? p : 0.0f, pz = c == 2 ? p : 0.0f;
-  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(o2w[r * 4 + 0], px), __fmul_rn(o2w[r * 4 + 1], py)), __fmul_rn(o2w[r * 4 + 2], pz)), o2w[r * 4 + 3]);
-}
-
-// per instance, what the cell and brick tests need
-struct SInst {
-  uint32_t id;
-  DUST_RO(float) o2w;
-  bool aligned;
-  int col[3];
-  int vlo[3], vhi[3];               // the voxel range (inclusive)
-  float ctr[3], ext[3];             // general instances: the box's centre at t = 0; per world axis, the half extent of a unit voxel
-};
-
 // general instance: the times t in which the parallelepiped o2w([x, x + size]^3) and the box grown by tau / 2 overlap, [tin, tout];
 // kin: the axis that enters last (-1: none moves)
-__device__ __forceinline__ void sat_times(const SweepLds& L, const SInst& in, float x, float y, float z, float size, const Sweep& q,
+__device__ __forceinline__ void sat_times(const SweepLds& L, const BoxInst& in, float x, float y, float z, float size, const Sweep& q,
                                           float& tin, float& tout, int& kin) {
   const float hx = x + 0.5f * size, hy = y + 0.5f * size, hz = z + 0.5f * size;
   float c[3], big = q.big;
@@ -153,7 +121,7 @@ __device__ __forceinline__ void sat_times(const SweepLds& L, const SInst& in, fl
 }
 
 // the entry time (clamped to 0; +inf: never in [0, 1)) of the block of cells at model (x, y, z) of `size` voxels a side
-__device__ __forceinline__ float cell_entry(const SweepLds& L, const SInst& in, const Sweep& q, int x, int y, int z, float size) {
+__device__ __forceinline__ float cell_entry(const SweepLds& L, const BoxInst& in, const Sweep& q, int x, int y, int z, float size) {
   float tin = -INFINITY, tout = INFINITY;
   if (in.aligned) {
 #pragma unroll
@@ -177,7 +145,7 @@ __device__ __forceinline__ float sel4(const float v[4], uint32_t i) {  // (selec
 }
 
 // axis-aligned instance, the brick at model (bx, by, bz): the lane's first hit voxel (best t, lowest bit on ties) and its normal
-__device__ __forceinline__ void aligned_brick(const SInst& in, const Sweep& q, int bx, int by, int bz, uint64_t mask, float& best, uint32_t& bit,
+__device__ __forceinline__ void aligned_brick(const BoxInst& in, const Sweep& q, int bx, int by, int bz, uint64_t mask, float& best, uint32_t& bit,
                                               float nrm[3]) {
   float w[3][5];
   float btin = -INFINITY, btout = INFINITY;
@@ -244,7 +212,7 @@ __device__ __forceinline__ void aligned_brick(const SInst& in, const Sweep& q, i
 }
 
 // general instance, the brick at model (bx, by, bz): as aligned_brick, by the continuous separating-axis test
-__device__ __forceinline__ void general_brick(const SweepLds& L, const SInst& in, const Sweep& q, int bx, int by, int bz, uint64_t mask, float& best,
+__device__ __forceinline__ void general_brick(const SweepLds& L, const BoxInst& in, const Sweep& q, int bx, int by, int bz, uint64_t mask, float& best,
                                               uint32_t& bit, float nrm[3]) {
   float tin, tout;
   int k;
@@ -274,19 +242,16 @@ __device__ __forceinline__ void general_brick(const SweepLds& L, const SInst& in
   }
 }
 
-// one mid node: a lane per brick. Returns true when the query is over (any-hit with a hit)
+// one mid node (16-cell idx of the node at base): a lane per brick. Returns true when the query is over (any-hit with a hit)
 template <int MODE>
-__device__ __forceinline__ bool sweep_mid(Sweep& q, const SInst& in, ModelRef m, const SweepLds& L, uint32_t mid, int gx, int gy, int gz, uint32_t lane) {
-  const u32x4 n = *(DUST_RO(u32x4))(m.mid + mid);
-  const uint64_t mm = ((uint64_t)n.y << 32) | n.x;
-  const int bx = gx + (int)((lane >> 4) & 3u) * 4, by = gy + (int)((lane >> 2) & 3u) * 4, bz = gz + (int)(lane & 3u) * 4;
-  const bool in_range = bx <= in.vhi[0] && bx + 3 >= in.vlo[0] && by <= in.vhi[1] && by + 3 >= in.vlo[1] && bz <= in.vhi[2] && bz + 3 >= in.vlo[2];
+__device__ __forceinline__ bool sweep_mid(Sweep& q, const BoxInst& in, ModelRef m, const SweepLds& L, uint32_t mid, const int base[3], uint32_t idx,
+                                          uint32_t lane) {
+  int bx, by, bz;
   float best = INFINITY, nrm[3] = {0.0f, 0.0f, 0.0f};
-  uint32_t bit = 0, block = 0;
+  uint32_t bit = 0, block;
   DustHipBlock b;
   b.x = b.y = b.z = b.w = 0; b.mask = 0; b.material_ptr = 0; b.avg_albedo = 0;
-  if (((mm >> lane) & 1ull) && in_range) {
-    block = n.z + (uint32_t)__popcll(mm & ((1ull << lane) - 1ull));
+  if (lane_brick(m, in, mid, base, idx, lane, bx, by, bz, block)) {
     b = load_block(m.blocks + block);
     if (in.aligned) aligned_brick(in, q, bx, by, bz, b.mask, best, bit, nrm);
     else general_brick(L, in, q, bx, by, bz, b.mask, best, bit, nrm);
@@ -300,14 +265,7 @@ __device__ __forceinline__ bool sweep_mid(Sweep& q, const SInst& in, ModelRef m,
   const bool better = t < q.t || (t == q.t && (in.id < q.inst || (in.id == q.inst && (blk < q.block || (blk == q.block && vb < q.voxel)))));
   if (better) {
     uint32_t w2 = 0, w3 = 0;
-    if (lane == src) {
-      const uint32_t m1 = (uint32_t)b.mask, m2 = (uint32_t)(b.mask >> 32);
-      const uint32_t ma = vb < 32u ? (m1 & ((1u << (vb & 31u)) - 1u)) : m1;
-      const uint32_t mb = vb >= 32u ? (m2 & ((1u << ((vb - 32u) & 31u)) - 1u)) : 0u;
-      const uint32_t pal = m.materials[b.material_ptr + (uint32_t)__popc(ma) + (uint32_t)__popc(mb)];
-      w2 = ((uint32_t)b.x + (vb >> 4)) | (((uint32_t)b.y + ((vb >> 2) & 3u)) << 16);
-      w3 = ((uint32_t)b.z + (vb & 3u)) | ((pal & 0xFFu) << 16) | (vb << 24);
-    }
+    if (lane == src) voxel_words(b, m.materials, vb, w2, w3);
     q.t = t; q.inst = in.id; q.block = blk; q.voxel = vb;
     q.w2 = uniform((uint32_t)__shfl((int)w2, (int)src, 64));
     q.w3 = uniform((uint32_t)__shfl((int)w3, (int)src, 64));
@@ -317,28 +275,21 @@ __device__ __forceinline__ bool sweep_mid(Sweep& q, const SInst& in, ModelRef m,
   return q.any_hit;
 }
 
-// the 16-cells in [c0, c1] (16-cell coordinates, inclusive) of one N16 node -- the root of a 256^3 tree (l2 < 0) or level-2 node l2 of
-// a 4096^3 tree --: a lane per cell, only the cells the box enters before the best t looked up, the occupied ones in (entry, child) order
+// the 16-cells in [c0, c1] of one node (box_query.hpp, visit_nodes): a lane per cell, only the cells the box enters before the best t
+// looked up, the occupied ones in (entry, child) order
 template <int MODE>
-__device__ __forceinline__ bool sweep_cells(Sweep& q, const SInst& in, ModelRef m, const SweepLds& L, int l2, const int base[3], const int c0[3],
+__device__ __forceinline__ bool sweep_cells(Sweep& q, const BoxInst& in, ModelRef m, const SweepLds& L, int l2, const int base[3], const int c0[3],
                                             const int c1[3], uint32_t lane) {
-  const uint32_t nx = (uint32_t)(c1[0] - c0[0] + 1), ny = (uint32_t)(c1[1] - c0[1] + 1), nz = (uint32_t)(c1[2] - c0[2] + 1);
-  const uint32_t cells = nx * ny * nz;
-  for (uint32_t s = 0; s < cells; s += 64u) {
+  const CellRange range(base, c0, c1);
+  for (uint32_t s = 0; s < range.cells; s += 64u) {
     const uint32_t j = s + lane;
     uint32_t mid = kNoMid, idx = 0, key = kNoKey;
-    if (j < cells) {
-      const uint32_t cz = j % nz, t = j / nz, cy = t % ny, cx = t / ny;
-      idx = ((uint32_t)(c0[0] + (int)cx - base[0] / 16) << 8) | ((uint32_t)(c0[1] + (int)cy - base[1] / 16) << 4) | (uint32_t)(c0[2] + (int)cz - base[2] / 16);
-      const float ent = cell_entry(L, in, q, (c0[0] + (int)cx) * 16, (c0[1] + (int)cy) * 16, (c0[2] + (int)cz) * 16, 16.0f);
+    if (j < range.cells) {
+      int x, y, z;
+      idx = range.index(j, x, y, z);
+      const float ent = cell_entry(L, in, q, x, y, z, 16.0f);
       if (ent <= q.t) {
-        if (DEEP && l2 >= 0) {
-          const u32x4 cell = *(DUST_RO(u32x4))(m.l2_cells + ((size_t)l2 * 4096u + idx));
-          mid = cell.x;
-        } else {
-          uint32_t child;
-          if (n16_child(m.root, -1, idx, child)) mid = child;
-        }
+        mid = cell_mid<MODE>(m, l2, idx);
         key = mid != kNoMid ? __float_as_uint(ent) : kNoKey;
       }
     }
@@ -349,8 +300,7 @@ __device__ __forceinline__ bool sweep_cells(Sweep& q, const SInst& in, ModelRef 
       const uint32_t mu = uniform((uint32_t)__shfl((int)mid, (int)src, 64));
       const uint32_t iu = uniform((uint32_t)__shfl((int)idx, (int)src, 64));
       if (lane == src) key = kNoKey;
-      const int gx = base[0] + (int)(iu >> 8) * 16, gy = base[1] + (int)((iu >> 4) & 15u) * 16, gz = base[2] + (int)(iu & 15u) * 16;
-      if (sweep_mid<MODE>(q, in, m, L, mu, gx, gy, gz, lane)) return true;
+      if (sweep_mid<MODE>(q, in, m, L, mu, base, iu, lane)) return true;
     }
   }
   return false;
@@ -359,71 +309,19 @@ __device__ __forceinline__ bool sweep_cells(Sweep& q, const SInst& in, ModelRef 
 // one instance the box may enter. Returns true when the query is over (any-hit with a hit)
 template <int MODE>
 __device__ __forceinline__ bool sweep_instance(ArgsRef a, Sweep& q, uint32_t id, uint32_t lane, SweepLds& L) {
-  const DUST_CONST_AS DevVisit& v = a.visits[id];
-  ModelRef m = v.m;
-  SInst in;
-  in.id = id;
-  in.o2w = a.instances[id].o2w;
-  int nz_row[3], nz_col[3] = {0, 0, 0};
-  bool aligned = true;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    nz_row[r] = 0;
-    in.col[r] = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      if (in.o2w[r * 4 + c] != 0.0f) { nz_row[r] += 1; nz_col[c] += 1; in.col[r] = c; }
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) aligned = aligned && nz_row[k] == 1 && nz_col[k] == 1;
-  in.aligned = aligned;
-  // the voxel range: the swept box (grown by tau / 2 of the box) through w2o, floored, with the box queries' margin for the rounding
-  const float grow = aligned ? 0.0f : 0.5e-5f * (1.0f + q.big);
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int c = 0; c < 8; ++c) {
-    const V3 p = mk((c & 1) ? q.shi[0] + grow : q.slo[0] - grow, (c & 2) ? q.shi[1] + grow : q.slo[1] - grow, (c & 4) ? q.shi[2] + grow : q.slo[2] - grow);
-    const V3 w = xform_point(v.w2o, p);
-    mn[0] = fminf(mn[0], w.x); mn[1] = fminf(mn[1], w.y); mn[2] = fminf(mn[2], w.z);
-    mx[0] = fmaxf(mx[0], w.x); mx[1] = fmaxf(mx[1], w.y); mx[2] = fmaxf(mx[2], w.z);
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float margin = 1.0f + 1e-5f * (((fabsf(v.w2o[k * 4]) + fabsf(v.w2o[k * 4 + 1])) + fabsf(v.w2o[k * 4 + 2])) * (q.big + grow) + fabsf(v.w2o[k * 4 + 3]));
-    const float lo = fmaxf(floorf(mn[k] - margin), m.bmin[k]), hi = fminf(floorf(mx[k] + margin), m.bmax[k] - 1.0f);
-    if (!(lo <= hi)) return false;
-    in.vlo[k] = (int)lo; in.vhi[k] = (int)hi;
-  }
-  if (!aligned) {
-    float half[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      half[r] = 0.5f * q.hi[r] - 0.5f * q.lo[r];
-      in.ctr[r] = 0.5f * q.lo[r] + 0.5f * q.hi[r];
-      in.ext[r] = 0.5f * ((fabsf(in.o2w[r * 4]) + fabsf(in.o2w[r * 4 + 1])) + fabsf(in.o2w[r * 4 + 2]));
-    }
-    // the instance's 15 axes (lane k makes axis k; as overlap.hip), with their speed and the box's support on them
+  ModelRef m = a.visits[id].m;
+  BoxInst in;
+  if (!box_instance(in, a, id, q.slo, q.shi, q.lo, q.hi, q.big)) return false;
+  if (!in.aligned) {
+    // the instance's 15 axes (lane k makes axis k), with their speed and the box's support on them
     if (lane < 15u) {
-      V3 l;
-      if (lane < 3u) {
-        l = mk(lane == 0u ? 1.0f : 0.0f, lane == 1u ? 1.0f : 0.0f, lane == 2u ? 1.0f : 0.0f);
-      } else if (lane < 6u) {
-        const int i = ((int)lane - 2) % 3, j = ((int)lane - 1) % 3;
-        const V3 u = mk(in.o2w[i], in.o2w[4 + i], in.o2w[8 + i]), w = mk(in.o2w[j], in.o2w[4 + j], in.o2w[8 + j]);
-        l = mk(u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x);
-      } else {
-        const int r = ((int)lane - 6) / 3, i = ((int)lane - 6) % 3;
-        const V3 e = mk(in.o2w[i], in.o2w[4 + i], in.o2w[8 + i]);  // (unit r) x column i
-        l = r == 0 ? mk(0.0f, -e.z, e.y) : (r == 1 ? mk(e.z, 0.0f, -e.x) : mk(-e.y, e.x, 0.0f));
-      }
-      float rp = 0.0f;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) rp += 0.5f * fabsf(dot3(l, mk(in.o2w[k], in.o2w[4 + k], in.o2w[8 + k])));
-      f32x4 ax, am;
-      ax.x = l.x; ax.y = l.y; ax.z = l.z; ax.w = rp * (1.0f + 1e-6f);
+      const f32x4 ax = box_axis(in.o2w, lane);
+      const V3 l = mk(ax.x, ax.y, ax.z);
+      f32x4 am;
       const float s = (l.x * q.d[0] + l.y * q.d[1]) + l.z * q.d[2];
       const float len = sqrtf(dot3(l, l));
       am.x = s;
-      am.y = (half[0] * fabsf(l.x) + half[1] * fabsf(l.y)) + half[2] * fabsf(l.z);
+      am.y = (in.half[0] * fabsf(l.x) + in.half[1] * fabsf(l.y)) + in.half[2] * fabsf(l.z);
       am.z = (fabsf(l.x) + fabsf(l.y)) + fabsf(l.z);
       am.w = len > 0.0f ? 1.0f / len : 0.0f;
       L.axis[lane] = ax;
@@ -431,32 +329,11 @@ __device__ __forceinline__ bool sweep_instance(ArgsRef a, Sweep& q, uint32_t id,
       L.axis_r[lane] = s != 0.0f ? 1.0f / s : 0.0f;
     }
     wave_sync_lds();
-  } else {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) in.ctr[r] = in.ext[r] = 0.0f;
   }
-  const int c0[3] = {in.vlo[0] >> 4, in.vlo[1] >> 4, in.vlo[2] >> 4}, c1[3] = {in.vhi[0] >> 4, in.vhi[1] >> 4, in.vhi[2] >> 4};
-  if (!DEEP || m.n_levels == 2) {
-    const int base[3] = {0, 0, 0};
-    return sweep_cells<MODE>(q, in, m, L, -1, base, c0, c1, lane);
-  }
-  // 4096^3: the root's 256-cells the box enters before the best t, in ascending child order, then each one's 16-cells
-  for (int rx = in.vlo[0] >> 8; rx <= (in.vhi[0] >> 8); ++rx)
-    for (int ry = in.vlo[1] >> 8; ry <= (in.vhi[1] >> 8); ++ry)
-      for (int rz = in.vlo[2] >> 8; rz <= (in.vhi[2] >> 8); ++rz) {
-        if (!(cell_entry(L, in, q, rx * 256, ry * 256, rz * 256, 256.0f) <= q.t)) continue;
-        uint32_t l2;
-        if (!n16_child(m.root, -1, ((uint32_t)rx << 8) | ((uint32_t)ry << 4) | (uint32_t)rz, l2)) continue;
-        const int base[3] = {rx * 256, ry * 256, rz * 256};
-        const int s0[3] = {max(c0[0], rx * 16), max(c0[1], ry * 16), max(c0[2], rz * 16)};
-        const int s1[3] = {min(c1[0], rx * 16 + 15), min(c1[1], ry * 16 + 15), min(c1[2], rz * 16 + 15)};
-        if (sweep_cells<MODE>(q, in, m, L, (int)uniform(l2), base, s0, s1, lane)) return true;
-      }
-  return false;
-}
-
-__device__ __forceinline__ bool box_meets(const Sweep& q, f32x4 blo, f32x4 bhi) {  // (the swept box)
-  return q.slo[0] <= bhi.x && blo.x <= q.shi[0] && q.slo[1] <= bhi.y && blo.y <= q.shi[1] && q.slo[2] <= bhi.z && blo.z <= q.shi[2];
+  // (4096^3: only the 256-cells the box enters before the best t)
+  return visit_nodes<MODE>(
+      m, in, [&](int x, int y, int z, float size) { return cell_entry(L, in, q, x, y, z, size) <= q.t; },
+      [&](int l2, const int base[3], const int c0[3], const int c1[3]) { return sweep_cells<MODE>(q, in, m, L, l2, base, c0, c1, lane); });
 }
 
 // when the box enters instance id's DevBox, grown by 2^-22 |translation| per axis: float32 voxel corners round by up to about
@@ -490,13 +367,13 @@ __device__ __forceinline__ bool sweep_listed(ArgsRef a, Sweep& q, uint32_t n_can
       const float ei = L.entry[i];
       rank += (ei < e || (ei == e && L.cand[i] < v)) ? 1u : 0u;
     }
-    L.cand[kSweepCand + rank] = v;
-    L.entry[kSweepCand + rank] = e;
+    L.cand[kBoxCand + rank] = v;
+    L.entry[kBoxCand + rank] = e;
   }
   wave_sync_lds();
   for (uint32_t i = 0; i < n_cand; ++i) {
-    if (!(uniform_f(L.entry[kSweepCand + i]) <= q.t)) break;
-    if (sweep_instance<MODE>(a, q, uniform(L.cand[kSweepCand + i]), lane, L)) return true;
+    if (!(uniform_f(L.entry[kBoxCand + i]) <= q.t)) break;
+    if (sweep_instance<MODE>(a, q, uniform(L.cand[kBoxCand + i]), lane, L)) return true;
   }
   return false;
 }
@@ -530,87 +407,21 @@ __device__ void sweep_query(ArgsRef a, const SweepArgs& o, uint32_t qi, uint32_t
     q.rcp[k] = 1.0f / q.d[k];
   }
   if (ok) {
-    bool done = false, listed = false;
-    const uint64_t lower = (1ull << lane) - 1ull;
-    // (1) the grid: the block of cells the swept box covers (as overlap.hip)
-    const DUST_CONST_AS DevGrid& g = a.grid;
-    uint32_t cl[3] = {0, 0, 0}, ch[3] = {0, 0, 0};
-    bool use_grid = g.cells != nullptr;
-    if (use_grid) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        cl[k] = (uint32_t)f2i_clamp(floorf((q.slo[k] - g.lo[k]) * g.inv_cell[k]), 0, (int)g.dim[k] - 1);
-        ch[k] = (uint32_t)f2i_clamp(floorf((q.shi[k] - g.lo[k]) * g.inv_cell[k]), 0, (int)g.dim[k] - 1);
-      }
-      use_grid = (ch[0] - cl[0] + 1u) * (ch[1] - cl[1] + 1u) * (ch[2] - cl[2] + 1u) <= kSweepGridCells;
-    }
-    if (use_grid) {
-      uint32_t n_cand = 0;
-      for (uint32_t z = cl[2]; z <= ch[2]; ++z)
-        for (uint32_t y = cl[1]; y <= ch[1]; ++y)
-          for (uint32_t x = cl[0]; x <= ch[0]; ++x) {
-            const uint32_t packed = g.cells[(z * g.dim[1] + y) * g.dim[0] + x];
-            const uint32_t first = packed & ((1u << kGridItemBits) - 1u), count = packed >> kGridItemBits;
-            for (uint32_t s = 0; s < count; s += 64u) {
-              bool keep = false;
-              uint32_t ii = 0;
-              if (s + lane < count) {
-                ii = g.items[first + s + lane];
-                const f32x4 blo = *(DUST_RO(f32x4))(&a.boxes[ii].lo[0]), bhi = *(DUST_RO(f32x4))(&a.boxes[ii].hi[0]);
-                const uint32_t rl = __float_as_uint(blo.w);
-                // the one cell the instance is accepted in: max(the box's low cell, the instance's low cell), per axis
-                const bool here = max(cl[0], rl & 255u) == x && max(cl[1], (rl >> 9) & 255u) == y && max(cl[2], (rl >> 18) & 255u) == z;
-                keep = here && box_meets(q, blo, bhi);
-              }
-              const uint64_t bal = __ballot(keep);
-              const uint32_t at = n_cand + (uint32_t)__popcll(bal & lower);
-              if (keep && at < kSweepCand) L.cand[at] = ii;
-              n_cand += (uint32_t)__popcll(bal);
-            }
-          }
-      if (n_cand <= kSweepCand) { listed = true; done = sweep_listed<MODE>(a, q, n_cand, lane, L); }
-    } else if (LARGE) {
-      // (2) a large scene: the group boxes, then the slots of the groups the swept box meets
-      uint32_t n_cand = 0;
-      for (uint32_t s = 0; s < a.n_groups && n_cand <= kSweepCand; s += 64u) {
-        bool meet = false;
-        if (s + lane < a.n_groups) {
-          const f32x4 glo = *(DUST_RO(f32x4))(&a.gboxes[s + lane].lo[0]), ghi = *(DUST_RO(f32x4))(&a.gboxes[s + lane].hi[0]);
-          meet = box_meets(q, glo, ghi);
+    const uint32_t n_cand = list_instances<MODE>(a, q.slo, q.shi, L.cand, lane);
+    if (n_cand <= kBoxCand) {
+      sweep_listed<MODE>(a, q, n_cand, lane, L);
+    } else {
+      // not listed: every instance box in id order, 64 per step; each skipped once the best t is earlier than its entry
+      bool done = false;
+      for (uint32_t s = 0; !done && s < a.n_instances; s += 64u) {
+        float ent = INFINITY;
+        if (s + lane < a.n_instances && instance_meets(a, s + lane, q.slo, q.shi)) ent = instance_entry(a, q, s + lane);
+        uint64_t bal = __ballot(ent <= q.t);
+        while (bal != 0ull && !done) {
+          const uint32_t src = (uint32_t)__builtin_ctzll(bal);
+          bal &= bal - 1ull;
+          if (uniform_f(__shfl(ent, (int)src, 64)) <= q.t) done = sweep_instance<MODE>(a, q, s + src, lane, L);
         }
-        uint64_t groups = __ballot(meet);
-        while (groups != 0ull && n_cand <= kSweepCand) {
-          const uint32_t gi = s + (uint32_t)__builtin_ctzll(groups);
-          groups &= groups - 1ull;
-          const uint32_t sc = gi * 64u + lane;
-          bool keep = false;
-          uint32_t ii = 0;
-          if (sc < a.n_instances) {
-            const f32x4 blo = *(DUST_RO(f32x4))(&a.sboxes[sc].lo[0]), bhi = *(DUST_RO(f32x4))(&a.sboxes[sc].hi[0]);
-            ii = __float_as_uint(blo.w);
-            keep = box_meets(q, blo, bhi);
-          }
-          const uint64_t bal = __ballot(keep);
-          const uint32_t at = n_cand + (uint32_t)__popcll(bal & lower);
-          if (keep && at < kSweepCand) L.cand[at] = ii;
-          n_cand += (uint32_t)__popcll(bal);
-        }
-      }
-      if (n_cand <= kSweepCand) { listed = true; done = sweep_listed<MODE>(a, q, n_cand, lane, L); }
-    }
-    // (3) every instance box in id order, 64 per step (no grid, or a list longer than the LDS takes); each skipped once the best t is
-    // earlier than its entry
-    for (uint32_t s = 0; !listed && !done && s < a.n_instances; s += 64u) {
-      float ent = INFINITY;
-      if (s + lane < a.n_instances) {
-        const f32x4 blo = *(DUST_RO(f32x4))(&a.boxes[s + lane].lo[0]), bhi = *(DUST_RO(f32x4))(&a.boxes[s + lane].hi[0]);
-        if (box_meets(q, blo, bhi)) ent = instance_entry(a, q, s + lane);
-      }
-      uint64_t bal = __ballot(ent <= q.t);
-      while (bal != 0ull && !done) {
-        const uint32_t src = (uint32_t)__builtin_ctzll(bal);
-        bal &= bal - 1ull;
-        if (uniform_f(__shfl(ent, (int)src, 64)) <= q.t) done = sweep_instance<MODE>(a, q, s + src, lane, L);
       }
     }
   }
@@ -626,7 +437,7 @@ __device__ void sweep_query(ArgsRef a, const SweepArgs& o, uint32_t qi, uint32_t
 
 }  // namespace
 
-// MODE: bit 1 = DEEP (the scene holds a 4096^3 model), bit 2 = LARGE (more than kFlatCullMax instances: the group boxes exist)
+// MODE: launch_by_mode (box_query.hpp)
 template <int MODE>
 __global__ void __launch_bounds__(kSweepWaves * 64) k_sweep_boxes(const FrameArgs, const SweepArgs o) {
   ArgsRef a = launch_args();
@@ -634,9 +445,7 @@ __global__ void __launch_bounds__(kSweepWaves * 64) k_sweep_boxes(const FrameArg
   const uint32_t lane = threadIdx.x & 63u;
   SweepLds& L = g_sweep[threadIdx.x >> 6];
   for (;;) {  // the wave's next chunk of queries
-    unsigned long long k = 0;
-    if (lane == 0) k = atomicAdd(o.counter, (unsigned long long)kSweepChunk);
-    k = ((unsigned long long)uniform((uint32_t)(k >> 32)) << 32) | uniform((uint32_t)k);
+    const unsigned long long k = next_chunk(o.counter, kSweepChunk, lane);
     if (k >= o.n) break;
     const uint32_t end = (uint32_t)min((unsigned long long)o.n, k + kSweepChunk);
     for (uint32_t qi = (uint32_t)k; qi < end; ++qi) sweep_query<MODE>(a, o, qi, lane, L);
@@ -645,13 +454,7 @@ __global__ void __launch_bounds__(kSweepWaves * 64) k_sweep_boxes(const FrameArg
 
 // grid, block: the host's choice (capi_scene.cpp sweep_boxes_impl); no dynamic LDS
 hipError_t launch_sweep_boxes(const FrameArgs& a, const SweepArgs& o, uint32_t grid, uint32_t block, hipStream_t s) {
-  switch ((a.deep ? 2 : 0) | (a.n_groups ? 4 : 0)) {
-    case 0: hipLaunchKernelGGL(k_sweep_boxes<0>, dim3(grid), dim3(block), 0, s, a, o); break;
-    case 2: hipLaunchKernelGGL(k_sweep_boxes<2>, dim3(grid), dim3(block), 0, s, a, o); break;
-    case 4: hipLaunchKernelGGL(k_sweep_boxes<4>, dim3(grid), dim3(block), 0, s, a, o); break;
-    default: hipLaunchKernelGGL(k_sweep_boxes<6>, dim3(grid), dim3(block), 0, s, a, o); break;
-  }
-  return hipGetLastError();
+  return launch_by_mode(a, [&](auto mode) { hipLaunchKernelGGL(k_sweep_boxes<decltype(mode)::value>, dim3(grid), dim3(block), 0, s, a, o); });
 }
 
 }  // namespace dust

@@ -1,6 +1,7 @@
 """Scene box queries (dust_hip_scene_overlap_boxes / _async) on the castle stand-in (synth.castle_scene): the host round trip of one
 synchronous player-sized box (1 x 2 x 1 voxels), 65 536 player-sized boxes on the device path and 256 boxes of 64^3 (blasts), each
-counted and with up to 64 records apiece. Device times are hipEvents (torch.cuda.Event) around the launch on the context's stream (a torch
+counted and with up to 64 records apiece; then 16 384 boxes of 8^3 on a LARGE scene (4 096 scattered, rotated instances) and on a DEEP
+one (a 4096^3 model), the other variants of the kernel. Device times are hipEvents (torch.cuda.Event) around the launch on the context's stream (a torch
 stream handed to the context and made current) after a warm-up, median of the repetitions; the single query is host wall clock around the whole call, median of --single calls.
 
     python tools/overlap_timing.py [--reps 20] [--single 1000]
@@ -31,6 +32,24 @@ def world_box(desc):
     return lo, hi
 
 
+def extra_scenes(ctx):
+    """[(name, scene, world lo, world hi)]: a LARGE scene (more than 256 instances: the kernels' MODE bit 2) and a DEEP one (a 4096^3
+    model: bit 1), as the GPU tests build them"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import parity_util as P
+    from test_gpu_many_instances import scattered_scene
+    desc = scattered_scene(4096, seed=11)
+    out = [("large_4096", scenes.hip_scene(ctx, desc)) + world_box(desc)]
+    blocks, mats, pal = P.clustered_deep_model(n_cells=6000)
+    deep = api.Scene(ctx)
+    xf = np.eye(3, 4, dtype=np.float32)
+    xf[:, 3] = -2048.0
+    deep.add_instance(api.Model(ctx, blocks, mats, pal, tree_extent_log2=12), xf.reshape(12))
+    deep.commit()
+    out.append(("deep_4096cubed", deep, np.full(3, -512.0), np.full(3, 512.0)))   # (the occupied 16-cells: 96 .. 160, minus 2048)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
@@ -56,8 +75,11 @@ def main():
         b_lo = np.round(c).astype(np.float32)
         return b_lo, (b_lo + np.asarray(size, np.float32)).astype(np.float32)
 
-    for name, n, size in (("player_65536", 65536, player), ("blast64_256", 256, (64.0, 64.0, 64.0))):
-        b_lo, b_hi = boxes_at(n, size, 0.0 if size == player else -32.0)
+    cases = [("player_65536", scene, 65536) + boxes_at(65536, player, 0.0), ("blast64_256", scene, 256) + boxes_at(256, (64.0, 64.0, 64.0), -32.0)]
+    for name, other, w_lo, w_hi in extra_scenes(ctx):
+        b_lo = np.round(w_lo + rng.random((16384, 3)) * (w_hi - w_lo)).astype(np.float32)
+        cases.append((name + "_box8_16384", other, 16384, b_lo, b_lo + np.float32(8.0)))
+    for name, scene, n, b_lo, b_hi in cases:
         boxes = api.box_queries(b_lo, b_hi, 64)
         dev = torch.from_numpy(boxes.view(np.int32).reshape(-1, 8).copy()).to("cuda")
         counts = torch.zeros(n, dtype=torch.int32, device="cuda")
@@ -82,6 +104,7 @@ def main():
                             "voxels": int(cnt.astype(np.int64).sum())}
             print(key, results[key], flush=True)
     lib = L.load()
+    scene = cases[0][1]
     b_lo, b_hi = boxes_at(64, player, 0.0)
     one = api.box_queries(b_lo[:1], b_hi[:1], 64)
     cnt = np.zeros(1, np.uint32)

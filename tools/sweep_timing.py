@@ -1,6 +1,7 @@
 """Scene box sweeps (dust_hip_scene_sweep_boxes / _async) on the castle stand-in (synth.castle_scene): 65 536 player-box steps (1 x 2 x 1
 voxels at ground level, |delta| <= 1), closest and any hit; 4 096 long sweeps (0.5^3 boxes over 64 to 256 voxels); the host round trip
-of one synchronous sweep; and the same 65 536 player boxes through dust_hip_scene_overlap_boxes (64 records each) in the same run, for
+of one synchronous sweep; 16 384 sweeps of a 2^3 box over 8 to 64 voxels on a LARGE and on a DEEP scene (overlap_timing.py's
+extra_scenes: the other variants of the kernel); and the same 65 536 player boxes through dust_hip_scene_overlap_boxes (64 records each) in the same run, for
 comparison. Device times are hipEvents (torch.cuda.Event) around the launch on the context's stream (a torch stream handed to the
 context and made current) after a warm-up, median of the repetitions; the single sweep is host wall clock around the whole call, median
 of --single calls.
@@ -20,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dust_amd import _lib as L  # noqa: E402
 from dust_amd import api, scenes, synth  # noqa: E402
-from overlap_timing import world_box  # noqa: E402
+from overlap_timing import extra_scenes, world_box  # noqa: E402
 
 
 def main():
@@ -69,12 +70,16 @@ def main():
     c[:, 1] = rng.uniform(-4.0, 40.0, 4096)
     l_lo = c.astype(np.float32)
     l_hi = (l_lo + np.float32(0.5)).astype(np.float32)
-    for name, s_lo, s_hi, d in (("player_65536", p_lo, p_hi, directions(n, 0.0, 1.0)), ("long_4096", l_lo, l_hi, directions(4096, 64.0, 256.0))):
+    cases = [("player_65536", scene, p_lo, p_hi, directions(n, 0.0, 1.0)), ("long_4096", scene, l_lo, l_hi, directions(4096, 64.0, 256.0))]
+    for name, other, w_lo, w_hi in extra_scenes(ctx):
+        s_lo = np.round(w_lo + rng.random((16384, 3)) * (w_hi - w_lo)).astype(np.float32)
+        cases.append((name + "_16384", other, s_lo, s_lo + np.float32(2.0), directions(16384, 8.0, 64.0)))
+    for name, sc, s_lo, s_hi, d in cases:
         dev = torch.from_numpy(api.box_sweeps(s_lo, s_hi, d).view(np.int32).reshape(-1, 12).copy()).to("cuda")
         hits = torch.zeros((len(s_lo), 8), dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
         for any_hit in (False, True):
-            ms = timed(lambda: scene.sweep_boxes(dev, hits=hits, any_hit=any_hit))
+            ms = timed(lambda: sc.sweep_boxes(dev, hits=hits, any_hit=any_hit))
             h = hits.cpu().numpy().reshape(-1).view(api.SWEEP_HIT_DTYPE)
             key = f"{name}_{'any' if any_hit else 'closest'}"
             results[key] = {"ms": ms, "sweeps": len(s_lo), "hit": round(float((h["instance"] != L.NO_HIT).mean()), 4),
