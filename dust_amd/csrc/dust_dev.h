@@ -246,7 +246,8 @@ struct FrameArgs {
   uint32_t prio_floor;        // lowest issue priority this launch's waves run at (the surfel pass on the second stream, beside the next frame's kernels: 3)
   uint32_t debug;             // DUST_HIP_DEBUG ablation bits (1: skip tracing, 2: skip culling, 4: walk every instance in
                               // index order instead of the packet's sorted candidate list, 8: gather / surfel rays take the
-                              // wave-uniform candidate walk of the coherent ray types); 0 in production
+                              // wave-uniform candidate walk of the coherent ray types, 64: a view run's tiles with one AO
+                              // candidate walk their list per member instead of setting the visit up once); 0 in production
   // ---- round 5, appended (the fields above keep the offsets the packet kernels were tuned with: their scalar loads come in aligned runs)
   DUST_RO(DevEnter) enters;     // n_instances compact enter records (the ray streams' instance set-up)
   // Large scenes (more than kFlatCullMax instances; n_groups != 0): the packet cull's 64-wide hierarchy. The instances in the order

@@ -357,6 +357,14 @@ __device__ __forceinline__ void view_run_packet(ArgsRef a, const DUST_CONST_AS F
   Range3 cube;
 #pragma unroll
   for (int q = 0; q < 3; ++q) { cube.lo[q] = -1.000001f; cube.hi[q] = 1.000001f; }
+  // ONE set-up per tile when that list holds one candidate -- the common tile: the instance its pixels hit. Which instance that is and where its
+  // record lies are the same for every member, so they are worked out here, once, and trace_run_ray takes them instead of reading the list: per
+  // member that leaves the direction, its reciprocals, the object-space ray, the world-box slab with the entry-time limit -- the tests that decide
+  // WHICH lanes enter stay per ray, bit for bit -- and trace_instance. Lists of two or more, lists that overflow and debug bit 4 walk the list as
+  // before; debug bit 64 sends every tile that way (tests, A/B in one binary). (The origins in object space, xform_point(w2o, loc), are the same
+  // for every member too; kept across the members' walks they cost 3 to 11 VGPR spills per variant and measured +1 %: they are worked out per member.)
+  TileVisit tv;
+  tv.v = nullptr; tv.inst = 0;
   Hit h;
   uint32_t ncand = 0;
 #pragma unroll 1
@@ -364,7 +372,15 @@ __device__ __forceinline__ void view_run_packet(ArgsRef a, const DUST_CONST_AS F
     ArgsRef b = reload_args(a);
     const DUST_CONST_AS FrameArgs* mq = members + (uint32_t)__builtin_amdgcn_readfirstlane((int)(k ? k - 1u : 0u));   // the member whose AO ray this is (k = 0, the sun ray: nobody's)
     asm volatile("" : "+s"(mq));
+    const bool act = k == 0u ? sun_live : live;
+    const float tmax = k == 0u ? 10000.0f : 8.0f;
+    if (k <= 1u) ncand = cull_instances<MODE>(b, __any(act), org, k == 0u ? point_range(sd) : cube, tmax, cand);   // k >= 2: member 0's list
+    if (k == 1u && (uint32_t)__builtin_amdgcn_readfirstlane((int)ncand) == 1u && !(b.debug & (4u | 64u))) {   // (the cull ends behind a fence and a wave barrier: cand[0] is there)
+      tv.inst = (uint32_t)__builtin_amdgcn_readfirstlane((int)cand[0]) & 0xFFFFu;
+      tv.v = &b.visits[tv.inst];
+    }
     V3 ad = mk(0, 0, 1);
+    PROF_ENTER_IF(k != 0u, P_M_DIR);
     if (k != 0u && live) {  // ambient_occlusion.rgen:52-58 with the member's frame index: its noise slice and rand
       const uint32_t nx = (p.px + 7u + mq->rand) % 128u, ny = (p.py + 183u + mq->rand) % 128u;
       const uint32_t tex = ((DUST_RO(uint32_t))mq->noise5)[ny * 128u + nx];
@@ -372,18 +388,18 @@ __device__ __forceinline__ void view_run_packet(ArgsRef a, const DUST_CONST_AS F
                  div_const((float)((tex >> 16) & 255u), 255.0f) * 2.0f - 1.0f);
       ad = normalize3(rotate_by_normal(n, ns));
     }
-    const bool act = k == 0u ? sun_live : live;
+    PROF_LEAVE_IF(k != 0u, P_M_DIR);
     const V3 dir = k == 0u ? sd : ad;
-    const float tmax = k == 0u ? 10000.0f : 8.0f;
-    if (k <= 1u) ncand = cull_instances<MODE>(b, __any(act), org, k == 0u ? point_range(sd) : cube, tmax, cand);   // k >= 2: member 0's list
     LaneStats cur = {0, 0, 0, 0, 0, 0};
-    trace_ray<1, MODE>(b, act, loc, dir, 0.1f, tmax, k == 0u, cand, ncand, h, cur);
+    trace_run_ray<MODE>(b, act, loc, dir, 0.1f, tmax, k == 0u, cand, ncand, tv, h, cur);
     __builtin_amdgcn_wave_barrier();
     if (k == 0u && sun_live && !h.found) {
       const float dn = dot3(n, sd);
       payload.x += b.sun_term[0] * dn; payload.y += b.sun_term[1] * dn; payload.z += b.sun_term[2] * dn;
     }
+    PROF_ENTER_IF(k != 0u, P_M_STORE);
     if (k != 0u && live) store_radiance(mq->g.illuminance, pix, payload, h.found ? h.t : 0.0f);
+    PROF_LEAVE_IF(k != 0u, P_M_STORE);
   }
 }
 // k_primary_ao_batch over view runs instead of frames (launch_primary_ao_batch launches it when a run of the launch is longer than one frame). A run

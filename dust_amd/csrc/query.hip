@@ -165,6 +165,9 @@ hipError_t launch_ray_query(const FrameArgs& a, const QueryArgs& q, uint32_t gri
 }
 hipError_t configure_query_kernels(size_t max_lds) {  // (as configure_gi_kernels: dynamic LDS beyond 64 KiB must be asked for)
   const void* fns[] = {(const void*)k_ray_query<0>, (const void*)k_ray_query<2>, (const void*)k_ray_query<4>, (const void*)k_ray_query<6>};
+#ifdef DUST_PROFILE
+  max_lds -= sizeof(g_prof);  // (as configure_kernels: the profiling build's static buckets come out of the same 160 KB)
+#endif
   for (const void* f : fns) {
     const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
     if (e != hipSuccess) return e;

@@ -49,7 +49,7 @@ static __device__ unsigned long long g_wave_times[8192][12];
 static __device__ unsigned long long g_launch_clock[256][3];  // per launch (frame_index & 255): wave 0's shader ticks, wall ticks (10 ns), frame index
 #endif
 #ifdef DUST_PROFILE
-constexpr int kProfBuckets = 24;
+constexpr int kProfBuckets = 32;
 __shared__ unsigned long long g_prof[16][kProfBuckets];
 static __device__ unsigned long long g_prof_out[kProfBuckets];  // (one per translation unit: dust_hip_profile_read adds them up)
 __device__ __forceinline__ void prof_mark(int idx, bool leave) {
@@ -64,12 +64,16 @@ __device__ __forceinline__ void prof_count(int idx, unsigned long long n) {
 }
 #define PROF_ENTER(i) prof_mark(i, false)
 #define PROF_LEAVE(i) prof_mark(i, true)
+#define PROF_ENTER_IF(c, i) do { if (c) prof_mark(i, false); } while (0)
+#define PROF_LEAVE_IF(c, i) do { if (c) prof_mark(i, true); } while (0)
 #define PROF_COUNT(i, n) prof_count(i, n)
 #define PROF_COUNT_LANES(i, pred) prof_count(i, (unsigned long long)__popcll(__ballot(pred)))
 #else
 #define PROF_COUNT_LANES(i, pred)
 #define PROF_ENTER(i)
 #define PROF_LEAVE(i)
+#define PROF_ENTER_IF(c, i)
+#define PROF_LEAVE_IF(c, i)
 #define PROF_COUNT(i, n)
 #endif
 // -DDUST_TRACE_DEBUG (never shipped): printf what the final gather does for ONE pixel, DUST_HIP_DEBUG = (pixel index + 1) << 12
@@ -91,6 +95,9 @@ enum { P_TOTAL = 0, P_GRAB, P_CULL, P_TRACE_RAY, P_INSTANCE, P_FIND, P_BRICK, P_
        P_N_TRACES, P_N_CAND, P_N_CAND_ITER, P_N_VISITS, P_N_STEPS };
 enum { P_N_NEIGHBOUR_CALLS = 10 };  // (reuses the unused P_SHADE bucket)
 enum { P_L_TRIPS = 16, P_L_BRICK, P_L_EMPTY4, P_L_EMPTY16, P_SETUP = 20, P_PRIMARY_SHADE = 21, P_AO_SETUP = 22, P_CAND = 23 };  // lane-level trip outcomes  // the P_N_* buckets count events, not cycles
+// the AO rays alone (ray type 1, closest hit: a view run's members, k_primary_ao_runs): the member's direction, its trace_ray, its instance visits, their
+// set-up in front of the walk loop, and the member's store. The wave-uniform condition picks the bucket; the sun ray (any-hit) stays out of them.
+enum { P_M_DIR = 24, P_M_TRACE = 25, P_M_INSTANCE = 26, P_M_ISETUP = 27, P_M_STORE = 28 };
 
 // Earned priorities (round 4): per wave, when its tile began (shader clock) and the issue priority it runs at. A tile's position in the
 // cost order gives it a priority to start with (packet_of_tile); a tile that turns out longer than that promised -- a view that moves
@@ -692,17 +699,21 @@ __device__ __forceinline__ bool in_brick_plane(V3 o, V3 d) {
 // delta of a brick-grid edge or corner every brick around it is tested too (DESIGN.md "Conservative walk").
 // One loop iteration handles one cell; when its entry point lies within delta of other brick planes, the bricks across
 // those planes (one per non-empty subset of the near axes) are tested by visit_neighbours before the walk advances.
-template <int RT, int MODE>
+// (RUN: trace_ray's; it changes nothing here and only keeps the view runs' copy of the walk a function of its own, with its one caller)
+template <int RT, int MODE, bool RUN = false>
 __device__ void trace_instance(ModelRef m, uint32_t inst, V3 o, V3 d, float tmin, float tmax, bool any_hit,
                                Hit& best, LaneStats& st) {
   PROF_ENTER(P_SETUP);
+  PROF_ENTER_IF(RT == 1 && !any_hit, P_M_ISETUP);
   const V3 inv_d = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
   float te, tx;
   const bool in_bounds = slab_box(o, d, inv_d, m.bmin, m.bmax, te, tx);
   PROF_LEAVE(P_SETUP);
+  PROF_LEAVE_IF(RT == 1 && !any_hit, P_M_ISETUP);
   if (!in_bounds) return;
   if (in_brick_plane<RT>(o, d)) return;
   PROF_ENTER(P_CAND);
+  PROF_ENTER_IF(RT == 1 && !any_hit, P_M_ISETUP);
   const int E = (int)m.extent;
   const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z}, inv[3] = {inv_d.x, inv_d.y, inv_d.z};
   float t, near_tol, tx_stop;
@@ -716,6 +727,7 @@ __device__ void trace_instance(ModelRef m, uint32_t inst, V3 o, V3 d, float tmin
   const bool zero_axis = DEEP && __any(d.x == 0.0f || d.y == 0.0f || d.z == 0.0f);  // (of the lanes in this visit)
   bool prev_whole = false;  // DEEP: the cell the walk has just left was a whole 16-cell (or larger) with nothing untested in it
   PROF_LEAVE(P_CAND);
+  PROF_LEAVE_IF(RT == 1 && !any_hit, P_M_ISETUP);
   for (int guard = 0; guard < 200000; ++guard) {
     PROF_COUNT(P_N_STEPS, 1);
     // a tile that turns out to be a long one earns its priority as it goes (g_tile_start above); the camera, sun and AO rays only:
@@ -976,6 +988,7 @@ template <int RT, int MODE>
 __device__ void trace_ray(ArgsRef a_in, bool active, V3 o, V3 d, float tmin, float tmax, bool any_hit,
                           const uint32_t* cand, uint32_t ncand, Hit& best, LaneStats& st) {
   PROF_ENTER(P_TRACE_RAY);
+  PROF_ENTER_IF(RT == 1 && !any_hit, P_M_TRACE);
   best.found = false;
   best.t = tmax; best.inst = 0; best.block = 0; best.voxel = 0;
   if (COUNT && active) st.rays += 1;
@@ -1133,11 +1146,87 @@ __device__ void trace_ray(ArgsRef a_in, bool active, V3 o, V3 d, float tmin, flo
     if (go) {
       if (COUNT) st.instances_tested += 1;
       PROF_ENTER(P_INSTANCE);
+      PROF_ENTER_IF(RT == 1 && !any_hit, P_M_INSTANCE);
       trace_instance<RT, MODE>(v.m, ii, oo, od, tmin, tmax, any_hit, best, st);
+      PROF_LEAVE_IF(RT == 1 && !any_hit, P_M_INSTANCE);
       PROF_LEAVE(P_INSTANCE);
     }
   }
   if (COUNT && best.found) st.hits += 1;
+  PROF_LEAVE_IF(RT == 1 && !any_hit, P_M_TRACE);
+  PROF_LEAVE(P_TRACE_RAY);
+}
+
+// A view run's sun ray and its members' AO rays (k_primary_ao_runs, view_run_packet): trace_ray<1>'s wave-uniform loop, and -- tv.v set -- the ONE
+// visit a tile with a list of one candidate has set up for all of its members: which instance, and where its record lies. Then the list is not
+// read: one trip for tv's instance without the list word, its readfirstlane, the table pointer's reload, the settled test of a list of one (it is
+// "no active lane", which `go` says again) and the choice between list, every instance and groups. Every per-ray test that decides WHICH lanes
+// enter the instance stays, on the member's own direction: the world-box slab with v_rcp reciprocals and the entry-time limit, as trace_ray has them.
+// (Its own copy of trace_instance -- the RUN parameter -- so that the other kernels' trace_ray keeps its one caller of the walk: their code is what it was.)
+struct TileVisit { const DUST_CONST_AS DevVisit* v; uint32_t inst; };
+template <int MODE>
+__device__ void trace_run_ray(ArgsRef a_in, bool active, V3 o, V3 d, float tmin, float tmax, bool any_hit,
+                              const uint32_t* cand, uint32_t ncand, TileVisit tv, Hit& best, LaneStats& st) {
+  PROF_ENTER(P_TRACE_RAY);
+  PROF_ENTER_IF(!any_hit, P_M_TRACE);
+  best.found = false;
+  best.t = tmax; best.inst = 0; best.block = 0; best.voxel = 0;
+  ncand = (uint32_t)__builtin_amdgcn_readfirstlane((int)ncand);
+  PROF_COUNT(P_N_TRACES, 1);
+  PROF_COUNT(P_N_CAND, ncand);
+  const bool one = tv.v != nullptr;
+  const bool all = !one && (ncand > kMaxCand || (a_in.debug & 4u));
+  const bool by_groups = LARGE && all && !(a_in.debug & 4u);
+  const uint32_t n = one ? 1u : (all ? a_in.n_instances : ncand);
+  const V3 inv_d = mk(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z));
+  const bool zero_axis = __any(active && (d.x == 0.0f || d.y == 0.0f || d.z == 0.0f));
+  for (uint32_t ci = 0; ci < n; ++ci) {
+    ArgsRef a = reload_args(a_in);
+    uint32_t ii;
+    if (one) ii = tv.inst;
+    else if (all) {
+      ii = ci;
+      if (by_groups) {
+        if ((ci & 63u) == 0u) {
+          const uint32_t gbits = (uint32_t)__builtin_amdgcn_readfirstlane((int)cand[kMaxCand + (ci >> 11)]);
+          if (!((gbits >> ((ci >> 6) & 31u)) & 1u)) { ci += 63u; continue; }
+        }
+        ii = __float_as_uint(a.sboxes[ci].pad0);
+      }
+    } else {
+      const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)cand[ci]);
+      ii = c & 0xFFFFu;
+      const float t_lo = __uint_as_float(c & 0xFFFF0000u);
+      const bool settled = !active || (best.found && (any_hit || best.t < t_lo * (1.0f - 1e-5f) - 1e-4f));
+      if (__all(settled)) break;
+    }
+    ii = (uint32_t)__builtin_amdgcn_readfirstlane((int)ii);
+    const DUST_CONST_AS DevVisit& v = one ? *tv.v : a.visits[ii];
+    float lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { lo[k] = v.lo[k]; hi[k] = v.hi[k]; }
+    const V3 oo = xform_point(v.w2o, o), od = xform_dir(v.w2o, d);
+    const float b0 = v.m.bmin[0], b1 = v.m.bmin[1], b2 = v.m.bmin[2], b3 = v.m.bmax[0], b4 = v.m.bmax[1], b5 = v.m.bmax[2];
+    bool go = active && !(any_hit && best.found);
+    float te, tx;
+    bool box;
+    if (zero_axis) box = slab_box(o, d, inv_d, lo, hi, te, tx);
+    else box = slab_box_nonzero(o, inv_d, lo, hi, te, tx);
+    const float limit = best.found ? best.t : tmax;
+    go = go & box & !(te * (1.0f - 2e-6f) > limit);
+    asm volatile("" ::"v"(oo.x), "v"(oo.y), "v"(oo.z), "v"(od.x), "v"(od.y), "v"(od.z), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5));
+    PROF_COUNT(P_N_CAND_ITER, 1);
+    if (!__any(go)) continue;
+    PROF_COUNT(P_N_VISITS, 1);
+    if (go) {
+      PROF_ENTER(P_INSTANCE);
+      PROF_ENTER_IF(!any_hit, P_M_INSTANCE);
+      trace_instance<1, MODE, true>(v.m, ii, oo, od, tmin, tmax, any_hit, best, st);
+      PROF_LEAVE_IF(!any_hit, P_M_INSTANCE);
+      PROF_LEAVE(P_INSTANCE);
+    }
+  }
+  PROF_LEAVE_IF(!any_hit, P_M_TRACE);
   PROF_LEAVE(P_TRACE_RAY);
 }
 

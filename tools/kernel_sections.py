@@ -39,9 +39,26 @@ NAMES = ["total", "grab", "cull", "trace_ray", "instance", "find_brick", "brick_
 
 
 def read(lib):
-    buf = (ctypes.c_ulonglong * 24)()
-    assert lib.dust_hip_profile_read(buf, 24) == 0
+    buf = (ctypes.c_ulonglong * 32)()   # (a build with 24 buckets leaves the last eight zero)
+    assert lib.dust_hip_profile_read(buf, 32) == 0
     return [int(x) for x in buf]
+
+
+def report_members(b, K):
+    """the AO rays of a view run (buckets 24-28): what a member costs per tile outside and inside the walk"""
+    tot = b[0] or 1
+    if b[25] == 0:
+        print("  (this build has no member buckets)")
+        return
+    rows = (("member's direction (rand, noise texel, rotate, normalize)", b[24]),
+            ("candidate head + instance set-up", (b[25] - b[26]) + b[27]),
+            ("walk (trace_instance behind its set-up)", b[26] - b[27]),
+            ("member's store", b[28]))
+    print(f"  the {K} members' AO rays, inclusive wave cycles as a share of the kernel's:")
+    for name, x in rows:
+        print(f"    {name:58s}{100.0 * x / tot:6.1f} %")
+    m = sum(x for _, x in rows)
+    print(f"    {'all of a member':58s}{100.0 * m / tot:6.1f} %  ({100.0 * (m - (b[26] - b[27])) / max(1, m):.1f} % of it outside the walk)")
 
 
 def report(title, b, ms):
@@ -132,6 +149,7 @@ def main():
             ctx.sync()
             b = read(lib)
         report(f"k_primary_ao_runs ({K} same-view frames in one launch: camera + sun once, AO per frame)", b, pipe.pass_stats(0).ms)
+        report_members(b, K)
     for title, passes, slot in (("k_primary_ao (fused primary + sun + AO)", L.PASS_PRIMARY | L.PASS_AMBIENT_OCCLUSION, 0),
                                 ("k_final_gather", L.PASS_FINAL_GATHER, 3), ("k_surfel_trace", L.PASS_SURFEL, 4)):
         pipe.render(scene, cam, sky, passes, 5, synth.frame_rand(1, 5))
