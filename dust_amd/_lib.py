@@ -226,6 +226,17 @@ DISTANCE_MAX_RADIUS = 255
 DISTANCE_NO_KEY = 0xFFFFFFFF
 
 
+class Reduce(C.Structure):  # DustHipReduce, 16 bytes: how many times a model is halved and how many solid children make a coarse voxel solid
+    _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_uint32), ("min_solid", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ReduceResult(C.Structure):  # DustHipReduceResult, 16 bytes: the solid voxels of the source and of its reduction, and the reduction's extent
+    _fields_ = [("src_voxels", C.c_uint32), ("voxels", C.c_uint32), ("extent", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+REDUCE_MAX_LEVELS = 8
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -302,6 +313,7 @@ SYMBOLS = {
     "dust_hip_model_distance": (C.c_int, [_P, _P, _P]),
     "dust_hip_model_distance_at": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_distance_apply": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int32, _u32p]),
+    "dust_hip_model_reduce": (C.c_int, [_P, _P, C.POINTER(_P), _P]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

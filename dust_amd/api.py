@@ -47,6 +47,8 @@ FLOOD_RESULT_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("seeds_
                                ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 2)])
 # DustHipDistanceResult, 32 bytes: the counts of a dust_hip_model_distance field and where its largest value is
 DISTANCE_RESULT_DTYPE = np.dtype([("targets", "<u4"), ("near", "<u4"), ("far", "<u4"), ("largest", "<u4"), ("largest_key", "<u4"), ("reserved", "<u4", 3)])
+# DustHipReduceResult, 16 bytes: the voxel counts of a dust_hip_model_reduce and the extent of the new model
+REDUCE_RESULT_DTYPE = np.dtype([("src_voxels", "<u4"), ("voxels", "<u4"), ("extent", "<u4"), ("reserved", "<u4")])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -501,6 +503,20 @@ class Model:
         L.check(self._lib.dust_hip_model_distance_apply(self._h, int(lo), int(hi), int(value), C.byref(changed)))
         return changed.value
 
+    def reduce(self, levels=1, min_solid=1):
+        """A coarser copy of the model as it stands on the device (dust_hip_model_reduce): halved `levels` times (1..L.REDUCE_MAX_LEVELS),
+        a coarse voxel solid when at least min_solid (1..8) of its eight children are and carrying the palette index most of them carry
+        (the lowest among equals). Returns (model, result): a new editable Model of the same context and palette whose voxels occupy
+        [0, 256 >> levels)^3, and a REDUCE_RESULT_DTYPE record (src_voxels, voxels, extent). This model is only read. Instance the copy
+        with lod_transform(obj_to_world, levels) to show it where this model stands."""
+        q = L.Reduce(struct_size=C.sizeof(L.Reduce), levels=levels, min_solid=min_solid, flags=0)
+        h = C.c_void_p()
+        out = np.zeros(1, REDUCE_RESULT_DTYPE)
+        L.check(self._lib.dust_hip_model_reduce(self._h, C.byref(q), C.byref(h), _ptr(out)))
+        coarse = Model.__new__(Model)
+        coarse._ctx, coarse._lib, coarse._h = self._ctx, self._lib, h
+        return coarse, out[0]
+
     def read(self):
         """(blocks, materials) as they stand on the device"""
         nb, nm = C.c_uint32(), C.c_uint64()
@@ -720,6 +736,14 @@ def casts(offset, step, max_steps, orient=ORIENT_IDENTITY, flags=0, src_lo=(0, 0
     out["src_lo"] = np.broadcast_to(np.asarray(src_lo, np.uint8), (len(offset), 3))
     out["src_hi"] = np.broadcast_to(np.asarray(src_hi, np.uint8), (len(offset), 3))
     return out
+
+
+def lod_transform(obj_to_world, levels):
+    """The obj_to_world (3 x 4, row-major) of an instance of Model.reduce(levels)'s model that stands where an instance of the source
+    with `obj_to_world` stands: columns 0..2 scaled by 2^levels, the translation unchanged."""
+    m = np.array(obj_to_world, np.float32).reshape(3, 4)
+    m[:, :3] *= np.float32(2 ** int(levels))
+    return m
 
 
 def top_level_build(boxes):

@@ -153,6 +153,9 @@ struct DustHipContext : RefCounted {
   // needs it) -- expanded from a source that is not editable, or the copy of a model stamped onto itself. Filled by every such call:
   // nothing is cached across calls
   DeviceBuffer stamp_grid;
+  // model reductions (reduce.hip): the grid the levels of a dust_hip_model_reduce call with levels >= 2 take turns with the new model's
+  // (16 MiB, allocated by the first such call). A grid of its own: stamp_grid may hold the expansion of the source the first level reads
+  DeviceBuffer reduce_grid;
   // model floods (flood.hip): the worklists of a dust_hip_model_flood call -- two flag arrays and two brick lists that take turns, their
   // lengths and the accumulator of the result (dust::kFloodWorkWords); 4 MiB, allocated by the first call
   DeviceBuffer flood_work;

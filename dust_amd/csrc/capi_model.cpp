@@ -1,7 +1,8 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
-// edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip) and model floods (flood.hip). What
-// needs no device is in two headers: the hierarchy build itself (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp,
-// the arithmetic on the callers' records (conversion, chunks, cell lists, cast hits) in model_records.hpp.
+// edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip), model floods (flood.hip), model
+// distances (distance.hip) and model reductions (reduce.hip). What needs no device is in three headers: the hierarchy build itself
+// (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp, the arithmetic on the callers' records (conversion, chunks,
+// cell lists, cast hits) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,6 +16,8 @@
 #include "hierarchy.hpp"
 #include "island.hpp"
 #include "model_records.hpp"
+#include "reduce.hpp"
+#include "reduce_rule.hpp"
 
 void release(const DustHipModel* cm) {
   DustHipModel* m = const_cast<DustHipModel*>(cm);
@@ -416,17 +419,17 @@ DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* s
 
 // ---- model stamps (stamp.hip k_stamp)
 namespace {
-// The source as it stands now, as a grid: its own when it is editable (read in place), expanded into the context's scratch when it
-// is not (the source itself is not touched), and a copy of the destination's when a model is stamped onto itself
-DustStatus stamp_source_grid(DustHipModel* m, const DustHipModel* src, const uint8_t** source) {
-  DustHipContext* ctx = m->ctx;
+// A source model as it stands now, as a grid, for a call that only reads it (stamps, reductions): its own when it is editable (read
+// in place), expanded into the context's scratch when it is not (the source itself is not touched), and a copy of the grid of `m`,
+// the editable model the call writes (null: none), when that is the source too -- a model stamped onto itself
+DustStatus source_grid(DustHipContext* ctx, const DustHipModel* m, const DustHipModel* src, const uint8_t** source) {
   hipStream_t st = ctx->stream;
   if (src != m && src->edit) {
     *source = static_cast<const uint8_t*>(src->edit->grid.p);
     return DUST_OK;
   }
   const size_t grid_bytes = size_t(dust::kLattice) * 64;
-  DustStatus s = lazy_alloc(ctx->stamp_grid, grid_bytes, "the stamp source grid (16 MiB)");
+  DustStatus s = lazy_alloc(ctx->stamp_grid, grid_bytes, "the source grid (16 MiB)");
   if (s != DUST_OK) return s;
   if (src == m) {
     HIP_TRY(hipMemcpyAsync(ctx->stamp_grid.p, m->edit->grid.p, grid_bytes, hipMemcpyDeviceToDevice, st));
@@ -470,7 +473,7 @@ DustStatus dust_hip_model_stamp(DustHipModel* m, const DustHipModel* src, const 
     dust::live_records<dust::device_stamp>(stamps, n, dev, index);
     const uint8_t* source = nullptr;
     if (!dev.empty()) {
-      if ((s = stamp_source_grid(m, src, &source)) != DUST_OK) return s;
+      if ((s = source_grid(ctx, m, src, &source)) != DUST_OK) return s;
       if ((s = grow(ctx, ctx->stage_aux, sizeof(map))) != DUST_OK) return s;
       HIP_TRY(hipMemcpyAsync(ctx->stage_aux.p, map, sizeof(map), hipMemcpyHostToDevice, ctx->stream));
     }
@@ -892,6 +895,58 @@ DustStatus dust_hip_model_distance_at(DustHipModel* m, const uint32_t* xyz, uint
 
 DustStatus dust_hip_model_distance_apply(DustHipModel* m, uint32_t lo, uint32_t hi, int32_t value, uint32_t* changed) {
   return field_apply(m, &EditState::distance, no_distance, lo, hi, value, changed);
+}
+
+// ---- model reductions (reduce.hip): a new model that holds the source at 1 / 2^levels of its resolution, voted level by level
+static_assert(sizeof(DustHipReduce) == 16 && sizeof(DustHipReduceResult) == 16, "reduce records");
+DustStatus dust_hip_model_reduce(const DustHipModel* src, const DustHipReduce* q, DustHipModel** out, DustHipReduceResult* result) {
+  if (!src || !q || !out) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipReduce");
+  DustStatus s = editable_kind(src);  // (before the query's values are looked at)
+  if (s != DUST_OK) return s;
+  dust::ReducePlan plan{};
+  if (!dust::device_reduce(*q, plan)) return fail(DUST_ERR_INVALID_ARGUMENT, "levels must be 1..DUST_HIP_REDUCE_MAX_LEVELS, min_solid 1..8 and flags 0");
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = src->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));
+    hipStream_t st = ctx->stream;
+    const uint8_t* source = nullptr;
+    if ((s = source_grid(ctx, nullptr, src, &source)) != DUST_OK) return s;
+    if (dust::reduce_needs_scratch(plan) && (s = lazy_alloc(ctx->reduce_grid, size_t(dust::kLattice) * 64, "the reduction's second grid (16 MiB)")) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_aux, 8)) != DUST_OK) return s;
+    uint32_t pal[256];
+    HIP_TRY(hipMemcpyAsync(pal, src->palette.p, sizeof(pal), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // the new model: empty, editable, its grid filled by the last level and then rebuilt like any edit
+    struct Drop { DustHipModel* m; ~Drop() { release(m); } } fresh{nullptr};
+    s = dust_hip_model_create(ctx, nullptr, 0, nullptr, 0, reinterpret_cast<const uint8_t*>(pal), 8, &fresh.m);
+    if (s == DUST_OK) s = make_editable(fresh.m, false);
+    if (s != DUST_OK) return s;
+    uint32_t* counts = static_cast<uint32_t*>(ctx->stage_aux.p);  // {the source's solid voxels, the new model's}
+    HIP_TRY(hipMemsetAsync(counts, 0, 8, st));
+    uint8_t* grids[3] = {nullptr, static_cast<uint8_t*>(fresh.m->edit->grid.p), static_cast<uint8_t*>(ctx->reduce_grid.p)};
+    for (uint32_t k = 0; k < plan.n; ++k) {
+      const dust::ReduceLevel& l = plan.level[k];
+      dust::ReduceArgs a{};
+      a.src = l.from == dust::kReduceSource ? source : grids[l.from];
+      a.dst = grids[l.to];
+      a.extent = l.extent;
+      a.cover_log2 = 0;
+      while ((4u << a.cover_log2) < l.cover) ++a.cover_log2;
+      a.min_solid = plan.min_solid;
+      a.fresh = l.fresh;
+      a.count_src = l.count_src ? counts : nullptr;
+      a.count_dst = l.count_dst ? counts + 1 : nullptr;
+      HIP_TRY(dust::launch_reduce_level(a, st));
+    }
+    uint32_t n[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(n, counts, 8, hipMemcpyDeviceToHost, st));
+    if ((s = rebuild_and_refresh(fresh.m, *fresh.m->edit)) != DUST_OK) return s;  // synchronises
+    if (result) *result = dust::reduce_result(plan, n[0], n[1]);
+    *out = retain(fresh.m);  // the caller's reference (the guard drops the builder's)
+    return DUST_OK;
+  });
 }
 
 DustStatus dust_hip_model_info(const DustHipModel* m, uint32_t* n_blocks, uint64_t* n_materials) {

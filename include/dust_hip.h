@@ -563,6 +563,50 @@ typedef struct DustHipDistanceResult {  /* 32 bytes */
 DustStatus dust_hip_model_distance(DustHipModel*, const DustHipDistanceQuery*, DustHipDistanceResult* out /* may be NULL */);
 DustStatus dust_hip_model_distance_at(DustHipModel*, const uint32_t* xyz, uint16_t* values, uint32_t n);
 DustStatus dust_hip_model_distance_apply(DustHipModel*, uint32_t lo, uint32_t hi, int32_t value, uint32_t* changed /* may be NULL */);
+/* Model reductions: coarser copies of a model, level by level -- a level of detail for the instances that are far away, a cheap
+ * collision or line-of-sight proxy for the scene queries, a minimap, a half-resolution grid for flood and distance at an eighth of
+ * the cost. The copy is made from the model as it stands NOW on the device, edits included, without a round trip over the host.
+ *
+ * One level: values are a palette index (0..254) or None. Coarse voxel (X, Y, Z), X, Y, Z < 128, has the eight children
+ * (2X + i, 2Y + j, 2Z + k), i, j, k in {0, 1}. With s the number of solid children, the coarse voxel is solid iff s >= min_solid
+ * (1..8); its palette index is the one most of its solid children carry, and among indices with the same highest count the lowest
+ * index wins. Coarse voxels with a coordinate >= 128 are empty. min_solid = 1 never opens a hole (a render LOD, a collision proxy),
+ * min_solid = 4 keeps the volume roughly, min_solid = 8 keeps only the cells that are solid throughout (a safe interior for navigation).
+ * levels = n is that rule applied n times with the same min_solid -- the vote of votes, NOT one vote over 8^n voxels -- so a reduction
+ * by 2 levels holds exactly what the reduction by 1 level of a reduction by 1 level holds; levels = 8 is a single voxel at the origin.
+ * Everything is integer: two runs give the same bytes.
+ *
+ * The new model: *out is on the source's context and has the source's palette. It is a hierarchy (4,2,2) model (256^3 tree) whose
+ * voxels occupy [0, 256 >> levels)^3, born editable exactly as detach_islands' output is (about 44 MB, unlabelled, no fields, the
+ * caller's to destroy), its arrays byte for byte what dust_hip_model_create builds from those voxels. An instance whose obj_to_world
+ * is the source's times a uniform scale of 2^levels shows the reduction where the source stands. An empty result is a valid empty
+ * model, not an error. The result record: src_voxels, the solid voxels of the source; voxels, those of the new model; extent,
+ * 256 >> levels.
+ * The source is only read: one that is not editable stays not editable (it is expanded into the context's 16 MiB scratch grid, as a
+ * stamp's source is), its generation does not move -- committed scenes that instance it stay valid --, and its island labelling and
+ * fields stay valid. With levels >= 2 the levels take turns between the new model's grid and a second 16 MiB grid the context owns,
+ * allocated by the first such call.
+ * Refused, in this order, with *out and *result left as they were (as on any device failure): DUST_ERR_INVALID_ARGUMENT for a null
+ * src, query or out, or a struct_size below sizeof(DustHipReduce); DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3
+ * trees, models that hold material byte 255), before the query's values are looked at; DUST_ERR_INVALID_ARGUMENT for levels outside
+ * 1..DUST_HIP_REDUCE_MAX_LEVELS, min_solid outside 1..8, or nonzero flags. Synchronous, like every model call.
+ * Out of scope: reducing a sub-box of the source; an asynchronous form; 4096^3 trees; choosing between levels while rendering -- the
+ * renderer traces the model an instance names, level selection is the host's. */
+#define DUST_HIP_REDUCE_MAX_LEVELS 8u
+typedef struct DustHipReduce {        /* 16 bytes */
+  uint32_t struct_size;
+  uint32_t levels;                    /* 1..8: the result spans (256 >> levels)^3 voxels from the origin */
+  uint32_t min_solid;                 /* 1..8: a coarse voxel is solid when at least this many of its 8 children are */
+  uint32_t flags;                     /* 0 */
+} DustHipReduce;
+typedef struct DustHipReduceResult {  /* 16 bytes */
+  uint32_t src_voxels;                /* solid voxels of the source */
+  uint32_t voxels;                    /* solid voxels of the new model */
+  uint32_t extent;                    /* 256 >> levels */
+  uint32_t reserved;                  /* 0 */
+} DustHipReduceResult;
+DustStatus dust_hip_model_reduce(const DustHipModel* src, const DustHipReduce*, DustHipModel** out,
+                                 DustHipReduceResult* result /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

@@ -258,6 +258,29 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model reductions (dust_hip_model_reduce): a coarser copy of this geometry as it stands on the device, halved `levels` times, a
+  // coarse voxel solid when at least min_solid of its eight children are and carrying the palette index most of them carry. The copy
+  // is a geometry of its own in [0, 256 >> levels)^3 (spawn it with lod_transform); this one is only read. `result`, if given,
+  // receives the voxel counts and the extent.
+  std::unique_ptr<VoxGeometry> reduce(uint32_t levels = 1, uint32_t min_solid = 1, DustHipReduceResult* result = nullptr) const {
+    DustHipReduce query{};
+    query.struct_size = sizeof(query);
+    query.levels = levels;
+    query.min_solid = min_solid;
+    DustHipModel* coarse = nullptr;
+    check(dust_hip_model_reduce(h_, &query, &coarse, result));
+    return std::unique_ptr<VoxGeometry>(new VoxGeometry(coarse));
+  }
+  // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
+  // stands: columns 0..2 scaled by 2^levels, the translation unchanged
+  static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
+    std::array<float, 12> m{};
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) m[size_t(r * 4 + c)] = obj_to_world_3x4[r * 4 + c] * float(1u << levels);
+      m[size_t(r * 4 + 3)] = obj_to_world_3x4[r * 4 + 3];
+    }
+    return m;
+  }
   std::optional<uint8_t> get(UVec3 c) {
     int32_t v = -1;
     check(dust_hip_model_get_voxels(h_, c.data(), &v, 1));
@@ -265,7 +288,7 @@ class VoxGeometry {
   }
   uint32_t num_blocks;
  private:
-  explicit VoxGeometry(DustHipModel* adopted) : num_blocks(0), h_(adopted) {  // (detach_islands: the handle is already ours)
+  explicit VoxGeometry(DustHipModel* adopted) : num_blocks(0), h_(adopted) {  // (detach_islands, reduce: the handle is already ours)
     uint64_t nm = 0;
     check(dust_hip_model_info(h_, &num_blocks, &nm));
   }
