@@ -237,6 +237,16 @@ class ReduceResult(C.Structure):  # DustHipReduceResult, 16 bytes: the solid vox
 REDUCE_MAX_LEVELS = 8
 
 
+class Census(C.Structure):  # DustHipCensus, 40 bytes: what the voxels a shape covers hold -- counts, the bounds and the coordinate sums of the solid ones
+    _fields_ = [("covered", C.c_uint32), ("solid", C.c_uint32), ("lo", C.c_uint8 * 3), ("reserved0", C.c_uint8), ("hi", C.c_uint8 * 3),
+                ("reserved1", C.c_uint8), ("sum", C.c_uint64 * 3)]
+
+
+MAX_CENSUS_SHAPES = 65536
+MAX_CENSUS_TABLES = 4096
+CENSUS_BINS = 256
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -314,6 +324,7 @@ SYMBOLS = {
     "dust_hip_model_distance_at": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_distance_apply": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_reduce": (C.c_int, [_P, _P, C.POINTER(_P), _P]),
+    "dust_hip_model_census": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

@@ -49,6 +49,8 @@ FLOOD_RESULT_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("seeds_
 DISTANCE_RESULT_DTYPE = np.dtype([("targets", "<u4"), ("near", "<u4"), ("far", "<u4"), ("largest", "<u4"), ("largest_key", "<u4"), ("reserved", "<u4", 3)])
 # DustHipReduceResult, 16 bytes: the voxel counts of a dust_hip_model_reduce and the extent of the new model
 REDUCE_RESULT_DTYPE = np.dtype([("src_voxels", "<u4"), ("voxels", "<u4"), ("extent", "<u4"), ("reserved", "<u4")])
+# DustHipCensus, 40 bytes: one shape's record of dust_hip_model_census
+CENSUS_DTYPE = np.dtype([("covered", "<u4"), ("solid", "<u4"), ("lo", "u1", 3), ("reserved0", "u1"), ("hi", "u1", 3), ("reserved1", "u1"), ("sum", "<u8", 3)])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -362,6 +364,18 @@ class Model:
         changed = np.zeros(len(shapes), np.uint32)
         L.check(self._lib.dust_hip_model_edit_shapes(self._h, _ptr(shapes), len(shapes), _ptr(changed)))
         return changed
+
+    def census(self, shapes, tables=True):
+        """What the voxels inside shapes hold (dust_hip_model_census): `shapes` an EDIT_SHAPE_DTYPE array as Model.edit_shapes takes
+        it (op and palette are ignored), each counted on its own against the model as it stands; nothing changes. Returns (records,
+        counts): records a CENSUS_DTYPE array (covered, solid, the bounds lo / hi and the coordinate sums of the solid covered voxels),
+        counts (n, 256) uint32 with counts[i, 0] the covered voxels that hold None and counts[i, 1 + p] those that hold palette index p
+        -- or None with tables=False (then up to L.MAX_CENSUS_SHAPES shapes instead of L.MAX_CENSUS_TABLES)."""
+        shapes = np.ascontiguousarray(shapes, EDIT_SHAPE_DTYPE).reshape(-1)
+        records = np.zeros(len(shapes), CENSUS_DTYPE)
+        counts = np.zeros((len(shapes), L.CENSUS_BINS), np.uint32) if tables else None
+        L.check(self._lib.dust_hip_model_census(self._h, _ptr(shapes), len(shapes), _ptr(records), _ptr(counts) if tables else None))
+        return records, counts
 
     def find_islands(self, connectivity=L.ISLANDS_FACES, anchor=None, capacity=None, records=None):
         """Label the model's connected solid voxels (dust_hip_model_find_islands): returns (n, records) -- n the number of islands,

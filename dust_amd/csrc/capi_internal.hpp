@@ -162,6 +162,9 @@ struct DustHipContext : RefCounted {
   // model casts (cast.hip): the brick masks of a dust_hip_model_cast source that is not editable (2 MiB, EditArgs::brick_mask's layout),
   // scattered from its blocks by every such call: nothing is cached across calls
   DeviceBuffer cast_mask;
+  // model censuses (census.hip): one chunk's cell lists. The context's, not an EditState's: the model of a dust_hip_model_census may not
+  // be editable (its shape records, accumulators and tables go through stage_in / stage_out / stage_aux)
+  DeviceBuffer census_cells, census_starts, census_ids;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)

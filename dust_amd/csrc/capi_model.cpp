@@ -1,8 +1,8 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
 // edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip), model floods (flood.hip), model
-// distances (distance.hip) and model reductions (reduce.hip). What needs no device is in three headers: the hierarchy build itself
+// distances (distance.hip), model reductions (reduce.hip) and model censuses (census.hip). What needs no device is in three headers: the hierarchy build itself
 // (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp, the arithmetic on the callers' records (conversion, chunks,
-// cell lists, cast hits) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
+// cell lists, cast hits, census records) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -306,10 +306,40 @@ DustStatus field_apply(DustHipModel* m, VoxelField EditState::*which, DustStatus
   });
 }
 
-// The calls batched by root cell (shape edits, stamps), from the records that cover something (`dev`, in call order; index[k] is record
-// k's place among the caller's n) to the caller's `changed`. Order-preserving chunks, each one launch: its records binned into the 4096
-// root cells, an ascending list of u16 record ids per cell in CSR form, one workgroup per non-empty cell. `launch(c0, a)` gets the
-// chunk's first record and the arguments every such kernel takes (grid, cell lists, changed, n_cells); it adds its own and launches.
+// The chunks of a call batched by root cell (shape edits, stamps, censuses), from the records that cover something (`dev`, in call
+// order) to one launch each. Order-preserving chunks: a chunk's records binned into the 4096 root cells, an ascending list of u16
+// record ids per cell in CSR form, uploaded into `cells` / `starts` / `ids` (the caller's buffers: an EditState's, or the context's for a
+// model that has none); one workgroup per non-empty cell. `launch(c0, a)` gets the chunk's first record and arguments with the cell
+// lists filled in (cells, cell_start, ids, n_cells); it adds its own and launches. `lists` is the caller's: the last chunk's copies read
+// it until the caller has waited for the stream.
+template <class Args, class Rec, class Launch>
+DustStatus for_each_chunk(DustHipContext* ctx, const std::vector<Rec>& dev, dust::CellLists& lists, DeviceBuffer& cells, DeviceBuffer& starts, DeviceBuffer& ids,
+                          Launch&& launch) {
+  hipStream_t st = ctx->stream;
+  DustStatus s;
+  for (size_t c0 = 0; c0 < dev.size();) {
+    const size_t c1 = dust::chunk_end(dev, c0, dust::kShapeChunkIds, dust::kShapeChunkRecords);
+    if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
+    lists.bin(dev, c0, c1);
+    if ((s = grow(ctx, cells, lists.cells.size() * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, starts, lists.starts.size() * 4)) != DUST_OK) return s;
+    if ((s = grow(ctx, ids, lists.ids.size() * 2)) != DUST_OK) return s;
+    HIP_TRY(hipMemcpyAsync(cells.p, lists.cells.data(), lists.cells.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(starts.p, lists.starts.data(), lists.starts.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ids.p, lists.ids.data(), lists.ids.size() * 2, hipMemcpyHostToDevice, st));
+    Args a{};
+    a.cells = static_cast<const uint32_t*>(cells.p);
+    a.cell_start = static_cast<const uint32_t*>(starts.p);
+    a.ids = static_cast<const uint16_t*>(ids.p);
+    a.n_cells = uint32_t(lists.cells.size());
+    if ((s = launch(c0, a)) != DUST_OK) return s;
+    c0 = c1;
+  }
+  return DUST_OK;
+}
+
+// The calls that write the grid (shape edits, stamps): index[k] is record k's place among the caller's n. The chunks as above; `launch`
+// gets the grid and the chunk's part of `changed` besides. Then the rebuild, and the counts to the caller's `changed`.
 template <class Args, class Rec, class Launch>
 DustStatus batched_edit(DustHipModel* m, const std::vector<Rec>& dev, const std::vector<uint32_t>& index, uint32_t n, uint32_t* changed, Launch&& launch) {
   DustHipContext* ctx = m->ctx;
@@ -325,26 +355,12 @@ DustStatus batched_edit(DustHipModel* m, const std::vector<Rec>& dev, const std:
     HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
   }
   dust::CellLists lists;
-  for (size_t c0 = 0; c0 < live;) {
-    const size_t c1 = dust::chunk_end(dev, c0, dust::kShapeChunkIds, dust::kShapeChunkRecords);
-    if (c0 != 0) HIP_TRY(hipStreamSynchronize(st));  // the previous chunk's copies have left the host lists
-    lists.bin(dev, c0, c1);
-    if ((s = grow(ctx, es.shape_cells, lists.cells.size() * 4)) != DUST_OK) return s;
-    if ((s = grow(ctx, es.shape_starts, lists.starts.size() * 4)) != DUST_OK) return s;
-    if ((s = grow(ctx, es.shape_ids, lists.ids.size() * 2)) != DUST_OK) return s;
-    HIP_TRY(hipMemcpyAsync(es.shape_cells.p, lists.cells.data(), lists.cells.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(es.shape_starts.p, lists.starts.data(), lists.starts.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(es.shape_ids.p, lists.ids.data(), lists.ids.size() * 2, hipMemcpyHostToDevice, st));
-    Args a{};
+  s = for_each_chunk<Args>(ctx, dev, lists, es.shape_cells, es.shape_starts, es.shape_ids, [&](size_t c0, Args& a) -> DustStatus {
     a.grid = static_cast<uint8_t*>(es.grid.p);
-    a.cells = static_cast<const uint32_t*>(es.shape_cells.p);
-    a.cell_start = static_cast<const uint32_t*>(es.shape_starts.p);
-    a.ids = static_cast<const uint16_t*>(es.shape_ids.p);
     a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
-    a.n_cells = uint32_t(lists.cells.size());
-    if ((s = launch(c0, a)) != DUST_OK) return s;
-    c0 = c1;
-  }
+    return launch(c0, a);
+  });
+  if (s != DUST_OK) return s;
   if (live) HIP_TRY(hipMemcpyAsync(counts.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
   s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
   if (s != DUST_OK) return s;
@@ -945,6 +961,58 @@ DustStatus dust_hip_model_reduce(const DustHipModel* src, const DustHipReduce* q
     if ((s = rebuild_and_refresh(fresh.m, *fresh.m->edit)) != DUST_OK) return s;  // synchronises
     if (result) *result = dust::reduce_result(plan, n[0], n[1]);
     *out = retain(fresh.m);  // the caller's reference (the guard drops the builder's)
+    return DUST_OK;
+  });
+}
+
+// ---- model censuses (census.hip k_census): the shapes of edit_shapes held against the grid, nothing written, no rebuild
+DustStatus dust_hip_model_census(const DustHipModel* m, const DustHipEditShape* shapes, uint32_t n, DustHipCensus* records, uint32_t* counts) {
+  if (!m || (n && !shapes)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (n > DUST_HIP_MAX_CENSUS_SHAPES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_CENSUS_SHAPES shapes in one call");
+  if (counts && n > DUST_HIP_MAX_CENSUS_TABLES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_CENSUS_TABLES shapes in a call that asks for tables");
+  DustStatus s = editable_kind(m);  // (before the shapes are looked at)
+  if (s != DUST_OK) return s;
+  for (uint32_t i = 0; i < n; ++i)
+    if (shapes[i].kind > DUST_HIP_SHAPE_CAPSULE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown shape kind");
+  if (n == 0 || (!records && !counts)) return DUST_OK;
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    std::vector<dust::DevEditShape> dev;
+    std::vector<uint32_t> index;
+    dust::live_records<dust::device_census_shape>(shapes, n, dev, index);
+    const size_t live = dev.size();
+    std::vector<dust::CensusAcc> acc(live);
+    std::vector<uint32_t> rows(counts ? live * dust::kCensusBins : 0);
+    if (live) {
+      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_TRY(join_side(ctx));
+      hipStream_t st = ctx->stream;
+      const uint8_t* grid = nullptr;
+      if ((s = source_grid(ctx, nullptr, m, &grid)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_in, live * sizeof(dust::DevEditShape))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, live * sizeof(dust::CensusAcc))) != DUST_OK) return s;
+      if (counts && (s = grow(ctx, ctx->stage_aux, rows.size() * 4)) != DUST_OK) return s;
+      dust::CensusAcc* dev_acc = static_cast<dust::CensusAcc*>(ctx->stage_out.p);
+      uint32_t* dev_rows = counts ? static_cast<uint32_t*>(ctx->stage_aux.p) : nullptr;
+      HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, dev.data(), live * sizeof(dust::DevEditShape), hipMemcpyHostToDevice, st));
+      HIP_TRY(dust::launch_census_init(dev_acc, uint32_t(live), st));
+      if (counts) HIP_TRY(hipMemsetAsync(dev_rows, 0, rows.size() * 4, st));
+      dust::CellLists lists;
+      s = for_each_chunk<dust::CensusArgs>(ctx, dev, lists, ctx->census_cells, ctx->census_starts, ctx->census_ids, [&](size_t c0, dust::CensusArgs& a) -> DustStatus {
+        a.grid = grid;
+        a.shapes = static_cast<const dust::DevEditShape*>(ctx->stage_in.p) + c0;
+        a.acc = dev_acc + c0;
+        a.tables = counts ? dev_rows + c0 * dust::kCensusBins : nullptr;
+        HIP_TRY(dust::launch_census(a, st));
+        return DUST_OK;
+      });
+      if (s != DUST_OK) return s;
+      HIP_TRY(hipMemcpyAsync(acc.data(), dev_acc, live * sizeof(dust::CensusAcc), hipMemcpyDeviceToHost, st));
+      if (counts) HIP_TRY(hipMemcpyAsync(rows.data(), dev_rows, rows.size() * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));  // (the host vectors and lists above stay alive until the copies are done)
+    }
+    if (records) dust::census_records(acc.data(), index, n, records);
+    if (counts) dust::census_tables(rows.data(), index, n, counts);
     return DUST_OK;
   });
 }

@@ -26,6 +26,7 @@
 #include "cell_records.hpp"
 #include "edit.hpp"
 #include "scan.hpp"
+#include "shape_cover.hpp"
 
 namespace dust {
 
@@ -68,11 +69,8 @@ __global__ void k_edit_read(EditArgs e) {
 
 // dust_hip_model_edit_shapes: carve / fill / paint / place boxes, spheres and capsules straight into the grid, on the skeleton of
 // cell_records.hpp: a workgroup per root cell that some shape's bounds reach, the cell's shape list walked once in call order. Every
-// shape record is wave-uniform and rejected by its integer brick bounds before any per-voxel arithmetic. Membership is the header's float32 contract, operation for operation (-ffp-contract=off; `/` is the IEEE division).
-namespace {
-__device__ __forceinline__ float dot3(float u0, float u1, float u2, float v0, float v1, float v2) { return (u0 * v0 + u1 * v1) + u2 * v2; }
-}  // namespace
-
+// shape record is wave-uniform and rejected by its integer brick bounds before any per-voxel arithmetic. Membership is the header's
+// float32 contract, operation for operation: shape_cover.hpp, the text k_census (census.hip) runs too.
 __global__ void __launch_bounds__(256) k_edit_shapes(EditShapeArgs a) {
   walk_cell_records(a, [&](CellBricks& c, uint32_t id) -> uint32_t {
     const DevEditShape s = a.shapes[id];
@@ -82,29 +80,14 @@ __global__ void __launch_bounds__(256) k_edit_shapes(EditShapeArgs a) {
     // voxel centres: small integers + 0.5, exact in float32
     const Voxel p = brick_voxel(c.bx, c.by0, c.bz0, c.lane);
     const float cx = (float)p.x + 0.5f, cy0 = (float)p.y + 0.5f, cz0 = (float)p.z + 0.5f;
-    const float rr = s.radius * s.radius;
-    const float ab0 = s.b[0] - s.a[0], ab1 = s.b[1] - s.a[1], ab2 = s.b[2] - s.a[2];
-    const float l = dot3(ab0, ab1, ab2, ab0, ab1, ab2);
-    const float d0 = cx - s.a[0];
+    const ShapeCover cover = shape_cover(s.a, s.b, s.kind, s.radius);
     uint32_t n = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       const uint32_t by = c.by0 + (uint32_t)(k >> 2), bz = c.bz0 + (uint32_t)(k & 3);
       if (by < lo_y || by > hi_y || bz < lo_z || bz > hi_z) continue;
       const float cy = cy0 + (float)((k >> 2) * 4), cz = cz0 + (float)((k & 3) * 4);  // exact
-      bool in;
-      if (s.kind == 0u) {
-        in = s.a[0] <= cx && cx <= s.b[0] && s.a[1] <= cy && cy <= s.b[1] && s.a[2] <= cz && cz <= s.b[2];
-      } else {
-        const float d1 = cy - s.a[1], d2 = cz - s.a[2];
-        if (s.kind == 1u) {
-          in = dot3(d0, d1, d2, d0, d1, d2) <= rr;
-        } else {
-          const float h = l == 0.0f ? 0.0f : fminf(fmaxf(dot3(d0, d1, d2, ab0, ab1, ab2) / l, 0.0f), 1.0f);
-          const float q0 = d0 - ab0 * h, q1 = d1 - ab1 * h, q2 = d2 - ab2 * h;
-          in = dot3(q0, q1, q2, q0, q1, q2) <= rr;
-        }
-      }
+      const bool in = shape_covers(cover, cx, cy, cz);
       const uint32_t g = c.v[k];
       const uint32_t to = g ? (s.solid_to == kEditKeep ? g : s.solid_to) : s.empty_to;
       n += c.set(k, in && to != g, to);

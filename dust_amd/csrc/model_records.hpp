@@ -1,6 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp), cuts a call into chunks, bins a chunk's records into
-// root cells and decodes a cast's result. No HIP call, no handle, no error state: tests/cpp/model_records_test.cpp drives it on a CPU.
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp), cuts a call into chunks, bins a chunk's records into
+// root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
+// tests/cpp/model_records_test.cpp and tests/cpp/census_records_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -9,12 +10,14 @@
 
 #include "../../include/dust_hip.h"
 #include "cast.hpp"
+#include "census.hpp"
 #include "distance.hpp"
 #include "edit.hpp"
 #include "stamp.hpp"
 
 namespace dust {
 
+static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
 static_assert(sizeof(DustHipCast) == 48 && sizeof(DustHipCastHit) == 32 && sizeof(DevCast) == 48 && sizeof(CastItem) == 8 && sizeof(CastAcc) == 16,
               "cast records");
@@ -31,9 +34,11 @@ inline bool valid_orient(uint32_t o) {
   return ((1u << p0) | (1u << p1) | (1u << p2)) == 7u;
 }
 
-// The two grid bytes of the operation and conservative voxel bounds -- the shape's extent padded by more than a voxel (the float32
-// formulas stay within a small fraction of a voxel of the real distance for coordinates up to 65 536), clipped to the tree.
-inline bool device_shape(const DustHipEditShape& s, DevEditShape& d) {
+// Conservative voxel bounds of a shape (packed x | y << 8 | z << 16, inclusive) -- its extent padded by more than a voxel (the float32
+// formulas stay within a small fraction of a voxel of the real distance for coordinates up to 65 536), clipped to the tree. false: the
+// shape covers nothing (a non-finite value, a box with a > b, a radius or coordinate outside its limits, wholly outside the tree).
+// `op`, `palette` and `reserved` are not looked at: the half of device_shape a census shares with an edit.
+inline bool shape_bounds(const DustHipEditShape& s, uint32_t& packed_lo, uint32_t& packed_hi) {
   const bool box = s.kind == DUST_HIP_SHAPE_BOX, sphere = s.kind == DUST_HIP_SHAPE_SPHERE;
   double lo[3], hi[3];
   for (int r = 0; r < 3; ++r) {
@@ -55,10 +60,23 @@ inline bool device_shape(const DustHipEditShape& s, DevEditShape& d) {
     vlo[r] = l < 0.0 ? 0u : uint32_t(l);
     vhi[r] = h > 255.0 ? 255u : uint32_t(h);
   }
+  packed_lo = vlo[0] | (vlo[1] << 8) | (vlo[2] << 16);
+  packed_hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
+  return true;
+}
+// ... and the shape itself as the membership text (shape_cover.hpp) reads it: a box without a radius, a sphere's b its centre
+inline void device_shape_geometry(const DustHipEditShape& s, DevEditShape& d) {
   std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.b, s.b, sizeof(d.b));
   d.kind = s.kind;
-  d.radius = box ? 0.0f : s.radius;
-  if (sphere) std::memcpy(d.b, s.a, sizeof(d.b));
+  d.radius = s.kind == DUST_HIP_SHAPE_BOX ? 0.0f : s.radius;
+  if (s.kind == DUST_HIP_SHAPE_SPHERE) std::memcpy(d.b, s.a, sizeof(d.b));
+}
+
+// A shape edit's record: the bounds, the geometry and the two grid bytes of the operation.
+inline bool device_shape(const DustHipEditShape& s, DevEditShape& d) {
+  uint32_t lo, hi;
+  if (!shape_bounds(s, lo, hi)) return false;
+  device_shape_geometry(s, d);
   const uint32_t byte = uint32_t(s.palette) + 1u;
   switch (s.op) {
     case DUST_HIP_EDIT_CARVE: d.solid_to = 0; d.empty_to = 0; break;
@@ -66,9 +84,40 @@ inline bool device_shape(const DustHipEditShape& s, DevEditShape& d) {
     case DUST_HIP_EDIT_PAINT: d.solid_to = byte; d.empty_to = 0; break;
     default: d.solid_to = kEditKeep; d.empty_to = byte; break;  // PLACE
   }
-  d.lo = vlo[0] | (vlo[1] << 8) | (vlo[2] << 16);
-  d.hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
+  d.lo = lo; d.hi = hi;
   return true;
+}
+
+// A census's record (dust_hip_model_census): the same bounds and geometry; the operation is ignored, its two bytes stay 0.
+inline bool device_census_shape(const DustHipEditShape& s, DevEditShape& d) {
+  if (!shape_bounds(s, d.lo, d.hi)) return false;
+  device_shape_geometry(s, d);
+  d.solid_to = d.empty_to = 0;
+  return true;
+}
+
+// What a census's caller gets from the device's accumulator; null: a shape that covers nothing -- the zero record, bounds 255 / 0
+// (what a shape whose covered voxels are all empty has too).
+inline DustHipCensus census_record(const CensusAcc* acc) {
+  DustHipCensus c{};
+  const bool solid = acc && acc->solid != 0u;
+  for (int r = 0; r < 3; ++r) {
+    c.lo[r] = solid ? uint8_t(acc->lo[r]) : uint8_t(255);
+    c.hi[r] = solid ? uint8_t(acc->hi[r]) : uint8_t(0);
+    c.sum[r] = solid ? acc->sum[r] : 0u;
+  }
+  if (acc) { c.covered = acc->covered; c.solid = acc->solid; }
+  return c;
+}
+// the n records of a call: those of its live shapes (acc[k] belongs to the caller's shape index[k]), the zero record for the rest
+inline void census_records(const CensusAcc* acc, const std::vector<uint32_t>& index, uint32_t n, DustHipCensus* records) {
+  for (uint32_t i = 0; i < n; ++i) records[i] = census_record(nullptr);
+  for (size_t k = 0; k < index.size(); ++k) records[index[k]] = census_record(acc + k);
+}
+// ... and its n rows of per-material counts (DUST_HIP_CENSUS_BINS each): zero rows for the shapes that cover nothing
+inline void census_tables(const uint32_t* rows, const std::vector<uint32_t>& index, uint32_t n, uint32_t* counts) {
+  std::fill(counts, counts + size_t(n) * kCensusBins, 0u);
+  for (size_t k = 0; k < index.size(); ++k) std::memcpy(counts + size_t(index[k]) * kCensusBins, rows + k * kCensusBins, kCensusBins * 4);
 }
 
 // The image box clipped to the tree, one affine map per destination axis, the operation as a table. Everything in int64: any int32

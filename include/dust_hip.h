@@ -607,6 +607,47 @@ typedef struct DustHipReduceResult {  /* 16 bytes */
 } DustHipReduceResult;
 DustStatus dust_hip_model_reduce(const DustHipModel* src, const DustHipReduce*, DustHipModel** out,
                                  DustHipReduceResult* result /* may be NULL */);
+/* Model censuses: what a region holds, counted on the device without changing anything -- what a blast will remove and of which
+ * materials (loot, debris colour, damage, score), how much ore a chunk has, what a piece weighs given a density per material, whether
+ * a box is empty enough to build in. The read-only sibling of edit_shapes: ask first, carve after.
+ *
+ * Shapes: they are edit_shapes' shapes, DustHipEditShape records in the model's tree coordinates. A shape covers the voxels whose centre
+ * it contains, under the float32 contract stated at edit_shapes, operation for operation (the device runs one text for both calls),
+ * clipped to the tree. op, palette and reserved are ignored and not validated: an array built for edit_shapes can be passed unchanged.
+ * Independence: every shape is counted on its own against the model as it stands. Unlike edits, order does not matter and overlapping
+ * shapes each see every voxel.
+ * Records: covered, the voxels of the tree whose centre the shape contains; solid, those of them that are solid; lo / hi, the inclusive
+ * bounds of the solid covered voxels (255, 255, 255 / 0, 0, 0 when solid == 0); sum, the sums of x, of y and of z over the solid
+ * covered voxels (centre of mass = sum / solid + 0.5); the reserved bytes are 0. An edit_shapes CARVE of the same shape changes exactly
+ * `solid` voxels, a PLACE exactly covered - solid.
+ * Tables: counts[i * 256 + 0] is the number of covered voxels that hold None, counts[i * 256 + 1 + p] the number that hold palette
+ * index p (0..254). A row sums to covered, and its entries 1..255 sum to solid.
+ * Shapes that cover nothing get the zero record (bounds 255 / 0, as for solid == 0) and a zero row. The cases are exactly those of
+ * edit_shapes: a non-finite value in a field the kind reads; a[r] > b[r] on a box; radius < 0 on a sphere or capsule; for spheres and
+ * capsules any |coordinate| or radius above 65 536; and a shape wholly outside the tree.
+ * The model is only read. One that is not editable stays not editable (it is expanded into the context's 16 MiB scratch grid, as a
+ * stamp's or a reduction's source is); an editable one is read in place, edits included. The generation does not move -- committed
+ * scenes that instance the model stay valid --, and the island labelling and both fields stay valid.
+ * Everything is integer arithmetic: two runs give the same bytes.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, the outputs untouched: a null model; null shapes with n > 0; n > DUST_HIP_MAX_CENSUS_SHAPES;
+ * counts != NULL with n > DUST_HIP_MAX_CENSUS_TABLES (a row is 1 KiB); a kind above CAPSULE. DUST_ERR_UNSUPPORTED exactly where
+ * set_voxels returns it (4096^3 trees, models that hold material byte 255), before the shapes are looked at. n == 0 is a no-op; records
+ * and counts may each be NULL, and with both NULL the call validates and returns. Synchronous, like every model call.
+ * Out of scope: an asynchronous form; world-space shapes over a scene's instances; regions named by an island key or by a
+ * field's range; second moments (an inertia tensor). */
+#define DUST_HIP_MAX_CENSUS_SHAPES 65536u   /* records only */
+#define DUST_HIP_MAX_CENSUS_TABLES 4096u    /* with per-material tables (1 KiB each) */
+#define DUST_HIP_CENSUS_BINS 256u
+typedef struct DustHipCensus {   /* 40 bytes, laid out like DustHipIsland */
+  uint32_t covered;              /* voxels of the tree whose centre the shape contains */
+  uint32_t solid;                /* ... of them solid */
+  uint8_t lo[3], reserved0;      /* inclusive bounds of the solid covered voxels; 255,255,255 when solid == 0 */
+  uint8_t hi[3], reserved1;      /* 0,0,0 when solid == 0; reserved bytes 0 */
+  uint64_t sum[3];               /* sums of x, of y, of z over the solid covered voxels */
+} DustHipCensus;
+DustStatus dust_hip_model_census(const DustHipModel*, const DustHipEditShape* shapes, uint32_t n,
+                                 DustHipCensus* records /* n, may be NULL */,
+                                 uint32_t* counts /* n * 256, may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

@@ -271,6 +271,16 @@ class VoxGeometry {
     check(dust_hip_model_reduce(h_, &query, &coarse, result));
     return std::unique_ptr<VoxGeometry>(new VoxGeometry(coarse));
   }
+  // Model censuses (dust_hip_model_census): what the voxels inside edit_shapes' shapes hold, each shape counted on its own against
+  // the geometry as it stands on the device; nothing changes (op and palette are ignored: ask first, carve after). Returns one record
+  // per shape; `counts`, if given, receives DUST_HIP_CENSUS_BINS counters per shape: [0] the covered voxels that hold None, [1 + p] those
+  // that hold palette index p (at most DUST_HIP_MAX_CENSUS_TABLES shapes then).
+  std::vector<DustHipCensus> census(const std::vector<DustHipEditShape>& shapes, std::vector<uint32_t>* counts = nullptr) const {
+    std::vector<DustHipCensus> records(shapes.size());
+    if (counts) counts->assign(shapes.size() * size_t(DUST_HIP_CENSUS_BINS), 0u);
+    check(dust_hip_model_census(h_, shapes.data(), uint32_t(shapes.size()), records.data(), counts ? counts->data() : nullptr));
+    return records;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
