@@ -247,6 +247,26 @@ MAX_CENSUS_TABLES = 4096
 CENSUS_BINS = 256
 
 
+class SurfaceQuery(C.Structure):  # DustHipSurfaceQuery, 48 bytes: the directions that count, the palette filter and the inclusive region box
+    _fields_ = [("struct_size", C.c_uint32), ("faces", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class SurfaceResult(C.Structure):  # DustHipSurfaceResult, 64 bytes: listed voxels, their exposed faces (in all, per direction), solid voxels, bounds
+    _fields_ = [("voxels", C.c_uint32), ("faces", C.c_uint32), ("by_face", C.c_uint32 * 6), ("solid", C.c_uint32),
+                ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("reserved", C.c_uint32 * 5)]
+
+
+class SurfaceVoxel(C.Structure):  # DustHipSurfaceVoxel, 8 bytes: a listed voxel's key, its exposed faces and its palette index
+    _fields_ = [("key", C.c_uint32), ("faces", C.c_uint8), ("palette", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+FACE_NEG_X, FACE_POS_X, FACE_NEG_Y, FACE_POS_Y, FACE_NEG_Z, FACE_POS_Z = 1, 2, 4, 8, 16, 32
+FACES_ALL = 63
+SURFACE_WALLS = 1
+SURFACE_BINS = 256
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -325,6 +345,8 @@ SYMBOLS = {
     "dust_hip_model_distance_apply": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_reduce": (C.c_int, [_P, _P, C.POINTER(_P), _P]),
     "dust_hip_model_census": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    "dust_hip_model_surface": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
+    "dust_hip_model_surface_apply": (C.c_int, [_P, _P, C.c_int32, _u32p]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

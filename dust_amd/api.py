@@ -51,6 +51,10 @@ DISTANCE_RESULT_DTYPE = np.dtype([("targets", "<u4"), ("near", "<u4"), ("far", "
 REDUCE_RESULT_DTYPE = np.dtype([("src_voxels", "<u4"), ("voxels", "<u4"), ("extent", "<u4"), ("reserved", "<u4")])
 # DustHipCensus, 40 bytes: one shape's record of dust_hip_model_census
 CENSUS_DTYPE = np.dtype([("covered", "<u4"), ("solid", "<u4"), ("lo", "u1", 3), ("reserved0", "u1"), ("hi", "u1", 3), ("reserved1", "u1"), ("sum", "<u8", 3)])
+# DustHipSurfaceResult (64 bytes) and DustHipSurfaceVoxel (8 bytes): the result and the list entries of dust_hip_model_surface
+SURFACE_RESULT_DTYPE = np.dtype([("voxels", "<u4"), ("faces", "<u4"), ("by_face", "<u4", 6), ("solid", "<u4"), ("lo", "u1", 3), ("pad0", "u1"),
+                                 ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 5)])
+SURFACE_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("faces", "u1"), ("palette", "u1"), ("reserved", "<u2")])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -376,6 +380,43 @@ class Model:
         counts = np.zeros((len(shapes), L.CENSUS_BINS), np.uint32) if tables else None
         L.check(self._lib.dust_hip_model_census(self._h, _ptr(shapes), len(shapes), _ptr(records), _ptr(counts) if tables else None))
         return records, counts
+
+    def _surface_query(self, faces, palette, region, walls):
+        q = L.SurfaceQuery(struct_size=C.sizeof(L.SurfaceQuery), faces=faces, flags=L.SURFACE_WALLS if walls else 0, palette=palette)
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        return q
+
+    def surface(self, faces=L.FACES_ALL, palette=-1, region=None, walls=False, capacity=None, tables=False):
+        """The exposed faces of the model's solid voxels (dust_hip_model_surface): a face is exposed when the voxel across it is empty
+        (across a face of the tree: empty, or solid with walls=True). `faces` the L.FACE_* directions that count, `palette` -1 for every
+        solid voxel or the one palette index that counts, region = (lo, hi) an inclusive voxel box (None: the whole tree; neighbours
+        outside it are consulted as they are). Returns (result, voxels, counts): result a SURFACE_RESULT_DTYPE record (voxels, faces,
+        by_face, solid, lo, hi); voxels a SURFACE_VOXEL_DTYPE array (key x << 16 | y << 8 | z, faces, palette) of the first
+        min(result.voxels, capacity) listed voxels in the order of Model.read()'s blocks, then ascending voxel bit -- capacity=None makes
+        two calls, one to count and one to list everything; counts (6, 256) uint32 with counts[d, 1 + p] the exposed faces of direction
+        d on listed voxels of palette index p, or None with tables=False. The model is only read."""
+        q = self._surface_query(faces, palette, region, walls)
+        out = np.zeros(1, SURFACE_RESULT_DTYPE)
+        counts = np.zeros((6, L.SURFACE_BINS), np.uint32) if tables else None
+        if capacity is None:
+            L.check(self._lib.dust_hip_model_surface(self._h, C.byref(q), _ptr(out), None, 0, None))
+            capacity = int(out[0]["voxels"])
+        voxels = np.zeros(int(capacity), SURFACE_VOXEL_DTYPE)
+        L.check(self._lib.dust_hip_model_surface(self._h, C.byref(q), _ptr(out), _ptr(voxels) if capacity else None, int(capacity),
+                                                 _ptr(counts) if tables else None))
+        return out[0], voxels[: min(int(capacity), int(out[0]["voxels"]))], counts
+
+    def surface_apply(self, value, faces=L.FACES_ALL, palette=-1, region=None, walls=False):
+        """Every voxel Model.surface would list under the same query takes `value`, a palette index or -1 for None
+        (dust_hip_model_surface_apply); what is listed is decided on the model as it stood when the call began, so -1 peels exactly one
+        layer. Returns the number of voxels that changed. Scenes instancing the model must be committed again; both fields and the
+        island labelling are invalid afterwards."""
+        q = self._surface_query(faces, palette, region, walls)
+        changed = C.c_uint32()
+        L.check(self._lib.dust_hip_model_surface_apply(self._h, C.byref(q), int(value), C.byref(changed)))
+        return changed.value
 
     def find_islands(self, connectivity=L.ISLANDS_FACES, anchor=None, capacity=None, records=None):
         """Label the model's connected solid voxels (dust_hip_model_find_islands): returns (n, records) -- n the number of islands,

@@ -1,8 +1,8 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
 // edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip), model floods (flood.hip), model
-// distances (distance.hip), model reductions (reduce.hip) and model censuses (census.hip). What needs no device is in three headers: the hierarchy build itself
+// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip) and model surfaces (surface.hip). What needs no device is in three headers: the hierarchy build itself
 // (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp, the arithmetic on the callers' records (conversion, chunks,
-// cell lists, cast hits, census records) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
+// cell lists, cast hits, census records, surface queries) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -18,6 +18,7 @@
 #include "model_records.hpp"
 #include "reduce.hpp"
 #include "reduce_rule.hpp"
+#include "scan.hpp"
 
 void release(const DustHipModel* cm) {
   DustHipModel* m = const_cast<DustHipModel*>(cm);
@@ -1013,6 +1014,104 @@ DustStatus dust_hip_model_census(const DustHipModel* m, const DustHipEditShape* 
     }
     if (records) dust::census_records(acc.data(), index, n, records);
     if (counts) dust::census_tables(rows.data(), index, n, counts);
+    return DUST_OK;
+  });
+}
+
+// ---- model surfaces (surface.hip): the exposed faces of the solid voxels, decided from the brick masks; counted and listed without
+// writing anything (k_surface_count, k_surface_list), or repainted with the rebuild of an edit behind it (k_surface_apply)
+namespace {
+// what both calls refuse, in the order the header gives: the model's kind before anything of the query is looked at
+DustStatus surface_query(const DustHipModel* m, const DustHipSurfaceQuery* q, dust::SurfaceArgs& a, bool& empty) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  const DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipSurfaceQuery");
+  if (const char* why = dust::device_surface(*q, a, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return DUST_OK;
+}
+}  // namespace
+
+DustStatus dust_hip_model_surface(const DustHipModel* m, const DustHipSurfaceQuery* q, DustHipSurfaceResult* result, DustHipSurfaceVoxel* voxels,
+                                  uint32_t capacity, uint32_t* counts) {
+  dust::SurfaceArgs a{};
+  bool empty = false;
+  DustStatus s = surface_query(m, q, a, empty);
+  if (s != DUST_OK) return s;
+  if (capacity && !voxels) return fail(DUST_ERR_INVALID_ARGUMENT, "null voxels with capacity > 0");
+  return guarded([&]() -> DustStatus {
+    const size_t table_words = size_t(dust::kSurfaceFaces) * dust::kSurfaceBins;
+    uint32_t acc[dust::kSurfaceAccWords] = {};
+    std::vector<uint32_t> rows(counts ? table_words : 0, 0u);
+    if (!empty) {
+      DustHipContext* ctx = m->ctx;
+      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_TRY(join_side(ctx));
+      hipStream_t st = ctx->stream;
+      if ((s = cast_source_masks(ctx, m, &a.brick_mask)) != DUST_OK) return s;
+      // the grid only where a material is needed: for the count pass under a filter or with tables, for the list pass once it is
+      // known that something is listed
+      if ((a.byte != 0u || counts) && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, (dust::kSurfaceAccWords + table_words) * 4)) != DUST_OK) return s;
+      const size_t L = dust::kLattice;
+      if (capacity && (s = lazy_alloc(ctx->surface_table, (L + dust::kSurfaceScanWords) * 4, "the surface list's per-brick table (1 MiB)")) != DUST_OK) return s;
+      a.acc = static_cast<uint32_t*>(ctx->stage_out.p);
+      a.tables = counts ? a.acc + dust::kSurfaceAccWords : nullptr;
+      a.brick_count = capacity ? static_cast<uint32_t*>(ctx->surface_table.p) : nullptr;
+      HIP_TRY(hipMemsetAsync(a.acc, 0, (dust::kSurfaceAccWords + table_words) * 4, st));
+      if (capacity) HIP_TRY(hipMemsetAsync(a.brick_count, 0, L * 4, st));
+      HIP_TRY(dust::launch_surface_count(a, st));
+      HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+      if (counts) HIP_TRY(hipMemcpyAsync(rows.data(), a.tables, table_words * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      const uint32_t staged = std::min(acc[0], capacity);
+      if (staged) {
+        if (!a.grid && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+        if ((s = grow(ctx, ctx->stage_aux, size_t(staged) * sizeof(DustHipSurfaceVoxel))) != DUST_OK) return s;
+        uint32_t* scan_tmp = a.brick_count + L;  // 256 block sums, then the total (acc[0] again)
+        HIP_TRY(dust::launch_table_scan(dust::TableScan{{a.brick_count, nullptr}, {scan_tmp + 256, nullptr}, scan_tmp}, 1, st));
+        a.scan_tmp = scan_tmp;
+        a.voxels = static_cast<uint64_t*>(ctx->stage_aux.p);
+        a.capacity = staged;
+        HIP_TRY(dust::launch_surface_list(a, st));
+        HIP_TRY(hipMemcpyAsync(voxels, a.voxels, size_t(staged) * sizeof(DustHipSurfaceVoxel), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+    }
+    if (result) *result = dust::surface_result(empty ? nullptr : acc);
+    if (counts) std::memcpy(counts, rows.data(), table_words * 4);
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_surface_apply(DustHipModel* m, const DustHipSurfaceQuery* q, int32_t value, uint32_t* changed) {
+  dust::SurfaceApplyArgs a{};
+  bool empty = false;
+  DustStatus s = surface_query(m, q, a.q, empty);
+  if (s != DUST_OK) return s;
+  if (value > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254 (or negative to clear the voxels)");
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    s = begin_edit(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    invalidate_derived(es);
+    uint32_t n = 0;
+    if (!empty) {
+      if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;
+      a.q.brick_mask = static_cast<const uint64_t*>(es.brick_mask.p);  // as the last rebuild left it: nothing writes it before the next
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.to = value < 0 ? 0u : uint32_t(value) + 1u;
+      a.changed = static_cast<uint32_t*>(es.changed.p);
+      HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
+      HIP_TRY(dust::launch_surface_apply(a, st));
+      HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
+    }
+    s = rebuild_and_refresh(m, es);  // synchronises; k_edit_brick_masks makes the masks again from the grid
+    if (s != DUST_OK) return s;
+    if (changed) *changed = n;
     return DUST_OK;
   });
 }

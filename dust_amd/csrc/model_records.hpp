@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp and tests/cpp/census_records_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp and tests/cpp/surface_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -14,8 +14,12 @@
 #include "distance.hpp"
 #include "edit.hpp"
 #include "stamp.hpp"
+#include "surface.hpp"
 
 namespace dust {
+
+static_assert(sizeof(DustHipSurfaceQuery) == 48 && sizeof(DustHipSurfaceResult) == 64 && sizeof(DustHipSurfaceVoxel) == 8 && kSurfaceBins == DUST_HIP_SURFACE_BINS,
+              "surface records");
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
@@ -242,6 +246,40 @@ inline DustHipDistanceResult distance_result(const DistanceAcc& acc) {
     r.largest = uint32_t(acc.best >> 32);
     r.largest_key = 0xFFFFFFu - uint32_t(acc.best & 0xFFFFFFu);
   }
+  return r;
+}
+
+// A surface query as the kernels read it (dust_hip_model_surface, _surface_apply): the directions, the walls, the filter's grid byte,
+// the region clipped to the tree and the root cells it reaches. The pointers are the caller's. nullptr: the query is fine; otherwise
+// why the call refuses it. `empty` (lo > hi on an axis): legal, nothing is looked at and no launch is made -- lo, hi and box are not set.
+inline const char* device_surface(const DustHipSurfaceQuery& q, SurfaceArgs& d, bool& empty) {
+  if (q.faces == 0u || q.faces > DUST_HIP_FACES_ALL) return "faces must be 1..DUST_HIP_FACES_ALL";
+  if ((q.flags & ~DUST_HIP_SURFACE_WALLS) != 0u) return "unknown surface flag";
+  if (q.palette < -1 || q.palette > 254) return "palette must be -1 (every solid voxel) or 0..254";
+  for (int r = 0; r < 3; ++r)
+    if (q.lo[r] >= 256u || q.hi[r] >= 256u) return "region coordinate outside the tree extent";
+  d.faces = q.faces;
+  d.walls = (q.flags & DUST_HIP_SURFACE_WALLS) ? 1u : 0u;
+  d.byte = q.palette < 0 ? 0u : uint32_t(q.palette) + 1u;
+  empty = false;
+  for (int r = 0; r < 3; ++r) empty |= q.lo[r] > q.hi[r];
+  if (empty) return nullptr;
+  for (int r = 0; r < 3; ++r) {
+    d.lo[r] = q.lo[r]; d.hi[r] = q.hi[r];
+    d.box.lo[r] = q.lo[r] >> 4; d.box.hi[r] = q.hi[r] >> 4;
+  }
+  return nullptr;
+}
+// What a surface call's caller gets from the device's kSurfaceAccWords accumulator; null: nothing was looked at -- the zero result,
+// bounds 255 / 0 (what a region without a listed voxel has too).
+inline DustHipSurfaceResult surface_result(const uint32_t* acc) {
+  DustHipSurfaceResult r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  if (!acc) return r;
+  r.voxels = acc[0];
+  for (int d = 0; d < 6; ++d) { r.by_face[d] = acc[1 + d]; r.faces += acc[1 + d]; }
+  r.solid = acc[7];
+  for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[8 + k]); r.hi[k] = uint8_t(acc[11 + k]); }
   return r;
 }
 

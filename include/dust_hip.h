@@ -648,6 +648,78 @@ typedef struct DustHipCensus {   /* 40 bytes, laid out like DustHipIsland */
 DustStatus dust_hip_model_census(const DustHipModel*, const DustHipEditShape* shapes, uint32_t n,
                                  DustHipCensus* records /* n, may be NULL */,
                                  uint32_t* counts /* n * 256, may be NULL */);
+/* Model surfaces: where the solid meets the air, and facing which way -- grass or snow on every voxel whose top face is open, soot on
+ * the faces a blast opened, the surface area of a piece per material (drag, burn rate, paint needed), the surface voxels as a list
+ * with their open faces (spawn points for particles and decals, the input of a host-side mesher or a physics engine, the only voxels
+ * worth sending over a network), and peeling exactly one layer off a solid (weathering) without a cascade.
+ *
+ * Exposed: face d of a solid voxel is exposed when the voxel across d is empty. Across a face of the tree the neighbour is empty, or
+ * solid under DUST_HIP_SURFACE_WALLS. The directions are the DUST_HIP_FACE_* bits: bit 0 -x, 1 +x, 2 -y, 3 +y, 4 -z, 5 +z.
+ * Region: lo / hi is an inclusive voxel box, clipped to the tree (as DustHipFloodQuery's). It selects which voxels are looked at;
+ * neighbours outside the region, but inside the tree, are consulted as they are. lo > hi on an axis is legal and empty: the zero
+ * result (bounds 255 / 0), changed 0.
+ * Listed: a voxel is listed when it is solid, lies inside the clipped region, passes the palette filter (palette -1: every solid
+ * voxel; 0..254: only voxels of that palette index) and has at least one exposed face among query.faces.
+ * Order and capacity: the listed voxels come in the order of the model's Blocks (Tree::iter_leaf, the order dust_hip_model_read
+ * uses), then ascending voxel bit (x&3)<<4 | (y&3)<<2 | (z&3). The first min(result.voxels, capacity) entries are written; the slots
+ * past them are left untouched. result.voxels is the full count whatever the capacity (the convention of find_islands); capacity 0
+ * counts only. A record's faces are its exposed faces among query.faces, never 0; its palette is the voxel's, 0..254.
+ * Tables: counts[d * 256 + 1 + p] is the number of exposed faces of direction d, among query.faces, on listed voxels of palette index
+ * p. Bin 0 of every row is 0, rows of directions not in query.faces are 0, and the table sums to result.faces.
+ * Result: voxels, the listed voxels; faces, their exposed faces among query.faces; by_face, the same per direction (sums to faces);
+ * solid, the solid voxels in the region that pass the palette filter, listed or hidden; lo / hi, the inclusive bounds of the listed
+ * voxels (255, 255, 255 / 0, 0, 0 when there is none, as in DustHipCensus); the reserved words are 0.
+ * dust_hip_model_surface only reads the model, with census's guarantees: one that is not editable stays not editable (its blocks'
+ * masks are scattered into the context's 2 MiB scratch as for a cast's source, and it is expanded into the 16 MiB scratch grid only
+ * when a material is needed: a palette filter, tables, a list); the generation does not move; the island labelling and both fields
+ * stand.
+ * dust_hip_model_surface_apply gives every listed voxel `value`: a palette index 0..254, or negative for None. What is listed is
+ * decided on the model as it stood when the call began: a None peels exactly one layer, the voxels behind do not follow. *changed is
+ * the number of voxels whose value differs afterwards. The model is rebuilt as after flood_apply, byte for byte a host build; the
+ * generation is bumped, the island labelling and both fields are invalid afterwards.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, the outputs untouched: a null model or query; a struct_size below the struct's size; faces
+ * of 0 or above 63; an unknown flag bit; a palette below -1 or above 254; a region coordinate >= 256; null voxels with capacity > 0;
+ * a value > 254. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material byte 255),
+ * before the query is looked at. Both calls are synchronous, like every model call. Everything is integer arithmetic: two runs give
+ * the same bytes.
+ * Out of scope: merged quads (greedy meshing); seams between different materials as faces; faces across the instances of a scene in
+ * world space; 4096^3 trees; an asynchronous form. */
+#define DUST_HIP_FACE_NEG_X 1u
+#define DUST_HIP_FACE_POS_X 2u
+#define DUST_HIP_FACE_NEG_Y 4u
+#define DUST_HIP_FACE_POS_Y 8u
+#define DUST_HIP_FACE_NEG_Z 16u
+#define DUST_HIP_FACE_POS_Z 32u
+#define DUST_HIP_FACES_ALL 63u
+#define DUST_HIP_SURFACE_WALLS 1u  /* flags: the outside of the tree counts as solid (as DUST_HIP_CAST_WALLS, DUST_HIP_DISTANCE_WALLS) */
+#define DUST_HIP_SURFACE_BINS 256u
+typedef struct DustHipSurfaceQuery {   /* 48 bytes */
+  uint32_t struct_size;
+  uint32_t faces;                /* 1..63: the directions that count */
+  uint32_t flags;                /* DUST_HIP_SURFACE_WALLS or 0 */
+  int32_t palette;               /* -1: every solid voxel; 0..254: only voxels of this palette index */
+  uint32_t lo[3], hi[3];         /* inclusive region, clipped to the tree */
+  uint32_t reserved[2];          /* 0 */
+} DustHipSurfaceQuery;
+typedef struct DustHipSurfaceResult {  /* 64 bytes */
+  uint32_t voxels;               /* listed voxels */
+  uint32_t faces;                /* their exposed faces among query.faces */
+  uint32_t by_face[6];           /* ... per direction; sums to faces */
+  uint32_t solid;                /* solid voxels in the region that pass the palette filter (listed + hidden) */
+  uint8_t lo[3], pad0;           /* inclusive bounds of the listed voxels; 255,255,255 when there is none */
+  uint8_t hi[3], pad1;           /* 0,0,0 when there is none; pad bytes 0 */
+  uint32_t reserved[5];          /* 0 */
+} DustHipSurfaceResult;
+typedef struct DustHipSurfaceVoxel {   /* 8 bytes */
+  uint32_t key;                  /* x << 16 | y << 8 | z */
+  uint8_t faces;                 /* exposed & query.faces, never 0 */
+  uint8_t palette;               /* 0..254 */
+  uint16_t reserved;             /* 0 */
+} DustHipSurfaceVoxel;
+DustStatus dust_hip_model_surface(const DustHipModel*, const DustHipSurfaceQuery*, DustHipSurfaceResult* result /* may be NULL */,
+                                  DustHipSurfaceVoxel* voxels /* capacity; may be NULL when capacity == 0 */, uint32_t capacity,
+                                  uint32_t* counts /* 6 * 256, may be NULL */);
+DustStatus dust_hip_model_surface_apply(DustHipModel*, const DustHipSurfaceQuery*, int32_t value, uint32_t* changed /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

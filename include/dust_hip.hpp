@@ -281,6 +281,28 @@ class VoxGeometry {
     check(dust_hip_model_census(h_, shapes.data(), uint32_t(shapes.size()), records.data(), counts ? counts->data() : nullptr));
     return records;
   }
+  // Model surfaces (dust_hip_model_surface / surface_apply): the solid voxels with an exposed face among query.faces inside the
+  // query's region -- counted into the result, listed (every one of them, in the order of the blocks: two calls, one to count), and per
+  // direction and palette index into `counts` (6 * DUST_HIP_SURFACE_BINS), if given. Only reads. surface_apply gives every listed
+  // voxel a palette index (nullopt: None -- exactly one layer is peeled); scenes that instance this geometry must commit() again.
+  std::vector<DustHipSurfaceVoxel> surface(DustHipSurfaceQuery query, DustHipSurfaceResult* result = nullptr, std::vector<uint32_t>* counts = nullptr) const {
+    query.struct_size = sizeof(query);
+    DustHipSurfaceResult r{};
+    check(dust_hip_model_surface(h_, &query, &r, nullptr, 0, nullptr));
+    std::vector<DustHipSurfaceVoxel> voxels(r.voxels);
+    if (counts) counts->assign(6 * size_t(DUST_HIP_SURFACE_BINS), 0u);
+    check(dust_hip_model_surface(h_, &query, &r, voxels.data(), uint32_t(voxels.size()), counts ? counts->data() : nullptr));
+    if (result) *result = r;
+    return voxels;
+  }
+  uint32_t surface_apply(DustHipSurfaceQuery query, std::optional<uint8_t> palette_index) {
+    query.struct_size = sizeof(query);
+    uint32_t changed = 0;
+    check(dust_hip_model_surface_apply(h_, &query, palette_index ? int32_t(*palette_index) : -1, &changed));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
