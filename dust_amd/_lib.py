@@ -267,6 +267,24 @@ SURFACE_WALLS = 1
 SURFACE_BINS = 256
 
 
+class MeshQuery(C.Structure):  # DustHipMeshQuery, 48 bytes: field for field a SurfaceQuery; flags MESH_WALLS | MESH_ANY_PALETTE
+    _fields_ = [("struct_size", C.c_uint32), ("faces", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class MeshQuad(C.Structure):  # DustHipMeshQuad, 8 bytes: the key of the quad's lowest corner voxel, its direction index, palette index and extents - 1
+    _fields_ = [("key", C.c_uint32), ("face", C.c_uint8), ("palette", C.c_uint8), ("du", C.c_uint8), ("dv", C.c_uint8)]
+
+
+class MeshResult(C.Structure):  # DustHipMeshResult, 64 bytes: quads and their area, in all and per direction, the largest quad's area
+    _fields_ = [("quads", C.c_uint32), ("faces", C.c_uint32), ("quads_by_face", C.c_uint32 * 6), ("faces_by_face", C.c_uint32 * 6),
+                ("largest", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+MESH_WALLS = 1
+MESH_ANY_PALETTE = 2
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -347,6 +365,7 @@ SYMBOLS = {
     "dust_hip_model_census": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     "dust_hip_model_surface": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_surface_apply": (C.c_int, [_P, _P, C.c_int32, _u32p]),
+    "dust_hip_model_mesh": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

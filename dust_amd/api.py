@@ -55,6 +55,9 @@ CENSUS_DTYPE = np.dtype([("covered", "<u4"), ("solid", "<u4"), ("lo", "u1", 3), 
 SURFACE_RESULT_DTYPE = np.dtype([("voxels", "<u4"), ("faces", "<u4"), ("by_face", "<u4", 6), ("solid", "<u4"), ("lo", "u1", 3), ("pad0", "u1"),
                                  ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 5)])
 SURFACE_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("faces", "u1"), ("palette", "u1"), ("reserved", "<u2")])
+# DustHipMeshResult (64 bytes) and DustHipMeshQuad (8 bytes): the result and the list entries of dust_hip_model_mesh
+MESH_RESULT_DTYPE = np.dtype([("quads", "<u4"), ("faces", "<u4"), ("quads_by_face", "<u4", 6), ("faces_by_face", "<u4", 6), ("largest", "<u4"), ("reserved", "<u4")])
+MESH_QUAD_DTYPE = np.dtype([("key", "<u4"), ("face", "u1"), ("palette", "u1"), ("du", "u1"), ("dv", "u1")])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -417,6 +420,29 @@ class Model:
         changed = C.c_uint32()
         L.check(self._lib.dust_hip_model_surface_apply(self._h, C.byref(q), int(value), C.byref(changed)))
         return changed.value
+
+    def mesh(self, faces=L.FACES_ALL, palette=-1, region=None, walls=False, any_palette=False, capacity=None):
+        """The exposed faces of the model's solid voxels merged into axis-aligned rectangles (dust_hip_model_mesh). `faces`, `palette`,
+        `region` and `walls` select the faces exactly as in Model.surface. Per direction and slice of its normal axis a run is a maximal
+        stretch of faces of one palette index along u (z for the x and y directions, y for the z directions), and a quad a maximal
+        stack of identical runs along v (y for the x directions, x otherwise); any_palette=True merges across palette indices. This is
+        a canonical partition, not the minimum-count greedy mesh. Returns (result, quads): result a MESH_RESULT_DTYPE record (quads,
+        faces, quads_by_face, faces_by_face, largest); quads a MESH_QUAD_DTYPE array (key x << 16 | y << 8 | z of the lowest corner
+        voxel, face 0..5, palette, du and dv the extents minus 1) of the first min(result.quads, capacity) quads in ascending (face,
+        slice, v0, u0) -- capacity=None makes two calls, one to count and one to list everything. mesh_corners turns the records into
+        corner positions. The model is only read."""
+        q = L.MeshQuery(struct_size=C.sizeof(L.MeshQuery), faces=faces, palette=palette,
+                        flags=(L.MESH_WALLS if walls else 0) | (L.MESH_ANY_PALETTE if any_palette else 0))
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        out = np.zeros(1, MESH_RESULT_DTYPE)
+        if capacity is None:
+            L.check(self._lib.dust_hip_model_mesh(self._h, C.byref(q), _ptr(out), None, 0))
+            capacity = int(out[0]["quads"])
+        quads = np.zeros(int(capacity), MESH_QUAD_DTYPE)
+        L.check(self._lib.dust_hip_model_mesh(self._h, C.byref(q), _ptr(out), _ptr(quads) if capacity else None, int(capacity)))
+        return out[0], quads[: min(int(capacity), int(out[0]["quads"]))]
 
     def find_islands(self, connectivity=L.ISLANDS_FACES, anchor=None, capacity=None, records=None):
         """Label the model's connected solid voxels (dust_hip_model_find_islands): returns (n, records) -- n the number of islands,
@@ -799,6 +825,33 @@ def lod_transform(obj_to_world, levels):
     m = np.array(obj_to_world, np.float32).reshape(3, 4)
     m[:, :3] *= np.float32(2 ** int(levels))
     return m
+
+
+def mesh_corners(quads):
+    """Host only: the corners and normals of Model.mesh's quads -> (corners int32 (N, 4, 3), normals int8 (N, 3)). Corner positions are
+    on the voxel-corner lattice 0..256: voxel (x, y, z) spans x..x+1, y..y+1, z..z+1, and a face of a + direction lies on the plane
+    coordinate + 1. The corners go counter-clockwise seen from outside: cross(c1 - c0, c3 - c0) is normal * area; c0 is the corner
+    at the quad's lowest u and v."""
+    quads = np.asarray(quads, MESH_QUAD_DTYPE)
+    n_quads = len(quads)
+    key = quads["key"].astype(np.int64)
+    face = quads["face"].astype(np.int64)
+    axis = face >> 1
+    rows = np.arange(n_quads)
+    base = np.stack([key >> 16, (key >> 8) & 255, key & 255], axis=1)
+    base[rows, axis] += face & 1
+    u_axis = np.where(axis == 2, 1, 2)                    # the higher-numbered remaining axis
+    v_axis = np.where(axis == 0, 1, 0)
+    along_u = np.zeros((n_quads, 3), np.int64)
+    along_v = np.zeros((n_quads, 3), np.int64)
+    along_u[rows, u_axis] = quads["du"].astype(np.int64) + 1
+    along_v[rows, v_axis] = quads["dv"].astype(np.int64) + 1
+    v_first = np.isin(face, (1, 2, 5))[:, None]           # e_v x e_u points along +n for n = x and z, e_u x e_v for n = y
+    first, second = np.where(v_first, along_v, along_u), np.where(v_first, along_u, along_v)
+    corners = np.stack([base, base + first, base + first + second, base + second], axis=1).astype(np.int32)
+    normals = np.zeros((n_quads, 3), np.int8)
+    normals[rows, axis] = np.where(face & 1, 1, -1)
+    return corners, normals
 
 
 def top_level_build(boxes):

@@ -166,7 +166,8 @@ struct DustHipContext : RefCounted {
   // be editable (its shape records, accumulators and tables go through stage_in / stage_out / stage_aux)
   DeviceBuffer census_cells, census_starts, census_ids;
   // model surfaces (surface.hip): the listed voxels per brick of a dust_hip_model_surface call that lists, scanned in place, with the
-  // scan's block sums and total behind them (1 MiB, allocated by the first such call). The context's: the model may not be editable
+  // scan's block sums and total behind them (1 MiB, allocated by the first such call). The context's: the model may not be editable.
+  // A dust_hip_model_mesh call that lists (mesh.hip) keeps its quads per (direction, slice) in the same table: both calls are synchronous
   DeviceBuffer surface_table;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging

@@ -1,8 +1,8 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
 // edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip), model floods (flood.hip), model
-// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip) and model surfaces (surface.hip). What needs no device is in three headers: the hierarchy build itself
+// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip) model surfaces (surface.hip) and model meshes (mesh.hip). What needs no device is in three headers: the hierarchy build itself
 // (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp, the arithmetic on the callers' records (conversion, chunks,
-// cell lists, cast hits, census records, surface queries) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
+// cell lists, cast hits, census records, surface and mesh queries) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1112,6 +1112,60 @@ DustStatus dust_hip_model_surface_apply(DustHipModel* m, const DustHipSurfaceQue
     s = rebuild_and_refresh(m, es);  // synchronises; k_edit_brick_masks makes the masks again from the grid
     if (s != DUST_OK) return s;
     if (changed) *changed = n;
+    return DUST_OK;
+  });
+}
+
+// ---- model meshes (mesh.hip): the exposed faces merged into rectangles under mesh_rule.hpp's rule, counted (k_mesh_count) and listed
+// (k_mesh_list) without writing anything. Reads the model as dust_hip_model_surface does; the per-slice table is the surface list's.
+DustStatus dust_hip_model_mesh(const DustHipModel* m, const DustHipMeshQuery* q, DustHipMeshResult* result, DustHipMeshQuad* quads, uint32_t capacity) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);  // (before the query is looked at)
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipMeshQuery");
+  dust::MeshArgs a{};
+  bool empty = false;
+  if (const char* why = dust::device_mesh(*q, a, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  if (capacity && !quads) return fail(DUST_ERR_INVALID_ARGUMENT, "null quads with capacity > 0");
+  return guarded([&]() -> DustStatus {
+    uint32_t acc[dust::kMeshAccWords] = {};
+    if (!empty) {
+      DustHipContext* ctx = m->ctx;
+      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_TRY(join_side(ctx));
+      hipStream_t st = ctx->stream;
+      if ((s = cast_source_masks(ctx, m, &a.brick_mask)) != DUST_OK) return s;
+      // the grid only where a material is needed: for the count pass under a filter or where runs stop at a change of material, for
+      // the list pass (a record's palette) once it is known that something is listed
+      if ((a.byte != 0u || !a.any_palette) && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, dust::kMeshAccWords * 4)) != DUST_OK) return s;
+      const size_t L = dust::kLattice;
+      static_assert(dust::kMeshScanWords <= dust::kSurfaceScanWords && dust::kMeshSlices <= dust::kLattice, "the mesh list fits the surface list's table");
+      if (capacity && (s = lazy_alloc(ctx->surface_table, (L + dust::kSurfaceScanWords) * 4, "the surface and mesh lists' table (1 MiB)")) != DUST_OK) return s;
+      a.acc = static_cast<uint32_t*>(ctx->stage_out.p);
+      a.slice_count = capacity ? static_cast<uint32_t*>(ctx->surface_table.p) : nullptr;
+      HIP_TRY(hipMemsetAsync(a.acc, 0, dust::kMeshAccWords * 4, st));
+      if (capacity) HIP_TRY(hipMemsetAsync(a.slice_count, 0, L * 4, st));
+      HIP_TRY(dust::launch_mesh_count(a, st));
+      HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      const DustHipMeshResult counted = dust::mesh_result(acc);
+      const uint32_t staged = std::min(counted.quads, capacity);
+      if (staged) {
+        if (!a.grid && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+        if ((s = grow(ctx, ctx->stage_aux, size_t(staged) * sizeof(DustHipMeshQuad))) != DUST_OK) return s;
+        uint32_t* scan_tmp = a.slice_count + L;  // 256 block sums, then the total (the quads again)
+        HIP_TRY(dust::launch_table_scan(dust::TableScan{{a.slice_count, nullptr}, {scan_tmp + 256, nullptr}, scan_tmp}, 1, st));
+        a.scan_tmp = scan_tmp;
+        a.quads = static_cast<uint64_t*>(ctx->stage_aux.p);
+        a.capacity = staged;
+        HIP_TRY(dust::launch_mesh_list(a, st));
+        HIP_TRY(hipMemcpyAsync(quads, a.quads, size_t(staged) * sizeof(DustHipMeshQuad), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+    }
+    if (result) *result = dust::mesh_result(empty ? nullptr : acc);
     return DUST_OK;
   });
 }

@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp and tests/cpp/surface_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp and tests/cpp/mesh_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -13,6 +13,7 @@
 #include "census.hpp"
 #include "distance.hpp"
 #include "edit.hpp"
+#include "mesh.hpp"
 #include "stamp.hpp"
 #include "surface.hpp"
 
@@ -20,6 +21,9 @@ namespace dust {
 
 static_assert(sizeof(DustHipSurfaceQuery) == 48 && sizeof(DustHipSurfaceResult) == 64 && sizeof(DustHipSurfaceVoxel) == 8 && kSurfaceBins == DUST_HIP_SURFACE_BINS,
               "surface records");
+static_assert(sizeof(DustHipMeshQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipMeshResult) == 64 && sizeof(DustHipMeshQuad) == 8 &&
+                  DUST_HIP_MESH_WALLS == DUST_HIP_SURFACE_WALLS,
+              "mesh records");
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
@@ -280,6 +284,37 @@ inline DustHipSurfaceResult surface_result(const uint32_t* acc) {
   for (int d = 0; d < 6; ++d) { r.by_face[d] = acc[1 + d]; r.faces += acc[1 + d]; }
   r.solid = acc[7];
   for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[8 + k]); r.hi[k] = uint8_t(acc[11 + k]); }
+  return r;
+}
+
+// A mesh query as the kernels read it (dust_hip_model_mesh): a surface query field for field -- device_surface's refusals, WALLS, filter
+// and clipped region -- with one flag more. nullptr: the query is fine; otherwise why the call refuses it. `empty` as in device_surface.
+inline const char* device_mesh(const DustHipMeshQuery& q, MeshArgs& d, bool& empty) {
+  DustHipSurfaceQuery sq{};
+  sq.struct_size = sizeof(sq);
+  sq.faces = q.faces;
+  sq.flags = q.flags & DUST_HIP_MESH_WALLS;
+  sq.palette = q.palette;
+  for (int r = 0; r < 3; ++r) { sq.lo[r] = q.lo[r]; sq.hi[r] = q.hi[r]; }
+  SurfaceArgs s{};
+  if (const char* why = device_surface(sq, s, empty)) return why;
+  if ((q.flags & ~(DUST_HIP_MESH_WALLS | DUST_HIP_MESH_ANY_PALETTE)) != 0u) return "unknown mesh flag";
+  d.faces = s.faces;
+  d.walls = s.walls;
+  d.byte = s.byte;
+  d.any_palette = (q.flags & DUST_HIP_MESH_ANY_PALETTE) ? 1u : 0u;
+  for (int r = 0; r < 3; ++r) { d.lo[r] = s.lo[r]; d.hi[r] = s.hi[r]; }  // (not set when empty)
+  return nullptr;
+}
+// What a mesh call's caller gets from the device's kMeshAccWords accumulator; null: nothing was looked at -- the zero result.
+inline DustHipMeshResult mesh_result(const uint32_t* acc) {
+  DustHipMeshResult r{};
+  if (!acc) return r;
+  for (int d = 0; d < 6; ++d) {
+    r.quads_by_face[d] = acc[d]; r.quads += acc[d];
+    r.faces_by_face[d] = acc[6 + d]; r.faces += acc[6 + d];
+  }
+  r.largest = acc[12];
   return r;
 }
 

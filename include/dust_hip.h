@@ -720,6 +720,69 @@ DustStatus dust_hip_model_surface(const DustHipModel*, const DustHipSurfaceQuery
                                   DustHipSurfaceVoxel* voxels /* capacity; may be NULL when capacity == 0 */, uint32_t capacity,
                                   uint32_t* counts /* 6 * 256, may be NULL */);
 DustStatus dust_hip_model_surface_apply(DustHipModel*, const DustHipSurfaceQuery*, int32_t value, uint32_t* changed /* may be NULL */);
+/* Model meshes: a model in the form everything outside a ray tracer wants, a short list of rectangles -- flat colliders for a
+ * physics engine, quads for a rasterised fallback, a shadow proxy, an editor gizmo, an export or a network snapshot.
+ * dust_hip_model_mesh returns the exposed faces of the solid voxels, per direction, merged into axis-aligned rectangles under one
+ * canonical rule: the output is a function of the model and the query alone, two runs or two implementations give the same bytes.
+ *
+ * Face set: for direction d, F_d is exactly what dust_hip_model_surface counts in by_face[d] for the same faces, palette, region and
+ * WALLS: the voxels that are solid, lie inside the clipped inclusive region, pass the palette filter and whose face d is exposed (the
+ * neighbour across d is empty, or lies off the tree without DUST_HIP_MESH_WALLS), for the d among query.faces.
+ * Axes: the normal axis n is that of d. In the plane, u is the higher-numbered remaining axis and v the other one: faces -x / +x have
+ * u = z, v = y; faces -y / +y have u = z, v = x; faces -z / +z have u = y, v = x. A slice is one value of the n coordinate, a row one
+ * value of v within a slice.
+ * Run: a maximal set of consecutive u in one row whose voxels are all in F_d and all hold the same palette index (under
+ * DUST_HIP_MESH_ANY_PALETTE the palette condition is dropped).
+ * Quad: a maximal set of consecutive rows v0..v1 of one slice that each contain the identical run: the same u0, the same u1 and the
+ * same palette index (unless ANY_PALETTE). Rows v0 - 1 and v1 + 1 do not contain that run; a longer or shorter run in a neighbouring
+ * row does not merge. The quads partition F_d into rectangles. This is NOT the minimum-count greedy mesh: a greedy mesher may split a
+ * long run to grow a taller rectangle, this rule never does. In exchange the answer depends on no processing order.
+ * Order and capacity: the quads come in ascending order of face index d (0..5, the bit order of DUST_HIP_FACE_*), then slice, then
+ * v0, then u0. The first min(result.quads, capacity) records are written; the slots past them are left untouched. result.quads is
+ * the full count whatever the capacity; capacity 0 counts only.
+ * Record: key is x << 16 | y << 8 | z of the voxel at (u0, v0), the quad's lowest corner; face the direction index 0..5 (not the
+ * bit); palette 0..254, under ANY_PALETTE that of the key voxel; du and dv the extents along u and v minus 1 (extents run 1..256).
+ * The device writes a record as one 64-bit word.
+ * Result: quads; faces, the sum of the quads' areas, which equals dust_hip_model_surface's faces for the same query;
+ * quads_by_face; faces_by_face, which equals its by_face; largest, the area of the largest quad (0 when there is none); reserved 0.
+ * lo > hi on an axis is legal and gives the zero result.
+ * The model is only read, with dust_hip_model_surface's guarantees: one that is not editable stays not editable (its blocks' masks
+ * are scattered into the context's 2 MiB scratch, and it is expanded into the 16 MiB scratch grid only when a material is needed:
+ * a palette filter, runs that stop at a change of material, a list); the generation does not move; the island labelling and both
+ * fields stand.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, every output untouched: a null model or query; a struct_size below the struct's size;
+ * faces of 0 or above 63; a flag bit above 3; a palette below -1 or above 254; a region coordinate >= 256; null quads with
+ * capacity > 0. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material byte 255), before
+ * the query is looked at. The call is synchronous, like every model call. Everything is integer arithmetic.
+ * Out of scope: the minimum-count greedy mesh; T-junction-free output; seams between different materials as faces; vertex or index
+ * buffers on the device; faces across the instances of a scene; 4096^3 trees; an asynchronous form. */
+#define DUST_HIP_MESH_WALLS 1u        /* flags: the outside of the tree counts as solid (DUST_HIP_SURFACE_WALLS) */
+#define DUST_HIP_MESH_ANY_PALETTE 2u  /* flags: runs and quads merge across palette indices */
+typedef struct DustHipMeshQuery {      /* 48 bytes, field for field DustHipSurfaceQuery */
+  uint32_t struct_size;
+  uint32_t faces;                /* 1..63: the directions that count (DUST_HIP_FACE_*) */
+  uint32_t flags;                /* DUST_HIP_MESH_WALLS | DUST_HIP_MESH_ANY_PALETTE */
+  int32_t palette;               /* -1: every solid voxel; 0..254: only voxels of this palette index */
+  uint32_t lo[3], hi[3];         /* inclusive region, clipped to the tree */
+  uint32_t reserved[2];          /* 0 */
+} DustHipMeshQuery;
+typedef struct DustHipMeshQuad {       /* 8 bytes */
+  uint32_t key;                  /* x << 16 | y << 8 | z of the voxel at (u0, v0) */
+  uint8_t face;                  /* direction index 0..5 */
+  uint8_t palette;               /* 0..254; under ANY_PALETTE that of the key voxel */
+  uint8_t du;                    /* extent along u minus 1 */
+  uint8_t dv;                    /* extent along v minus 1 */
+} DustHipMeshQuad;
+typedef struct DustHipMeshResult {     /* 64 bytes */
+  uint32_t quads;                /* number of quads */
+  uint32_t faces;                /* the sum of their areas */
+  uint32_t quads_by_face[6];     /* quads per direction; sums to quads */
+  uint32_t faces_by_face[6];     /* area per direction; sums to faces */
+  uint32_t largest;              /* area of the largest quad; 0 when there is none */
+  uint32_t reserved;             /* 0 */
+} DustHipMeshResult;
+DustStatus dust_hip_model_mesh(const DustHipModel*, const DustHipMeshQuery*, DustHipMeshResult* result /* may be NULL */,
+                               DustHipMeshQuad* quads /* capacity; may be NULL when capacity == 0 */, uint32_t capacity);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

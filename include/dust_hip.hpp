@@ -303,6 +303,18 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model meshes (dust_hip_model_mesh): the exposed faces among query.faces inside the query's region merged into axis-aligned
+  // rectangles under the header's canonical rule (not the minimum-count greedy mesh) -- every quad, in ascending (face, slice, v0, u0):
+  // two calls, one to count. Only reads.
+  std::vector<DustHipMeshQuad> mesh(DustHipMeshQuery query, DustHipMeshResult* result = nullptr) const {
+    query.struct_size = sizeof(query);
+    DustHipMeshResult r{};
+    check(dust_hip_model_mesh(h_, &query, &r, nullptr, 0));
+    std::vector<DustHipMeshQuad> quads(r.quads);
+    check(dust_hip_model_mesh(h_, &query, &r, quads.data(), uint32_t(quads.size())));
+    if (result) *result = r;
+    return quads;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
