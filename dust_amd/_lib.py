@@ -285,6 +285,29 @@ MESH_WALLS = 1
 MESH_ANY_PALETTE = 2
 
 
+class DeltaQuery(C.Structure):  # DustHipDeltaQuery, 48 bytes: a SurfaceQuery's layout with the kinds that count where its faces stand
+    _fields_ = [("struct_size", C.c_uint32), ("kinds", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class DeltaResult(C.Structure):  # DustHipDeltaResult, 64 bytes: listed voxels, in all and per kind, both models' solid voxels, the listed voxels' bounds
+    _fields_ = [("voxels", C.c_uint32), ("added", C.c_uint32), ("removed", C.c_uint32), ("repainted", C.c_uint32), ("solid_before", C.c_uint32),
+                ("solid_after", C.c_uint32), ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("hi", C.c_uint8 * 3), ("pad1", C.c_uint8),
+                ("reserved", C.c_uint32 * 8)]
+
+
+class DeltaVoxel(C.Structure):  # DustHipDeltaVoxel, 8 bytes: a voxel's key, the kind of its change, its value before and after (DELTA_NONE: no voxel)
+    _fields_ = [("key", C.c_uint32), ("kind", C.c_uint8), ("before", C.c_uint8), ("after", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+DELTA_ADDED, DELTA_REMOVED, DELTA_REPAINTED = 1, 2, 4
+DELTA_ALL = 7
+DELTA_NONE = 255
+DELTA_BACKWARD = 1
+DELTA_BINS = 256
+MAX_DELTA_RECORDS = 1 << 24
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -366,6 +389,8 @@ SYMBOLS = {
     "dust_hip_model_surface": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_surface_apply": (C.c_int, [_P, _P, C.c_int32, _u32p]),
     "dust_hip_model_mesh": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    "dust_hip_model_delta": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P]),
+    "dust_hip_model_delta_apply": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

@@ -58,6 +58,11 @@ SURFACE_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("faces", "u1"), ("palette", "u1
 # DustHipMeshResult (64 bytes) and DustHipMeshQuad (8 bytes): the result and the list entries of dust_hip_model_mesh
 MESH_RESULT_DTYPE = np.dtype([("quads", "<u4"), ("faces", "<u4"), ("quads_by_face", "<u4", 6), ("faces_by_face", "<u4", 6), ("largest", "<u4"), ("reserved", "<u4")])
 MESH_QUAD_DTYPE = np.dtype([("key", "<u4"), ("face", "u1"), ("palette", "u1"), ("du", "u1"), ("dv", "u1")])
+# DustHipDeltaResult (64 bytes) and DustHipDeltaVoxel (8 bytes): the result and the list entries of dust_hip_model_delta, and the
+# records dust_hip_model_delta_apply takes
+DELTA_RESULT_DTYPE = np.dtype([("voxels", "<u4"), ("added", "<u4"), ("removed", "<u4"), ("repainted", "<u4"), ("solid_before", "<u4"), ("solid_after", "<u4"),
+                               ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 8)])
+DELTA_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("kind", "u1"), ("before", "u1"), ("after", "u1"), ("reserved", "u1")])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -443,6 +448,42 @@ class Model:
         quads = np.zeros(int(capacity), MESH_QUAD_DTYPE)
         L.check(self._lib.dust_hip_model_mesh(self._h, C.byref(q), _ptr(out), _ptr(quads) if capacity else None, int(capacity)))
         return out[0], quads[: min(int(capacity), int(out[0]["quads"]))]
+
+    def delta(self, after, kinds=L.DELTA_ALL, palette=-1, region=None, capacity=None, tables=False):
+        """The voxels in which `after` differs from this model at the same tree coordinates (dust_hip_model_delta). `kinds` the
+        L.DELTA_ADDED / DELTA_REMOVED / DELTA_REPAINTED changes that count, `palette` -1 for every change or the one palette index a
+        voxel's value before or after must be, region = (lo, hi) an inclusive voxel box (None: the whole tree). Returns (result, voxels,
+        counts): result a DELTA_RESULT_DTYPE record (voxels, added, removed, repainted, solid_before, solid_after, lo, hi); voxels a
+        DELTA_VOXEL_DTYPE array (key x << 16 | y << 8 | z, kind, before, after -- palette indices, L.DELTA_NONE for no voxel) of the
+        first min(result.voxels, capacity) listed voxels in the order of Model.read()'s blocks, then ascending voxel bit --
+        capacity=None makes two calls, one to count and one to list everything; counts (2, 256) uint32 with counts[0, b] the listed
+        voxels whose value before has bin b and counts[1, b] the same for the value after (bin 0 None, bin 1 + p palette index p), or
+        None with tables=False. Both models are only read; the same model twice gives the zero result."""
+        q = L.DeltaQuery(struct_size=C.sizeof(L.DeltaQuery), kinds=kinds, flags=0, palette=palette)
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        out = np.zeros(1, DELTA_RESULT_DTYPE)
+        counts = np.zeros((2, L.DELTA_BINS), np.uint32) if tables else None
+        if capacity is None:
+            L.check(self._lib.dust_hip_model_delta(self._h, after._h, C.byref(q), _ptr(out), None, 0, None))
+            capacity = int(out[0]["voxels"])
+        voxels = np.zeros(int(capacity), DELTA_VOXEL_DTYPE)
+        L.check(self._lib.dust_hip_model_delta(self._h, after._h, C.byref(q), _ptr(out), _ptr(voxels) if capacity else None, int(capacity),
+                                               _ptr(counts) if tables else None))
+        return out[0], voxels[: min(int(capacity), int(out[0]["voxels"]))], counts
+
+    def delta_apply(self, records, backward=False):
+        """Play a DELTA_VOXEL_DTYPE list onto the model (dust_hip_model_delta_apply): every record's voxel takes `after` and is expected
+        to hold `before`, or the other way round with backward=True; a key named more than once keeps its last record. Returns
+        (changed, conflicts): the voxels whose value differs afterwards, and the records whose voxel did not hold the expected value
+        when the call began (they are applied all the same). Scenes instancing the model must be committed again; both fields and the
+        island labelling are invalid afterwards."""
+        records = np.ascontiguousarray(records, DELTA_VOXEL_DTYPE)
+        changed, conflicts = C.c_uint32(), C.c_uint32()
+        L.check(self._lib.dust_hip_model_delta_apply(self._h, _ptr(records) if len(records) else None, len(records),
+                                                     L.DELTA_BACKWARD if backward else 0, C.byref(changed), C.byref(conflicts)))
+        return changed.value, conflicts.value
 
     def find_islands(self, connectivity=L.ISLANDS_FACES, anchor=None, capacity=None, records=None):
         """Label the model's connected solid voxels (dust_hip_model_find_islands): returns (n, records) -- n the number of islands,

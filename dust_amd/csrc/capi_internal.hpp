@@ -169,6 +169,10 @@ struct DustHipContext : RefCounted {
   // scan's block sums and total behind them (1 MiB, allocated by the first such call). The context's: the model may not be editable.
   // A dust_hip_model_mesh call that lists (mesh.hip) keeps its quads per (direction, slice) in the same table: both calls are synchronous
   DeviceBuffer surface_table;
+  // model deltas (delta.hip): a dust_hip_model_delta call reads two models at once. One that is not editable goes through cast_mask and
+  // stamp_grid; when neither is, the second goes through this pair (2 MiB and 16 MiB, allocated by the first call that needs them).
+  // Its listed voxels per brick are kept in surface_table
+  DeviceBuffer delta_mask, delta_grid;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)

@@ -1,8 +1,9 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
 // edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip), model floods (flood.hip), model
-// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip) model surfaces (surface.hip) and model meshes (mesh.hip). What needs no device is in three headers: the hierarchy build itself
+// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip), model surfaces (surface.hip), model meshes (mesh.hip) and model deltas
+// (delta.hip). What needs no device is in three headers: the hierarchy build itself
 // (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp, the arithmetic on the callers' records (conversion, chunks,
-// cell lists, cast hits, census records, surface and mesh queries) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
+// cell lists, cast hits, census records, surface, mesh and delta queries, a delta_apply's records) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -437,26 +438,28 @@ DustStatus dust_hip_model_edit_shapes(DustHipModel* m, const DustHipEditShape* s
 // ---- model stamps (stamp.hip k_stamp)
 namespace {
 // A source model as it stands now, as a grid, for a call that only reads it (stamps, reductions): its own when it is editable (read
-// in place), expanded into the context's scratch when it is not (the source itself is not touched), and a copy of the grid of `m`,
-// the editable model the call writes (null: none), when that is the source too -- a model stamped onto itself
-DustStatus source_grid(DustHipContext* ctx, const DustHipModel* m, const DustHipModel* src, const uint8_t** source) {
+// in place), expanded into a scratch grid when it is not (the source itself is not touched), and a copy of the grid of `m`,
+// the editable model the call writes (null: none), when that is the source too -- a model stamped onto itself. `scratch`: the
+// context's stamp_grid unless the call holds two expansions at once (dust_hip_model_delta)
+DustStatus source_grid(DustHipContext* ctx, const DustHipModel* m, const DustHipModel* src, const uint8_t** source, DeviceBuffer* scratch = nullptr) {
   hipStream_t st = ctx->stream;
   if (src != m && src->edit) {
     *source = static_cast<const uint8_t*>(src->edit->grid.p);
     return DUST_OK;
   }
+  DeviceBuffer& grid = scratch ? *scratch : ctx->stamp_grid;
   const size_t grid_bytes = size_t(dust::kLattice) * 64;
-  DustStatus s = lazy_alloc(ctx->stamp_grid, grid_bytes, "the source grid (16 MiB)");
+  DustStatus s = lazy_alloc(grid, grid_bytes, "the source grid (16 MiB)");
   if (s != DUST_OK) return s;
   if (src == m) {
-    HIP_TRY(hipMemcpyAsync(ctx->stamp_grid.p, m->edit->grid.p, grid_bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(grid.p, m->edit->grid.p, grid_bytes, hipMemcpyDeviceToDevice, st));
   } else {
-    HIP_TRY(hipMemsetAsync(ctx->stamp_grid.p, 0, grid_bytes, st));
+    HIP_TRY(hipMemsetAsync(grid.p, 0, grid_bytes, st));
     dust::EditArgs e{};  // (expand only writes the grid)
-    e.grid = static_cast<uint8_t*>(ctx->stamp_grid.p);
+    e.grid = static_cast<uint8_t*>(grid.p);
     HIP_TRY(dust::launch_edit_expand(e, static_cast<const DustHipBlock*>(src->blocks.p), static_cast<const uint8_t*>(src->materials.p), src->dev.n_blocks, st));
   }
-  *source = static_cast<const uint8_t*>(ctx->stamp_grid.p);
+  *source = static_cast<const uint8_t*>(grid.p);
   return DUST_OK;
 }
 }  // namespace
@@ -506,19 +509,21 @@ DustStatus dust_hip_model_stamp(DustHipModel* m, const DustHipModel* src, const 
 
 // ---- model casts (cast.hip k_cast_walk / k_cast_count): both models are only read, through their brick masks
 namespace {
-// The source's brick masks: its own when it is editable (dst itself included); otherwise its blocks' masks scattered into the
-// context's scratch -- the source is not touched
-DustStatus cast_source_masks(DustHipContext* ctx, const DustHipModel* src, const uint64_t** src_mask) {
+// The source's brick masks: its own when it is editable (dst itself included); otherwise its blocks' masks scattered into a scratch
+// array -- the source is not touched. `scratch`: the context's cast_mask unless the call holds two such arrays at once
+// (dust_hip_model_delta)
+DustStatus cast_source_masks(DustHipContext* ctx, const DustHipModel* src, const uint64_t** src_mask, DeviceBuffer* scratch = nullptr) {
   if (src->edit) {
     *src_mask = static_cast<const uint64_t*>(src->edit->brick_mask.p);
     return DUST_OK;
   }
+  DeviceBuffer& mask = scratch ? *scratch : ctx->cast_mask;
   const size_t bytes = size_t(dust::kLattice) * 8;
-  DustStatus s = lazy_alloc(ctx->cast_mask, bytes, "the cast source masks (2 MiB)");
+  DustStatus s = lazy_alloc(mask, bytes, "the cast source masks (2 MiB)");
   if (s != DUST_OK) return s;
-  HIP_TRY(hipMemsetAsync(ctx->cast_mask.p, 0, bytes, ctx->stream));
-  HIP_TRY(dust::launch_cast_masks(static_cast<uint64_t*>(ctx->cast_mask.p), static_cast<const DustHipBlock*>(src->blocks.p), src->dev.n_blocks, ctx->stream));
-  *src_mask = static_cast<const uint64_t*>(ctx->cast_mask.p);
+  HIP_TRY(hipMemsetAsync(mask.p, 0, bytes, ctx->stream));
+  HIP_TRY(dust::launch_cast_masks(static_cast<uint64_t*>(mask.p), static_cast<const DustHipBlock*>(src->blocks.p), src->dev.n_blocks, ctx->stream));
+  *src_mask = static_cast<const uint64_t*>(mask.p);
   return DUST_OK;
 }
 }  // namespace
@@ -1166,6 +1171,118 @@ DustStatus dust_hip_model_mesh(const DustHipModel* m, const DustHipMeshQuery* q,
       }
     }
     if (result) *result = dust::mesh_result(empty ? nullptr : acc);
+    return DUST_OK;
+  });
+}
+
+// ---- model deltas (delta.hip): the voxels two models differ in, decided from both models' brick masks and, where only they can tell,
+// their grid bytes; counted and listed without writing anything (k_delta_count, k_delta_list), or a list played onto a model with the
+// rebuild of an edit behind it (k_delta_apply). The per-brick table is the surface list's.
+DustStatus dust_hip_model_delta(const DustHipModel* before, const DustHipModel* after, const DustHipDeltaQuery* q, DustHipDeltaResult* result,
+                                DustHipDeltaVoxel* voxels, uint32_t capacity, uint32_t* counts) {
+  if (!before || !after) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(before);  // (before the query is looked at)
+  if (s == DUST_OK) s = editable_kind(after);
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (before->ctx != after->ctx) return fail(DUST_ERR_INVALID_ARGUMENT, "the two models belong to different contexts");
+  STRUCT_TRY(q, "DustHipDeltaQuery");
+  dust::DeltaArgs a{};
+  bool empty = false;
+  if (const char* why = dust::device_delta(*q, a, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  if (capacity && !voxels) return fail(DUST_ERR_INVALID_ARGUMENT, "null voxels with capacity > 0");
+  empty |= before == after;  // the same handle: nothing differs, and nothing is looked at
+  return guarded([&]() -> DustStatus {
+    const size_t table_words = size_t(dust::kDeltaRows) * dust::kDeltaBins;
+    uint32_t acc[dust::kDeltaAccWords] = {};
+    std::vector<uint32_t> rows(counts ? table_words : 0, 0u);
+    if (!empty) {
+      DustHipContext* ctx = before->ctx;
+      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_TRY(join_side(ctx));
+      hipStream_t st = ctx->stream;
+      // a model that is not editable is read through the context's scratch arrays; `after` through the second pair when `before` holds the first
+      DeviceBuffer* second_mask = before->edit ? nullptr : &ctx->delta_mask;
+      DeviceBuffer* second_grid = before->edit ? nullptr : &ctx->delta_grid;
+      auto grids = [&]() -> DustStatus {
+        if (a.grid_a) return DUST_OK;
+        DustStatus g = source_grid(ctx, nullptr, before, &a.grid_a);
+        if (g == DUST_OK) g = source_grid(ctx, nullptr, after, &a.grid_b, second_grid);
+        return g;
+      };
+      if ((s = cast_source_masks(ctx, before, &a.mask_a)) != DUST_OK) return s;
+      if ((s = cast_source_masks(ctx, after, &a.mask_b, second_mask)) != DUST_OK) return s;
+      // the grids only where a byte is needed: for the count pass to tell a repaint, under a filter or with tables, for the list pass
+      // once it is known that something is listed
+      if (((a.kinds & dust::kDeltaRepainted) || a.byte != 0u || counts) && (s = grids()) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, (dust::kDeltaAccWords + table_words) * 4)) != DUST_OK) return s;
+      const size_t L = dust::kLattice;
+      if (capacity && (s = lazy_alloc(ctx->surface_table, (L + dust::kSurfaceScanWords) * 4, "the surface, mesh and delta lists' table (1 MiB)")) != DUST_OK) return s;
+      a.acc = static_cast<uint32_t*>(ctx->stage_out.p);
+      a.tables = counts ? a.acc + dust::kDeltaAccWords : nullptr;
+      a.brick_count = capacity ? static_cast<uint32_t*>(ctx->surface_table.p) : nullptr;
+      HIP_TRY(hipMemsetAsync(a.acc, 0, (dust::kDeltaAccWords + table_words) * 4, st));
+      if (capacity) HIP_TRY(hipMemsetAsync(a.brick_count, 0, L * 4, st));
+      HIP_TRY(dust::launch_delta_count(a, st));
+      HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+      if (counts) HIP_TRY(hipMemcpyAsync(rows.data(), a.tables, table_words * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      const uint32_t staged = std::min(dust::delta_result(acc).voxels, capacity);
+      if (staged) {
+        if ((s = grids()) != DUST_OK) return s;
+        if ((s = grow(ctx, ctx->stage_aux, size_t(staged) * sizeof(DustHipDeltaVoxel))) != DUST_OK) return s;
+        uint32_t* scan_tmp = a.brick_count + L;  // 256 block sums, then the total (the listed voxels again)
+        HIP_TRY(dust::launch_table_scan(dust::TableScan{{a.brick_count, nullptr}, {scan_tmp + 256, nullptr}, scan_tmp}, 1, st));
+        a.scan_tmp = scan_tmp;
+        a.voxels = static_cast<uint64_t*>(ctx->stage_aux.p);
+        a.capacity = staged;
+        HIP_TRY(dust::launch_delta_list(a, st));
+        HIP_TRY(hipMemcpyAsync(voxels, a.voxels, size_t(staged) * sizeof(DustHipDeltaVoxel), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+    }
+    if (result) *result = dust::delta_result(empty ? nullptr : acc);
+    if (counts) std::memcpy(counts, rows.data(), table_words * 4);
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_delta_apply(DustHipModel* m, const DustHipDeltaVoxel* records, uint32_t n, uint32_t flags, uint32_t* changed,
+                                      uint32_t* conflicts) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);  // (before the records are looked at)
+  if (s != DUST_OK) return s;
+  if ((flags & ~DUST_HIP_DELTA_BACKWARD) != 0u) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown delta_apply flag");
+  if (n && !records) return fail(DUST_ERR_INVALID_ARGUMENT, "null records with n > 0");
+  if (n > DUST_HIP_MAX_DELTA_RECORDS) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_DELTA_RECORDS records in one call");
+  return guarded([&]() -> DustStatus {
+    std::vector<uint64_t> words;
+    if (const char* why = dust::delta_apply_records(records, n, words)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+    DustHipContext* ctx = m->ctx;
+    s = begin_edit(m);
+    if (s != DUST_OK) return s;
+    uint32_t counters[2] = {0u, 0u};
+    if (n != 0) {
+      EditState& es = *m->edit;
+      hipStream_t st = ctx->stream;
+      invalidate_derived(es);
+      if ((s = grow(ctx, es.shapes, words.size() * 8)) != DUST_OK) return s;
+      if ((s = grow(ctx, es.changed, sizeof(counters))) != DUST_OK) return s;
+      dust::DeltaApplyArgs a{};
+      a.records = static_cast<const uint64_t*>(es.shapes.p);
+      a.n = uint32_t(words.size());
+      a.backward = (flags & DUST_HIP_DELTA_BACKWARD) ? 1u : 0u;
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.counters = static_cast<uint32_t*>(es.changed.p);
+      HIP_TRY(hipMemcpyAsync(es.shapes.p, words.data(), words.size() * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(counters), st));
+      HIP_TRY(dust::launch_delta_apply(a, st));
+      HIP_TRY(hipMemcpyAsync(counters, a.counters, sizeof(counters), hipMemcpyDeviceToHost, st));
+      s = rebuild_and_refresh(m, es);  // synchronises: `words` stays alive until the copy is done
+      if (s != DUST_OK) return s;
+    }
+    if (changed) *changed = counters[0];
+    if (conflicts) *conflicts = counters[1];
     return DUST_OK;
   });
 }

@@ -61,6 +61,7 @@ __host__ __device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { retu
 __host__ __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 #ifdef __HIPCC__
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }  // v is the same in every lane: keep it in an SGPR
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) { return ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v); }
 #endif
 
 }  // namespace dust

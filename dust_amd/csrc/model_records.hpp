@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp and tests/cpp/mesh_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp and tests/cpp/delta_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -11,6 +11,7 @@
 #include "../../include/dust_hip.h"
 #include "cast.hpp"
 #include "census.hpp"
+#include "delta.hpp"
 #include "distance.hpp"
 #include "edit.hpp"
 #include "mesh.hpp"
@@ -24,6 +25,10 @@ static_assert(sizeof(DustHipSurfaceQuery) == 48 && sizeof(DustHipSurfaceResult) 
 static_assert(sizeof(DustHipMeshQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipMeshResult) == 64 && sizeof(DustHipMeshQuad) == 8 &&
                   DUST_HIP_MESH_WALLS == DUST_HIP_SURFACE_WALLS,
               "mesh records");
+static_assert(sizeof(DustHipDeltaQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipDeltaResult) == 64 && sizeof(DustHipDeltaVoxel) == 8 &&
+                  kDeltaBins == DUST_HIP_DELTA_BINS && kDeltaMaxRecords == DUST_HIP_MAX_DELTA_RECORDS && kDeltaAdded == DUST_HIP_DELTA_ADDED &&
+                  kDeltaRemoved == DUST_HIP_DELTA_REMOVED && kDeltaRepainted == DUST_HIP_DELTA_REPAINTED,
+              "delta records");
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
@@ -316,6 +321,60 @@ inline DustHipMeshResult mesh_result(const uint32_t* acc) {
   }
   r.largest = acc[12];
   return r;
+}
+
+// A delta query as the kernels read it (dust_hip_model_delta): the kinds, the filter's grid byte, the region clipped to the tree and the
+// root cells it reaches. The pointers are the caller's. nullptr: the query is fine; otherwise why the call refuses it, in the header's
+// order. `empty` as in device_surface: nothing is looked at and no launch is made -- lo, hi and box are not set.
+inline const char* device_delta(const DustHipDeltaQuery& q, DeltaArgs& d, bool& empty) {
+  if (q.kinds == 0u || q.kinds > DUST_HIP_DELTA_ALL) return "kinds must be 1..DUST_HIP_DELTA_ALL";
+  if (q.flags != 0u) return "unknown delta flag";
+  if (q.palette < -1 || q.palette > 254) return "palette must be -1 (every change) or 0..254";
+  for (int r = 0; r < 3; ++r)
+    if (q.lo[r] >= 256u || q.hi[r] >= 256u) return "region coordinate outside the tree extent";
+  d.kinds = q.kinds;
+  d.byte = q.palette < 0 ? 0u : uint32_t(q.palette) + 1u;
+  empty = false;
+  for (int r = 0; r < 3; ++r) empty |= q.lo[r] > q.hi[r];
+  if (empty) return nullptr;
+  for (int r = 0; r < 3; ++r) {
+    d.lo[r] = q.lo[r]; d.hi[r] = q.hi[r];
+    d.box.lo[r] = q.lo[r] >> 4; d.box.hi[r] = q.hi[r] >> 4;
+  }
+  return nullptr;
+}
+// What a delta call's caller gets from the device's kDeltaAccWords accumulator; null: nothing was looked at -- the zero result, bounds
+// 255 / 0 (what a pair without a listed voxel has too).
+inline DustHipDeltaResult delta_result(const uint32_t* acc) {
+  DustHipDeltaResult r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  if (!acc) return r;
+  r.added = acc[0]; r.removed = acc[1]; r.repainted = acc[2];
+  r.voxels = acc[0] + acc[1] + acc[2];
+  r.solid_before = acc[3]; r.solid_after = acc[4];
+  for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[5 + k]); r.hi[k] = uint8_t(acc[8 + k]); }
+  return r;
+}
+// The records of a dust_hip_model_delta_apply call as k_delta_apply takes them: one 64-bit word each, a key named more than once
+// keeping its LAST record (set_voxels' rule, and its walk: from the back, first come first kept). Seen keys are a bit each of the
+// tree's 2^24 (2 MiB): a list may name every voxel, and a hash set took 0.6 s over the 12.6 M records of a half-density pair.
+// nullptr: fine; otherwise why the call refuses them, `out` left alone.
+inline const char* delta_apply_records(const DustHipDeltaVoxel* records, uint32_t n, std::vector<uint64_t>& out) {
+  for (uint32_t i = 0; i < n; ++i)
+    if (records[i].key >= (1u << 24)) return "record key outside the tree extent (x << 16 | y << 8 | z)";
+  out.clear();
+  if (n == 0) return nullptr;
+  out.reserve(n);
+  std::vector<uint64_t> seen(size_t(1) << 18, 0ull);
+  for (uint32_t k = n; k-- > 0;) {
+    const DustHipDeltaVoxel& v = records[k];
+    uint64_t& word = seen[v.key >> 6];
+    const uint64_t bit = 1ull << (v.key & 63u);
+    if (word & bit) continue;
+    word |= bit;
+    out.push_back(uint64_t(v.key) | (uint64_t(v.kind) << 32) | (uint64_t(v.before) << 40) | (uint64_t(v.after) << 48));
+  }
+  return nullptr;
 }
 
 // the records of a call that cover something, in call order: `index` maps them back to the caller's

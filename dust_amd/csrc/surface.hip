@@ -31,8 +31,6 @@ namespace dust {
 
 namespace {
 
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) { return ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v); }
-
 // the word of brick (bx, by, bz), or `outside` off the tree (coordinates -1 and 64 wrap to above 63)
 __device__ __forceinline__ uint64_t brick_word(const uint64_t* mask, uint32_t bx, uint32_t by, uint32_t bz, uint64_t outside) {
   if (bx > 63u || by > 63u || bz > 63u) return outside;
@@ -73,17 +71,6 @@ __device__ __forceinline__ void brick_faces(const SurfaceArgs& a, const uint8_t*
   }
 }
 
-// the lowest and highest of a brick's four coordinates on an axis that `listed` touches (plane0: the axis's c == 0 plane)
-__device__ __forceinline__ void axis_bounds(uint64_t listed, uint64_t plane0, uint32_t shift, uint32_t base, uint32_t& lo, uint32_t& hi) {
-#pragma unroll
-  for (uint32_t c = 0; c < 4u; ++c) {
-    if (listed & (plane0 << (shift * c))) {
-      lo = umin(lo, base + c);
-      hi = umax(hi, base + c);
-    }
-  }
-}
-
 }  // namespace
 
 __global__ void __launch_bounds__(256) k_surface_count(SurfaceArgs a) {
@@ -109,9 +96,9 @@ __global__ void __launch_bounds__(256) k_surface_count(SurfaceArgs a) {
     voxels += n;
     n0 += (uint32_t)__popcll(b.e[0]); n1 += (uint32_t)__popcll(b.e[1]); n2 += (uint32_t)__popcll(b.e[2]);
     n3 += (uint32_t)__popcll(b.e[3]); n4 += (uint32_t)__popcll(b.e[4]); n5 += (uint32_t)__popcll(b.e[5]);
-    axis_bounds(b.listed, kSurfaceX0, 16u, b.bx * 4u, lo_x, hi_x);
-    axis_bounds(b.listed, kSurfaceY0, 4u, b.by * 4u, lo_y, hi_y);
-    axis_bounds(b.listed, kSurfaceZ0, 1u, b.bz * 4u, lo_z, hi_z);
+    surface_axis_bounds(b.listed, kSurfaceX0, 16u, b.bx * 4u, lo_x, hi_x);
+    surface_axis_bounds(b.listed, kSurfaceY0, 4u, b.by * 4u, lo_y, hi_y);
+    surface_axis_bounds(b.listed, kSurfaceZ0, 1u, b.bz * 4u, lo_z, hi_z);
     if (a.brick_count && lane == 0u) a.brick_count[b.code] = n;
     if (tables) {  // one LDS add per distinct byte among the listed lanes and direction it is exposed in
       for (uint64_t rest = b.listed; rest != 0ull;) {

@@ -42,6 +42,18 @@ struct SurfaceApplyArgs {
   uint32_t* changed;  // one word, zeroed by the caller
 };
 
+// the lowest and highest of a brick's four coordinates on an axis that `listed` touches (plane0: the axis's c == 0 plane); surface.hip
+// and delta.hip keep their bounds with it
+__device__ __forceinline__ void surface_axis_bounds(uint64_t listed, uint64_t plane0, uint32_t shift, uint32_t base, uint32_t& lo, uint32_t& hi) {
+#pragma unroll
+  for (uint32_t c = 0; c < 4u; ++c) {
+    if (listed & (plane0 << (shift * c))) {
+      lo = umin(lo, base + c);
+      hi = umax(hi, base + c);
+    }
+  }
+}
+
 hipError_t launch_surface_count(const SurfaceArgs& a, hipStream_t s);
 hipError_t launch_surface_list(const SurfaceArgs& a, hipStream_t s);
 hipError_t launch_surface_apply(const SurfaceApplyArgs& a, hipStream_t s);

@@ -783,6 +783,90 @@ typedef struct DustHipMeshResult {     /* 64 bytes */
 } DustHipMeshResult;
 DustStatus dust_hip_model_mesh(const DustHipModel*, const DustHipMeshQuery*, DustHipMeshResult* result /* may be NULL */,
                                DustHipMeshQuad* quads /* capacity; may be NULL when capacity == 0 */, uint32_t capacity);
+/* Model deltas: what changed between two states of a model, as a list -- an edit replicated to clients without sending the model, an
+ * undo / redo stack, an incremental save, the voxels a blast removed as particles of the right materials -- and the list handed back:
+ * dust_hip_model_delta_apply plays it onto a model in either direction and says how many voxels were not in the state it assumes.
+ *
+ * Kinds: a voxel differs when its value differs between the two models at the same tree coordinates; a value is None or a palette
+ * index 0..254. DUST_HIP_DELTA_ADDED: None before, solid after. DUST_HIP_DELTA_REMOVED: solid before, None after.
+ * DUST_HIP_DELTA_REPAINTED: solid in both, the palette index differs. The two palettes' colours are not compared, only indices.
+ * Query: DustHipSurfaceQuery's layout with `kinds` where `faces` stands. palette -1: every change; 0..254: only voxels whose value
+ * before or after is that index. lo / hi is an inclusive voxel box under the surface query's rules: clipped to the tree, lo > hi on
+ * an axis legal and empty -- the zero result (bounds 255 / 0), nothing written.
+ * Listed: a voxel is listed when it lies inside the clipped region, differs, its kind is among query.kinds and it passes the palette
+ * filter.
+ * Record: key is x << 16 | y << 8 | z; kind the one DUST_HIP_DELTA_* bit; before and after a palette index 0..254 or
+ * DUST_HIP_DELTA_NONE (255, free because models that hold material byte 255 are unsupported); reserved 0. The device writes a record
+ * as one 64-bit word.
+ * Order and capacity: the records come in ascending brick code (leaf_code: Tree::iter_leaf, the order in which dust_hip_model_read
+ * lists any model's blocks), then ascending voxel bit (x&3)<<4 | (y&3)<<2 | (z&3). The first min(result.voxels, capacity) records are
+ * written; the slots past them are left untouched. result.voxels is the full count whatever the capacity; capacity 0 counts only
+ * (dust_hip_model_surface's convention).
+ * Result: voxels, the listed voxels; added, removed, repainted, which sum to voxels; solid_before and solid_after, the solid voxels
+ * of each model inside the clipped region, whatever the kinds and the filter; lo / hi, the inclusive bounds of the listed voxels
+ * (255, 255, 255 / 0, 0, 0 when there is none); pad and reserved bytes 0.
+ * Tables: counts[0 * 256 + b] is the number of listed voxels whose value before has bin b, counts[1 * 256 + b] the same for the value
+ * after; bin 0 is None and bin 1 + p palette index p (dust_hip_model_census's convention). Each row sums to result.voxels; row 0 bin 0
+ * equals added, row 1 bin 0 equals removed.
+ * dust_hip_model_delta only reads both models, with dust_hip_model_surface's guarantees: one that is not editable stays not editable
+ * (its blocks' masks are scattered into a 2 MiB scratch of the context, and it is expanded into a 16 MiB scratch grid only when a
+ * byte is needed: REPAINTED among the kinds, a palette filter, tables, a list; the context has one pair of each, and a second one from
+ * the first call in which neither model is editable); generations do not move, so committed scenes stay valid; island labellings and
+ * both fields stand. before == after, the same handle, is legal and gives the zero result.
+ * dust_hip_model_delta_apply walks records[0..n) and reads key, before and after; kind and reserved are ignored. With flags 0 a voxel
+ * takes `after` and is expected to hold `before`; with DUST_HIP_DELTA_BACKWARD it takes `before` and is expected to hold `after`. A
+ * key named more than once keeps its last record (set_voxels' rule). *conflicts is the number of surviving records whose voxel did not
+ * hold the expected value, judged on the model as it stood when the call began; those records are applied all the same. *changed is
+ * the number of voxels whose value differs afterwards. The model is rebuilt as after surface_apply, byte for byte a host build; the
+ * generation is bumped, the island labelling and both fields are invalid afterwards. n == 0 is a no-op that may make the model
+ * editable, as with set_voxels.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, every output untouched: a null model or query; models of two contexts; a struct_size below
+ * the struct's size; kinds of 0 or above 7; any flag bit for delta, a bit above 0 for delta_apply; a palette below -1 or above 254; a
+ * region coordinate >= 256; null voxels with capacity > 0; null records with n > 0; n above 16 777 216; a record key >= 2^24.
+ * DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material byte 255), for either model,
+ * before the query is looked at. Both calls are synchronous, like every model call. Everything is integer arithmetic: two runs give
+ * the same bytes.
+ * Out of scope: an offset or orientation between the two models (stamp's job); a device-side copy of a model (a snapshot today is an
+ * empty model with one OVERWRITE stamp of the whole tree); run-length or otherwise packed deltas; 4096^3 trees; an asynchronous
+ * form; a strict apply that changes nothing on a conflict. */
+#define DUST_HIP_DELTA_ADDED 1u
+#define DUST_HIP_DELTA_REMOVED 2u
+#define DUST_HIP_DELTA_REPAINTED 4u
+#define DUST_HIP_DELTA_ALL 7u
+#define DUST_HIP_DELTA_NONE 255u      /* a record's before / after: no voxel */
+#define DUST_HIP_DELTA_BACKWARD 1u    /* delta_apply flags: voxels take `before` and are expected to hold `after` */
+#define DUST_HIP_DELTA_BINS 256u
+#define DUST_HIP_MAX_DELTA_RECORDS 16777216u
+typedef struct DustHipDeltaQuery {     /* 48 bytes, DustHipSurfaceQuery's layout */
+  uint32_t struct_size;
+  uint32_t kinds;                /* 1..7: the DUST_HIP_DELTA_* kinds that count */
+  uint32_t flags;                /* 0 */
+  int32_t palette;               /* -1: every change; 0..254: only voxels whose value before or after is this palette index */
+  uint32_t lo[3], hi[3];         /* inclusive region, clipped to the tree */
+  uint32_t reserved[2];          /* 0 */
+} DustHipDeltaQuery;
+typedef struct DustHipDeltaResult {    /* 64 bytes */
+  uint32_t voxels;               /* listed voxels */
+  uint32_t added, removed, repainted;  /* ... per kind; they sum to voxels */
+  uint32_t solid_before;         /* solid voxels of `before` in the clipped region, whatever the kinds and the filter */
+  uint32_t solid_after;          /* ... of `after` */
+  uint8_t lo[3], pad0;           /* inclusive bounds of the listed voxels; 255,255,255 when there is none */
+  uint8_t hi[3], pad1;           /* 0,0,0 when there is none; pad bytes 0 */
+  uint32_t reserved[8];          /* 0 */
+} DustHipDeltaResult;
+typedef struct DustHipDeltaVoxel {     /* 8 bytes */
+  uint32_t key;                  /* x << 16 | y << 8 | z */
+  uint8_t kind;                  /* the one DUST_HIP_DELTA_* bit */
+  uint8_t before;                /* palette index 0..254, or DUST_HIP_DELTA_NONE */
+  uint8_t after;                 /* palette index 0..254, or DUST_HIP_DELTA_NONE */
+  uint8_t reserved;              /* 0 */
+} DustHipDeltaVoxel;
+DustStatus dust_hip_model_delta(const DustHipModel* before, const DustHipModel* after, const DustHipDeltaQuery*,
+                                DustHipDeltaResult* result /* may be NULL */,
+                                DustHipDeltaVoxel* voxels /* capacity; may be NULL when capacity == 0 */, uint32_t capacity,
+                                uint32_t* counts /* 2 * 256, may be NULL */);
+DustStatus dust_hip_model_delta_apply(DustHipModel*, const DustHipDeltaVoxel* records, uint32_t n, uint32_t flags,
+                                      uint32_t* changed /* may be NULL */, uint32_t* conflicts /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

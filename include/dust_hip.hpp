@@ -315,6 +315,29 @@ class VoxGeometry {
     if (result) *result = r;
     return quads;
   }
+  // Model deltas (dust_hip_model_delta / delta_apply): the voxels in which `after` differs from this geometry, of the kinds among
+  // query.kinds inside the query's region -- counted into the result, listed (every one of them, in the order of the blocks: two calls,
+  // one to count), and per value before and after into `counts` (2 * DUST_HIP_DELTA_BINS), if given. Only reads both. delta_apply plays
+  // such a list onto this geometry, backwards on request; `conflicts` receives the records whose voxel was not in the state the list
+  // assumes. Scenes that instance this geometry must commit() again.
+  std::vector<DustHipDeltaVoxel> delta(const VoxGeometry& after, DustHipDeltaQuery query, DustHipDeltaResult* result = nullptr,
+                                       std::vector<uint32_t>* counts = nullptr) const {
+    query.struct_size = sizeof(query);
+    DustHipDeltaResult r{};
+    check(dust_hip_model_delta(h_, after.h_, &query, &r, nullptr, 0, nullptr));
+    std::vector<DustHipDeltaVoxel> voxels(r.voxels);
+    if (counts) counts->assign(2 * size_t(DUST_HIP_DELTA_BINS), 0u);
+    check(dust_hip_model_delta(h_, after.h_, &query, &r, voxels.data(), uint32_t(voxels.size()), counts ? counts->data() : nullptr));
+    if (result) *result = r;
+    return voxels;
+  }
+  uint32_t delta_apply(const std::vector<DustHipDeltaVoxel>& records, bool backward = false, uint32_t* conflicts = nullptr) {
+    uint32_t changed = 0;
+    check(dust_hip_model_delta_apply(h_, records.data(), uint32_t(records.size()), backward ? DUST_HIP_DELTA_BACKWARD : 0u, &changed, conflicts));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
