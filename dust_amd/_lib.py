@@ -308,6 +308,26 @@ DELTA_BINS = 256
 MAX_DELTA_RECORDS = 1 << 24
 
 
+class ColumnsQuery(C.Structure):  # DustHipColumnsQuery, 48 bytes: a SurfaceQuery's layout with the one side looked from where its faces stand, and the layer
+    _fields_ = [("struct_size", C.c_uint32), ("face", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("layer", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ColumnsResult(C.Structure):  # DustHipColumnsResult, 64 bytes: columns, those with the layer, their runs' voxels, every run, depths, the two keys, bounds
+    _fields_ = [("columns", C.c_uint32), ("hit", C.c_uint32), ("voxels", C.c_uint32), ("runs", C.c_uint32), ("depth_sum", C.c_uint32),
+                ("nearest_key", C.c_uint32), ("farthest_key", C.c_uint32), ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("hi", C.c_uint8 * 3),
+                ("pad1", C.c_uint8), ("reserved", C.c_uint32 * 7)]
+
+
+class ColumnCell(C.Structure):  # DustHipColumnCell, 4 bytes: where a column's run starts, the palette index there (255: a miss), its length - 1, the column's runs
+    _fields_ = [("at", C.c_uint8), ("palette", C.c_uint8), ("length_minus_1", C.c_uint8), ("runs", C.c_uint8)]
+
+
+COLUMNS_RUN, COLUMNS_GAP = 0, 1
+COLUMNS_BINS = 256
+COLUMNS_NO_KEY = 0xFFFFFFFF
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -391,6 +411,8 @@ SYMBOLS = {
     "dust_hip_model_mesh": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
     "dust_hip_model_delta": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_delta_apply": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _u32p, _u32p]),
+    "dust_hip_model_columns": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
+    "dust_hip_model_columns_apply": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

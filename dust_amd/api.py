@@ -63,6 +63,10 @@ MESH_QUAD_DTYPE = np.dtype([("key", "<u4"), ("face", "u1"), ("palette", "u1"), (
 DELTA_RESULT_DTYPE = np.dtype([("voxels", "<u4"), ("added", "<u4"), ("removed", "<u4"), ("repainted", "<u4"), ("solid_before", "<u4"), ("solid_after", "<u4"),
                                ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 8)])
 DELTA_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("kind", "u1"), ("before", "u1"), ("after", "u1"), ("reserved", "u1")])
+# DustHipColumnsResult (64 bytes) and DustHipColumnCell (4 bytes): the result and the map entries of dust_hip_model_columns
+COLUMNS_RESULT_DTYPE = np.dtype([("columns", "<u4"), ("hit", "<u4"), ("voxels", "<u4"), ("runs", "<u4"), ("depth_sum", "<u4"), ("nearest_key", "<u4"),
+                                 ("farthest_key", "<u4"), ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 7)])
+COLUMN_CELL_DTYPE = np.dtype([("at", "u1"), ("palette", "u1"), ("length_minus_1", "u1"), ("runs", "u1")])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -484,6 +488,52 @@ class Model:
         L.check(self._lib.dust_hip_model_delta_apply(self._h, _ptr(records) if len(records) else None, len(records),
                                                      L.DELTA_BACKWARD if backward else 0, C.byref(changed), C.byref(conflicts)))
         return changed.value, conflicts.value
+
+    def _columns_query(self, face, palette, region, layer):
+        q = L.ColumnsQuery(struct_size=C.sizeof(L.ColumnsQuery), face=face, flags=0, palette=palette, layer=layer)
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        return q
+
+    @staticmethod
+    def columns_shape(face, region=None):
+        """(nv, nu) of the map Model.columns returns for `face` and `region`: the clipped region's extent along v and along u (u = z
+        and v = y for the x sides, u = z and v = x for the y sides, u = y and v = x for the z sides); (0, 0) for an empty region"""
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        extent = [min(int(h), 255) - int(l) + 1 for l, h in zip(lo, hi)]
+        if min(extent) <= 0:
+            return 0, 0
+        axis = {L.FACE_NEG_X: 0, L.FACE_POS_X: 0, L.FACE_NEG_Y: 1, L.FACE_POS_Y: 1, L.FACE_NEG_Z: 2, L.FACE_POS_Z: 2}[face]
+        return extent[1 if axis == 0 else 0], extent[1 if axis == 2 else 2]
+
+    def columns(self, face, palette=-1, region=None, layer=0, cells=True, tables=False):
+        """The model seen from one side, column by column (dust_hip_model_columns). `face` the one L.FACE_* side the columns are
+        looked at from (L.FACE_POS_Y: from above, walking down), `palette` -1 for every solid voxel or the one palette index that counts
+        (everything else is see-through), region = (lo, hi) an inclusive voxel box outside which nothing exists for the call (None: the
+        whole tree), `layer` the run of every column that is asked for, 0 the nearest. Returns (result, map, counts): result a
+        COLUMNS_RESULT_DTYPE record (columns, hit, voxels, runs, depth_sum, nearest_key, farthest_key, lo, hi); map a (nv, nu)
+        COLUMN_CELL_DTYPE array (at, palette -- 255 for a miss --, length_minus_1, runs), or None with cells=False; counts (256,) uint32
+        with counts[0] the missed columns and counts[1 + p] the hit columns whose nearest voxel has palette index p, or None with
+        tables=False. The model is only read."""
+        q = self._columns_query(face, palette, region, layer)
+        out = np.zeros(1, COLUMNS_RESULT_DTYPE)
+        counts = np.zeros(L.COLUMNS_BINS, np.uint32) if tables else None
+        grid = np.zeros(self.columns_shape(face, region), COLUMN_CELL_DTYPE) if cells else None
+        L.check(self._lib.dust_hip_model_columns(self._h, C.byref(q), _ptr(out), _ptr(grid) if cells and grid.size else None,
+                                                 grid.size if cells else 0, _ptr(counts) if tables else None))
+        return out[0], grid, counts
+
+    def columns_apply(self, value, face, where=L.COLUMNS_RUN, depth=1, palette=-1, region=None, layer=0):
+        """In every column Model.columns would report a hit for under the same query, the nearest min(depth, length) voxels of the run
+        (where=L.COLUMNS_RUN) or the min(depth, gap) voxels of the gap directly in front of it (L.COLUMNS_GAP) take `value`, a palette
+        index or -1 for None (dust_hip_model_columns_apply); decided on the model as it stood when the call began. Returns the number
+        of voxels that changed. Scenes instancing the model must be committed again; both fields and the island labelling are invalid
+        afterwards."""
+        q = self._columns_query(face, palette, region, layer)
+        changed = C.c_uint32()
+        L.check(self._lib.dust_hip_model_columns_apply(self._h, C.byref(q), int(where), int(depth), int(value), C.byref(changed)))
+        return changed.value
 
     def find_islands(self, connectivity=L.ISLANDS_FACES, anchor=None, capacity=None, records=None):
         """Label the model's connected solid voxels (dust_hip_model_find_islands): returns (n, records) -- n the number of islands,

@@ -1,9 +1,9 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
 // edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip), model floods (flood.hip), model
-// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip), model surfaces (surface.hip), model meshes (mesh.hip) and model deltas
-// (delta.hip). What needs no device is in three headers: the hierarchy build itself
+// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip), model surfaces (surface.hip), model meshes (mesh.hip), model deltas
+// (delta.hip) and model columns (column.hip). What needs no device is in three headers: the hierarchy build itself
 // (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp, the arithmetic on the callers' records (conversion, chunks,
-// cell lists, cast hits, census records, surface, mesh and delta queries, a delta_apply's records) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
+// cell lists, cast hits, census records, surface, mesh, delta and columns queries, a delta_apply's records) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1283,6 +1283,95 @@ DustStatus dust_hip_model_delta_apply(DustHipModel* m, const DustHipDeltaVoxel* 
     }
     if (changed) *changed = counters[0];
     if (conflicts) *conflicts = counters[1];
+    return DUST_OK;
+  });
+}
+
+// ---- model columns (column.hip): run `layer` of every voxel column along an axis, decided from the brick masks (and the grid bytes
+// under a palette filter); mapped and counted without writing anything (k_columns), or written into with the rebuild of an edit
+// behind it (k_columns_apply). Reads the model as dust_hip_model_surface does.
+namespace {
+// what both calls refuse, in the order the header gives: the model's kind before anything of the query is looked at
+DustStatus columns_query(const DustHipModel* m, const DustHipColumnsQuery* q, dust::ColumnArgs& a, bool& empty, uint32_t& nu, uint32_t& nv) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  const DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipColumnsQuery");
+  if (const char* why = dust::device_columns(*q, a, empty, nu, nv)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return DUST_OK;
+}
+}  // namespace
+
+DustStatus dust_hip_model_columns(const DustHipModel* m, const DustHipColumnsQuery* q, DustHipColumnsResult* result, DustHipColumnCell* cells,
+                                  uint32_t capacity, uint32_t* counts) {
+  dust::ColumnArgs a{};
+  bool empty = false;
+  uint32_t nu = 0, nv = 0;
+  DustStatus s = columns_query(m, q, a, empty, nu, nv);
+  if (s != DUST_OK) return s;
+  const uint32_t columns = nu * nv;
+  if (cells && capacity < columns) return fail(DUST_ERR_INVALID_ARGUMENT, "capacity below the columns of the clipped region");
+  return guarded([&]() -> DustStatus {
+    uint32_t acc[dust::kColumnAccWords] = {};
+    std::vector<uint32_t> bins(counts ? dust::kColumnBins : 0, 0u);
+    if (!empty) {
+      DustHipContext* ctx = m->ctx;
+      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_TRY(join_side(ctx));
+      hipStream_t st = ctx->stream;
+      if ((s = cast_source_masks(ctx, m, &a.brick_mask)) != DUST_OK) return s;
+      // the grid only where a byte is needed: under a filter, or for the hit voxels' palette in the map or the table
+      if ((a.byte != 0u || cells || counts) && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, (dust::kColumnAccWords + dust::kColumnBins) * 4)) != DUST_OK) return s;
+      if (cells && (s = grow(ctx, ctx->stage_aux, size_t(columns) * sizeof(DustHipColumnCell))) != DUST_OK) return s;
+      a.acc = static_cast<uint32_t*>(ctx->stage_out.p);
+      a.bins = counts ? a.acc + dust::kColumnAccWords : nullptr;
+      a.cells = cells ? static_cast<uint32_t*>(ctx->stage_aux.p) : nullptr;
+      HIP_TRY(hipMemsetAsync(a.acc, 0, (dust::kColumnAccWords + dust::kColumnBins) * 4, st));
+      HIP_TRY(dust::launch_columns(a, st));
+      HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+      if (counts) HIP_TRY(hipMemcpyAsync(bins.data(), a.bins, dust::kColumnBins * 4, hipMemcpyDeviceToHost, st));
+      if (cells) HIP_TRY(hipMemcpyAsync(cells, a.cells, size_t(columns) * sizeof(DustHipColumnCell), hipMemcpyDeviceToHost, st));  // (every cell of the map is written)
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (result) *result = dust::columns_result(empty ? nullptr : acc, nu, nv);
+    if (counts) std::memcpy(counts, bins.data(), dust::kColumnBins * 4);
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_columns_apply(DustHipModel* m, const DustHipColumnsQuery* q, uint32_t where, uint32_t depth, int32_t value, uint32_t* changed) {
+  dust::ColumnApplyArgs a{};
+  bool empty = false;
+  uint32_t nu = 0, nv = 0;
+  DustStatus s = columns_query(m, q, a.q, empty, nu, nv);
+  if (s != DUST_OK) return s;
+  if (const char* why = dust::columns_apply_arguments(where, depth, value)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    s = begin_edit(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    invalidate_derived(es);
+    uint32_t n = 0;
+    if (!empty) {
+      if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;
+      a.q.brick_mask = static_cast<const uint64_t*>(es.brick_mask.p);  // as the last rebuild left it: nothing writes it before the next
+      a.q.grid = static_cast<const uint8_t*>(es.grid.p);               // (the filter's bytes: a lane reads its own column's only)
+      a.grid = static_cast<uint8_t*>(es.grid.p);
+      a.where = where;
+      a.depth = depth;
+      a.to = value < 0 ? 0u : uint32_t(value) + 1u;
+      a.changed = static_cast<uint32_t*>(es.changed.p);
+      HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
+      HIP_TRY(dust::launch_columns_apply(a, st));
+      HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
+    }
+    s = rebuild_and_refresh(m, es);  // synchronises; k_edit_brick_masks makes the masks again from the grid
+    if (s != DUST_OK) return s;
+    if (changed) *changed = n;
     return DUST_OK;
   });
 }

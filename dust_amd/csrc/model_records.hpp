@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp and tests/cpp/delta_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp and tests/cpp/column_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -11,6 +11,7 @@
 #include "../../include/dust_hip.h"
 #include "cast.hpp"
 #include "census.hpp"
+#include "column.hpp"
 #include "delta.hpp"
 #include "distance.hpp"
 #include "edit.hpp"
@@ -29,6 +30,10 @@ static_assert(sizeof(DustHipDeltaQuery) == sizeof(DustHipSurfaceQuery) && sizeof
                   kDeltaBins == DUST_HIP_DELTA_BINS && kDeltaMaxRecords == DUST_HIP_MAX_DELTA_RECORDS && kDeltaAdded == DUST_HIP_DELTA_ADDED &&
                   kDeltaRemoved == DUST_HIP_DELTA_REMOVED && kDeltaRepainted == DUST_HIP_DELTA_REPAINTED,
               "delta records");
+static_assert(sizeof(DustHipColumnsQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipColumnsResult) == 64 && sizeof(DustHipColumnCell) == 4 &&
+                  kColumnBins == DUST_HIP_COLUMNS_BINS && kColumnsRun == DUST_HIP_COLUMNS_RUN && kColumnsGap == DUST_HIP_COLUMNS_GAP &&
+                  kColumnNoKey == DUST_HIP_COLUMNS_NO_KEY,
+              "columns records");
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
@@ -375,6 +380,65 @@ inline const char* delta_apply_records(const DustHipDeltaVoxel* records, uint32_
     out.push_back(uint64_t(v.key) | (uint64_t(v.kind) << 32) | (uint64_t(v.before) << 40) | (uint64_t(v.after) << 48));
   }
   return nullptr;
+}
+
+// A columns query as the kernels read it (dust_hip_model_columns, _columns_apply): the axis and the end the walk starts at, the filter's
+// grid byte, the layer, the region clipped to the tree (a coordinate past 255 is cut back to it; lo past hi is the empty region) and the
+// root-cell columns it reaches in the (u, v) plane. The pointers are the caller's. nullptr: the query is fine; otherwise why the call
+// refuses it, in the header's order. `nu`, `nv`: the size of the map, 0 x 0 when `empty` -- then nothing is looked at, no launch is
+// made and the region fields are not set.
+inline const char* device_columns(const DustHipColumnsQuery& q, ColumnArgs& d, bool& empty, uint32_t& nu, uint32_t& nv) {
+  if (q.face == 0u || q.face > DUST_HIP_FACES_ALL || (q.face & (q.face - 1u)) != 0u) return "face must be exactly one DUST_HIP_FACE_* bit";
+  if (q.flags != 0u) return "unknown columns flag";
+  if (q.reserved != 0u) return "reserved word not 0";
+  if (q.palette < -1 || q.palette > 254) return "palette must be -1 (every solid voxel) or 0..254";
+  if (q.layer > 255u) return "layer must be 0..255";
+  uint32_t index = 0;  // the direction's index: -x, +x, -y, +y, -z, +z
+  while ((q.face >> index) != 1u) ++index;
+  d.axis = index >> 1;
+  d.from_high = index & 1u;
+  d.byte = q.palette < 0 ? 0u : uint32_t(q.palette) + 1u;
+  d.layer = q.layer;
+  uint32_t lo[3], hi[3];
+  empty = false;
+  for (int r = 0; r < 3; ++r) {
+    lo[r] = q.lo[r]; hi[r] = std::min(q.hi[r], 255u);
+    empty |= lo[r] > hi[r];
+  }
+  nu = nv = 0;
+  if (empty) return nullptr;
+  const uint32_t ua = column_u_axis(d.axis), va = column_v_axis(d.axis);
+  d.lo_n = lo[d.axis]; d.hi_n = hi[d.axis];
+  d.lo_u = lo[ua]; d.hi_u = hi[ua];
+  d.lo_v = lo[va]; d.hi_v = hi[va];
+  d.cell_u = d.lo_u >> 4; d.cells_u = (d.hi_u >> 4) - d.cell_u + 1u;
+  d.cell_v = d.lo_v >> 4; d.cells_v = (d.hi_v >> 4) - d.cell_v + 1u;
+  nu = d.hi_u - d.lo_u + 1u; nv = d.hi_v - d.lo_v + 1u;
+  return nullptr;
+}
+// what dust_hip_model_columns_apply refuses beyond the query
+inline const char* columns_apply_arguments(uint32_t where, uint32_t depth, int32_t value) {
+  if (where > DUST_HIP_COLUMNS_GAP) return "where must be DUST_HIP_COLUMNS_RUN or DUST_HIP_COLUMNS_GAP";
+  if (depth == 0u || depth > 256u) return "depth must be 1..256";
+  if (value < -1 || value > 254) return "value must be -1 (None) or a palette index 0..254";
+  return nullptr;
+}
+// What a columns call's caller gets from the device's kColumnAccWords accumulator and the size of the map; null: nothing was looked
+// at -- the zero result, keys DUST_HIP_COLUMNS_NO_KEY, bounds 255 / 0 (what a region without a hit column has too, beside its columns
+// and runs).
+inline DustHipColumnsResult columns_result(const uint32_t* acc, uint32_t nu, uint32_t nv) {
+  DustHipColumnsResult r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  r.nearest_key = r.farthest_key = kColumnNoKey;
+  if (!acc) return r;
+  r.columns = nu * nv;
+  r.hit = acc[0]; r.voxels = acc[1]; r.runs = acc[2]; r.depth_sum = acc[3];
+  if (r.hit != 0u) {
+    r.nearest_key = column_near_key(acc[4]);
+    r.farthest_key = column_far_key(acc[5]);
+  }
+  for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[6 + k]); r.hi[k] = uint8_t(acc[9 + k]); }
+  return r;
 }
 
 // the records of a call that cover something, in call order: `index` maps them back to the caller's

@@ -867,6 +867,93 @@ DustStatus dust_hip_model_delta(const DustHipModel* before, const DustHipModel* 
                                 uint32_t* counts /* 2 * 256, may be NULL */);
 DustStatus dust_hip_model_delta_apply(DustHipModel*, const DustHipDeltaVoxel* records, uint32_t n, uint32_t flags,
                                       uint32_t* changed /* may be NULL */, uint32_t* conflicts /* may be NULL */);
+/* Model columns: the 2.5-D view of a model -- for every voxel column along an axis, where the solid starts, how thick it is and what
+ * lies behind it: the height of the ground at (x, z) for spawning and placing, a heightfield collider, a minimap or an orthographic
+ * thumbnail (height plus the palette of the top voxel), sky exposure (snow, rain and sunlight reach a voxel only when nothing is above
+ * it), the ceiling and the floor of the cave under an overhang (the second layer), and the oldest terrain edit there is: the top
+ * voxel becomes grass, the three below it dirt.
+ *
+ * Side and axis: query.face names exactly one DUST_HIP_FACE_* bit, the side the columns are looked at FROM. DUST_HIP_FACE_POS_Y looks
+ * down from above: a column is walked from hi[1] down to lo[1]; DUST_HIP_FACE_NEG_Y looks up from below, from lo[1] up to hi[1]; the
+ * other axes work alike. "Near" is the end the walk starts at.
+ * Region: lo / hi is an inclusive voxel box, clipped to the tree (a coordinate above 255 is cut back to 255); lo > hi on an axis is
+ * legal and empty. Unlike dust_hip_model_surface, voxels outside the region do not exist for this call: a run is cut at the region's
+ * faces, and nothing outside is consulted.
+ * Counted voxel: with palette -1 every solid voxel; with palette 0..254 only voxels of that index -- every other voxel, solid or
+ * not, is see-through.
+ * Run: a maximal stretch of consecutive counted voxels in a column, numbered 0, 1, 2, ... from the near end; a column of 256 voxels
+ * has at most 128. Gap of run k: the stretch of not-counted voxels between run k - 1 (or the near region face) and run k; it may be
+ * empty. Layer: query.layer (0..255) selects run `layer` of every column; a column with fewer runs is a miss.
+ * Map: one DustHipColumnCell per column of the clipped region, row-major [v][u] with u fastest; u / v are dust_hip_model_mesh's axes:
+ * u = z and v = y for the x sides, u = z and v = x for the y sides, u = y and v = x for the z sides. at is the coordinate, on the
+ * axis, of the run's nearest voxel; palette that voxel's index 0..254, or 255 for a miss (then at = length_minus_1 = 0);
+ * length_minus_1 the run length 1..256 minus one; runs the number of runs of the whole column, valid for a miss too. The device writes
+ * a cell as one 32-bit word.
+ * Result, all of it defined for the empty region as well: columns, the columns of the clipped region; hit, those that have the layer;
+ * voxels, the sum of the listed runs' lengths; runs, the sum of every column's run count; depth_sum, the sum over the hit columns of
+ * the number of voxels between the near region face and `at` (the mean height is depth_sum / hit); nearest_key and farthest_key, the
+ * key x << 16 | y << 8 | z of the hit voxel (a listed run's nearest voxel) with the smallest and with the largest depth, among equals
+ * the lowest key, DUST_HIP_COLUMNS_NO_KEY without a hit; lo / hi, the inclusive bounds of the hit voxels (255, 255, 255 / 0, 0, 0
+ * when there is none, as in DustHipSurfaceResult); pad and reserved 0.
+ * cells may be NULL: counts only. Otherwise capacity, counted in cells, must be at least result.columns; a smaller one is refused and
+ * nothing is written. counts may be NULL; otherwise DUST_HIP_COLUMNS_BINS words: bin 0 the missed columns, bin 1 + p the hit columns
+ * whose nearest voxel has palette index p (dust_hip_model_census's bins); the table sums to columns.
+ * dust_hip_model_columns only reads the model, with dust_hip_model_surface's guarantees: one that is not editable stays not editable
+ * (its blocks' masks are scattered into the context's 2 MiB scratch as for a cast's source, and it is expanded into the 16 MiB
+ * scratch grid only when a grid byte is needed: a palette filter, a map, the table); the generation does not move; the island
+ * labelling and both fields stand.
+ * dust_hip_model_columns_apply, decided on the model as it stood when the call began, in every column that has the layer: with
+ * DUST_HIP_COLUMNS_RUN the nearest min(depth, length) voxels of the run take `value`; with DUST_HIP_COLUMNS_GAP the min(depth, gap
+ * length) voxels of the gap that lie directly in front of the run take `value`, whatever they hold. depth is 1..256; value -1 for
+ * None or a palette index 0..254; *changed the number of voxels whose value changed. The model is then made editable and rebuilt
+ * exactly as after dust_hip_model_surface_apply, byte for byte a host build; the generation is bumped, the island labelling and both
+ * fields are invalid afterwards. With DUST_HIP_FACE_POS_Y and layer 0: RUN 1 grass, then RUN 4 under a stone filter, is grass over
+ * dirt; GAP 1 snow is snow only under open sky; RUN 256 None peels the top layer off; GAP 256 water with the region's hi[1] at sea
+ * level fills to sea level from above and stops at the first roof.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything happens, every output untouched: a null model or query; a struct_size below
+ * the struct's size; a face that is not a single bit below 64; a non-zero flag or reserved word; a palette below -1 or above 254; a
+ * layer above 255; a capacity below result.columns with cells given; a where above DUST_HIP_COLUMNS_GAP; a depth of 0 or above 256; a
+ * value below -1 or above 254. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material
+ * byte 255), before the query is looked at. Both calls are synchronous, like every model call. Everything is integer arithmetic: two
+ * runs give the same bytes.
+ * Out of scope: columns across the instances of a scene in world space; walls (the outside of the tree as solid); arbitrary
+ * directions; 4096^3 trees; an asynchronous form; more than one layer per call. */
+#define DUST_HIP_COLUMNS_RUN 0u        /* columns_apply where: the nearest voxels of the run */
+#define DUST_HIP_COLUMNS_GAP 1u        /* ... the voxels of the gap directly in front of the run */
+#define DUST_HIP_COLUMNS_BINS 256u
+#define DUST_HIP_COLUMNS_NO_KEY 0xFFFFFFFFu
+typedef struct DustHipColumnsQuery {   /* 48 bytes, DustHipSurfaceQuery's layout */
+  uint32_t struct_size;
+  uint32_t face;                 /* exactly one DUST_HIP_FACE_* bit: the side the columns are looked at from */
+  uint32_t flags;                /* 0 */
+  int32_t palette;               /* -1: every solid voxel counts; 0..254: only voxels of this palette index */
+  uint32_t lo[3], hi[3];         /* inclusive region, clipped to the tree */
+  uint32_t layer;                /* 0..255: the run of every column that is asked for */
+  uint32_t reserved;             /* 0 */
+} DustHipColumnsQuery;
+typedef struct DustHipColumnsResult {  /* 64 bytes */
+  uint32_t columns;              /* columns of the clipped region */
+  uint32_t hit;                  /* ... that have the layer */
+  uint32_t voxels;               /* the sum of the listed runs' lengths */
+  uint32_t runs;                 /* the sum of every column's run count */
+  uint32_t depth_sum;            /* the sum over hit columns of the voxels between the near region face and `at` */
+  uint32_t nearest_key;          /* x << 16 | y << 8 | z of the hit voxel with the smallest depth; DUST_HIP_COLUMNS_NO_KEY without a hit */
+  uint32_t farthest_key;         /* ... with the largest depth */
+  uint8_t lo[3], pad0;           /* inclusive bounds of the hit voxels; 255,255,255 when there is none */
+  uint8_t hi[3], pad1;           /* 0,0,0 when there is none; pad bytes 0 */
+  uint32_t reserved[7];          /* 0 */
+} DustHipColumnsResult;
+typedef struct DustHipColumnCell {     /* 4 bytes */
+  uint8_t at;                    /* the coordinate on the axis of the run's nearest voxel; 0 for a miss */
+  uint8_t palette;               /* that voxel's palette index 0..254; 255 for a miss */
+  uint8_t length_minus_1;        /* the run's length 1..256, minus one; 0 for a miss */
+  uint8_t runs;                  /* the runs of the whole column, 0..128 */
+} DustHipColumnCell;
+DustStatus dust_hip_model_columns(const DustHipModel*, const DustHipColumnsQuery*, DustHipColumnsResult* result /* may be NULL */,
+                                  DustHipColumnCell* cells /* capacity >= result.columns; may be NULL: counts only */, uint32_t capacity,
+                                  uint32_t* counts /* 256, may be NULL */);
+DustStatus dust_hip_model_columns_apply(DustHipModel*, const DustHipColumnsQuery*, uint32_t where, uint32_t depth, int32_t value,
+                                        uint32_t* changed /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

@@ -338,6 +338,30 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model columns (dust_hip_model_columns / columns_apply): this geometry seen from the ONE side query.face, column by column inside
+  // the query's region -- run query.layer of every column as a map, row-major [v][u] (result.columns cells; the result says how many
+  // columns have the layer, how deep they lie, which is nearest and farthest), and the hit columns per palette index into `counts`
+  // (DUST_HIP_COLUMNS_BINS), if given. Only reads. columns_apply writes `depth` voxels of every hit column's run
+  // (DUST_HIP_COLUMNS_RUN) or of the gap in front of it (DUST_HIP_COLUMNS_GAP) with a palette index (nullopt: None); scenes that
+  // instance this geometry must commit() again.
+  std::vector<DustHipColumnCell> columns(DustHipColumnsQuery query, DustHipColumnsResult* result = nullptr, std::vector<uint32_t>* counts = nullptr) const {
+    query.struct_size = sizeof(query);
+    DustHipColumnsResult r{};
+    check(dust_hip_model_columns(h_, &query, &r, nullptr, 0, nullptr));
+    std::vector<DustHipColumnCell> cells(r.columns);
+    if (counts) counts->assign(size_t(DUST_HIP_COLUMNS_BINS), 0u);
+    check(dust_hip_model_columns(h_, &query, &r, cells.empty() ? nullptr : cells.data(), uint32_t(cells.size()), counts ? counts->data() : nullptr));
+    if (result) *result = r;
+    return cells;
+  }
+  uint32_t columns_apply(DustHipColumnsQuery query, uint32_t where, uint32_t depth, std::optional<uint8_t> palette_index) {
+    query.struct_size = sizeof(query);
+    uint32_t changed = 0;
+    check(dust_hip_model_columns_apply(h_, &query, where, depth, palette_index ? int32_t(*palette_index) : -1, &changed));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
