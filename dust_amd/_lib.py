@@ -328,6 +328,28 @@ COLUMNS_BINS = 256
 COLUMNS_NO_KEY = 0xFFFFFFFF
 
 
+class NeighboursQuery(C.Structure):  # DustHipNeighboursQuery, 48 bytes: a SurfaceQuery's layout with the neighbourhood where its faces stand, and the two masks
+    _fields_ = [("struct_size", C.c_uint32), ("neighbourhood", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("birth", C.c_uint32), ("survive", C.c_uint32)]
+
+
+class NeighboursResult(C.Structure):  # DustHipNeighboursResult, 64 bytes: the region's voxels, the solid ones, what one generation would do, its bounds
+    _fields_ = [("voxels", C.c_uint32), ("solid", C.c_uint32), ("born", C.c_uint32), ("died", C.c_uint32), ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8),
+                ("hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("reserved", C.c_uint32 * 10)]
+
+
+class NeighboursApplied(C.Structure):  # DustHipNeighboursApplied, 64 bytes: the generations that changed something, solid before and after, the sums, the bounds
+    _fields_ = [("generations", C.c_uint32), ("solid_before", C.c_uint32), ("solid_after", C.c_uint32), ("reserved0", C.c_uint32),
+                ("born", C.c_uint64), ("died", C.c_uint64), ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("hi", C.c_uint8 * 3), ("pad1", C.c_uint8),
+                ("reserved", C.c_uint32 * 6)]
+
+
+NEIGHBOURS_FACES, NEIGHBOURS_EDGES, NEIGHBOURS_CORNERS = 6, 18, 26
+NEIGHBOURS_WALLS, NEIGHBOURS_MAJORITY = 1, 2
+NEIGHBOURS_BINS = 27
+NEIGHBOURS_MAX_GENERATIONS = 256
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -413,6 +435,8 @@ SYMBOLS = {
     "dust_hip_model_delta_apply": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     "dust_hip_model_columns": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_columns_apply": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int32, _u32p]),
+    "dust_hip_model_neighbours": (C.c_int, [_P, _P, _P, _P]),
+    "dust_hip_model_neighbours_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

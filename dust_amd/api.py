@@ -67,11 +67,30 @@ DELTA_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("kind", "u1"), ("before", "u1"), 
 COLUMNS_RESULT_DTYPE = np.dtype([("columns", "<u4"), ("hit", "<u4"), ("voxels", "<u4"), ("runs", "<u4"), ("depth_sum", "<u4"), ("nearest_key", "<u4"),
                                  ("farthest_key", "<u4"), ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 7)])
 COLUMN_CELL_DTYPE = np.dtype([("at", "u1"), ("palette", "u1"), ("length_minus_1", "u1"), ("runs", "u1")])
+# DustHipNeighboursQuery (48 bytes), DustHipNeighboursResult and DustHipNeighboursApplied (64 bytes each): the query of
+# dust_hip_model_neighbours and _neighbours_apply and what each of them returns
+NEIGHBOURS_QUERY_DTYPE = np.dtype([("struct_size", "<u4"), ("neighbourhood", "<u4"), ("flags", "<u4"), ("palette", "<i4"), ("lo", "<u4", 3), ("hi", "<u4", 3),
+                                   ("birth", "<u4"), ("survive", "<u4")])
+NEIGHBOURS_RESULT_DTYPE = np.dtype([("voxels", "<u4"), ("solid", "<u4"), ("born", "<u4"), ("died", "<u4"), ("lo", "u1", 3), ("pad0", "u1"),
+                                    ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 10)])
+NEIGHBOURS_APPLIED_DTYPE = np.dtype([("generations", "<u4"), ("solid_before", "<u4"), ("solid_after", "<u4"), ("reserved0", "<u4"), ("born", "<u8"), ("died", "<u8"),
+                                     ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 6)])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
 ISLAND_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("flags", "u1"), ("hi", "u1", 3), ("reserved", "u1"), ("sum", "<u8", 3)])
 FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def count_mask(*ranges):
+    """The bit mask over neighbour counts that Model.neighbours and Model.neighbours_apply take as `birth` and `survive`: each argument a
+    count or an inclusive (first, last) pair -- count_mask((14, 26)) is bits 14..26, count_mask(5, 6) bits 5 and 6, count_mask() 0."""
+    mask = 0
+    for r in ranges:
+        first, last = (r, r) if isinstance(r, (int, np.integer)) else r
+        for n in range(int(first), int(last) + 1):
+            mask |= 1 << n
+    return mask
 
 PLANE_DTYPES = {
     L.PLANE_ILLUMINANCE: (np.uint16, 4), L.PLANE_DENOISED: (np.uint16, 4), L.PLANE_ALBEDO: (np.uint32, 1),
@@ -534,6 +553,43 @@ class Model:
         changed = C.c_uint32()
         L.check(self._lib.dust_hip_model_columns_apply(self._h, C.byref(q), int(where), int(depth), int(value), C.byref(changed)))
         return changed.value
+
+    def _neighbours_query(self, neighbourhood, birth, survive, palette, flags, region):
+        q = L.NeighboursQuery(struct_size=C.sizeof(L.NeighboursQuery), neighbourhood=neighbourhood, flags=flags, palette=palette, birth=birth, survive=survive)
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        return q
+
+    def neighbours(self, neighbourhood, birth=0, survive=None, palette=0, region=None, walls=False, tables=True):
+        """How many solid neighbours the voxels of a region have, and what one generation of a birth / survive rule would do to them
+        (dust_hip_model_neighbours). `neighbourhood` L.NEIGHBOURS_FACES (6), L.NEIGHBOURS_EDGES (18) or L.NEIGHBOURS_CORNERS (26);
+        `birth` / `survive` bit masks over the count (count_mask; survive None: every count survives); region = (lo, hi) an inclusive
+        voxel box (None: the whole tree); walls: the outside of the tree counts as solid. Returns (result, counts): result a
+        NEIGHBOURS_RESULT_DTYPE record (voxels, solid, born, died, lo, hi); counts (2, 27) uint32 with counts[0, n] the empty and
+        counts[1, n] the solid voxels with n neighbours, or None with tables=False. The model is only read: no grid is made."""
+        if survive is None:
+            survive = (2 << neighbourhood) - 1 if neighbourhood in (6, 18, 26) else 0
+        q = self._neighbours_query(neighbourhood, birth, survive, palette, L.NEIGHBOURS_WALLS if walls else 0, region)
+        out = np.zeros(1, NEIGHBOURS_RESULT_DTYPE)
+        counts = np.zeros((2, L.NEIGHBOURS_BINS), np.uint32) if tables else None
+        L.check(self._lib.dust_hip_model_neighbours(self._h, C.byref(q), _ptr(out), _ptr(counts) if tables else None))
+        return out[0], counts
+
+    def neighbours_apply(self, neighbourhood, birth, survive, generations=1, palette=0, majority=False, region=None, walls=False, per_generation=False):
+        """Run `generations` (1..256) synchronous generations of a birth / survive rule on the device (dust_hip_model_neighbours_apply):
+        an empty voxel of the region with bit n of `birth` set becomes solid, a solid one with bit n of `survive` clear becomes empty, n
+        its solid neighbours. A born voxel takes `palette`, or under majority=True the palette index most of its solid neighbours carry
+        (the lowest among equals; `palette` where nobody votes). Returns the NEIGHBOURS_APPLIED_DTYPE record (generations -- 1 + the last
+        one that changed a voxel --, solid_before, solid_after, born, died, lo, hi), with per_generation=True (record, table), table a
+        (generations, 2) uint32 array of born and died per generation. Scenes instancing the model must be committed again; both fields
+        and the island labelling are invalid afterwards."""
+        flags = (L.NEIGHBOURS_WALLS if walls else 0) | (L.NEIGHBOURS_MAJORITY if majority else 0)
+        q = self._neighbours_query(neighbourhood, birth, survive, palette, flags, region)
+        out = np.zeros(1, NEIGHBOURS_APPLIED_DTYPE)
+        table = np.zeros((max(int(generations), 0), 2), np.uint32) if per_generation else None
+        L.check(self._lib.dust_hip_model_neighbours_apply(self._h, C.byref(q), int(generations), _ptr(out), _ptr(table) if per_generation and table.size else None))
+        return (out[0], table) if per_generation else out[0]
 
     def find_islands(self, connectivity=L.ISLANDS_FACES, anchor=None, capacity=None, records=None):
         """Label the model's connected solid voxels (dust_hip_model_find_islands): returns (n, records) -- n the number of islands,

@@ -1376,6 +1376,109 @@ DustStatus dust_hip_model_columns_apply(DustHipModel* m, const DustHipColumnsQue
   });
 }
 
+// ---- model neighbourhoods (neighbour.hip): how many of a voxel's 6, 18 or 26 neighbours are solid, decided from the brick masks alone;
+// counted, with what one generation of a birth / survive rule would do, without writing anything (k_neighbours), or run generation by
+// generation between the model's grid and masks and the context's scratch pair, with ONE rebuild behind them (k_neighbours_step).
+namespace {
+// what both calls refuse, in the order the header gives: the model's kind before anything of the query is looked at
+DustStatus neighbours_query(const DustHipModel* m, const DustHipNeighboursQuery* q, dust::NeighbourArgs& a, uint32_t& byte, uint32_t& majority, bool& empty) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  const DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipNeighboursQuery");
+  if (const char* why = dust::device_neighbours(*q, a, byte, majority, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return DUST_OK;
+}
+}  // namespace
+
+DustStatus dust_hip_model_neighbours(const DustHipModel* m, const DustHipNeighboursQuery* q, DustHipNeighboursResult* result, uint32_t* counts) {
+  dust::NeighbourArgs a{};
+  bool empty = false;
+  uint32_t byte = 0, majority = 0;  // (an apply's)
+  DustStatus s = neighbours_query(m, q, a, byte, majority, empty);
+  if (s != DUST_OK) return s;
+  return guarded([&]() -> DustStatus {
+    uint32_t acc[dust::kNeighbourAccWords + dust::kNeighbourTableWords] = {};
+    if (!empty) {
+      DustHipContext* ctx = m->ctx;
+      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_TRY(join_side(ctx));
+      hipStream_t st = ctx->stream;
+      if ((s = cast_source_masks(ctx, m, &a.brick_mask)) != DUST_OK) return s;  // the masks are all this call reads: no grid is made
+      if ((s = grow(ctx, ctx->stage_out, sizeof(acc))) != DUST_OK) return s;
+      a.acc = static_cast<uint32_t*>(ctx->stage_out.p);
+      a.table = counts ? a.acc + dust::kNeighbourAccWords : nullptr;
+      HIP_TRY(hipMemsetAsync(a.acc, 0, sizeof(acc), st));
+      HIP_TRY(dust::launch_neighbours(a, st));
+      HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (result) *result = dust::neighbours_result(empty ? nullptr : acc);
+    if (counts) std::memcpy(counts, acc + dust::kNeighbourAccWords, dust::kNeighbourTableWords * 4);
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_neighbours_apply(DustHipModel* m, const DustHipNeighboursQuery* q, uint32_t generations, DustHipNeighboursApplied* applied,
+                                           uint32_t* per_generation) {
+  dust::NeighbourStepArgs a{};
+  bool empty = false;
+  DustStatus s = neighbours_query(m, q, a.q, a.byte, a.majority, empty);
+  if (s != DUST_OK) return s;
+  if (const char* why = dust::neighbours_apply_arguments(generations)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    s = begin_edit(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    invalidate_derived(es);
+    std::vector<uint32_t> slots(empty ? 0 : dust::kNeighbourApplyWords, 0u);
+    if (!empty) {
+      const size_t L = dust::kLattice;
+      if ((s = lazy_alloc(ctx->reduce_grid, L * 64, "the generations' second grid (16 MiB)")) != DUST_OK) return s;
+      if ((s = lazy_alloc(ctx->delta_mask, L * 8, "the generations' second masks (2 MiB)")) != DUST_OK) return s;
+      if ((s = grow(ctx, es.changed, slots.size() * 4)) != DUST_OK) return s;
+      // The generations take turns between the model's grid and masks (0) and the scratch pair (1). Both start equal -- so outside the
+      // region they stay equal, and a generation writes only the bricks the region reaches --, and the first generation reads the side
+      // that makes the last one write the model's own grid.
+      uint8_t* grids[2] = {static_cast<uint8_t*>(es.grid.p), static_cast<uint8_t*>(ctx->reduce_grid.p)};
+      uint64_t* masks[2] = {static_cast<uint64_t*>(es.brick_mask.p), static_cast<uint64_t*>(ctx->delta_mask.p)};
+      uint32_t* dev_slots = static_cast<uint32_t*>(es.changed.p);
+      HIP_TRY(hipMemcpyAsync(grids[1], grids[0], L * 64, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(masks[1], masks[0], L * 8, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemsetAsync(dev_slots, 0, slots.size() * 4, st));
+      for (uint32_t g = 0; g < generations; ++g) {
+        const uint32_t to = (generations - 1u - g) & 1u;  // the last generation writes side 0
+        a.q.brick_mask = masks[to ^ 1u];
+        a.grid = grids[to ^ 1u];
+        a.grid_out = grids[to];
+        a.mask_out = masks[to];
+        a.slot = dev_slots + size_t(g) * dust::kNeighbourSlotWords;
+        a.solid = g == 0 ? dev_slots + size_t(dust::kNeighbourMaxGenerations) * dust::kNeighbourSlotWords : nullptr;
+        HIP_TRY(dust::launch_neighbours_step(a, st));
+        // Every kNeighbourCheckEvery generations: has one of them changed nothing? Then the model is at a fixed point, both sides hold it
+        // and no later generation would change anything -- their slots stay 0, which is what they would have added.
+        if ((g + 1u) % dust::kNeighbourCheckEvery == 0u && g + 1u < generations) {
+          HIP_TRY(hipMemcpyAsync(slots.data(), dev_slots, size_t(g + 1u) * dust::kNeighbourSlotWords * 4, hipMemcpyDeviceToHost, st));
+          HIP_TRY(hipStreamSynchronize(st));
+          bool still = false;
+          for (uint32_t k = 0; k <= g; ++k) still |= slots[size_t(k) * dust::kNeighbourSlotWords] + slots[size_t(k) * dust::kNeighbourSlotWords + 1] == 0u;
+          if (still) break;
+        }
+      }
+      HIP_TRY(hipMemcpyAsync(slots.data(), dev_slots, slots.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    s = rebuild_and_refresh(m, es);  // synchronises; k_edit_brick_masks makes the masks again from the grid
+    if (s != DUST_OK) return s;
+    const DustHipNeighboursApplied record =
+        dust::neighbours_applied(empty ? nullptr : slots.data(), generations, empty ? 0u : slots[size_t(dust::kNeighbourMaxGenerations) * dust::kNeighbourSlotWords], per_generation);
+    if (applied) *applied = record;
+    return DUST_OK;
+  });
+}
+
 DustStatus dust_hip_model_info(const DustHipModel* m, uint32_t* n_blocks, uint64_t* n_materials) {
   if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
   if (n_blocks) *n_blocks = m->dev.n_blocks;

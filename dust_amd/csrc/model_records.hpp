@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp and tests/cpp/column_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp and tests/cpp/neighbour_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -16,6 +16,7 @@
 #include "distance.hpp"
 #include "edit.hpp"
 #include "mesh.hpp"
+#include "neighbour.hpp"
 #include "stamp.hpp"
 #include "surface.hpp"
 
@@ -34,6 +35,11 @@ static_assert(sizeof(DustHipColumnsQuery) == sizeof(DustHipSurfaceQuery) && size
                   kColumnBins == DUST_HIP_COLUMNS_BINS && kColumnsRun == DUST_HIP_COLUMNS_RUN && kColumnsGap == DUST_HIP_COLUMNS_GAP &&
                   kColumnNoKey == DUST_HIP_COLUMNS_NO_KEY,
               "columns records");
+static_assert(sizeof(DustHipNeighboursQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipNeighboursResult) == 64 && sizeof(DustHipNeighboursApplied) == 64 &&
+                  kNeighbourFaces == DUST_HIP_NEIGHBOURS_FACES && kNeighbourEdges == DUST_HIP_NEIGHBOURS_EDGES && kNeighbourCorners == DUST_HIP_NEIGHBOURS_CORNERS &&
+                  kNeighbourBins == DUST_HIP_NEIGHBOURS_BINS && kNeighbourMaxGenerations == DUST_HIP_NEIGHBOURS_MAX_GENERATIONS &&
+                  DUST_HIP_NEIGHBOURS_WALLS == DUST_HIP_SURFACE_WALLS,
+              "neighbours records");
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
@@ -438,6 +444,72 @@ inline DustHipColumnsResult columns_result(const uint32_t* acc, uint32_t nu, uin
     r.farthest_key = column_far_key(acc[5]);
   }
   for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[6 + k]); r.hi[k] = uint8_t(acc[9 + k]); }
+  return r;
+}
+
+// A neighbours query as the kernels read it (dust_hip_model_neighbours, _neighbours_apply): the neighbourhood, the walls, the two masks,
+// the region and the root cells it reaches; `byte` and `majority` are what a born voxel takes (an apply's). The pointers are the
+// caller's. nullptr: the query is fine; otherwise why the call refuses it, in the header's order. `empty` as in device_surface: nothing
+// is looked at and no launch is made -- lo, hi and box are not set.
+inline const char* device_neighbours(const DustHipNeighboursQuery& q, NeighbourArgs& d, uint32_t& byte, uint32_t& majority, bool& empty) {
+  if (q.neighbourhood != kNeighbourFaces && q.neighbourhood != kNeighbourEdges && q.neighbourhood != kNeighbourCorners)
+    return "neighbourhood must be DUST_HIP_NEIGHBOURS_FACES, _EDGES or _CORNERS";
+  if ((q.flags & ~(DUST_HIP_NEIGHBOURS_WALLS | DUST_HIP_NEIGHBOURS_MAJORITY)) != 0u) return "unknown neighbours flag";
+  if (q.palette < 0 || q.palette > 254) return "palette must be 0..254";
+  const uint32_t known = (2u << q.neighbourhood) - 1u;  // bits 0..neighbourhood
+  if ((q.birth & ~known) != 0u || (q.survive & ~known) != 0u) return "birth or survive bit above the neighbourhood's size";
+  for (int r = 0; r < 3; ++r)
+    if (q.lo[r] >= 256u || q.hi[r] >= 256u) return "region coordinate outside the tree extent";
+  d.neighbourhood = q.neighbourhood;
+  d.walls = (q.flags & DUST_HIP_NEIGHBOURS_WALLS) ? 1u : 0u;
+  d.birth = q.birth;
+  d.survive = q.survive;
+  byte = uint32_t(q.palette) + 1u;
+  majority = (q.flags & DUST_HIP_NEIGHBOURS_MAJORITY) ? 1u : 0u;
+  empty = false;
+  for (int r = 0; r < 3; ++r) empty |= q.lo[r] > q.hi[r];
+  if (empty) return nullptr;
+  for (int r = 0; r < 3; ++r) {
+    d.lo[r] = q.lo[r]; d.hi[r] = q.hi[r];
+    d.box.lo[r] = q.lo[r] >> 4; d.box.hi[r] = q.hi[r] >> 4;
+  }
+  return nullptr;
+}
+// what dust_hip_model_neighbours_apply refuses beyond the query
+inline const char* neighbours_apply_arguments(uint32_t generations) {
+  if (generations == 0u || generations > kNeighbourMaxGenerations) return "generations must be 1..DUST_HIP_NEIGHBOURS_MAX_GENERATIONS";
+  return nullptr;
+}
+// What a neighbours call's caller gets from the device's kNeighbourAccWords accumulator; null: nothing was looked at -- the zero
+// result, bounds 255 / 0 (what a region in which nothing would change has too).
+inline DustHipNeighboursResult neighbours_result(const uint32_t* acc) {
+  DustHipNeighboursResult r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  if (!acc) return r;
+  r.voxels = acc[0]; r.solid = acc[1]; r.born = acc[2]; r.died = acc[3];
+  for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[4 + k]); r.hi[k] = uint8_t(acc[7 + k]); }
+  return r;
+}
+// What an apply's caller gets from the device's array of `generations` slots (kNeighbourSlotWords each: a generation that never ran
+// left its slot 0) and the solid voxels the first generation found; null: nothing was looked at -- the zero record. per_generation
+// (may be null): 2 * generations words, born and died per generation.
+inline DustHipNeighboursApplied neighbours_applied(const uint32_t* slots, uint32_t generations, uint32_t solid_before, uint32_t* per_generation) {
+  DustHipNeighboursApplied r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  if (per_generation) std::fill(per_generation, per_generation + size_t(generations) * 2, 0u);
+  if (!slots) return r;
+  uint32_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // (lo as 255 - the bound)
+  for (uint32_t g = 0; g < generations; ++g) {
+    const uint32_t* s = slots + size_t(g) * kNeighbourSlotWords;
+    if (s[0] + s[1] == 0u) continue;  // (a fixed point: no later generation changes anything either)
+    r.generations = g + 1u;
+    r.born += s[0]; r.died += s[1];
+    for (int k = 0; k < 3; ++k) { lo[k] = std::max(lo[k], s[2 + k]); hi[k] = std::max(hi[k], s[5 + k]); }
+    if (per_generation) { per_generation[2 * g] = s[0]; per_generation[2 * g + 1] = s[1]; }
+  }
+  r.solid_before = solid_before;
+  r.solid_after = uint32_t(uint64_t(solid_before) + r.born - r.died);
+  for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - lo[k]); r.hi[k] = uint8_t(hi[k]); }
   return r;
 }
 

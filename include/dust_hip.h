@@ -954,6 +954,89 @@ DustStatus dust_hip_model_columns(const DustHipModel*, const DustHipColumnsQuery
                                   uint32_t* counts /* 256, may be NULL */);
 DustStatus dust_hip_model_columns_apply(DustHipModel*, const DustHipColumnsQuery*, uint32_t where, uint32_t depth, int32_t value,
                                         uint32_t* changed /* may be NULL */);
+/* Model neighbourhoods: a voxel decided from how many of its neighbours are solid -- the one-voxel spikes taken off and the one-voxel
+ * pits filled round a crater, specks removed and pinholes closed, caves and rough terrain from a random fill (the "4-5 rule" family,
+ * run for a handful of generations), moss, fire, rot or crystal spreading by contact, one ring per generation, in the material most
+ * neighbours carry.
+ *
+ * Neighbourhood: query.neighbourhood is DUST_HIP_NEIGHBOURS_FACES (6: the offsets with |d|1 == 1), DUST_HIP_NEIGHBOURS_EDGES (18:
+ * |d|1 <= 2 within the 3^3 box) or DUST_HIP_NEIGHBOURS_CORNERS (26: the 3^3 box without its centre). A voxel's count n is the number
+ * of solid voxels at those offsets. A neighbour outside the tree is empty, or solid under DUST_HIP_NEIGHBOURS_WALLS (the convention
+ * of DUST_HIP_SURFACE_WALLS).
+ * Birth and survival: query.birth and query.survive are bit masks over n. An empty voxel with bit n of birth set becomes solid; a
+ * solid voxel with bit n of survive clear becomes empty; every other voxel keeps its value, and survivors keep their material. All
+ * voxels of a generation are decided on the model as it stood before that generation: a synchronous update.
+ * Material of a born voxel: query.palette (0..254). Under DUST_HIP_NEIGHBOURS_MAJORITY it takes the palette index that most of its
+ * solid neighbours in the same neighbourhood carry, the lowest index among equals (dust_hip_model_reduce's tie rule). Walls carry no
+ * material and do not vote; where no neighbour votes (bit 0 of birth, or only walls were counted) the fallback is query.palette.
+ * Region: lo / hi is an inclusive voxel box under dust_hip_model_surface's rules. Only voxels inside it are counted or changed;
+ * neighbours outside it, but inside the tree, are consulted as they are, in every generation. lo > hi on an axis is legal and empty:
+ * the zero result (bounds 255 / 0), and an apply that changes nothing.
+ * Result (dust_hip_model_neighbours): voxels, the voxels of the clipped region; solid, the solid ones; born and died, what ONE
+ * generation of the query's rule would do -- ask first, apply after; lo / hi, the inclusive bounds of the voxels that would change
+ * (255, 255, 255 / 0, 0, 0 when there is none); pad and reserved 0.
+ * Table: counts[n] is the number of empty voxels of the region with n neighbours, counts[27 + n] the same for the solid ones; bins
+ * above the neighbourhood's size are 0; the two rows sum to voxels - solid and to solid.
+ * Applied (dust_hip_model_neighbours_apply): generations, 1 + the index of the last generation that changed a voxel, 0 when none did;
+ * solid_before and solid_after, the region's solid voxels; born and died, the sums over all generations (64 bits: 256 generations of
+ * 16.7 M voxels do not fit 32); lo / hi, the bounds of every voxel born or killed in any generation; pad and reserved 0.
+ * per_generation[2 g] and per_generation[2 g + 1] are the born and the died of generation g; the rows after a fixed point are 0.
+ * Generations: 1..256. The library may stop launching once a generation changed nothing; how often it looks does not show in any
+ * output. A rule that oscillates simply runs all its generations.
+ * dust_hip_model_neighbours only reads the model, with dust_hip_model_surface's guarantees and a stronger one: it needs no grid byte at
+ * all. One that is not editable stays not editable (its blocks' masks are scattered into the context's 2 MiB scratch as for a cast's
+ * source) and is never expanded; the generation does not move; the island labelling and both fields stand.
+ * dust_hip_model_neighbours_apply makes the model editable as every apply does, runs the generations on the device between the
+ * model's grid and the context's scratch grid, and then rebuilds ONCE as after dust_hip_model_surface_apply, byte for byte a host
+ * build. The generation is bumped and the island labelling and both fields are invalid afterwards, even when nothing changed (as
+ * after dust_hip_model_columns_apply).
+ * Refused with DUST_ERR_INVALID_ARGUMENT, the outputs untouched: a null model or query; a struct_size below the struct's size; a
+ * neighbourhood other than 6, 18 or 26; an unknown flag bit; a palette outside 0..254; a birth or survive bit above the
+ * neighbourhood's size; a region coordinate >= 256; generations of 0 or above 256. A null per_generation is fine.
+ * DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material byte 255), before the query is
+ * looked at. Both calls are synchronous, like every model call. Everything is integer arithmetic: two runs give the same bytes.
+ * Out of scope: a list of the voxels that would change; radius above 1, weighted or asymmetric neighbourhoods; rules that count only
+ * one material; asynchronous (sequential-sweep) updates; neighbourhoods across the instances of a scene; 4096^3 trees; an
+ * asynchronous form; a brick worklist between generations. */
+#define DUST_HIP_NEIGHBOURS_FACES 6u
+#define DUST_HIP_NEIGHBOURS_EDGES 18u
+#define DUST_HIP_NEIGHBOURS_CORNERS 26u
+#define DUST_HIP_NEIGHBOURS_WALLS 1u     /* flags: the outside of the tree counts as solid (DUST_HIP_SURFACE_WALLS) */
+#define DUST_HIP_NEIGHBOURS_MAJORITY 2u  /* flags: a born voxel takes the palette index most of its solid neighbours carry */
+#define DUST_HIP_NEIGHBOURS_BINS 27u
+#define DUST_HIP_NEIGHBOURS_MAX_GENERATIONS 256u
+typedef struct DustHipNeighboursQuery {   /* 48 bytes, DustHipSurfaceQuery's layout */
+  uint32_t struct_size;
+  uint32_t neighbourhood;        /* DUST_HIP_NEIGHBOURS_FACES, _EDGES or _CORNERS */
+  uint32_t flags;                /* DUST_HIP_NEIGHBOURS_WALLS | DUST_HIP_NEIGHBOURS_MAJORITY or 0 */
+  int32_t palette;               /* 0..254: what a born voxel takes (under MAJORITY: where nobody votes) */
+  uint32_t lo[3], hi[3];         /* inclusive region, clipped to the tree */
+  uint32_t birth;                /* bit n: an empty voxel with n solid neighbours becomes solid */
+  uint32_t survive;              /* bit n: a solid voxel with n solid neighbours stays */
+} DustHipNeighboursQuery;
+typedef struct DustHipNeighboursResult {  /* 64 bytes */
+  uint32_t voxels;               /* voxels of the clipped region */
+  uint32_t solid;                /* ... that are solid */
+  uint32_t born, died;           /* what one generation of the query's rule would do */
+  uint8_t lo[3], pad0;           /* inclusive bounds of the voxels that would change; 255,255,255 when there is none */
+  uint8_t hi[3], pad1;           /* 0,0,0 when there is none; pad bytes 0 */
+  uint32_t reserved[10];         /* 0 */
+} DustHipNeighboursResult;
+typedef struct DustHipNeighboursApplied { /* 64 bytes */
+  uint32_t generations;          /* 1 + the index of the last generation that changed a voxel; 0 when none did */
+  uint32_t solid_before;         /* the region's solid voxels before the first generation */
+  uint32_t solid_after;          /* ... after the last */
+  uint32_t reserved0;            /* 0 */
+  uint64_t born, died;           /* sums over all generations */
+  uint8_t lo[3], pad0;           /* inclusive bounds of every voxel born or killed; 255,255,255 when there is none */
+  uint8_t hi[3], pad1;           /* 0,0,0 when there is none; pad bytes 0 */
+  uint32_t reserved[6];          /* 0 */
+} DustHipNeighboursApplied;
+DustStatus dust_hip_model_neighbours(const DustHipModel*, const DustHipNeighboursQuery*, DustHipNeighboursResult* result /* may be NULL */,
+                                     uint32_t* counts /* 2 * 27, may be NULL */);
+DustStatus dust_hip_model_neighbours_apply(DustHipModel*, const DustHipNeighboursQuery*, uint32_t generations,
+                                           DustHipNeighboursApplied* applied /* may be NULL */,
+                                           uint32_t* per_generation /* 2 * generations, may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

@@ -362,6 +362,27 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model neighbourhoods (dust_hip_model_neighbours / neighbours_apply): how many of the 6, 18 or 26 neighbours of the voxels inside
+  // the query's region are solid -- the result says what ONE generation of the query's birth / survive masks would do, `counts`
+  // (2 * DUST_HIP_NEIGHBOURS_BINS: the empty row, then the solid row), if given, is the histogram. Only reads, and needs no grid.
+  // neighbours_apply runs `generations` synchronous generations of the rule and rebuilds once; per_generation, if given, receives the
+  // born and the died of every generation; scenes that instance this geometry must commit() again.
+  DustHipNeighboursResult neighbours(DustHipNeighboursQuery query, std::vector<uint32_t>* counts = nullptr) const {
+    query.struct_size = sizeof(query);
+    DustHipNeighboursResult r{};
+    if (counts) counts->assign(size_t(2) * DUST_HIP_NEIGHBOURS_BINS, 0u);
+    check(dust_hip_model_neighbours(h_, &query, &r, counts ? counts->data() : nullptr));
+    return r;
+  }
+  DustHipNeighboursApplied neighbours_apply(DustHipNeighboursQuery query, uint32_t generations = 1, std::vector<uint32_t>* per_generation = nullptr) {
+    query.struct_size = sizeof(query);
+    DustHipNeighboursApplied applied{};
+    if (per_generation) per_generation->assign(size_t(2) * generations, 0u);
+    check(dust_hip_model_neighbours_apply(h_, &query, generations, &applied, per_generation && generations ? per_generation->data() : nullptr));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return applied;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
