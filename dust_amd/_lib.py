@@ -350,6 +350,26 @@ NEIGHBOURS_BINS = 27
 NEIGHBOURS_MAX_GENERATIONS = 256
 
 
+class SettleQuery(C.Structure):  # DustHipSettleQuery, 72 bytes: the side things fall toward, the region, and the palette indices that are loose as 256 bits
+    _fields_ = [("struct_size", C.c_uint32), ("toward", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("loose", C.c_uint32 * 8)]
+
+
+class SettleResult(C.Structure):  # DustHipSettleResult, 64 bytes: what one fall would do
+    _fields_ = [("columns", C.c_uint32), ("loose", C.c_uint32), ("fixed", C.c_uint32), ("moved", C.c_uint32), ("changed", C.c_uint32), ("fall_max", C.c_uint32),
+                ("fall_sum", C.c_uint64), ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("changed_columns", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
+
+class SettleApplied(C.Structure):  # DustHipSettleApplied, 64 bytes: the generations that moved something, the sums over the slides and the falls, the bounds
+    _fields_ = [("generations", C.c_uint32), ("first_moved", C.c_uint32), ("loose", C.c_uint32), ("reserved0", C.c_uint32), ("slid", C.c_uint64),
+                ("fell", C.c_uint64), ("fall_sum", C.c_uint64), ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("hi", C.c_uint8 * 3), ("pad1", C.c_uint8),
+                ("reserved", C.c_uint32 * 4)]
+
+
+SETTLE_MAX_GENERATIONS = 256
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -437,6 +457,8 @@ SYMBOLS = {
     "dust_hip_model_columns_apply": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_neighbours": (C.c_int, [_P, _P, _P, _P]),
     "dust_hip_model_neighbours_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    "dust_hip_model_settle": (C.c_int, [_P, _P, _P]),
+    "dust_hip_model_settle_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

@@ -75,6 +75,13 @@ NEIGHBOURS_RESULT_DTYPE = np.dtype([("voxels", "<u4"), ("solid", "<u4"), ("born"
                                     ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 10)])
 NEIGHBOURS_APPLIED_DTYPE = np.dtype([("generations", "<u4"), ("solid_before", "<u4"), ("solid_after", "<u4"), ("reserved0", "<u4"), ("born", "<u8"), ("died", "<u8"),
                                      ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 6)])
+# DustHipSettleQuery (72 bytes), DustHipSettleResult and DustHipSettleApplied (64 bytes each): the query of dust_hip_model_settle and
+# _settle_apply and what each of them returns
+SETTLE_QUERY_DTYPE = np.dtype([("struct_size", "<u4"), ("toward", "<u4"), ("flags", "<u4"), ("reserved", "<u4"), ("lo", "<u4", 3), ("hi", "<u4", 3), ("loose", "<u4", 8)])
+SETTLE_RESULT_DTYPE = np.dtype([("columns", "<u4"), ("loose", "<u4"), ("fixed", "<u4"), ("moved", "<u4"), ("changed", "<u4"), ("fall_max", "<u4"), ("fall_sum", "<u8"),
+                                ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("changed_columns", "<u4"), ("reserved", "<u4", 5)])
+SETTLE_APPLIED_DTYPE = np.dtype([("generations", "<u4"), ("first_moved", "<u4"), ("loose", "<u4"), ("reserved0", "<u4"), ("slid", "<u8"), ("fell", "<u8"),
+                                 ("fall_sum", "<u8"), ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 4)])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -91,6 +98,18 @@ def count_mask(*ranges):
         for n in range(int(first), int(last) + 1):
             mask |= 1 << n
     return mask
+
+
+def loose_mask(indices=None):
+    """The eight words Model.settle and Model.settle_apply take as `loose`: bit p set for every palette index p named -- each item an
+    index 0..254 or an inclusive (first, last) pair. None: all 255 indices, everything is loose."""
+    bits = (1 << 255) - 1 if indices is None else 0
+    for r in () if indices is None else indices:
+        first, last = (r, r) if isinstance(r, (int, np.integer)) else r
+        for p in range(int(first), int(last) + 1):
+            bits |= 1 << p
+    return tuple((bits >> (32 * w)) & 0xFFFFFFFF for w in range(8))
+
 
 PLANE_DTYPES = {
     L.PLANE_ILLUMINANCE: (np.uint16, 4), L.PLANE_DENOISED: (np.uint16, 4), L.PLANE_ALBEDO: (np.uint32, 1),
@@ -589,6 +608,35 @@ class Model:
         out = np.zeros(1, NEIGHBOURS_APPLIED_DTYPE)
         table = np.zeros((max(int(generations), 0), 2), np.uint32) if per_generation else None
         L.check(self._lib.dust_hip_model_neighbours_apply(self._h, C.byref(q), int(generations), _ptr(out), _ptr(table) if per_generation and table.size else None))
+        return (out[0], table) if per_generation else out[0]
+
+    def _settle_query(self, toward, loose, lo, hi):
+        q = L.SettleQuery(struct_size=C.sizeof(L.SettleQuery), toward=toward)
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        q.loose[:] = [int(w) for w in (loose_mask() if loose is None else loose)]
+        return q
+
+    def settle(self, toward, loose=None, lo=(0, 0, 0), hi=(255, 255, 255)):
+        """What one fall of the loose voxels of a region toward a side would do (dust_hip_model_settle). `toward` one L.FACE_* bit
+        (L.FACE_NEG_Y: ordinary gravity); `loose` the eight words of loose_mask (None: every palette index is loose); lo / hi an
+        inclusive voxel box. Returns a SETTLE_RESULT_DTYPE record (columns, loose, fixed, moved, changed, fall_max, fall_sum, lo, hi,
+        changed_columns). The model is only read; a grid is made only when `loose` is not all-ones."""
+        q = self._settle_query(toward, loose, lo, hi)
+        out = np.zeros(1, SETTLE_RESULT_DTYPE)
+        L.check(self._lib.dust_hip_model_settle(self._h, C.byref(q), _ptr(out)))
+        return out[0]
+
+    def settle_apply(self, toward, loose=None, lo=(0, 0, 0), hi=(255, 255, 255), generations=0, per_generation=False):
+        """Let the loose voxels of a region fall toward a side, then run `generations` (0..256) generations of a 45 degree slide in
+        +u, -u, +v, -v by turns and a fall (dust_hip_model_settle_apply); 0 generations is a plain vertical settle. Returns the
+        SETTLE_APPLIED_DTYPE record (generations -- 1 + the last one that moved a voxel --, first_moved, loose, slid, fell, fall_sum,
+        lo, hi), with per_generation=True (record, table), table a (generations, 2) uint32 array of slid and fell per generation.
+        Scenes instancing the model must be committed again; both fields and the island labelling are invalid afterwards."""
+        q = self._settle_query(toward, loose, lo, hi)
+        out = np.zeros(1, SETTLE_APPLIED_DTYPE)
+        table = np.zeros((max(int(generations), 0), 2), np.uint32) if per_generation else None
+        L.check(self._lib.dust_hip_model_settle_apply(self._h, C.byref(q), int(generations), _ptr(out), _ptr(table) if per_generation and table.size else None))
         return (out[0], table) if per_generation else out[0]
 
     def find_islands(self, connectivity=L.ISLANDS_FACES, anchor=None, capacity=None, records=None):

@@ -173,6 +173,9 @@ struct DustHipContext : RefCounted {
   // stamp_grid; when neither is, the second goes through this pair (2 MiB and 16 MiB, allocated by the first call that needs them).
   // Its listed voxels per brick are kept in surface_table
   DeviceBuffer delta_mask, delta_grid;
+  // model settling (settle.hip): three arrays in EditArgs::brick_mask's layout (6 MiB, allocated by the first call that needs them) --
+  // the loose voxels of every brick, and the pair of masks a slide writes beside the scratch grid
+  DeviceBuffer settle_masks;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)

@@ -1479,6 +1479,146 @@ DustStatus dust_hip_model_neighbours_apply(DustHipModel* m, const DustHipNeighbo
   });
 }
 
+// ---- model settling (settle.hip): loose voxels fall along an axis and slide down 45 degree slopes. What is loose is a second set of
+// brick masks made from the grid bytes (k_settle_masks), so that every decision is made from masks; counted without writing anything
+// (k_settle), or run step by step -- falls in place, slides between the model's grid and the context's scratch grid -- with ONE
+// rebuild behind them (k_settle_fall, k_settle_slide).
+namespace {
+// what both calls refuse, in the order the header gives: the model's kind before anything of the query is looked at
+DustStatus settle_query(const DustHipModel* m, const DustHipSettleQuery* q, dust::SettleArgs& a, dust::CellBox& box, bool& all_loose, bool& empty, uint32_t& nu,
+                        uint32_t& nv) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  const DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipSettleQuery");
+  if (const char* why = dust::device_settle(*q, a, box, all_loose, empty, nu, nv)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return DUST_OK;
+}
+// the loose voxels of every brick of `box` (and the solid ones, unless `solid` is null) from a grid's bytes
+DustStatus settle_masks(const DustHipSettleQuery* q, const dust::CellBox& box, const uint8_t* grid, uint64_t* solid, uint64_t* loose, hipStream_t st) {
+  dust::SettleMaskArgs ma{};
+  ma.grid = grid;
+  ma.brick_mask = solid;
+  ma.loose_mask = loose;
+  std::memcpy(ma.loose, q->loose, sizeof(ma.loose));
+  ma.box = box;
+  HIP_TRY(dust::launch_settle_masks(ma, st));
+  return DUST_OK;
+}
+}  // namespace
+
+DustStatus dust_hip_model_settle(const DustHipModel* m, const DustHipSettleQuery* q, DustHipSettleResult* result) {
+  dust::SettleArgs a{};
+  dust::CellBox box{};
+  bool all_loose = false, empty = false;
+  uint32_t nu = 0, nv = 0;
+  DustStatus s = settle_query(m, q, a, box, all_loose, empty, nu, nv);
+  if (s != DUST_OK) return s;
+  return guarded([&]() -> DustStatus {
+    uint32_t acc[dust::kSettleAccWords] = {};
+    if (!empty) {
+      DustHipContext* ctx = m->ctx;
+      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_TRY(join_side(ctx));
+      hipStream_t st = ctx->stream;
+      if ((s = cast_source_masks(ctx, m, &a.brick_mask)) != DUST_OK) return s;
+      a.loose_mask = a.brick_mask;  // every index is loose: the masks are all the call reads, no grid is made
+      if (!all_loose) {
+        const uint8_t* grid = nullptr;
+        if ((s = source_grid(ctx, nullptr, m, &grid)) != DUST_OK) return s;
+        if ((s = lazy_alloc(ctx->settle_masks, size_t(dust::kLattice) * 8 * 3, "the settle masks (6 MiB)")) != DUST_OK) return s;
+        uint64_t* loose = static_cast<uint64_t*>(ctx->settle_masks.p);
+        if ((s = settle_masks(q, box, grid, nullptr, loose, st)) != DUST_OK) return s;
+        a.loose_mask = loose;
+      }
+      if ((s = grow(ctx, ctx->stage_out, sizeof(acc))) != DUST_OK) return s;
+      a.acc = static_cast<uint32_t*>(ctx->stage_out.p);
+      HIP_TRY(hipMemsetAsync(a.acc, 0, sizeof(acc), st));
+      HIP_TRY(dust::launch_settle(a, st));
+      HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (result) *result = dust::settle_result(empty ? nullptr : acc, nu, nv);
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_settle_apply(DustHipModel* m, const DustHipSettleQuery* q, uint32_t generations, DustHipSettleApplied* applied,
+                                       uint32_t* per_generation) {
+  dust::SettleArgs a{};
+  dust::SettleSlideArgs sl{};
+  bool all_loose = false, empty = false;
+  uint32_t nu = 0, nv = 0;
+  DustStatus s = settle_query(m, q, a, sl.box, all_loose, empty, nu, nv);
+  if (s != DUST_OK) return s;
+  if (const char* why = dust::settle_apply_arguments(generations)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    s = begin_edit(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    invalidate_derived(es);
+    std::vector<uint32_t> slots(empty ? 0 : dust::kSettleApplyWords, 0u);
+    if (!empty) {
+      const size_t L = dust::kLattice;
+      if (generations != 0u && (s = lazy_alloc(ctx->reduce_grid, L * 64, "the slides' second grid (16 MiB)")) != DUST_OK) return s;
+      if ((s = lazy_alloc(ctx->settle_masks, L * 8 * 3, "the settle masks (6 MiB)")) != DUST_OK) return s;
+      if ((s = grow(ctx, es.changed, slots.size() * 4)) != DUST_OK) return s;
+      // A fall moves bytes in place; a slide reads one grid and writes the other, so the two take turns. Both start equal -- so outside
+      // the region they stay equal, and a slide writes only the bricks the region reaches. Masks 0 (the model's own and the loose ones
+      // beside them) are made from the grid at hand before every slide, which writes masks 1 for the fall behind it.
+      uint8_t* grids[2] = {static_cast<uint8_t*>(es.grid.p), static_cast<uint8_t*>(ctx->reduce_grid.p)};
+      uint64_t* solid0 = static_cast<uint64_t*>(es.brick_mask.p);
+      uint64_t* loose0 = static_cast<uint64_t*>(ctx->settle_masks.p);
+      uint64_t *solid1 = loose0 + L, *loose1 = loose0 + 2 * L;
+      uint32_t* dev_slots = static_cast<uint32_t*>(es.changed.p);
+      if (generations != 0u) HIP_TRY(hipMemcpyAsync(grids[1], grids[0], L * 64, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemsetAsync(dev_slots, 0, slots.size() * 4, st));
+      for (int r = 0; r < 3; ++r) { sl.lo[r] = q->lo[r]; sl.hi[r] = q->hi[r]; }
+      sl.g_axis = a.axis;
+      sl.g_up = a.from_high;
+      if ((s = settle_masks(q, sl.box, grids[0], nullptr, loose0, st)) != DUST_OK) return s;  // (the solid masks stand since the last rebuild)
+      a.brick_mask = solid0;
+      a.loose_mask = loose0;
+      a.grid = grids[0];
+      a.acc = dev_slots;
+      HIP_TRY(dust::launch_settle_fall(a, st));
+      uint32_t at = 0;  // the grid that holds the model
+      for (uint32_t g = 0; g < generations; ++g) {
+        uint32_t* slot = dev_slots + size_t(1u + 2u * g) * dust::kSettleAccWords;
+        if ((s = settle_masks(q, sl.box, grids[at], solid0, loose0, st)) != DUST_OK) return s;
+        dust::settle_slide_direction(a.axis, g, sl.d_axis, sl.d_up);
+        sl.brick_mask = solid0; sl.loose_mask = loose0; sl.grid = grids[at];
+        sl.grid_out = grids[at ^ 1u]; sl.mask_out = solid1; sl.loose_out = loose1;
+        sl.acc = slot;
+        HIP_TRY(dust::launch_settle_slide(sl, st));
+        at ^= 1u;
+        a.brick_mask = solid1;
+        a.loose_mask = loose1;
+        a.grid = grids[at];
+        a.acc = slot + dust::kSettleAccWords;
+        HIP_TRY(dust::launch_settle_fall(a, st));
+        // Every kSettleCheckEvery generations: have four in a row moved nothing? Then the model is at rest and no later generation would
+        // move anything -- their records stay 0, which is what they would have added.
+        if ((g + 1u) % dust::kSettleCheckEvery == 0u && g + 1u < generations) {
+          HIP_TRY(hipMemcpyAsync(slots.data(), dev_slots, size_t(1u + 2u * (g + 1u)) * dust::kSettleAccWords * 4, hipMemcpyDeviceToHost, st));
+          HIP_TRY(hipStreamSynchronize(st));
+          if (dust::settle_at_rest(slots.data(), g + 1u)) break;
+        }
+      }
+      if (at != 0u) HIP_TRY(hipMemcpyAsync(grids[0], grids[1], L * 64, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(slots.data(), dev_slots, slots.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    s = rebuild_and_refresh(m, es);  // synchronises; k_edit_brick_masks makes the masks again from the grid
+    if (s != DUST_OK) return s;
+    const DustHipSettleApplied record = dust::settle_applied(empty ? nullptr : slots.data(), generations, per_generation);
+    if (applied) *applied = record;
+    return DUST_OK;
+  });
+}
+
 DustStatus dust_hip_model_info(const DustHipModel* m, uint32_t* n_blocks, uint64_t* n_materials) {
   if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
   if (n_blocks) *n_blocks = m->dev.n_blocks;

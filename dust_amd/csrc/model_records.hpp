@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp and tests/cpp/neighbour_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp and tests/cpp/settle_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -17,6 +17,7 @@
 #include "edit.hpp"
 #include "mesh.hpp"
 #include "neighbour.hpp"
+#include "settle.hpp"
 #include "stamp.hpp"
 #include "surface.hpp"
 
@@ -40,6 +41,9 @@ static_assert(sizeof(DustHipNeighboursQuery) == sizeof(DustHipSurfaceQuery) && s
                   kNeighbourBins == DUST_HIP_NEIGHBOURS_BINS && kNeighbourMaxGenerations == DUST_HIP_NEIGHBOURS_MAX_GENERATIONS &&
                   DUST_HIP_NEIGHBOURS_WALLS == DUST_HIP_SURFACE_WALLS,
               "neighbours records");
+static_assert(sizeof(DustHipSettleQuery) == 72 && sizeof(DustHipSettleResult) == 64 && sizeof(DustHipSettleApplied) == 64 &&
+                  kSettleMaxGenerations == DUST_HIP_SETTLE_MAX_GENERATIONS,
+              "settle records");
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
@@ -511,6 +515,103 @@ inline DustHipNeighboursApplied neighbours_applied(const uint32_t* slots, uint32
   r.solid_after = uint32_t(uint64_t(solid_before) + r.born - r.died);
   for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - lo[k]); r.hi[k] = uint8_t(hi[k]); }
   return r;
+}
+
+// A settle query as the kernels read it (dust_hip_model_settle, _settle_apply): the axis and the end things fall toward, the region and
+// the root-cell columns it reaches in the (u, v) plane; `box` the root cells it reaches; `all_loose`: every palette index is loose (the
+// loose masks are the brick masks then). The pointers are the caller's. nullptr: the query is fine; otherwise why the call refuses it, in
+// the header's order. `nu`, `nv`: the columns of the region along u and v, 0 x 0 when `empty` -- then nothing is looked at, no launch is
+// made and the region fields are not set.
+inline const char* device_settle(const DustHipSettleQuery& q, SettleArgs& d, CellBox& box, bool& all_loose, bool& empty, uint32_t& nu, uint32_t& nv) {
+  if (q.toward == 0u || q.toward > DUST_HIP_FACES_ALL || (q.toward & (q.toward - 1u)) != 0u) return "toward must be exactly one DUST_HIP_FACE_* bit";
+  if (q.flags != 0u) return "unknown settle flag";
+  if (q.reserved != 0u) return "reserved word not 0";
+  for (int r = 0; r < 3; ++r)
+    if (q.lo[r] >= 256u || q.hi[r] >= 256u) return "region coordinate outside the tree extent";
+  if ((q.loose[7] >> 31) != 0u) return "loose bit 255 is set (palette indices are 0..254)";
+  uint32_t index = 0;  // the direction's index: -x, +x, -y, +y, -z, +z
+  while ((q.toward >> index) != 1u) ++index;
+  d.axis = index >> 1;
+  d.from_high = index & 1u;
+  all_loose = q.loose[7] == 0x7FFFFFFFu;
+  for (int w = 0; w < 7; ++w) all_loose &= q.loose[w] == 0xFFFFFFFFu;
+  empty = false;
+  for (int r = 0; r < 3; ++r) empty |= q.lo[r] > q.hi[r];
+  nu = nv = 0;
+  if (empty) return nullptr;
+  const uint32_t ua = column_u_axis(d.axis), va = column_v_axis(d.axis);
+  d.lo_n = q.lo[d.axis]; d.hi_n = q.hi[d.axis];
+  d.lo_u = q.lo[ua]; d.hi_u = q.hi[ua];
+  d.lo_v = q.lo[va]; d.hi_v = q.hi[va];
+  d.cell_u = d.lo_u >> 4; d.cells_u = (d.hi_u >> 4) - d.cell_u + 1u;
+  d.cell_v = d.lo_v >> 4; d.cells_v = (d.hi_v >> 4) - d.cell_v + 1u;
+  nu = d.hi_u - d.lo_u + 1u; nv = d.hi_v - d.lo_v + 1u;
+  for (int r = 0; r < 3; ++r) { box.lo[r] = q.lo[r] >> 4; box.hi[r] = q.hi[r] >> 4; }
+  return nullptr;
+}
+// what dust_hip_model_settle_apply refuses beyond the query
+inline const char* settle_apply_arguments(uint32_t generations) {
+  if (generations > kSettleMaxGenerations) return "generations must be 0..DUST_HIP_SETTLE_MAX_GENERATIONS";
+  return nullptr;
+}
+// the slide of generation k: along +u, -u, +v, -v of the fall's axis for k mod 4 = 0, 1, 2, 3
+inline void settle_slide_direction(uint32_t axis, uint32_t k, uint32_t& d_axis, uint32_t& d_up) {
+  d_axis = (k & 2u) ? column_v_axis(axis) : column_u_axis(axis);
+  d_up = (k & 1u) ? 0u : 1u;
+}
+// the bounds of one step's record into a running pair (lo as 255 - the bound)
+inline void settle_fold_bounds(const uint32_t* acc, uint32_t (&lo)[3], uint32_t (&hi)[3]) {
+  for (int k = 0; k < 3; ++k) { lo[k] = std::max(lo[k], acc[kSettleLo + k]); hi[k] = std::max(hi[k], acc[kSettleHi + k]); }
+}
+// What a settle call's caller gets from the device's kSettleAccWords accumulator and the size of the region; null: nothing was looked
+// at -- the zero result, bounds 255 / 0 (what a region in which nothing would move has too, beside its columns and counts).
+inline DustHipSettleResult settle_result(const uint32_t* acc, uint32_t nu, uint32_t nv) {
+  DustHipSettleResult r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  if (!acc) return r;
+  r.columns = nu * nv;
+  r.loose = acc[0]; r.fixed = acc[1]; r.moved = acc[2]; r.changed = acc[3]; r.fall_sum = acc[4]; r.changed_columns = acc[5];
+  r.fall_max = acc[kSettleFallMax];
+  for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[kSettleLo + k]); r.hi[k] = uint8_t(acc[kSettleHi + k]); }
+  return r;
+}
+// What an apply's caller gets from the device's array of 1 + 2 * generations records (kSettleAccWords each: the initial fall, then the
+// slide and the fall of every generation; a step that never ran left its record 0); null: nothing was looked at -- the zero record.
+// per_generation (may be null): 2 * generations words, slid and fell per generation.
+inline DustHipSettleApplied settle_applied(const uint32_t* slots, uint32_t generations, uint32_t* per_generation) {
+  DustHipSettleApplied r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  if (per_generation) std::fill(per_generation, per_generation + size_t(generations) * 2, 0u);
+  if (!slots) return r;
+  uint32_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  r.first_moved = slots[2];
+  r.loose = slots[0];
+  r.fall_sum = slots[4];
+  settle_fold_bounds(slots, lo, hi);
+  for (uint32_t g = 0; g < generations; ++g) {
+    const uint32_t* slide = slots + size_t(1u + 2u * g) * kSettleAccWords;
+    const uint32_t* fall = slide + kSettleAccWords;
+    const uint32_t slid = slide[kSettleSlid], fell = fall[2];
+    if (slid + fell == 0u) continue;
+    r.generations = g + 1u;
+    r.slid += slid; r.fell += fell; r.fall_sum += fall[4];
+    settle_fold_bounds(slide, lo, hi);
+    settle_fold_bounds(fall, lo, hi);
+    if (per_generation) { per_generation[2 * g] = slid; per_generation[2 * g + 1] = fell; }
+  }
+  for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - lo[k]); r.hi[k] = uint8_t(hi[k]); }
+  return r;
+}
+// Whether the first `ran` generations of an apply's records end in four that moved nothing: the model is at rest then -- the four
+// covered every direction -- and no later generation would move anything
+inline bool settle_at_rest(const uint32_t* slots, uint32_t ran) {
+  uint32_t still = 0;
+  for (uint32_t g = 0; g < ran; ++g) {
+    const uint32_t* slide = slots + size_t(1u + 2u * g) * kSettleAccWords;
+    still = slide[kSettleSlid] + slide[kSettleAccWords + 2] == 0u ? still + 1u : 0u;
+    if (still == 4u) return true;
+  }
+  return false;
 }
 
 // the records of a call that cover something, in call order: `index` maps them back to the caller's

@@ -1037,6 +1037,85 @@ DustStatus dust_hip_model_neighbours(const DustHipModel*, const DustHipNeighbour
 DustStatus dust_hip_model_neighbours_apply(DustHipModel*, const DustHipNeighboursQuery*, uint32_t generations,
                                            DustHipNeighboursApplied* applied /* may be NULL */,
                                            uint32_t* per_generation /* 2 * generations, may be NULL */);
+/* Model settling: granular material obeys gravity -- sand, gravel, snow and rubble stop hanging in the air after a crater is carved
+ * under them, fall until they rest and slide down slopes steeper than 45 degrees.
+ *
+ * Direction: query.toward is exactly one DUST_HIP_FACE_* bit, the side things fall toward (DUST_HIP_FACE_NEG_Y: ordinary gravity). g
+ * is the unit step toward that side, "above p" is p - g, and u / v are the plane axes of dust_hip_model_columns.
+ * Region: lo / hi is an inclusive voxel box under dust_hip_model_neighbours' rules (a coordinate >= 256 is refused; lo > hi on an
+ * axis is legal and empty). As for dust_hip_model_columns, voxels outside the region do not exist for the call: they are neither
+ * consulted nor changed. The region's face on the toward side is a floor, and nothing falls in from above the region.
+ * Loose and fixed: query.loose is a bit mask over the palette indices 0..254 (bit p of the 256: word p / 32, bit p % 32). A solid
+ * voxel whose index has its bit set is loose; every other solid voxel is fixed. All 255 bits set: everything is loose.
+ * Fall: in every voxel column of the region along the axis, with positions counted from the toward end, a loose voxel at position i
+ * has a floor f, one past the highest fixed position below i (0 when there is none), and moves to f + the number of loose voxels in
+ * [f, i): a stable compaction per stretch between fixed voxels. Loose voxels keep their order and their palette indices, fixed
+ * voxels do not move; the voxel's fall is i - its new position.
+ * Slide in a lateral direction d, decided on the model as it stood before the slide: a loose voxel at p moves to p + d + g when the
+ * voxel above p is empty or outside the region and p + d and p + d + g are both inside the region and empty. A destination has one
+ * possible source, and sources and destinations are disjoint: no voxel is lost or doubled and no order shows.
+ * Generation k (0, 1, ...): a slide with d = +u, -u, +v, -v for k mod 4 = 0, 1, 2, 3, then a fall.
+ * Result (dust_hip_model_settle): what ONE fall would do -- ask first, apply after. columns, the voxel columns of the region; loose
+ * and fixed, its loose and its fixed voxels; moved, the loose voxels whose position would change; changed, the voxels that would turn
+ * from solid to empty or from empty to solid (a loose voxel that takes the place of another loose voxel is not counted, whatever
+ * their materials: the record is decided from the two occupancies alone, which is why an all-ones mask needs no grid byte);
+ * fall_max and fall_sum over the falls; lo / hi, the inclusive bounds of the changed voxels (255, 255, 255 / 0, 0, 0 when there is
+ * none); changed_columns, the columns with a moved voxel; pad and reserved 0.
+ * Applied (dust_hip_model_settle_apply): one initial fall, then `generations` (0..256) generations; 0 is a plain vertical settle.
+ * generations, 1 + the index of the last generation that moved a voxel, 0 when none did; first_moved, the voxels the initial fall
+ * moved; loose, the region's loose voxels; slid and fell, the voxels moved by the slides and by the falls of the generations (the
+ * initial fall is not in fell); fall_sum, the sum of every fall's distance, the initial fall included, the slides not; lo / hi, the
+ * bounds of every voxel that turned solid or empty in any step. per_generation[2 k] and [2 k + 1] are the slid and the fell of
+ * generation k; the rows after a fixed point are 0. With s(M) the sum over the loose voxels of their position along the fall
+ * (counted from the toward end), s(before) - s(after) == fall_sum + slid: every fall of n takes n off, every slide takes 1.
+ * The library may stop launching once four consecutive generations (one per direction) moved nothing; how often it looks does not
+ * show in any output.
+ * dust_hip_model_settle only reads the model, with dust_hip_model_surface's guarantees: one that is not editable stays not editable
+ * and is expanded into the context's scratch grid only when a grid byte is needed, that is when loose is not all-ones; the
+ * generation does not move; the island labelling and both fields stand.
+ * dust_hip_model_settle_apply makes the model editable as every apply does, runs the steps on the device -- falls in place, slides
+ * between the model's grid and the context's scratch grid -- and then rebuilds ONCE as after dust_hip_model_neighbours_apply, byte
+ * for byte a host build. The generation is bumped and the island labelling and both fields are invalid afterwards, even when nothing
+ * moved.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, the outputs untouched: a null model or query; a struct_size below the struct's size; a
+ * toward that is not exactly one face bit; a flags or reserved word that is not 0; a region coordinate >= 256; loose bit 255;
+ * generations above 256. A null result, applied or per_generation is fine. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it
+ * (4096^3 trees, models that hold material byte 255), before the query is looked at. Both calls are synchronous, like every model
+ * call. Everything is integer arithmetic and every step is synchronous: two runs give the same bytes.
+ * Out of scope: angles of repose other than 45 degrees; liquids; settling across the instances of a scene; 4096^3 trees; an
+ * asynchronous form; a brick worklist between generations. */
+#define DUST_HIP_SETTLE_MAX_GENERATIONS 256u
+typedef struct DustHipSettleQuery {    /* 72 bytes */
+  uint32_t struct_size;
+  uint32_t toward;               /* exactly one DUST_HIP_FACE_* bit: the side loose voxels fall toward */
+  uint32_t flags;                /* 0 */
+  uint32_t reserved;             /* 0 */
+  uint32_t lo[3], hi[3];         /* inclusive region */
+  uint32_t loose[8];             /* bit p: palette index p is loose; bit 255 must be 0 */
+} DustHipSettleQuery;
+typedef struct DustHipSettleResult {   /* 64 bytes: what ONE fall would do -- ask first, apply after */
+  uint32_t columns, loose, fixed;      /* columns of the region; its loose and its fixed voxels */
+  uint32_t moved;                /* loose voxels whose position would change */
+  uint32_t changed;              /* voxels that would turn solid or empty */
+  uint32_t fall_max;             /* the longest fall, 0..255 */
+  uint64_t fall_sum;             /* the sum of all falls */
+  uint8_t lo[3], pad0, hi[3], pad1;    /* bounds of the changed voxels; 255,255,255 / 0,0,0 when none */
+  uint32_t changed_columns;      /* columns with at least one moved voxel */
+  uint32_t reserved[5];          /* 0 */
+} DustHipSettleResult;
+typedef struct DustHipSettleApplied {  /* 64 bytes */
+  uint32_t generations;          /* 1 + the index of the last generation that moved a voxel; 0 when none did */
+  uint32_t first_moved;          /* voxels moved by the initial fall */
+  uint32_t loose, reserved0;     /* the region's loose voxels; 0 */
+  uint64_t slid, fell;           /* sums over the generations (the initial fall is not in fell) */
+  uint64_t fall_sum;             /* the sum of every fall's distance, the initial fall included; slides are not */
+  uint8_t lo[3], pad0, hi[3], pad1;    /* bounds of every voxel that turned solid or empty in any step */
+  uint32_t reserved[4];          /* 0 */
+} DustHipSettleApplied;
+DustStatus dust_hip_model_settle(const DustHipModel*, const DustHipSettleQuery*, DustHipSettleResult* result /* may be NULL */);
+DustStatus dust_hip_model_settle_apply(DustHipModel*, const DustHipSettleQuery*, uint32_t generations /* 0..256 */,
+                                       DustHipSettleApplied* applied /* may be NULL */,
+                                       uint32_t* per_generation /* 2 * generations: slid, fell; may be NULL; rows after a fixed point 0 */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

@@ -383,6 +383,25 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return applied;
   }
+  // Model settling (dust_hip_model_settle / settle_apply): the loose voxels of the query's region -- those whose palette index has its
+  // bit in query.loose -- fall toward query.toward. settle says what ONE fall would do and only reads; settle_apply lets them fall,
+  // runs `generations` generations of a 45 degree slide and a fall, and rebuilds once; per_generation, if given, receives the slid and
+  // the fell of every generation; scenes that instance this geometry must commit() again.
+  DustHipSettleResult settle(DustHipSettleQuery query) const {
+    query.struct_size = sizeof(query);
+    DustHipSettleResult r{};
+    check(dust_hip_model_settle(h_, &query, &r));
+    return r;
+  }
+  DustHipSettleApplied settle_apply(DustHipSettleQuery query, uint32_t generations = 0, std::vector<uint32_t>* per_generation = nullptr) {
+    query.struct_size = sizeof(query);
+    DustHipSettleApplied applied{};
+    if (per_generation) per_generation->assign(size_t(2) * generations, 0u);
+    check(dust_hip_model_settle_apply(h_, &query, generations, &applied, per_generation && generations ? per_generation->data() : nullptr));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return applied;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
