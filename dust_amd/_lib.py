@@ -370,6 +370,26 @@ class SettleApplied(C.Structure):  # DustHipSettleApplied, 64 bytes: the generat
 SETTLE_MAX_GENERATIONS = 256
 
 
+class Triangle(C.Structure):  # DustHipTriangle, 48 bytes: three integer vertices in 1/256 voxel of a model's tree coordinates and what the triangle does to the voxels it touches
+    _fields_ = [("v", (C.c_int32 * 3) * 3), ("op", C.c_uint32), ("palette", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class FillMeshQuery(C.Structure):  # DustHipFillMeshQuery, 48 bytes: what the voxels inside a mesh take, and the region
+    _fields_ = [("struct_size", C.c_uint32), ("op", C.c_uint32), ("palette", C.c_int32), ("flags", C.c_uint32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class FillMeshResult(C.Structure):  # DustHipFillMeshResult, 48 bytes: the inside voxels of the region, those that changed, the triangles that counted, the bounds
+    _fields_ = [("covered", C.c_uint32), ("changed", C.c_uint32), ("live", C.c_uint32), ("crossing", C.c_uint32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
+
+
+TRIANGLE_UNIT = 256
+TRIANGLE_MAX_COORD = 262144
+MAX_EDIT_TRIANGLES = 65536
+MAX_MESH_TRIANGLES = 1 << 20
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -459,6 +479,8 @@ SYMBOLS = {
     "dust_hip_model_neighbours_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     "dust_hip_model_settle": (C.c_int, [_P, _P, _P]),
     "dust_hip_model_settle_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    "dust_hip_model_edit_triangles": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "dust_hip_model_fill_mesh": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

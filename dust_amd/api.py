@@ -82,6 +82,10 @@ SETTLE_RESULT_DTYPE = np.dtype([("columns", "<u4"), ("loose", "<u4"), ("fixed", 
                                 ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("changed_columns", "<u4"), ("reserved", "<u4", 5)])
 SETTLE_APPLIED_DTYPE = np.dtype([("generations", "<u4"), ("first_moved", "<u4"), ("loose", "<u4"), ("reserved0", "<u4"), ("slid", "<u8"), ("fell", "<u8"),
                                  ("fall_sum", "<u8"), ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4", 4)])
+# DustHipTriangle / DustHipFillMeshResult (model voxelisation): integer vertices in 1/256 voxel
+TRIANGLE_DTYPE = np.dtype([("v", "<i4", (3, 3)), ("op", "<u4"), ("palette", "<i4"), ("reserved", "<u4")])
+FILL_MESH_RESULT_DTYPE = np.dtype([("covered", "<u4"), ("changed", "<u4"), ("live", "<u4"), ("crossing", "<u4"), ("lo", "<u4", 3), ("hi", "<u4", 3),
+                                   ("reserved", "<u4", 2)])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -573,6 +577,32 @@ class Model:
         L.check(self._lib.dust_hip_model_columns_apply(self._h, C.byref(q), int(where), int(depth), int(value), C.byref(changed)))
         return changed.value
 
+    def edit_triangles(self, triangles, count=True):
+        """Carve / fill / paint / place the voxels triangles touch (dust_hip_model_edit_triangles): `triangles` a TRIANGLE_DTYPE array
+        (see triangles()), integer vertices in 1/256 voxel of the model's tree coordinates; a triangle covers every voxel whose closed
+        cube it shares a point with (exact: a 13-axis separating-axis test on integers), and the triangles apply in order. Returns
+        `changed`: per triangle, the voxels whose value it changed (None with count=False). Scenes instancing the model must be
+        committed again afterwards."""
+        triangles = np.ascontiguousarray(triangles, TRIANGLE_DTYPE).reshape(-1)
+        changed = np.zeros(len(triangles), np.uint32) if count else None
+        L.check(self._lib.dust_hip_model_edit_triangles(self._h, _ptr(triangles), len(triangles), _ptr(changed) if count else None))
+        return changed
+
+    def fill_mesh(self, triangles, op=L.EDIT_FILL, palette=0, region=None):
+        """The voxels whose centres lie inside a closed triangle mesh take `op` / `palette` (dust_hip_model_fill_mesh): `triangles` a
+        TRIANGLE_DTYPE array (their own op and palette are ignored), region = (lo, hi) an inclusive voxel box (None: the whole tree).
+        Inside is the parity of the triangles crossed above the centre along +z, exact on integers; winding and order do not matter.
+        Returns a FILL_MESH_RESULT_DTYPE record (covered, changed, live, crossing, lo, hi). Scenes instancing the model must be
+        committed again afterwards."""
+        triangles = np.ascontiguousarray(triangles, TRIANGLE_DTYPE).reshape(-1)
+        q = L.FillMeshQuery(struct_size=C.sizeof(L.FillMeshQuery), op=int(op), palette=int(palette), flags=0)
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        out = np.zeros(1, FILL_MESH_RESULT_DTYPE)
+        L.check(self._lib.dust_hip_model_fill_mesh(self._h, _ptr(triangles), len(triangles), C.byref(q), _ptr(out)))
+        return out[0]
+
     def _neighbours_query(self, neighbourhood, birth, survive, palette, flags, region):
         q = L.NeighboursQuery(struct_size=C.sizeof(L.NeighboursQuery), neighbourhood=neighbourhood, flags=flags, palette=palette, birth=birth, survive=survive)
         lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
@@ -976,6 +1006,31 @@ def edit_shapes(kind, a, b=None, radius=0.0, op=L.EDIT_CARVE, palette=0):
     shapes["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(a),))
     shapes["palette"] = np.broadcast_to(np.asarray(palette, np.int32), (len(a),))
     return shapes
+
+
+def triangles(vertices, op=L.EDIT_FILL, palette=0):
+    """DustHipTriangle records (TRIANGLE_DTYPE) for Model.edit_triangles and Model.fill_mesh: vertices a float (n, 3, 3) array in
+    voxels of the model's tree coordinates, rounded to the ABI's integers as rint(v * 256) and not clamped (a triangle with a coordinate
+    beyond +-1024 voxels covers nothing); op and palette scalars or (n,)."""
+    vertices = np.asarray(vertices, np.float64).reshape(-1, 3, 3)
+    out = np.zeros(len(vertices), TRIANGLE_DTYPE)
+    out["v"] = np.rint(vertices * L.TRIANGLE_UNIT).astype(np.int64).astype(np.int32)
+    out["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(vertices),))
+    out["palette"] = np.broadcast_to(np.asarray(palette, np.int32), (len(vertices),))
+    return out
+
+
+def quads_to_triangles(quads, op=L.EDIT_FILL, palette=0):
+    """Model.mesh's quads (MESH_QUAD_DTYPE) as TRIANGLE_DTYPE records, two per quad -- (c0, c1, c2) and (c0, c2, c3) of mesh_corners, on
+    integer voxel corners, so that Model.fill_mesh of a model's whole mesh gives the model's voxels back."""
+    corners, _ = mesh_corners(quads)
+    c = corners.astype(np.int32) * L.TRIANGLE_UNIT
+    out = np.zeros(2 * len(c), TRIANGLE_DTYPE)
+    out["v"][0::2] = c[:, [0, 1, 2]]
+    out["v"][1::2] = c[:, [0, 2, 3]]
+    out["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(out),))
+    out["palette"] = np.broadcast_to(np.asarray(palette, np.int32), (len(out),))
+    return out
 
 
 def orientation(perm=(0, 1, 2), flips=(False, False, False)):

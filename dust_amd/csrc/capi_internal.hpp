@@ -176,6 +176,9 @@ struct DustHipContext : RefCounted {
   // model settling (settle.hip): three arrays in EditArgs::brick_mask's layout (6 MiB, allocated by the first call that needs them) --
   // the loose voxels of every brick, and the pair of masks a slide writes beside the scratch grid
   DeviceBuffer settle_masks;
+  // model voxelisation (triangle.hip): the inside bit of every voxel of a dust_hip_model_fill_mesh call, in EditArgs::brick_mask's
+  // layout (2 MiB, allocated by the first such call; zeroed by every call)
+  DeviceBuffer fill_volume;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)

@@ -1619,6 +1619,95 @@ DustStatus dust_hip_model_settle_apply(DustHipModel* m, const DustHipSettleQuery
   });
 }
 
+// ---- model voxelisation (triangle.hip): the voxels triangles touch, on edit_shapes' path (k_edit_triangles), and the voxels whose
+// centres lie inside a mesh -- the columns' crossings XORed into the context's bit volume chunk by chunk (k_fill_columns), then the
+// operation on the region's inside voxels (k_fill_apply) -- with ONE rebuild behind either.
+DustStatus dust_hip_model_edit_triangles(DustHipModel* m, const DustHipTriangle* triangles, uint32_t n, uint32_t* changed) {
+  if (!m || (n && !triangles)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (n > DUST_HIP_MAX_EDIT_TRIANGLES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_EDIT_TRIANGLES triangles in one call");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (triangles[i].op > DUST_HIP_EDIT_PLACE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown edit op");
+    if (triangles[i].op != DUST_HIP_EDIT_CARVE && (triangles[i].palette < 0 || triangles[i].palette > 254))
+      return fail(DUST_ERR_INVALID_ARGUMENT, "palette index must be 0..254");
+  }
+  return guarded([&]() -> DustStatus {
+    DustStatus s = begin_edit(m);
+    if (s != DUST_OK || n == 0) return s;
+    EditState& es = *m->edit;
+    invalidate_derived(es);
+    std::vector<dust::DevTriangle> dev;
+    std::vector<uint32_t> index;
+    dust::live_records<dust::device_triangle>(triangles, n, dev, index);
+    return batched_edit<dust::EditTriangleArgs>(m, dev, index, n, changed, [&](size_t c0, dust::EditTriangleArgs& a) -> DustStatus {
+      a.triangles = static_cast<const dust::DevTriangle*>(es.shapes.p) + c0;
+      HIP_TRY(dust::launch_edit_triangles(a, m->ctx->stream));
+      return DUST_OK;
+    });
+  });
+}
+
+DustStatus dust_hip_model_fill_mesh(DustHipModel* m, const DustHipTriangle* triangles, uint32_t n, const DustHipFillMeshQuery* q,
+                                    DustHipFillMeshResult* result) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipFillMeshQuery");
+  if (n && !triangles) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (n > DUST_HIP_MAX_MESH_TRIANGLES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_MESH_TRIANGLES triangles in one call");
+  dust::FillApplyArgs a{};
+  bool empty = false;
+  if (const char* why = dust::device_fill_mesh(*q, a, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    s = begin_edit(m);
+    if (s != DUST_OK) return s;
+    if (n == 0 || empty) {  // nothing is looked at and nothing can change: no rebuild, and what is derived from the voxels stands
+      if (result) *result = dust::fill_mesh_result(nullptr, 0, 0);
+      return DUST_OK;
+    }
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    invalidate_derived(es);
+    uint32_t acc[dust::kFillAccWords] = {};
+    uint32_t live = 0, crossing = 0;
+    std::vector<dust::DevTriangle> dev;
+    dust::CellLists lists;  // (the last chunk's copies read it until rebuild_and_refresh has waited for the stream)
+    for (uint32_t i = 0; i < n; ++i) {
+      dust::DevTriangle d{};
+      bool is_live = false, is_crossing = false;
+      if (dust::device_fill_triangle(triangles[i], a.lo, a.hi, d, is_live, is_crossing)) dev.push_back(d);
+      live += is_live ? 1u : 0u;
+      crossing += is_crossing ? 1u : 0u;
+    }
+    const size_t words = dust::kLattice;
+    if ((s = lazy_alloc(ctx->fill_volume, words * 8, "the fill volume (2 MiB)")) != DUST_OK) return s;
+    if ((s = grow(ctx, es.changed, dust::kFillAccWords * 4)) != DUST_OK) return s;
+    HIP_TRY(hipMemsetAsync(ctx->fill_volume.p, 0, words * 8, st));
+    if (!dev.empty()) {
+      if ((s = grow(ctx, es.shapes, dev.size() * sizeof(dust::DevTriangle))) != DUST_OK) return s;
+      HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), dev.size() * sizeof(dust::DevTriangle), hipMemcpyHostToDevice, st));
+    }
+    s = for_each_chunk<dust::FillColumnsArgs>(ctx, dev, lists, es.shape_cells, es.shape_starts, es.shape_ids, [&](size_t c0, dust::FillColumnsArgs& f) -> DustStatus {
+      f.volume = static_cast<uint64_t*>(ctx->fill_volume.p);
+      f.triangles = static_cast<const dust::DevTriangle*>(es.shapes.p) + c0;
+      HIP_TRY(dust::launch_fill_columns(f, st));
+      return DUST_OK;
+    });
+    if (s != DUST_OK) return s;
+    a.grid = static_cast<uint8_t*>(es.grid.p);
+    a.volume = static_cast<const uint64_t*>(ctx->fill_volume.p);
+    a.acc = static_cast<uint32_t*>(es.changed.p);
+    HIP_TRY(hipMemsetAsync(a.acc, 0, sizeof(acc), st));
+    HIP_TRY(dust::launch_fill_apply(a, st));
+    HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+    s = rebuild_and_refresh(m, es);  // synchronises: the host vectors above stay alive until the copies are done
+    if (s != DUST_OK) return s;
+    if (result) *result = dust::fill_mesh_result(acc, live, crossing);
+    return DUST_OK;
+  });
+}
+
 DustStatus dust_hip_model_info(const DustHipModel* m, uint32_t* n_blocks, uint64_t* n_materials) {
   if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
   if (n_blocks) *n_blocks = m->dev.n_blocks;

@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp and tests/cpp/settle_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp and tests/cpp/triangle_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -20,6 +20,7 @@
 #include "settle.hpp"
 #include "stamp.hpp"
 #include "surface.hpp"
+#include "triangle.hpp"
 
 namespace dust {
 
@@ -44,6 +45,10 @@ static_assert(sizeof(DustHipNeighboursQuery) == sizeof(DustHipSurfaceQuery) && s
 static_assert(sizeof(DustHipSettleQuery) == 72 && sizeof(DustHipSettleResult) == 64 && sizeof(DustHipSettleApplied) == 64 &&
                   kSettleMaxGenerations == DUST_HIP_SETTLE_MAX_GENERATIONS,
               "settle records");
+
+static_assert(sizeof(DustHipTriangle) == 48 && sizeof(DustHipFillMeshQuery) == 48 && sizeof(DustHipFillMeshResult) == 48 && sizeof(DevTriangle) == 52 &&
+                  kTriangleUnit == DUST_HIP_TRIANGLE_UNIT && kTriangleMaxCoord == DUST_HIP_TRIANGLE_MAX_COORD,
+              "triangle records");
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
@@ -612,6 +617,103 @@ inline bool settle_at_rest(const uint32_t* slots, uint32_t ran) {
     if (still == 4u) return true;
   }
   return false;
+}
+
+// ---- model voxelisation (dust_hip_model_edit_triangles, _fill_mesh)
+// an edit operation as the two grid bytes it writes (device_shape's table)
+inline void edit_op_bytes(uint32_t op, int32_t palette, uint32_t& solid_to, uint32_t& empty_to) {
+  const uint32_t byte = uint32_t(palette) + 1u;
+  switch (op) {
+    case DUST_HIP_EDIT_CARVE: solid_to = 0; empty_to = 0; break;
+    case DUST_HIP_EDIT_FILL: solid_to = byte; empty_to = byte; break;
+    case DUST_HIP_EDIT_PAINT: solid_to = byte; empty_to = 0; break;
+    default: solid_to = kEditKeep; empty_to = byte; break;  // PLACE
+  }
+}
+// floor(v / 256) for any sign
+inline int32_t triangle_floor_voxel(int32_t v) { return v >= 0 ? v / kTriangleUnit : -((-v + kTriangleUnit - 1) / kTriangleUnit); }
+
+// A triangle of dust_hip_model_edit_triangles: the range check, n == 0, and the inclusive bounds of the voxels its vertices' extent
+// touches -- a coordinate at exactly 256 k touches voxels k - 1 and k -- clipped to the tree. false: it covers nothing (out of range,
+// zero normal, wholly outside the tree). They cull; the 13-axis test decides.
+inline bool device_triangle(const DustHipTriangle& s, DevTriangle& d) {
+  if (!triangle_in_range(s.v)) return false;
+  const TriangleSetup t = triangle_setup(s.v);
+  if (triangle_degenerate(t)) return false;
+  uint32_t vlo[3], vhi[3];
+  for (int r = 0; r < 3; ++r) {
+    const int32_t l = triangle_floor_voxel(t.lo[r] - 1), h = triangle_floor_voxel(t.hi[r]);
+    if (l > 255 || h < 0) return false;
+    vlo[r] = l < 0 ? 0u : uint32_t(l);
+    vhi[r] = h > 255 ? 255u : uint32_t(h);
+  }
+  std::memcpy(d.v, s.v, sizeof(d.v));
+  edit_op_bytes(s.op, s.palette, d.solid_to, d.empty_to);
+  d.lo = vlo[0] | (vlo[1] << 8) | (vlo[2] << 16);
+  d.hi = vhi[0] | (vhi[1] << 8) | (vhi[2] << 16);
+  return true;
+}
+
+// A triangle of dust_hip_model_fill_mesh. `live`: in range and not degenerate; `crossing`: live with n.z != 0. true: it is crossing and
+// some column centre (256 x + 128, 256 y + 128) of the region lo..hi lies in its vertices' extent -- d.lo / d.hi are those columns with
+// z = 0 (the tiles k_fill_columns is launched for), the operation bytes 0. Its height is not looked at: a triangle above or below the
+// tree still toggles the centres below it.
+inline bool device_fill_triangle(const DustHipTriangle& s, const uint32_t* lo, const uint32_t* hi, DevTriangle& d, bool& live, bool& crossing) {
+  live = crossing = false;
+  if (!triangle_in_range(s.v)) return false;
+  const TriangleColumn t = triangle_column(s.v);
+  if (triangle_degenerate(t)) return false;
+  live = true;
+  if (t.s == 0) return false;
+  crossing = true;
+  uint32_t clo[2], chi[2];
+  for (int r = 0; r < 2; ++r) {
+    const int32_t least = std::min({s.v[0][r], s.v[1][r], s.v[2][r]}), most = std::max({s.v[0][r], s.v[1][r], s.v[2][r]});
+    const int32_t l = triangle_floor_voxel(least - kTriangleUnit / 2 - 1) + 1, h = triangle_floor_voxel(most - kTriangleUnit / 2);  // ceil, floor
+    const int32_t first = std::max(l, int32_t(lo[r])), last = std::min(h, int32_t(hi[r]));
+    if (first > last) return false;
+    clo[r] = uint32_t(first); chi[r] = uint32_t(last);
+  }
+  std::memcpy(d.v, s.v, sizeof(d.v));
+  d.solid_to = d.empty_to = 0;
+  d.lo = clo[0] | (clo[1] << 8);
+  d.hi = chi[0] | (chi[1] << 8);
+  return true;
+}
+
+// A fill_mesh query as k_fill_apply reads it: the operation's two bytes, the region clipped to the tree as device_columns clips it (a
+// coordinate past 255 is cut back to it; lo past hi is the empty region) and the root cells it reaches. The pointers are the caller's.
+// nullptr: the query is fine; otherwise why the call refuses it, in the header's order. `empty`: nothing is looked at, no launch is made
+// and the region fields are not set.
+inline const char* device_fill_mesh(const DustHipFillMeshQuery& q, FillApplyArgs& d, bool& empty) {
+  if (q.op > DUST_HIP_EDIT_PLACE) return "unknown edit op";
+  if (q.op != DUST_HIP_EDIT_CARVE && (q.palette < 0 || q.palette > 254)) return "palette index must be 0..254";
+  if (q.flags != 0u) return "unknown fill_mesh flag";
+  if (q.reserved[0] != 0u || q.reserved[1] != 0u) return "reserved word not 0";
+  edit_op_bytes(q.op, q.palette, d.solid_to, d.empty_to);
+  uint32_t lo[3], hi[3];
+  empty = false;
+  for (int r = 0; r < 3; ++r) {
+    lo[r] = q.lo[r]; hi[r] = std::min(q.hi[r], 255u);
+    empty |= lo[r] > hi[r];
+  }
+  if (empty) return nullptr;
+  for (int r = 0; r < 3; ++r) {
+    d.lo[r] = lo[r]; d.hi[r] = hi[r];
+    d.box.lo[r] = lo[r] >> 4; d.box.hi[r] = hi[r] >> 4;
+  }
+  return nullptr;
+}
+// What a fill_mesh call's caller gets from the device's kFillAccWords accumulator and the host's triangle counts; null: nothing was
+// looked at -- the zero result, bounds 255 / 0 (what a region without a covered voxel has too, beside its counts).
+inline DustHipFillMeshResult fill_mesh_result(const uint32_t* acc, uint32_t live, uint32_t crossing) {
+  DustHipFillMeshResult r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  if (!acc) return r;
+  r.covered = acc[0]; r.changed = acc[1];
+  r.live = live; r.crossing = crossing;
+  for (int k = 0; k < 3; ++k) { r.lo[k] = 255u - acc[2 + k]; r.hi[k] = acc[5 + k]; }
+  return r;
 }
 
 // the records of a call that cover something, in call order: `index` maps them back to the caller's

@@ -1116,6 +1116,88 @@ DustStatus dust_hip_model_settle(const DustHipModel*, const DustHipSettleQuery*,
 DustStatus dust_hip_model_settle_apply(DustHipModel*, const DustHipSettleQuery*, uint32_t generations /* 0..256 */,
                                        DustHipSettleApplied* applied /* may be NULL */,
                                        uint32_t* per_generation /* 2 * generations: slid, fell; may be NULL; rows after a fixed point 0 */);
+/* Model voxelisation: triangles to voxels on the device -- an imported prop, a CSG result, a physics hull, the quads dust_hip_model_mesh
+ * itself handed out. The siblings of dust_hip_model_edit_shapes, and the inverse of dust_hip_model_mesh. Two calls:
+ *   dust_hip_model_edit_triangles  SURFACE: the voxels each triangle touches, triangle by triangle, in order, an op and a palette index
+ *                                  per triangle;
+ *   dust_hip_model_fill_mesh       SOLID: the voxels whose centres lie inside a closed triangle mesh, one op and palette index for all.
+ *
+ * Coordinates: INTEGERS, in units of 1 / DUST_HIP_TRIANGLE_UNIT = 1/256 voxel of the model's tree coordinates. Voxel (x, y, z) is the
+ * cube [256 x, 256 x + 256]^3, its centre (256 x + 128, 256 y + 128, 256 z + 128). Both rules are EXACT: every predicate below is a
+ * sign test on 64-bit integers that cannot overflow (every intermediate stays below 2^60), so the device, a host and a witness agree
+ * on every voxel, not within a voxel. Float vertices are not taken: the caller rounds (the Python binding: rint(v * 256)).
+ * Common to both calls. With e1 = v1 - v0 and e2 = v2 - v0 the normal is n = e1 x e2. A triangle with n == 0, or with any |coordinate|
+ * above DUST_HIP_TRIANGLE_MAX_COORD = 2^18 (+-1024 voxels), covers nothing: changed[i] = 0, it is not live, and that is not an error.
+ * Triangles are clipped to the tree; vertices may lie outside it, negative coordinates included. reserved is ignored.
+ *
+ * Surface rule (edit_triangles). Triangle i covers voxel (x, y, z) iff the closed triangle and the closed cube share a point, decided by
+ * the 13-axis separating-axis test on integers: the axes (1,0,0), (0,1,0), (0,0,1), n, and e x u for the three edges e (v0->v1, v1->v2,
+ * v2->v0) and the three unit axes u. An axis a separates the pair iff max over k of dot(a, v_k) < min over the cube's corners c of
+ * dot(a, c), or min over k of dot(a, v_k) > max over the corners of dot(a, c). The inequalities are strict, so touching covers: a
+ * triangle lying exactly on a voxel face covers the voxels on both sides, one that meets a cube at only a corner or an edge covers it.
+ * The voxel is covered iff no axis separates. Thin (6-separating) surfaces are not offered.
+ * Operations on a covered voxel are edit_shapes' (DUST_HIP_EDIT_CARVE, _FILL, _PAINT, _PLACE), per triangle. Order: the triangles of a
+ * call apply in array order, as n successive calls would. changed[i] is counted as edit_shapes counts it: the voxels whose value after
+ * triangle i differs from their value before it. Deterministic: two runs give the same bytes and the same counts. `changed` may be NULL.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything changes: a null model; null triangles with n > 0; n >
+ * DUST_HIP_MAX_EDIT_TRIANGLES; an unknown op; a palette outside 0..254 on an op that uses it. n == 0 is a no-op, whatever the arrays (it
+ * may move the model into its editable form). DUST_ERR_UNSUPPORTED exactly where edit_shapes returns it: 4096^3 trees, and models that
+ * hold material byte 255.
+ *
+ * Solid rule (fill_mesh). A voxel of the region is inside iff an odd number of triangles is CROSSED above its centre c = (px, py, cz).
+ * For one triangle let s = sign(n.z). If s == 0 the triangle crosses nothing. Otherwise it is crossed above c iff both hold:
+ *   Column test: for each edge a -> b in the order v0->v1, v1->v2, v2->v0, with d = s * (b - a) in xy and
+ *     E = d.x * (py - a.y) - d.y * (px - a.x): E > 0, or E == 0 and (d.y > 0, or d.y == 0 and d.x < 0), for every edge.
+ *   Height test: s * dot(n, c - v0) < 0. A centre exactly on the plane is not crossed.
+ * The rule does not depend on the winding or on the order of the triangles, and a column centre on an edge or a vertex shared by several
+ * triangles is counted for exactly the right ones: a closed mesh fills its inside, whatever passes through column centres. A triangle's
+ * own op and palette are ignored and not validated; query.op and query.palette apply to the inside voxels of the region (edit_shapes'
+ * operations). An OPEN mesh still gives a deterministic answer, the parity above, and nothing more is promised for it; open meshes are
+ * not repaired. The ray axis is z; there is no choice of axis. Two runs give the same bytes.
+ * Region: query.lo .. query.hi, inclusive, clipped to the tree as dust_hip_model_columns clips it (a coordinate past 255 is cut back to
+ * 255); lo > hi on an axis is the empty region: nothing is looked at, the triangles included, and the result is the zero result with
+ * bounds 255 / 0. Voxels outside the region are neither consulted nor changed.
+ * Result: covered, the voxels of the region inside the mesh; changed, those whose value changed; live, the triangles in range and not
+ * degenerate; crossing, those of them with n.z != 0 (vertical triangles cross nothing); lo / hi, the bounds of the covered voxels,
+ * 255 / 0 when there are none. `result` may be NULL.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything changes, in this order: a null model; (DUST_ERR_UNSUPPORTED for the model's
+ * kind, as above, before the query is looked at); a null query; a struct_size below this library's; null triangles with n > 0; n >
+ * DUST_HIP_MAX_MESH_TRIANGLES; an unknown query.op; a query.palette outside 0..254 on an op that uses it; a flag; a reserved word not 0.
+ * n == 0 is a no-op that may make the model editable; the result is the zero result. The empty region is the same no-op: the model
+ * is not rebuilt, and its island labelling and its fields stand.
+ *
+ * Both calls are synchronous, like edit_shapes: they return with the model rebuilt -- the device arrays byte for byte what
+ * dust_hip_model_create builds from the same voxels -- and the outputs written; whatever edit_shapes invalidates (the island labelling,
+ * the flood and distance fields) they invalidate. Scenes that instance the model must be committed again; until then frames and queries
+ * answer DUST_ERR_NOT_READY.
+ * Out of scope: thin (6-separating) surfaces; float vertices in the ABI; count-only dry runs; a choice of ray axis; repairing open
+ * meshes; 4096^3 trees; asynchronous forms; texture or colour sampling. */
+#define DUST_HIP_TRIANGLE_UNIT 256            /* vertex units per voxel; voxel (x,y,z) is [256x, 256x+256]^3, centre 256x+128 */
+#define DUST_HIP_TRIANGLE_MAX_COORD 262144    /* |coordinate| <= 2^18 units (+-1024 voxels); beyond: the triangle covers nothing */
+#define DUST_HIP_MAX_EDIT_TRIANGLES 65536u
+#define DUST_HIP_MAX_MESH_TRIANGLES 1048576u
+typedef struct DustHipTriangle {      /* 48 bytes */
+  int32_t v[3][3];                    /* three vertices, x y z, in 1/256 voxel of the model's tree coordinates */
+  uint32_t op; int32_t palette;       /* DUST_HIP_EDIT_*; palette 0..254 where the op uses it (fill_mesh ignores both) */
+  uint32_t reserved;                  /* ignored */
+} DustHipTriangle;
+DustStatus dust_hip_model_edit_triangles(DustHipModel*, const DustHipTriangle* triangles, uint32_t n,
+                                         uint32_t* changed /* n entries, may be NULL */);
+typedef struct DustHipFillMeshQuery {  /* 48 bytes */
+  uint32_t struct_size, op;           /* sizeof(DustHipFillMeshQuery); DUST_HIP_EDIT_* */
+  int32_t palette;                    /* 0..254 where the op uses it */
+  uint32_t flags;                     /* 0 */
+  uint32_t lo[3], hi[3];              /* inclusive region, clipped to the tree as dust_hip_model_columns clips it; lo > hi: nothing */
+  uint32_t reserved[2];               /* 0 */
+} DustHipFillMeshQuery;
+typedef struct DustHipFillMeshResult { /* 48 bytes */
+  uint32_t covered, changed;          /* voxels of the region inside the mesh; those whose value changed */
+  uint32_t live, crossing;            /* triangles in range and not degenerate; of those, with n.z != 0 */
+  uint32_t lo[3], hi[3];              /* bounds of the covered voxels, 255 / 0 when none */
+  uint32_t reserved[2];               /* 0 */
+} DustHipFillMeshResult;
+DustStatus dust_hip_model_fill_mesh(DustHipModel*, const DustHipTriangle* triangles, uint32_t n, const DustHipFillMeshQuery*,
+                                    DustHipFillMeshResult* result /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

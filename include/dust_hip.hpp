@@ -402,6 +402,26 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return applied;
   }
+  // Model voxelisation (dust_hip_model_edit_triangles / fill_mesh): triangles with integer vertices in 1/256 voxel of tree coordinates.
+  // edit_triangles carves, fills, paints or places the voxels each triangle touches, in array order, and returns per triangle the voxels
+  // whose value it changed; fill_mesh applies query.op / query.palette to the voxels of the query's region whose centres lie inside the
+  // mesh (the parity of the triangles crossed above the centre). Both are exact on integers; scenes that instance this geometry must
+  // commit() again.
+  std::vector<uint32_t> edit_triangles(const std::vector<DustHipTriangle>& triangles) {
+    std::vector<uint32_t> changed(triangles.size());
+    check(dust_hip_model_edit_triangles(h_, triangles.data(), uint32_t(triangles.size()), changed.data()));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
+  DustHipFillMeshResult fill_mesh(const std::vector<DustHipTriangle>& triangles, DustHipFillMeshQuery query) {
+    query.struct_size = sizeof(query);
+    DustHipFillMeshResult result{};
+    check(dust_hip_model_fill_mesh(h_, triangles.data(), uint32_t(triangles.size()), &query, &result));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return result;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
