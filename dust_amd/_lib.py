@@ -390,6 +390,34 @@ MAX_EDIT_TRIANGLES = 65536
 MAX_MESH_TRIANGLES = 1 << 20
 
 
+class FractureSeed(C.Structure):  # DustHipFractureSeed, 16 bytes: a seed point in voxel coordinates, -1024..1279 per axis
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class FractureQuery(C.Structure):  # DustHipFractureQuery, 48 bytes: the filter, the distance limit, the per-axis scales and the region of a fracture
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32), ("max_distance2", C.c_uint32),
+                ("scale", C.c_uint8 * 3), ("reserved0", C.c_uint8), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+class FractureResult(C.Structure):  # DustHipFractureResult, 64 bytes: the counted and labelled voxels, the cells, the cut faces, the bounds
+    _fields_ = [("solid", C.c_uint32), ("labelled", C.c_uint32), ("cells", C.c_uint32), ("largest_cell", C.c_uint32), ("largest_voxels", C.c_uint32),
+                ("cut_faces", C.c_uint32), ("max_d2", C.c_uint32), ("lo", C.c_uint8 * 3), ("reserved0", C.c_uint8), ("hi", C.c_uint8 * 3),
+                ("reserved1", C.c_uint8), ("reserved", C.c_uint32 * 7)]
+
+
+class FractureCell(C.Structure):  # DustHipFractureCell, 40 bytes, laid out like DustHipCensus: one cell's voxels, shared faces, bounds and coordinate sums
+    _fields_ = [("voxels", C.c_uint32), ("cut_faces", C.c_uint32), ("lo", C.c_uint8 * 3), ("reserved0", C.c_uint8), ("hi", C.c_uint8 * 3),
+                ("reserved1", C.c_uint8), ("sum", C.c_uint64 * 3)]
+
+
+MAX_FRACTURE_SEEDS = 4096
+FRACTURE_SEED_MIN, FRACTURE_SEED_MAX = -1024, 1279
+FRACTURE_MAX_SCALE = 16
+FRACTURE_NO_LIMIT = 0xFFFFFFFF
+NO_CELL = 0xFFFF
+FRACTURE_SEAMS, FRACTURE_LABELLED = 0, 1
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -481,6 +509,10 @@ SYMBOLS = {
     "dust_hip_model_settle_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     "dust_hip_model_edit_triangles": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "dust_hip_model_fill_mesh": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    "dust_hip_model_fracture": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
+    "dust_hip_model_fracture_at": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "dust_hip_model_fracture_detach": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "dust_hip_model_fracture_apply": (C.c_int, [_P, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

@@ -86,6 +86,11 @@ SETTLE_APPLIED_DTYPE = np.dtype([("generations", "<u4"), ("first_moved", "<u4"),
 TRIANGLE_DTYPE = np.dtype([("v", "<i4", (3, 3)), ("op", "<u4"), ("palette", "<i4"), ("reserved", "<u4")])
 FILL_MESH_RESULT_DTYPE = np.dtype([("covered", "<u4"), ("changed", "<u4"), ("live", "<u4"), ("crossing", "<u4"), ("lo", "<u4", 3), ("hi", "<u4", 3),
                                    ("reserved", "<u4", 2)])
+# DustHipFractureSeed / DustHipFractureResult / DustHipFractureCell (model fracture)
+FRACTURE_SEED_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("reserved", "<u4")])
+FRACTURE_RESULT_DTYPE = np.dtype([("solid", "<u4"), ("labelled", "<u4"), ("cells", "<u4"), ("largest_cell", "<u4"), ("largest_voxels", "<u4"), ("cut_faces", "<u4"),
+                                  ("max_d2", "<u4"), ("lo", "u1", 3), ("reserved0", "u1"), ("hi", "u1", 3), ("reserved1", "u1"), ("reserved", "<u4", 7)])
+FRACTURE_CELL_DTYPE = np.dtype([("voxels", "<u4"), ("cut_faces", "<u4"), ("lo", "u1", 3), ("reserved0", "u1"), ("hi", "u1", 3), ("reserved1", "u1"), ("sum", "<u8", 3)])
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
@@ -780,6 +785,59 @@ class Model:
         L.check(self._lib.dust_hip_model_flood_apply(self._h, 0xFFFFFFFF if max_steps is None else int(max_steps), int(value), C.byref(changed)))
         return changed.value
 
+    def fracture(self, seeds, region=None, palette=None, scale=(1, 1, 1), max_distance2=None, records=True):
+        """Label every counted voxel with the index of its nearest seed (dust_hip_model_fracture): `seeds` an (n, 3) integer array or a
+        FRACTURE_SEED_DTYPE array (see fracture_seeds()), coordinates -1024..1279; counted are the solid voxels of region = (lo, hi),
+        an inclusive voxel box (None: the whole tree), of palette index `palette` (None: any); the metric is
+        scale[0] dx^2 + scale[1] dy^2 + scale[2] dz^2, ties go to the lowest seed index; a voxel farther than max_distance2 (None: no
+        limit) from every seed stays unlabelled. Returns (result, cells): a FRACTURE_RESULT_DTYPE record and a FRACTURE_CELL_DTYPE
+        array with one record per seed -- or None with records=False, which only makes the labels. They stay on the device for
+        fracture_at, fracture_detach and fracture_apply until the next edit."""
+        seeds = fracture_seeds(seeds)
+        q = L.FractureQuery(struct_size=C.sizeof(L.FractureQuery), flags=0, palette=-1 if palette is None else int(palette),
+                            max_distance2=L.FRACTURE_NO_LIMIT if max_distance2 is None else int(max_distance2))
+        q.scale[:] = [int(v) for v in scale]
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        result = np.zeros(1, FRACTURE_RESULT_DTYPE)
+        cells = np.zeros(len(seeds), FRACTURE_CELL_DTYPE)
+        L.check(self._lib.dust_hip_model_fracture(self._h, C.byref(q), _ptr(seeds) if len(seeds) else None, len(seeds), _ptr(result) if records else None,
+                                                  _ptr(cells) if records and len(seeds) else None))
+        return (result[0], cells) if records else None
+
+    def fracture_at(self, xyz):
+        """the cell of each voxel under the last fracture (dust_hip_model_fracture_at): uint16, L.NO_CELL where the voxel has none"""
+        xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
+        cells = np.zeros(len(xyz), np.uint16)
+        L.check(self._lib.dust_hip_model_fracture_at(self._h, _ptr(xyz), _ptr(cells), len(cells)))
+        return cells
+
+    def fracture_detach(self, cells, keep_source=False, receive=True):
+        """Move the union of the cells named by `cells` (indices of the last fracture's seeds) out of the model
+        (dust_hip_model_fracture_detach). Returns a new Model holding exactly their voxels at the same tree coordinates -- or None with
+        receive=False (the cells are deleted) or with no cells. keep_source: copy, the source stays as it is. Otherwise scenes
+        instancing the source must be committed again; the removed voxels answer L.NO_CELL and the rest of the labelling stands. For
+        chunks: one fracture, one keep_source detach per piece, then one deleting detach of all of them."""
+        cells = np.ascontiguousarray(cells, np.uint32).reshape(-1)
+        h = C.c_void_p()
+        L.check(self._lib.dust_hip_model_fracture_detach(self._h, _ptr(cells) if len(cells) else None, len(cells), L.DETACH_KEEP_SOURCE if keep_source else 0,
+                                                         C.byref(h) if receive else None))
+        if not h:
+            return None
+        piece = Model.__new__(Model)
+        piece._ctx, piece._lib, piece._h = self._ctx, self._lib, h
+        return piece
+
+    def fracture_apply(self, value, where=L.FRACTURE_SEAMS):
+        """The seam voxels of the last fracture (where=L.FRACTURE_SEAMS: labelled voxels with a face-neighbour of a higher cell) or all
+        its labelled voxels (L.FRACTURE_LABELLED) take `value`, a palette index or -1 for None (dust_hip_model_fracture_apply). Returns
+        the number of voxels that changed. Scenes instancing the model must be committed again; the labelling, the fields and the
+        island labelling are invalid afterwards."""
+        changed = C.c_uint32()
+        L.check(self._lib.dust_hip_model_fracture_apply(self._h, int(where), int(value), C.byref(changed)))
+        return changed.value
+
     def distance(self, target=L.DISTANCE_TO_SOLID, metric=L.DISTANCE_EUCLIDEAN, max_radius=L.DISTANCE_MAX_RADIUS, walls=False, palette=0):
         """The exact distance from every voxel to the nearest target (dust_hip_model_distance): target L.DISTANCE_TO_SOLID (the solid
         voxels), L.DISTANCE_TO_EMPTY (the voxels holding None) or L.DISTANCE_TO_MATERIAL (the solid voxels of palette index `palette`);
@@ -1006,6 +1064,17 @@ def edit_shapes(kind, a, b=None, radius=0.0, op=L.EDIT_CARVE, palette=0):
     shapes["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(a),))
     shapes["palette"] = np.broadcast_to(np.asarray(palette, np.int32), (len(a),))
     return shapes
+
+
+def fracture_seeds(points):
+    """DustHipFractureSeed records (FRACTURE_SEED_DTYPE) for Model.fracture: points an (n, 3) integer array of voxel coordinates (may lie
+    outside the tree, -1024..1279; not clamped), or such records already"""
+    if isinstance(points, np.ndarray) and points.dtype == FRACTURE_SEED_DTYPE:
+        return np.ascontiguousarray(points).reshape(-1)
+    points = np.asarray(points, np.int64).reshape(-1, 3)
+    out = np.zeros(len(points), FRACTURE_SEED_DTYPE)
+    out["x"], out["y"], out["z"] = points[:, 0], points[:, 1], points[:, 2]
+    return out
 
 
 def triangles(vertices, op=L.EDIT_FILL, palette=0):

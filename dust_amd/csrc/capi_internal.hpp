@@ -215,6 +215,10 @@ struct EditState {
   // distance from the seeds / its distance to the nearest target (32 MiB each, allocated by the first call); valid until the next call
   // that may change a voxel
   VoxelField flood, distance;
+  // model fracture (dust_hip_model_fracture): per voxel the index of its cell, DUST_HIP_NO_CELL where it has none (32 MiB, allocated by
+  // the first call); `box` the root cells of the call's region; fracture_seeds the n_seeds of that call: the cell indices a detach may name
+  VoxelField fracture;
+  uint32_t fracture_seeds = 0;
 };
 
 struct DustHipModel : RefCounted {

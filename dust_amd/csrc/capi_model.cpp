@@ -1,7 +1,7 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
 // edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip), model floods (flood.hip), model
 // distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip), model surfaces (surface.hip), model meshes (mesh.hip), model deltas
-// (delta.hip) and model columns (column.hip). What needs no device is in three headers: the hierarchy build itself
+// (delta.hip), model columns (column.hip) and model fracture (fracture.hip). What needs no device is in three headers: the hierarchy build itself
 // (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp, the arithmetic on the callers' records (conversion, chunks,
 // cell lists, cast hits, census records, surface, mesh, delta and columns queries, a delta_apply's records) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
 #include <algorithm>
@@ -14,6 +14,7 @@
 #include "distance.hpp"
 #include "field.hpp"
 #include "flood.hpp"
+#include "fracture.hpp"
 #include "hierarchy.hpp"
 #include "island.hpp"
 #include "model_records.hpp"
@@ -203,7 +204,7 @@ DustStatus begin_edit(DustHipModel* m) {
   HIP_TRY(join_side(m->ctx));  // (a surfel pass on the second stream still traces the model as it is)
   return make_editable(m);
 }
-void invalidate_fields(EditState& es) { es.flood.valid = es.distance.valid = false; }  // (the fields describe the voxels as they were)
+void invalidate_fields(EditState& es) { es.flood.valid = es.distance.valid = es.fracture.valid = false; }  // (the fields describe the voxels as they were)
 // a call that may change a voxel is about to run
 void invalidate_derived(EditState& es) {
   es.labels_valid = false;  // (dust_hip_model_find_islands' labelling describes the voxels as they were)
@@ -227,6 +228,7 @@ DustStatus check_coordinates(const uint32_t* xyz, uint32_t n, uint32_t extent = 
 DustStatus no_labelling() { return fail(DUST_ERR_NOT_READY, "the model has no valid island labelling: call dust_hip_model_find_islands (again after an edit)"); }
 DustStatus no_distance() { return fail(DUST_ERR_NOT_READY, "the model has no valid distance field: call dust_hip_model_distance (again after an edit)"); }
 DustStatus no_field() { return fail(DUST_ERR_NOT_READY, "the model has no valid flood field: call dust_hip_model_flood (again after an edit)"); }
+DustStatus no_cells() { return fail(DUST_ERR_NOT_READY, "the model has no valid cell labelling: call dust_hip_model_fracture (again after an edit)"); }
 
 DustStatus upload_batch(DustHipModel* m, const uint32_t* xyz, const int32_t* values, uint32_t n, bool with_values) {
   EditState& e = *m->edit;
@@ -867,6 +869,157 @@ DustStatus dust_hip_model_flood_paths(DustHipModel* m, const uint32_t* starts_xy
 
 DustStatus dust_hip_model_flood_apply(DustHipModel* m, uint32_t max_steps, int32_t value, uint32_t* changed) {
   return field_apply(m, &EditState::flood, no_field, 0u, max_steps, value, changed);
+}
+
+// ---- model fracture (fracture.hip): every counted voxel labelled with its nearest seed, kept on the device with the model as a third
+// per-voxel field; whole cells detached as islands are; the seams or the labelled voxels given a value
+DustStatus dust_hip_model_fracture(DustHipModel* m, const DustHipFractureQuery* q, const DustHipFractureSeed* seeds, uint32_t n_seeds,
+                                   DustHipFractureResult* result, DustHipFractureCell* cells) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);  // (before anything else is looked at)
+  if (s != DUST_OK) return s;
+  if (!q || (n_seeds && !seeds)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipFractureQuery");
+  if (n_seeds > DUST_HIP_MAX_FRACTURE_SEEDS) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_FRACTURE_SEEDS seeds in one call");
+  dust::FractureArgs a{};
+  bool empty = false;
+  if (const char* why = dust::device_fracture(*q, a, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  if (const char* why = dust::fracture_seeds(seeds, n_seeds)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    DustStatus s = begin_edit(m);
+    if (s != DUST_OK) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    es.fracture.valid = false;  // until this labelling is complete
+    if ((s = lazy_alloc(es.fracture.values, size_t(dust::kLattice) * 64 * 2, "the cell field (32 MiB)")) != DUST_OK) return s;
+    // the context's scratch: the seeds; the result accumulator, the cells' accumulators and their records
+    const size_t acc_bytes = dust::kFractureAccWords * 4, cell_bytes = size_t(n_seeds) * sizeof(dust::FractureAcc);
+    if ((s = grow(ctx, ctx->stage_in, size_t(n_seeds) * sizeof(DustHipFractureSeed))) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_aux, acc_bytes + cell_bytes)) != DUST_OK) return s;
+    if ((s = grow(ctx, ctx->stage_out, size_t(n_seeds) * sizeof(dust::DevFractureCell))) != DUST_OK) return s;
+    a.grid = static_cast<const uint8_t*>(es.grid.p);
+    a.brick_mask = static_cast<const uint64_t*>(es.brick_mask.p);  // as the last rebuild left it
+    a.field = static_cast<uint16_t*>(es.fracture.values.p);
+    a.seeds = static_cast<const dust::DevFractureSeed*>(ctx->stage_in.p);
+    a.n_seeds = n_seeds;
+    a.cull = diag_env("NO_FRACTURE_CULL") ? 0u : 1u;  // (the measurement's switch: every seed a candidate of every cell)
+    a.acc = static_cast<uint32_t*>(ctx->stage_aux.p);
+    a.cells = reinterpret_cast<dust::FractureAcc*>(a.acc + dust::kFractureAccWords);
+    a.records = static_cast<dust::DevFractureCell*>(ctx->stage_out.p);
+    const bool describe = result || cells;
+    uint32_t acc[dust::kFractureAccWords] = {};
+    if (empty) {
+      HIP_TRY(hipMemsetAsync(a.field, 0xFF, size_t(dust::kLattice) * 64 * 2, st));  // every voxel DUST_HIP_NO_CELL
+    } else {
+      if (n_seeds) HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, seeds, size_t(n_seeds) * sizeof(DustHipFractureSeed), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemsetAsync(a.acc, 0, acc_bytes + (describe ? cell_bytes : 0), st));
+      HIP_TRY(dust::launch_fracture_label(a, st));
+      if (describe) {
+        HIP_TRY(dust::launch_fracture_records(a, st));
+        HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+        if (cells && n_seeds) HIP_TRY(hipMemcpyAsync(cells, a.records, size_t(n_seeds) * sizeof(dust::DevFractureCell), hipMemcpyDeviceToHost, st));
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(st));  // (the seeds have left the caller's array)
+    if (empty && cells) std::fill(cells, cells + n_seeds, dust::fracture_empty_cell());
+    es.fracture.count = 1;  // (an apply visits the region's cells whatever they hold)
+    es.fracture.box = empty ? dust::CellBox{{0, 0, 0}, {0, 0, 0}} : a.box;
+    es.fracture_seeds = n_seeds;
+    es.fracture.valid = true;
+    if (result) *result = dust::fracture_result(empty ? nullptr : acc);
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_fracture_at(DustHipModel* m, const uint32_t* xyz, uint16_t* cells, uint32_t n) {
+  return field_at(m, &EditState::fracture, no_cells, xyz, cells, n);
+}
+
+DustStatus dust_hip_model_fracture_detach(DustHipModel* m, const uint32_t* cells, uint32_t n, uint32_t flags, DustHipModel** out) {
+  if (!m || (n && !cells)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (flags & ~DUST_HIP_DETACH_KEEP_SOURCE) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown detach flags");
+  const bool keep = (flags & DUST_HIP_DETACH_KEEP_SOURCE) != 0;
+  if (keep && !out) return fail(DUST_ERR_INVALID_ARGUMENT, "DUST_HIP_DETACH_KEEP_SOURCE without a model to receive the cells does nothing");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (n == 0) { if (out) *out = nullptr; return DUST_OK; }
+  if (!m->edit || !m->edit->fracture.valid) return no_cells();
+  uint64_t selected[dust::kFractureSelectWords];
+  if (const char* why = dust::fracture_selection(cells, n, m->edit->fracture_seeds, selected)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    if ((s = grow(ctx, ctx->stage_in, sizeof(selected))) != DUST_OK) return s;
+    uint32_t pal[256];
+    HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, selected, sizeof(selected), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(pal, m->palette.p, sizeof(pal), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // the new model: empty, editable, its grid filled by the detach kernel and then rebuilt like any edit
+    struct Drop { DustHipModel* m; ~Drop() { release(m); } } fresh{nullptr};
+    if (out) {
+      s = dust_hip_model_create(ctx, nullptr, 0, nullptr, 0, reinterpret_cast<const uint8_t*>(pal), 8, &fresh.m);
+      if (s == DUST_OK) s = make_editable(fresh.m, false);
+      if (s != DUST_OK) return s;
+    }
+    dust::FractureDetachArgs a{};
+    a.src = static_cast<uint8_t*>(es.grid.p);
+    a.dst = fresh.m ? static_cast<uint8_t*>(fresh.m->edit->grid.p) : nullptr;
+    a.field = static_cast<uint16_t*>(es.fracture.values.p);
+    a.selected = static_cast<const uint64_t*>(ctx->stage_in.p);
+    // copy first and build the new model from the copy; the source is carved only once the voxels have somewhere to live, so a failure
+    // up to there leaves it as it was
+    if (fresh.m) {
+      a.carve = 0u;
+      HIP_TRY(dust::launch_fracture_detach(a, st));
+      if ((s = rebuild_and_refresh(fresh.m, *fresh.m->edit)) != DUST_OK) return s;
+    }
+    if (!keep) {
+      a.dst = nullptr;
+      a.carve = 1u;
+      invalidate_derived(es);  // (a cell's voxels left their islands: the island labelling goes with the flood and distance fields)
+      HIP_TRY(dust::launch_fracture_detach(a, st));
+      if ((s = rebuild_and_refresh(m, es)) != DUST_OK) return s;
+      es.fracture.valid = true;  // whole cells left and their voxels answer DUST_HIP_NO_CELL: the labelling of the rest stands
+    }
+    if (out) *out = retain(fresh.m);  // the caller's reference (the guard drops the builder's)
+    return DUST_OK;
+  });
+}
+
+DustStatus dust_hip_model_fracture_apply(DustHipModel* m, uint32_t where, int32_t value, uint32_t* changed) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);
+  if (s != DUST_OK) return s;
+  if (const char* why = dust::fracture_apply_arguments(where, value)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  if (!m->edit || !m->edit->fracture.valid) return no_cells();
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));  // (a surfel pass on the second stream still traces the model as it is)
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    invalidate_derived(es);
+    if ((s = grow(ctx, es.changed, 4)) != DUST_OK) return s;
+    dust::FractureApplyArgs a{};
+    a.grid = static_cast<uint8_t*>(es.grid.p);
+    a.field = static_cast<const uint16_t*>(es.fracture.values.p);
+    a.seams = where == DUST_HIP_FRACTURE_SEAMS ? 1u : 0u;
+    a.byte = value < 0 ? 0u : uint32_t(value) + 1u;
+    a.box = es.fracture.box;
+    a.changed = static_cast<uint32_t*>(es.changed.p);
+    uint32_t n = 0;
+    HIP_TRY(hipMemsetAsync(a.changed, 0, 4, st));
+    HIP_TRY(dust::launch_fracture_apply(a, st));
+    HIP_TRY(hipMemcpyAsync(&n, a.changed, 4, hipMemcpyDeviceToHost, st));
+    s = rebuild_and_refresh(m, es);  // synchronises; k_edit_brick_masks makes the masks again from the grid
+    if (s != DUST_OK) return s;
+    if (changed) *changed = n;
+    return DUST_OK;
+  });
 }
 
 // ---- model distances (distance.hip): the exact distance from every voxel to the nearest target voxel, kept on the device with the model

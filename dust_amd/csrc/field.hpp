@@ -1,4 +1,4 @@
-// field.hpp -- what the per-voxel uint16 fields of an editable model (the flood's steps, the distance transform's values) have in
+// field.hpp -- what the per-voxel uint16 fields of an editable model (the flood's steps, the distance transform's values, a fracture's cells) have in
 // common once they are computed: the value that means "none", looking values up, and writing a grid byte where the value is in a range
 // (kernels in field.hip). A field is brick-major like the grid (grid.hpp voxel_index).
 #pragma once

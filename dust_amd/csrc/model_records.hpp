@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp and tests/cpp/triangle_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp and tests/cpp/fracture_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include "delta.hpp"
 #include "distance.hpp"
 #include "edit.hpp"
+#include "fracture.hpp"
 #include "mesh.hpp"
 #include "neighbour.hpp"
 #include "settle.hpp"
@@ -49,6 +50,12 @@ static_assert(sizeof(DustHipSettleQuery) == 72 && sizeof(DustHipSettleResult) ==
 static_assert(sizeof(DustHipTriangle) == 48 && sizeof(DustHipFillMeshQuery) == 48 && sizeof(DustHipFillMeshResult) == 48 && sizeof(DevTriangle) == 52 &&
                   kTriangleUnit == DUST_HIP_TRIANGLE_UNIT && kTriangleMaxCoord == DUST_HIP_TRIANGLE_MAX_COORD,
               "triangle records");
+
+static_assert(sizeof(DustHipFractureSeed) == 16 && sizeof(DustHipFractureSeed) == sizeof(DevFractureSeed) && sizeof(DustHipFractureQuery) == 48 &&
+                  sizeof(DustHipFractureResult) == 64 && sizeof(DustHipFractureCell) == 40 && sizeof(DustHipFractureCell) == sizeof(DevFractureCell) &&
+                  kFractureMaxSeeds == DUST_HIP_MAX_FRACTURE_SEEDS && kFractureNoCell == DUST_HIP_NO_CELL && kFractureNoLimit == DUST_HIP_FRACTURE_NO_LIMIT &&
+                  kFractureSeedMin == DUST_HIP_FRACTURE_SEED_MIN && kFractureSeedMax == DUST_HIP_FRACTURE_SEED_MAX && kFractureMaxScale == DUST_HIP_FRACTURE_MAX_SCALE,
+              "fracture records");
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
@@ -714,6 +721,80 @@ inline DustHipFillMeshResult fill_mesh_result(const uint32_t* acc, uint32_t live
   r.live = live; r.crossing = crossing;
   for (int k = 0; k < 3; ++k) { r.lo[k] = 255u - acc[2 + k]; r.hi[k] = acc[5 + k]; }
   return r;
+}
+
+// A fracture query as k_fracture_label reads it (dust_hip_model_fracture): the filter's grid byte, the limit, the scales, the region
+// clipped to the tree as device_columns clips it and the root cells it reaches. The pointers, the seeds and `cull` are the caller's.
+// nullptr: the query is fine; otherwise why the call refuses it, in the header's order. `empty` as in device_surface: nothing is looked
+// at, no launch is made and the region fields are not set.
+inline const char* device_fracture(const DustHipFractureQuery& q, FractureArgs& d, bool& empty) {
+  for (int r = 0; r < 3; ++r)
+    if (q.scale[r] == 0u || q.scale[r] > kFractureMaxScale) return "scale must be 1..16 on every axis";
+  if (q.palette < -1 || q.palette > 254) return "palette must be -1 (every solid voxel) or 0..254";
+  if (q.flags != 0u) return "unknown fracture flag";
+  if (q.reserved0 != 0u || q.reserved != 0u) return "reserved word not 0";
+  d.byte = q.palette < 0 ? 0u : uint32_t(q.palette) + 1u;
+  d.limit = q.max_distance2;
+  empty = false;
+  for (int r = 0; r < 3; ++r) {
+    d.scale[r] = q.scale[r];
+    const uint32_t lo = q.lo[r], hi = std::min(q.hi[r], 255u);
+    empty |= lo > hi;
+    if (empty) continue;
+    d.lo[r] = lo; d.hi[r] = hi;
+    d.box.lo[r] = lo >> 4; d.box.hi[r] = hi >> 4;
+  }
+  return nullptr;
+}
+// what dust_hip_model_fracture refuses in its seeds
+inline const char* fracture_seeds(const DustHipFractureSeed* seeds, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) {
+    const int32_t c[3] = {seeds[i].x, seeds[i].y, seeds[i].z};
+    for (int32_t v : c)
+      if (v < kFractureSeedMin || v > kFractureSeedMax) return "seed coordinate outside -1024..1279";
+    if (seeds[i].reserved != 0u) return "a seed's reserved word is not 0";
+  }
+  return nullptr;
+}
+// what dust_hip_model_fracture_apply refuses
+inline const char* fracture_apply_arguments(uint32_t where, int32_t value) {
+  if (where > DUST_HIP_FRACTURE_LABELLED) return "where must be DUST_HIP_FRACTURE_SEAMS or DUST_HIP_FRACTURE_LABELLED";
+  if (value < -1 || value > 254) return "value must be -1 (None) or a palette index 0..254";
+  return nullptr;
+}
+// A detach's selection: a bit per named cell. nullptr, or why the call refuses (an index that is no cell of the labelling).
+inline const char* fracture_selection(const uint32_t* cells, uint32_t n, uint32_t n_seeds, uint64_t (&selected)[kFractureSelectWords]) {
+  std::memset(selected, 0, sizeof(selected));
+  for (uint32_t i = 0; i < n; ++i) {
+    if (cells[i] >= n_seeds) return "a cell index is not below the labelling's n_seeds";
+    selected[cells[i] >> 6] |= 1ull << (cells[i] & 63u);
+  }
+  return nullptr;
+}
+// What a fracture's caller gets from the device's kFractureAccWords accumulator; null: nothing was looked at -- the zero result with
+// no largest cell and bounds 255 / 0 (what a call that labels nothing has too, beside its `solid`).
+inline DustHipFractureResult fracture_result(const uint32_t* acc) {
+  DustHipFractureResult r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  r.largest_cell = 0xFFFFFFFFu;
+  if (!acc) return r;
+  r.solid = acc[kFractureSolid]; r.labelled = acc[kFractureLabelled]; r.cut_faces = acc[kFractureCut];
+  r.cells = acc[kFractureCells];
+  if (r.labelled != 0u) {
+    r.max_d2 = acc[kFractureMaxD2];
+    for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[kFractureLo + k]); r.hi[k] = uint8_t(acc[kFractureHi + k]); }
+  }
+  if (r.cells != 0u) {
+    r.largest_cell = 0xFFFFFFFFu - acc[kFractureLargest];
+    r.largest_voxels = acc[kFractureLargest + 1];
+  }
+  return r;
+}
+// the record of a cell without a voxel (what every cell of a call that labels nothing gets)
+inline DustHipFractureCell fracture_empty_cell() {
+  DustHipFractureCell c{};
+  for (int k = 0; k < 3; ++k) c.lo[k] = 255;
+  return c;
 }
 
 // the records of a call that cover something, in call order: `index` maps them back to the caller's

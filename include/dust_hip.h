@@ -1198,6 +1198,106 @@ typedef struct DustHipFillMeshResult { /* 48 bytes */
 } DustHipFillMeshResult;
 DustStatus dust_hip_model_fill_mesh(DustHipModel*, const DustHipTriangle* triangles, uint32_t n, const DustHipFillMeshQuery*,
                                     DustHipFillMeshResult* result /* may be NULL */);
+/* Model fracture: BREAKING A SOLID INTO PIECES. edit_shapes carves a crater, find_islands and detach_islands lift out what it cut
+ * loose, settle drops it, cast and stamp land it, delta replicates it -- but a wall that is hit stays one island. Fracture scatters seed
+ * points and gives every solid voxel to its nearest seed: a Voronoi partition, exact on integers, kept on the device with the model.
+ * Four calls:
+ *   dust_hip_model_fracture         labels the model's voxels with the index of their nearest seed and describes the cells;
+ *   dust_hip_model_fracture_at      reads labels at coordinates, as flood_at reads steps;
+ *   dust_hip_model_fracture_detach  moves the union of named cells into a model of its own, under detach_islands' contract;
+ *   dust_hip_model_fracture_apply   gives the seam voxels, or every labelled voxel, a value.
+ *
+ * Seeds: integer voxel coordinates, int32 per axis, each in DUST_HIP_FRACTURE_SEED_MIN .. DUST_HIP_FRACTURE_SEED_MAX = -1024 .. 1279;
+ * seeds may lie outside the tree. A voxel is the integer point (x, y, z). At most DUST_HIP_MAX_FRACTURE_SEEDS = 4096 seeds; n_seeds == 0
+ * is legal: nothing is labelled and `solid` is still counted.
+ * Metric: with scale = (sx, sy, sz), each in 1..16, d2(v, s) = sx (x - s.x)^2 + sy (y - s.y)^2 + sz (z - s.z)^2. d2 stays below 2^27 and
+ * every coordinate difference below 2^11, so the device, a host and a witness agree on every voxel. Unequal scales give splinters.
+ * Labelled voxels: a voxel is COUNTED when it is solid, lies inside the inclusive region lo..hi, clipped to the tree as
+ * dust_hip_model_columns clips it (a coordinate past 255 is cut back to 255; lo > hi on an axis is the empty region), and query.palette
+ * is -1 or the voxel holds that palette index. A counted voxel is labelled with the seed index i that minimises (d2, i)
+ * lexicographically: ties go to the lowest index; duplicate seeds are legal, the later one gets nothing. With max_distance2 !=
+ * DUST_HIP_FRACTURE_NO_LIMIT a counted voxel whose minimum d2 exceeds max_distance2 stays unlabelled: local damage, only the
+ * neighbourhood of the impact breaks. Every other voxel holds DUST_HIP_NO_CELL.
+ * A CELL is the set of voxels labelled i; it need not be connected (after a detach, find_islands on the piece splits it). A CUT FACE is
+ * a face shared by two face-neighbours that are both labelled, with different cells. A SEAM voxel is a labelled voxel with a
+ * face-neighbour labelled with a higher cell index: seams are one voxel thick.
+ *
+ * dust_hip_model_fracture makes the model editable first, exactly as flood does (scenes that instance it must then be committed again;
+ * on an editable model the call changes nothing a scene reads), and leaves the labels on the device with the model -- one uint16 per
+ * voxel, 32 MiB next to the flood and distance fields, allocated by the first call -- together with n_seeds. result: solid, the counted
+ * voxels; labelled; cells, the seeds with at least one voxel; largest_cell and largest_voxels, the lowest index among equals, 0xFFFFFFFF
+ * and 0 when cells == 0; cut_faces, each face once; max_d2, the largest d2 of a labelled voxel to its seed; lo / hi, the inclusive bounds
+ * of the labelled voxels, 255 / 0 when there are none. cells[i] for every seed: voxels; cut_faces, the faces this cell shares with other
+ * cells; lo / hi, 255,255,255 / 0,0,0 when empty; sum, the sums of x, y, z. The sum of cells[i].voxels equals labelled and the sum of
+ * cells[i].cut_faces equals 2 * cut_faces. `result` and `cells` may be NULL; with both NULL only the labels are made. Two runs give the
+ * same bytes.
+ * dust_hip_model_fracture_detach: *out is a new editable model of the same context and palette that holds the voxels of the named cells
+ * at the same tree coordinates, byte for byte a host build. DUST_HIP_DETACH_KEEP_SOURCE copies only; out == NULL deletes. The copy is
+ * made before the carve, so a failure leaves the source intact. Duplicates and empty cells are legal; n == 0 is detach_islands' no-op
+ * (*out = NULL). After a carving detach the removed voxels answer DUST_HIP_NO_CELL and the rest of the labelling STANDS. The recipe for
+ * chunks: one fracture, then one KEEP_SOURCE detach per piece, then one deleting detach of all of them -- the source is rebuilt once.
+ * dust_hip_model_fracture_apply: where = DUST_HIP_FRACTURE_SEAMS or DUST_HIP_FRACTURE_LABELLED; value a palette index 0..254, or -1 for
+ * None. Every decision is made on the labelling as it stands; *changed is the number of voxels whose value differs afterwards; the
+ * model is rebuilt as after surface_apply. Crack lines painted before the break; a one-voxel gap after which find_islands sees the
+ * pieces; scorch within max_distance2.
+ *
+ * Validity: the cell field is invalidated by exactly what invalidates the flood field (every set_voxels, edit_shapes, stamp as
+ * destination, carving detach_islands with n > 0, flood_apply, distance_apply and every other call that may change a voxel), by
+ * fracture_apply, and by a fracture that fails; a second fracture replaces it. fracture leaves the island labelling and both other
+ * fields standing. A carving fracture_detach invalidates the flood and distance fields as a carving detach_islands does, and the island
+ * labelling too (it cuts islands apart); the cell field itself stands. fracture_apply invalidates all of them.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, nothing changed: a null model or query; a struct_size below sizeof(DustHipFractureQuery); null
+ * seeds with n_seeds > 0; n_seeds > DUST_HIP_MAX_FRACTURE_SEEDS; a seed coordinate out of range or a seed's reserved word not 0; a scale
+ * outside 1..16; a palette outside -1..254; flags or reserved words not 0; null arrays with n > 0; a lookup coordinate >= 256; a cell
+ * index >= n_seeds; unknown detach flags, or KEEP_SOURCE without `out`; an unknown `where`; a value outside -1..254.
+ * DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material byte 255), before anything but the
+ * model pointer is looked at. DUST_ERR_NOT_READY from fracture_at, fracture_detach (n > 0) and fracture_apply without a standing
+ * labelling, as flood_at answers without a field.
+ * Out of scope: weighted (power) diagrams and non-integer seeds; seeds chosen by the library (a Poisson scatter); splitting a cell into
+ * its connected pieces inside the call (find_islands does it); world-space or scene-level fracture; an asynchronous form; 4096^3
+ * trees. */
+#define DUST_HIP_MAX_FRACTURE_SEEDS 4096u
+#define DUST_HIP_FRACTURE_SEED_MIN (-1024)
+#define DUST_HIP_FRACTURE_SEED_MAX 1279
+#define DUST_HIP_FRACTURE_MAX_SCALE 16u
+#define DUST_HIP_FRACTURE_NO_LIMIT 0xFFFFFFFFu
+#define DUST_HIP_NO_CELL 0xFFFFu
+#define DUST_HIP_FRACTURE_SEAMS    0u   /* fracture_apply: the labelled voxels with a face-neighbour of a higher cell index */
+#define DUST_HIP_FRACTURE_LABELLED 1u   /* fracture_apply: every labelled voxel */
+typedef struct DustHipFractureSeed {   /* 16 bytes */
+  int32_t x, y, z;                     /* voxel coordinates, -1024..1279 */
+  uint32_t reserved;                   /* 0 */
+} DustHipFractureSeed;
+typedef struct DustHipFractureQuery {  /* 48 bytes */
+  uint32_t struct_size, flags;         /* sizeof(DustHipFractureQuery); 0 */
+  int32_t palette;                     /* -1: every solid voxel; 0..254: the voxels of that palette index */
+  uint32_t max_distance2;              /* DUST_HIP_FRACTURE_NO_LIMIT, or the largest d2 at which a voxel is still labelled */
+  uint8_t scale[3], reserved0;         /* 1..16 per axis; 0 */
+  uint32_t lo[3], hi[3];               /* inclusive region, clipped to the tree; lo > hi: nothing */
+  uint32_t reserved;                   /* 0 */
+} DustHipFractureQuery;
+typedef struct DustHipFractureResult { /* 64 bytes */
+  uint32_t solid, labelled;            /* counted voxels; those that hold a cell index */
+  uint32_t cells;                      /* seeds with at least one voxel */
+  uint32_t largest_cell, largest_voxels; /* the lowest index among equals; 0xFFFFFFFF, 0 when cells == 0 */
+  uint32_t cut_faces;                  /* each face once */
+  uint32_t max_d2;                     /* the largest d2 of a labelled voxel to its seed */
+  uint8_t lo[3], reserved0;            /* inclusive bounds of the labelled voxels; 255,255,255 when there are none */
+  uint8_t hi[3], reserved1;            /* 0,0,0 when there are none; reserved bytes 0 */
+  uint32_t reserved[7];                /* 0 */
+} DustHipFractureResult;
+typedef struct DustHipFractureCell {   /* 40 bytes, laid out like DustHipCensus */
+  uint32_t voxels;                     /* voxels labelled with this cell */
+  uint32_t cut_faces;                  /* faces this cell shares with other cells */
+  uint8_t lo[3], reserved0;            /* inclusive bounds; 255,255,255 when voxels == 0 */
+  uint8_t hi[3], reserved1;            /* 0,0,0 when voxels == 0; reserved bytes 0 */
+  uint64_t sum[3];                     /* sums of x, of y, of z over the cell's voxels */
+} DustHipFractureCell;
+DustStatus dust_hip_model_fracture(DustHipModel*, const DustHipFractureQuery*, const DustHipFractureSeed* seeds, uint32_t n_seeds,
+                                   DustHipFractureResult* result /* may be NULL */, DustHipFractureCell* cells /* n_seeds, may be NULL */);
+DustStatus dust_hip_model_fracture_at(DustHipModel*, const uint32_t* xyz, uint16_t* cells, uint32_t n);
+DustStatus dust_hip_model_fracture_detach(DustHipModel*, const uint32_t* cells, uint32_t n, uint32_t flags, DustHipModel** out /* may be NULL */);
+DustStatus dust_hip_model_fracture_apply(DustHipModel*, uint32_t where, int32_t value, uint32_t* changed /* may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

@@ -422,6 +422,42 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return result;
   }
+  // Model fracture (dust_hip_model_fracture / fracture_at / fracture_detach / fracture_apply): every counted voxel of the query's
+  // region labelled with the index of its nearest seed (ties to the lowest index), the labels kept on the device until the next edit;
+  // the cell of each coordinate (DUST_HIP_NO_CELL where it has none); the union of the named cells moved into a geometry of its own --
+  // copied under DUST_HIP_DETACH_KEEP_SOURCE, only removed with want_geometry = false; and the seams or all labelled voxels given a
+  // palette index (nullopt: None). For chunks: one fracture, a KEEP_SOURCE detach per piece, then one deleting detach of all of them.
+  struct Fractured { DustHipFractureResult result; std::vector<DustHipFractureCell> cells; };
+  Fractured fracture(DustHipFractureQuery query, const std::vector<DustHipFractureSeed>& seeds) {
+    query.struct_size = sizeof(query);
+    Fractured out{};
+    out.cells.resize(seeds.size());
+    check(dust_hip_model_fracture(h_, &query, seeds.data(), uint32_t(seeds.size()), &out.result, out.cells.data()));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return out;
+  }
+  std::vector<uint16_t> fracture_at(const std::vector<UVec3>& coords) {
+    std::vector<uint32_t> xyz;
+    std::vector<uint16_t> cells(coords.size());
+    for (const UVec3& c : coords) xyz.insert(xyz.end(), c.begin(), c.end());
+    check(dust_hip_model_fracture_at(h_, xyz.data(), cells.data(), uint32_t(cells.size())));
+    return cells;
+  }
+  std::unique_ptr<VoxGeometry> fracture_detach(const std::vector<uint32_t>& cells, uint32_t flags = 0, bool want_geometry = true) {
+    DustHipModel* piece = nullptr;
+    check(dust_hip_model_fracture_detach(h_, cells.data(), uint32_t(cells.size()), flags, want_geometry ? &piece : nullptr));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return piece ? std::unique_ptr<VoxGeometry>(new VoxGeometry(piece)) : nullptr;
+  }
+  uint32_t fracture_apply(uint32_t where, std::optional<uint8_t> palette_index) {
+    uint32_t changed = 0;
+    check(dust_hip_model_fracture_apply(h_, where, palette_index ? int32_t(*palette_index) : -1, &changed));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return changed;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
