@@ -175,6 +175,22 @@ STAMP_PLACE, STAMP_OVERWRITE, STAMP_REPLACE, STAMP_CARVE, STAMP_PAINT = 0, 1, 2,
 MAX_STAMPS = 65536
 
 
+class Resample(C.Structure):  # DustHipResample, 96 bytes: the fixed-point inverse map, the destination box, the source sub-box and the stamp op
+    _fields_ = [("m", (C.c_int32 * 3) * 3), ("t", C.c_int32 * 3), ("dst_lo", C.c_int32 * 3), ("dst_hi", C.c_int32 * 3), ("src_lo", C.c_uint8 * 3),
+                ("pad0", C.c_uint8), ("src_hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("op", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class ResampleCount(C.Structure):  # DustHipResampleCount, 16 bytes
+    _fields_ = [("changed", C.c_uint32), ("covered", C.c_uint32), ("solid", C.c_uint32), ("blocked", C.c_uint32)]
+
+
+RESAMPLE_ONE = 65536
+RESAMPLE_MAX_M = 8 * 65536
+RESAMPLE_MAX_T = 1 << 28
+RESAMPLE_DRY_RUN = 1
+MAX_RESAMPLES = 65536
+
+
 class Cast(C.Structure):  # DustHipCast, 48 bytes: a sub-box of a source model, its orientation and offset in the destination, a step and a step limit
     _fields_ = [("offset", C.c_int32 * 3), ("orient", C.c_uint32), ("step", C.c_int32 * 3), ("max_steps", C.c_uint32), ("flags", C.c_uint32),
                 ("src_lo", C.c_uint8 * 3), ("pad0", C.c_uint8), ("src_hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("reserved", C.c_uint32)]
@@ -486,6 +502,7 @@ SYMBOLS = {
     "dust_hip_model_island_of": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_detach_islands": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "dust_hip_model_stamp": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
+    "dust_hip_model_resample": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     "dust_hip_model_cast": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_flood": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_flood_at": (C.c_int, [_P, _P, _P, C.c_uint32]),

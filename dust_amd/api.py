@@ -38,6 +38,10 @@ EDIT_SHAPE_DTYPE = np.dtype([("a", "<f4", 3), ("kind", "<u4"), ("b", "<f4", 3), 
 STAMP_DTYPE = np.dtype([("offset", "<i4", 3), ("orient", "<u4"), ("op", "<u4"), ("src_lo", "u1", 3), ("pad0", "u1"), ("src_hi", "u1", 3), ("pad1", "u1"),
                         ("reserved", "<u4")])   # DustHipStamp
 ORIENT_IDENTITY = 0x24   # p = (0, 1, 2), no flips
+# DustHipResample, 96 bytes, and DustHipResampleCount, 16 bytes: a record of dust_hip_model_resample and its counts
+RESAMPLE_DTYPE = np.dtype([("m", "<i4", (3, 3)), ("t", "<i4", 3), ("dst_lo", "<i4", 3), ("dst_hi", "<i4", 3), ("src_lo", "u1", 3), ("pad0", "u1"),
+                           ("src_hi", "u1", 3), ("pad1", "u1"), ("op", "<u4"), ("reserved", "<u4", 3)])
+RESAMPLE_COUNT_DTYPE = np.dtype([("changed", "<u4"), ("covered", "<u4"), ("solid", "<u4"), ("blocked", "<u4")])
 # DustHipCast, 48 bytes, and DustHipCastHit, 32 bytes: a cast of dust_hip_model_cast and its answer
 CAST_DTYPE = np.dtype([("offset", "<i4", 3), ("orient", "<u4"), ("step", "<i4", 3), ("max_steps", "<u4"), ("flags", "<u4"), ("src_lo", "u1", 3),
                        ("pad0", "u1"), ("src_hi", "u1", 3), ("pad1", "u1"), ("reserved", "<u4")])
@@ -732,6 +736,23 @@ class Model:
         L.check(self._lib.dust_hip_model_stamp(self._h, source._h, _ptr(stamps), len(stamps), None if pm is None else _ptr(pm), _ptr(changed)))
         return changed
 
+    def resample(self, source, records, palette_map=None, dry_run=False):
+        """Paste voxels of `source` (another Model of the same context, or this one) into this model under any rotation, scale or shear
+        (dust_hip_model_resample): `records` a RESAMPLE_DTYPE array (see resamples()), applied in order as stamps are; palette_map as
+        in stamp(). Each destination voxel's centre is taken through the record's fixed-point inverse map and reads the source voxel it
+        lands in; voxels that land outside the source sub-box keep their value. Returns a RESAMPLE_COUNT_DTYPE array: changed, covered,
+        solid and blocked per record. dry_run: nothing is written and every record is counted against this model as it stands
+        (blocked == 0: the piece fits). The result is defined by the integer record, not by the float matrix it was rounded from."""
+        records = np.ascontiguousarray(records, RESAMPLE_DTYPE).reshape(-1)
+        counts = np.zeros(len(records), RESAMPLE_COUNT_DTYPE)
+        pm = None
+        if palette_map is not None:
+            pm = np.ascontiguousarray(palette_map, np.uint8).reshape(-1)
+            assert len(pm) == 255
+        L.check(self._lib.dust_hip_model_resample(self._h, source._h, _ptr(records), len(records), None if pm is None else _ptr(pm),
+                                                  L.RESAMPLE_DRY_RUN if dry_run else 0, _ptr(counts)))
+        return counts
+
     def cast(self, source, casts):
         """How far pieces of `source` (another Model of the same context, or this one) move inside this model before a voxel of them is
         blocked (dust_hip_model_cast): `casts` a CAST_DTYPE array (see casts()), each independent of the others. Returns a CAST_HIT_DTYPE
@@ -1119,6 +1140,58 @@ def stamps(offset, orient=ORIENT_IDENTITY, op=L.STAMP_PLACE, src_lo=(0, 0, 0), s
     out["op"] = np.broadcast_to(np.asarray(op, np.uint32), (len(offset),))
     out["src_lo"] = np.broadcast_to(np.asarray(src_lo, np.uint8), (len(offset), 3))
     out["src_hi"] = np.broadcast_to(np.asarray(src_hi, np.uint8), (len(offset), 3))
+    return out
+
+
+def resamples(forward, op=L.STAMP_PLACE, src_lo=(0, 0, 0), src_hi=(255, 255, 255)):
+    """DustHipResample records (RESAMPLE_DTYPE) for Model.resample from FORWARD maps: `forward` (3, 4) or (n, 3, 4) float matrices that
+    take source voxel space to destination voxel space (voxel v covers [v, v + 1) on each axis; column 3 is the translation). Each is
+    inverted in float64 and the inverse rounded to 1 / 65536 -- the record holds the inverse, and the result is defined by that integer
+    record, not by the float matrix. The destination box is the forward image of [src_lo, src_hi + 1], padded by one voxel. op scalar
+    or (n,); src_lo / src_hi (3,) or (n, 3), the inclusive sub-box of the source. ValueError: a singular matrix, or an inverse beyond
+    the call's limits (|m| <= 8, |t| <= 4096 voxels)."""
+    forward = np.asarray(forward, np.float64).reshape(-1, 3, 4)
+    n = len(forward)
+    out = np.zeros(n, RESAMPLE_DTYPE)
+    out["op"] = np.broadcast_to(np.asarray(op, np.uint32), (n,))
+    out["src_lo"] = np.broadcast_to(np.asarray(src_lo, np.uint8), (n, 3))
+    out["src_hi"] = np.broadcast_to(np.asarray(src_hi, np.uint8), (n, 3))
+    for i, f in enumerate(forward):
+        a, b = f[:, :3], f[:, 3]
+        if not np.isfinite(f).all() or abs(np.linalg.det(a)) < 1e-12:
+            raise ValueError("resamples: the forward matrix is singular or not finite (write a singular inverse into the record directly)")
+        inv = np.linalg.inv(a)
+        m = np.rint(inv * L.RESAMPLE_ONE)
+        t = np.rint(-(inv @ b) * L.RESAMPLE_ONE)
+        if np.abs(m).max() > L.RESAMPLE_MAX_M or np.abs(t).max() > L.RESAMPLE_MAX_T:
+            raise ValueError("resamples: the inverse map is beyond the limits (|m| <= 8.0, |t| <= 4096 voxels)")
+        out["m"][i] = m.astype(np.int64)
+        out["t"][i] = t.astype(np.int64)
+        lo, hi = out["src_lo"][i].astype(np.float64), out["src_hi"][i].astype(np.float64) + 1.0
+        corners = np.array([[(lo, hi)[(c >> r) & 1][r] for r in range(3)] for c in range(8)])
+        image = corners @ a.T + b
+        limit = float(2 ** 31 - 1)
+        out["dst_lo"][i] = np.clip(np.floor(image.min(axis=0)) - 1.0, -limit - 1.0, limit).astype(np.int64)
+        out["dst_hi"][i] = np.clip(np.ceil(image.max(axis=0)), -limit - 1.0, limit).astype(np.int64)
+    return out
+
+
+def rotation_about(axis, degrees, pivot_src, pivot_dst, scale=1.0):
+    """A forward (3, 4) matrix for resamples(): the rotation by `degrees` about `axis` (0, 1, 2, "x", "y", "z" or any non-zero
+    3-vector; right-handed), scaled by `scale`, that takes the source position pivot_src to the destination position pivot_dst
+    (positions in voxel space: the centre of voxel v is v + 0.5)."""
+    if isinstance(axis, str):
+        axis = "xyz".index(axis)
+    if np.ndim(axis) == 0:
+        axis = np.eye(3)[int(axis)]
+    u = np.asarray(axis, np.float64).reshape(3)
+    u = u / np.linalg.norm(u)
+    a = np.radians(float(degrees))
+    k = np.array([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]])
+    r = (np.eye(3) + np.sin(a) * k + (1.0 - np.cos(a)) * (k @ k)) * float(scale)
+    out = np.zeros((3, 4))
+    out[:, :3] = r
+    out[:, 3] = np.asarray(pivot_dst, np.float64) - r @ np.asarray(pivot_src, np.float64)
     return out
 
 

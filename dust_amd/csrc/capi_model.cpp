@@ -509,6 +509,91 @@ DustStatus dust_hip_model_stamp(DustHipModel* m, const DustHipModel* src, const 
   });
 }
 
+// ---- model resampling (resample.hip k_resample / k_resample_count): a stamp whose geometry is a fixed-point affine map. The real call
+// goes through batched_edit as a stamp does -- `changed` in its one word per record, the three further counts in stage_out beside it --,
+// the dry run through the read-only chunking on the destination's own lists, with no rebuild and nothing invalidated
+DustStatus dust_hip_model_resample(DustHipModel* m, const DustHipModel* src, const DustHipResample* records, uint32_t n, const uint8_t* palette_map,
+                                   uint32_t flags, DustHipResampleCount* counts) {
+  if (!m || !src || (n && !records)) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  if (n > DUST_HIP_MAX_RESAMPLES) return fail(DUST_ERR_INVALID_ARGUMENT, "more than DUST_HIP_MAX_RESAMPLES records in one call");
+  if (m->ctx != src->ctx) return fail(DUST_ERR_INVALID_ARGUMENT, "the source and the destination belong to different contexts");
+  DustStatus s = editable_kind(m);  // (before the records are looked at)
+  if (s == DUST_OK) s = editable_kind(src);
+  if (s != DUST_OK) return s;
+  for (uint32_t i = 0; i < n; ++i)
+    if (const char* why = dust::resample_op_refusal(records[i])) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  if (flags & ~DUST_HIP_RESAMPLE_DRY_RUN) return fail(DUST_ERR_INVALID_ARGUMENT, "unknown resample flags");
+  for (uint32_t i = 0; i < n; ++i)
+    if (const char* why = dust::resample_map_refusal(records[i])) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  uint8_t map[256];  // grid byte (palette index + 1, 0 = None) -> grid byte
+  map[0] = 0;
+  for (uint32_t i = 0; i < 255; ++i) {
+    if (palette_map && palette_map[i] > 254) return fail(DUST_ERR_INVALID_ARGUMENT, "palette_map entries must be 0..254");
+    map[i + 1] = uint8_t((palette_map ? palette_map[i] : i) + 1u);
+  }
+  const bool dry = (flags & DUST_HIP_RESAMPLE_DRY_RUN) != 0u;
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    DustStatus s = begin_edit(m);
+    if (s != DUST_OK || n == 0) return s;
+    EditState& es = *m->edit;
+    hipStream_t st = ctx->stream;
+    if (!dry) invalidate_derived(es);
+    std::vector<dust::DevResample> dev;
+    std::vector<uint32_t> index;
+    dust::live_records<dust::device_resample>(records, n, dev, index);
+    const size_t live = dev.size();
+    const size_t extra_bytes = live * dust::kResampleExtra * 4;
+    std::vector<uint32_t> changed(counts ? n : 0u, 0u), extra(live * dust::kResampleExtra, 0u);
+    const uint8_t* source = nullptr;
+    if (live) {
+      // (a dry run writes nothing: a model held against itself is read in place)
+      if ((s = source_grid(ctx, dry ? nullptr : m, src, &source)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_aux, sizeof(map))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, extra_bytes)) != DUST_OK) return s;
+      HIP_TRY(hipMemcpyAsync(ctx->stage_aux.p, map, sizeof(map), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemsetAsync(ctx->stage_out.p, 0, extra_bytes, st));
+    }
+    auto launch = [&](size_t c0, dust::ResampleArgs& a) -> DustStatus {
+      a.src = source;
+      a.records = static_cast<const dust::DevResample*>(es.shapes.p) + c0;
+      a.extra = static_cast<uint32_t*>(ctx->stage_out.p) + c0 * dust::kResampleExtra;
+      a.palette_map = static_cast<const uint8_t*>(ctx->stage_aux.p);
+      HIP_TRY(dust::launch_resample(a, dry, st));
+      return DUST_OK;
+    };
+    if (dry) {
+      if (live) {
+        if ((s = grow(ctx, es.shapes, live * sizeof(dust::DevResample))) != DUST_OK) return s;
+        if ((s = grow(ctx, es.changed, live * 4)) != DUST_OK) return s;
+        HIP_TRY(hipMemcpyAsync(es.shapes.p, dev.data(), live * sizeof(dust::DevResample), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(es.changed.p, 0, live * 4, st));
+        dust::CellLists lists;
+        s = for_each_chunk<dust::ResampleArgs>(ctx, dev, lists, es.shape_cells, es.shape_starts, es.shape_ids, [&](size_t c0, dust::ResampleArgs& a) -> DustStatus {
+          a.grid = static_cast<uint8_t*>(es.grid.p);
+          a.changed = static_cast<uint32_t*>(es.changed.p) + c0;
+          return launch(c0, a);
+        });
+        if (s != DUST_OK) return s;
+        std::vector<uint32_t> would(live, 0u);
+        HIP_TRY(hipMemcpyAsync(would.data(), es.changed.p, live * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(extra.data(), ctx->stage_out.p, extra_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));  // (the host vectors and lists above stay alive until the copies are done)
+        if (counts)
+          for (size_t k = 0; k < live; ++k) changed[index[k]] = would[k];
+      }
+    } else {
+      if ((s = batched_edit<dust::ResampleArgs>(m, dev, index, n, counts ? changed.data() : nullptr, launch)) != DUST_OK) return s;
+      if (live) HIP_TRY(hipMemcpy(extra.data(), ctx->stage_out.p, extra_bytes, hipMemcpyDeviceToHost));  // (the rebuild has waited for the stream)
+    }
+    if (counts) {
+      for (uint32_t i = 0; i < n; ++i) counts[i] = dust::resample_count(0u, nullptr);
+      for (size_t k = 0; k < live; ++k) counts[index[k]] = dust::resample_count(changed[index[k]], extra.data() + k * dust::kResampleExtra);
+    }
+    return DUST_OK;
+  });
+}
+
 // ---- model casts (cast.hip k_cast_walk / k_cast_count): both models are only read, through their brick masks
 namespace {
 // The source's brick masks: its own when it is editable (dst itself included); otherwise its blocks' masks scattered into a scratch

@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp, resample.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp and tests/cpp/fracture_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp, tests/cpp/fracture_rule_test.cpp and tests/cpp/resample_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "fracture.hpp"
 #include "mesh.hpp"
 #include "neighbour.hpp"
+#include "resample.hpp"
 #include "settle.hpp"
 #include "stamp.hpp"
 #include "surface.hpp"
@@ -59,6 +60,10 @@ static_assert(sizeof(DustHipFractureSeed) == 16 && sizeof(DustHipFractureSeed) =
 
 static_assert(sizeof(DustHipCensus) == 40 && kCensusBins == DUST_HIP_CENSUS_BINS, "census records");
 static_assert(sizeof(DustHipStamp) == 32 && sizeof(DevStamp) == 32, "stamp records");
+static_assert(sizeof(DustHipResample) == 96 && sizeof(DustHipResampleCount) == 16 && sizeof(DevResample) == 72 && kResampleOne == DUST_HIP_RESAMPLE_ONE &&
+                  kResampleMaxM == DUST_HIP_RESAMPLE_MAX_M && kResampleMaxT == DUST_HIP_RESAMPLE_MAX_T && kResampleMaxRecords == DUST_HIP_MAX_RESAMPLES &&
+                  sizeof(DustHipResampleCount) == (1 + kResampleExtra) * 4,
+              "resample records");
 static_assert(sizeof(DustHipCast) == 48 && sizeof(DustHipCastHit) == 32 && sizeof(DevCast) == 48 && sizeof(CastItem) == 8 && sizeof(CastAcc) == 16,
               "cast records");
 
@@ -160,6 +165,20 @@ inline void census_tables(const uint32_t* rows, const std::vector<uint32_t>& ind
   for (size_t k = 0; k < index.size(); ++k) std::memcpy(counts + size_t(index[k]) * kCensusBins, rows + k * kCensusBins, kCensusBins * 4);
 }
 
+// A stamp's operation as the kernels read it: two bits per case (source solid) << 1 | (destination solid) -- keep the destination's
+// byte, take the source's, or None. (dust_hip_model_resample's records carry the same ops and the same table.)
+inline uint32_t stamp_table(uint32_t op) {
+  const uint32_t K = kStampKeep, T = kStampTake, N = kStampClear;
+  auto table = [](uint32_t ee, uint32_t es, uint32_t se, uint32_t ss) { return ee | (es << 2) | (se << 4) | (ss << 6); };
+  switch (op) {
+    case DUST_HIP_STAMP_PLACE: return table(K, K, T, K);
+    case DUST_HIP_STAMP_OVERWRITE: return table(K, K, T, T);
+    case DUST_HIP_STAMP_REPLACE: return table(T, T, T, T);
+    case DUST_HIP_STAMP_CARVE: return table(K, K, K, N);
+    default: return table(K, K, K, T);  // PAINT
+  }
+}
+
 // The image box clipped to the tree, one affine map per destination axis, the operation as a table. Everything in int64: any int32
 // offset is legal.
 inline bool device_stamp(const DustHipStamp& s, DevStamp& d) {
@@ -177,16 +196,7 @@ inline bool device_stamp(const DustHipStamp& s, DevStamp& d) {
   d.lo = lo[0] | (lo[1] << 8) | (lo[2] << 16);
   d.hi = hi[0] | (hi[1] << 8) | (hi[2] << 16);
   d.orient = s.orient;
-  // two bits per case (source solid) << 1 | (destination solid): keep the destination's byte, take the source's, or None
-  const uint32_t K = kStampKeep, T = kStampTake, N = kStampClear;
-  auto table = [](uint32_t ee, uint32_t es, uint32_t se, uint32_t ss) { return ee | (es << 2) | (se << 4) | (ss << 6); };
-  switch (s.op) {
-    case DUST_HIP_STAMP_PLACE: d.table = table(K, K, T, K); break;
-    case DUST_HIP_STAMP_OVERWRITE: d.table = table(K, K, T, T); break;
-    case DUST_HIP_STAMP_REPLACE: d.table = table(T, T, T, T); break;
-    case DUST_HIP_STAMP_CARVE: d.table = table(K, K, K, N); break;
-    default: d.table = table(K, K, K, T); break;  // PAINT
-  }
+  d.table = stamp_table(s.op);
   d.pad = 0;
   return true;
 }
@@ -797,6 +807,58 @@ inline DustHipFractureCell fracture_empty_cell() {
   return c;
 }
 
+// ---- model resampling (dust_hip_model_resample)
+// what the call refuses in a record; nullptr: fine. Two steps, because the header puts the flags between them: the op ...
+inline const char* resample_op_refusal(const DustHipResample& s) { return s.op > DUST_HIP_STAMP_PAINT ? "unknown stamp op" : nullptr; }
+// ... and the map's limits
+inline const char* resample_map_refusal(const DustHipResample& s) {
+  for (int k = 0; k < 3; ++k) {
+    for (int r = 0; r < 3; ++r)
+      if (s.m[k][r] > kResampleMaxM || s.m[k][r] < -kResampleMaxM) return "a matrix entry beyond 8 * DUST_HIP_RESAMPLE_ONE in magnitude";
+    if (s.t[k] > kResampleMaxT || s.t[k] < -kResampleMaxT) return "a translation beyond 2^28 in magnitude";
+  }
+  return nullptr;
+}
+// The destination box clipped to the tree, the map in the rule's form, the sub-box, the stamp's table. false: the record covers nothing --
+// an empty box of either kind, a box wholly outside the tree, or one the interval test rules out as a whole.
+inline bool device_resample(const DustHipResample& s, DevResample& d) {
+  int32_t lo[3], hi[3], sl[3], sh[3];
+  for (int k = 0; k < 3; ++k) {
+    if (s.src_lo[k] > s.src_hi[k]) return false;
+    lo[k] = std::max<int32_t>(s.dst_lo[k], 0); hi[k] = std::min<int32_t>(s.dst_hi[k], 255);
+    if (lo[k] > hi[k]) return false;
+    sl[k] = s.src_lo[k]; sh[k] = s.src_hi[k];
+    for (int r = 0; r < 3; ++r) d.map.m[k][r] = s.m[k][r];
+    d.map.t2[k] = 2 * s.t[k];
+  }
+  if (!resample_box_meets(d.map, lo, hi, sl, sh)) return false;
+  d.lo = uint32_t(lo[0]) | (uint32_t(lo[1]) << 8) | (uint32_t(lo[2]) << 16);
+  d.hi = uint32_t(hi[0]) | (uint32_t(hi[1]) << 8) | (uint32_t(hi[2]) << 16);
+  d.src_lo = uint32_t(sl[0]) | (uint32_t(sl[1]) << 8) | (uint32_t(sl[2]) << 16);
+  d.src_hi = uint32_t(sh[0]) | (uint32_t(sh[1]) << 8) | (uint32_t(sh[2]) << 16);
+  d.table = stamp_table(s.op);
+  d.pad = 0;
+  return true;
+}
+// whether root cell `cell` (x << 8 | y << 4 | z), clipped to the record's box, can hold a voxel of its image: the interval test
+inline bool resample_cell_meets(const DevResample& d, uint32_t cell) {
+  const int32_t c[3] = {int32_t(cell >> 8) * 16, int32_t((cell >> 4) & 15u) * 16, int32_t(cell & 15u) * 16};
+  int32_t lo[3], hi[3], sl[3], sh[3];
+  for (int r = 0; r < 3; ++r) {
+    lo[r] = std::max(c[r], int32_t((d.lo >> (8 * r)) & 255u)); hi[r] = std::min(c[r] + 15, int32_t((d.hi >> (8 * r)) & 255u));
+    if (lo[r] > hi[r]) return false;
+    sl[r] = int32_t((d.src_lo >> (8 * r)) & 255u); sh[r] = int32_t((d.src_hi >> (8 * r)) & 255u);
+  }
+  return resample_box_meets(d.map, lo, hi, sl, sh);
+}
+// what a resample's caller gets from a record's `changed` and its kResampleExtra further counts; null: it covers nothing
+inline DustHipResampleCount resample_count(uint32_t changed, const uint32_t* extra) {
+  DustHipResampleCount c{};
+  if (!extra) return c;
+  c.changed = changed; c.covered = extra[0]; c.solid = extra[1]; c.blocked = extra[2];
+  return c;
+}
+
 // the records of a call that cover something, in call order: `index` maps them back to the caller's
 template <auto Convert, class In, class Rec>  // (the conversion as a template argument: called directly, as it was before this header)
 void live_records(const In* in, uint32_t n, std::vector<Rec>& dev, std::vector<uint32_t>& index) {
@@ -820,6 +882,14 @@ inline __attribute__((always_inline)) void for_each_root_cell(uint32_t lo, uint3
       for (uint32_t z = ((lo >> 16) & 255u) >> 4; z <= ((hi >> 16) & 255u) >> 4; ++z) f((x << 8) | (y << 4) | z);
 }
 
+// the root cells a record is listed in: those its bounds reach -- for a resample, those of them the interval test cannot rule out
+template <class Rec, class F>
+inline __attribute__((always_inline)) void for_each_record_cell(const Rec& r, F&& f) { for_each_root_cell(r.lo, r.hi, f); }
+template <class F>
+inline __attribute__((always_inline)) void for_each_record_cell(const DevResample& r, F&& f) {
+  for_each_root_cell(r.lo, r.hi, [&](uint32_t cell) { if (resample_cell_meets(r, cell)) f(cell); });
+}
+
 // where the order-preserving chunk that begins at record c0 ends: before its root cells would pass max_entries (a single record is
 // never cut) or its records max_records
 template <class Rec>
@@ -839,7 +909,7 @@ struct CellLists {
   template <class Rec>
   void bin(const std::vector<Rec>& dev, size_t c0, size_t c1) {
     std::fill(fill.begin(), fill.end(), 0u);
-    for (size_t i = c0; i < c1; ++i) for_each_root_cell(dev[i].lo, dev[i].hi, [&](uint32_t cell) { ++fill[cell]; });
+    for (size_t i = c0; i < c1; ++i) for_each_record_cell(dev[i], [&](uint32_t cell) { ++fill[cell]; });
     cells.clear(); starts.clear();
     uint32_t run = 0;
     for (uint32_t cell = 0; cell < 4096; ++cell) {
@@ -849,7 +919,7 @@ struct CellLists {
     }
     starts.push_back(run);
     ids.resize(run);
-    for (size_t i = c0; i < c1; ++i) for_each_root_cell(dev[i].lo, dev[i].hi, [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
+    for (size_t i = c0; i < c1; ++i) for_each_record_cell(dev[i], [&](uint32_t cell) { ids[fill[cell]++] = uint16_t(i - c0); });
   }
 };
 

@@ -1298,6 +1298,67 @@ DustStatus dust_hip_model_fracture(DustHipModel*, const DustHipFractureQuery*, c
 DustStatus dust_hip_model_fracture_at(DustHipModel*, const uint32_t* xyz, uint16_t* cells, uint32_t n);
 DustStatus dust_hip_model_fracture_detach(DustHipModel*, const uint32_t* cells, uint32_t n, uint32_t flags, DustHipModel** out /* may be NULL */);
 DustStatus dust_hip_model_fracture_apply(DustHipModel*, uint32_t where, int32_t value, uint32_t* changed /* may be NULL */);
+/* Model resampling: A STAMP UNDER ANY ROTATION, SCALE OR SHEAR. stamp, cast and delta place a piece under the 48 signed axis
+ * permutations: a fallen wall segment lands at 0 or 90 degrees, never at 30; a prefab cannot be pasted at 1.5 times its size. A resample
+ * is a stamp whose geometry is a fixed-point affine map from the destination to the source -- the voxels of one model pasted into
+ * another, materials and all, with the stamp's five ops, its palette map, its order and its snapshot rule.
+ *
+ * Geometry: everything is integer. A record names an inclusive sub-box [src_lo, src_hi] of the source, an inclusive destination box
+ * [dst_lo, dst_hi] and the INVERSE map: a matrix m and a translation t that take a destination position to a source position, in units
+ * of 1 / DUST_HIP_RESAMPLE_ONE = 1 / 65536 voxel (16 fraction bits; m[k][r] = 65536 is 1.0). Sampling is point sampling at the
+ * destination voxel's centre: for destination voxel d = (x, y, z) and each source axis k,
+ *   Q[k] = m[k][0] * (2x + 1) + m[k][1] * (2y + 1) + m[k][2] * (2z + 1) + 2 * t[k],        s[k] = floor(Q[k] / 131072),
+ * the division rounding toward minus infinity: Q[k] = -1 gives s[k] = -1, not 0. Limits: |m[k][r]| <= 8 * 65536 and |t[k]| <= 2^28;
+ * with them |Q| <= 3 * 2^19 * 511 + 2^29 = 1 340 604 416 < 2^31, so the device computes in 32 bits. Any int32 dst_lo and dst_hi are
+ * legal; the box is clipped to the tree. The image box is the set of voxels d of the clipped destination box whose s lies inside
+ * [src_lo, src_hi] on all three axes. A voxel whose s lies outside is not part of the image: it keeps its value under every op,
+ * REPLACE included. A singular m is legal: every destination voxel then reads one plane, line or voxel of the source. A record covers
+ * nothing (all four counts 0, not an error, as a stamp's degenerate inputs) when dst_lo > dst_hi on some axis, when src_lo > src_hi on
+ * some axis, or when its destination box lies wholly outside the tree.
+ * Values: v is the source voxel's value at s -- None, or palette_map[index] when a map is given (255 entries, one per palette index
+ * 0..254), otherwise the index itself; w is the destination voxel's. The ops are the stamp's, DUST_HIP_STAMP_PLACE .. _PAINT with the
+ * same values and the same table, "image box" read as above. PLACE: v solid and w None -> v. OVERWRITE: v solid -> v. REPLACE: every
+ * voxel of the image box -> v, None included. CARVE: v solid -> None. PAINT: v solid and w solid -> v. Every other voxel keeps w.
+ * Counts: counts[i] (may be NULL) describes record i -- changed: voxels whose value after the record differs from their value before
+ * it (the stamp's changed); covered: voxels of the image box; solid: those whose v is solid; blocked: those where v and w are both
+ * solid, w the destination's value before the record.
+ * With flags == 0 the call behaves as a stamp does: the records apply in array order, as n successive calls would; the source is read
+ * as it stood when the call began, also when src == dst; the call is synchronous and returns with dst rebuilt -- the device arrays
+ * byte for byte what dust_hip_model_create builds from the resulting voxels -- its generation bumped and, when n > 0, its island
+ * labelling and every derived field (flood, distance, cells) invalidated exactly as by a stamp. The SOURCE is not modified unless it is
+ * dst and is not made editable; its generation stays. Deterministic: two runs give the same bytes and the same counts.
+ * DUST_HIP_RESAMPLE_DRY_RUN is the fit test for a rotated prefab: nothing is written. Every record is counted against dst as it stands,
+ * independently of the others: counts[i] is what a call with records[i] alone would return, changed included; blocked == 0 means the
+ * piece fits. Under a dry run dst is moved into its editable form first if it is not there yet, exactly as cast does (scenes that
+ * instance it must then be committed again); otherwise its generation, its island labelling and all its fields stay.
+ * Refused with DUST_ERR_INVALID_ARGUMENT before anything changes: a null dst or src; null records with n > 0;
+ * n > DUST_HIP_MAX_RESAMPLES; models of different contexts; an unknown op; flag bits other than DRY_RUN; an m or t beyond its limit; a
+ * palette_map entry above 254. n == 0 is a no-op in the set_voxels sense (it may move dst into its editable form).
+ * DUST_ERR_UNSUPPORTED exactly where stamp returns it (4096^3 trees, models that hold material byte 255), for dst and for src alike,
+ * before the records are looked at.
+ * The result is defined by the integer record, not by whatever float matrix it was rounded from.
+ * Out of scope: filtered sampling (shrinking drops thin features; dust_hip_model_reduce is the tool for whole levels); float matrices
+ * in the ABI; perspective maps; 4096^3 trees; an asynchronous form; a rotating cast. */
+#define DUST_HIP_RESAMPLE_ONE     65536   /* 1.0 in DustHipResample.m and .t */
+#define DUST_HIP_RESAMPLE_MAX_M   (8 * 65536)
+#define DUST_HIP_RESAMPLE_MAX_T   (1 << 28)
+#define DUST_HIP_RESAMPLE_DRY_RUN 1u      /* flags: count, write nothing */
+#define DUST_HIP_MAX_RESAMPLES    65536u
+typedef struct DustHipResample {     /* 96 bytes */
+  int32_t  m[3][3];                  /* the inverse map's matrix: destination -> source, 1 / 65536 per unit */
+  int32_t  t[3];                     /* its translation, in 1 / 65536 voxel */
+  int32_t  dst_lo[3], dst_hi[3];     /* inclusive destination box, clipped to the tree */
+  uint8_t  src_lo[3], pad0;          /* inclusive sub-box of the source, tree coordinates */
+  uint8_t  src_hi[3], pad1;
+  uint32_t op;                       /* DUST_HIP_STAMP_* */
+  uint32_t reserved[3];              /* ignored */
+} DustHipResample;
+typedef struct DustHipResampleCount { /* 16 bytes */
+  uint32_t changed, covered, solid, blocked;
+} DustHipResampleCount;
+DustStatus dust_hip_model_resample(DustHipModel* dst, const DustHipModel* src, const DustHipResample* records, uint32_t n,
+                                   const uint8_t* palette_map /* 255 entries, or NULL = identity */, uint32_t flags,
+                                   DustHipResampleCount* counts /* n, may be NULL */);
 /* current size of a model's Block array and material stream, and a synchronous copy of both to the host */
 DustStatus dust_hip_model_info(const DustHipModel*, uint32_t* n_blocks, uint64_t* n_materials);
 DustStatus dust_hip_model_read(const DustHipModel*, DustHipBlock* blocks, uint32_t block_capacity, uint8_t* materials, uint64_t material_capacity);

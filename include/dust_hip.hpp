@@ -186,6 +186,19 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model resampling (dust_hip_model_resample): stamp() under any rotation, scale or shear -- each record's fixed-point inverse map takes
+  // a destination voxel's centre to the source voxel it reads; voxels that land outside the record's source sub-box keep their value.
+  // Returns changed, covered, solid and blocked per record. dry_run: nothing is written, every record is counted against this
+  // geometry as it stands (blocked == 0: the piece fits).
+  std::vector<DustHipResampleCount> resample(const VoxGeometry& source, const std::vector<DustHipResample>& records,
+                                             const std::array<uint8_t, 255>* palette_map = nullptr, bool dry_run = false) {
+    std::vector<DustHipResampleCount> counts(records.size());
+    check(dust_hip_model_resample(h_, source.h_, records.data(), uint32_t(records.size()), palette_map ? palette_map->data() : nullptr,
+                                  dry_run ? DUST_HIP_RESAMPLE_DRY_RUN : 0u, counts.data()));
+    uint64_t nm = 0;
+    check(dust_hip_model_info(h_, &num_blocks, &nm));
+    return counts;
+  }
   // Model casts (dust_hip_model_cast): how far pieces of `source` (which may be this geometry) move inside this one before a voxel of
   // them is blocked, each cast on its own: hits[i].steps free steps (the piece rests at offset + steps * step, ready for stamp()),
   // flags, contacts and the first contact. Both geometries are only read (this one is moved into its editable form by the first call).
