@@ -42,8 +42,8 @@ def mat4(o2w):
     return m.T.reshape(16)  # column-major
 
 
-def pipeline(ctx, **kw):
-    pipe = api.StandardPipeline(ctx, W, H)
+def pipeline(ctx, w=W, h=H, **kw):
+    pipe = api.StandardPipeline(ctx, w, h)
     pipe.set_noise(0, synth.stbn_scalar(layers=8))
     pipe.set_noise(5, synth.stbn_unitvec3_cosine(layers=8))
     pipe.configure_gi(1 << 16, 8192)
@@ -54,12 +54,16 @@ def pipeline(ctx, **kw):
 PASSES = L.PASS_PRIMARY | L.PASS_AMBIENT_OCCLUSION | L.PASS_FINAL_GATHER | L.PASS_SURFEL | L.PASS_GI_ORDERED | L.PASS_DENOISE
 
 
-def test_denoiser_matches_oracle_over_a_moving_sequence():
+# 250x150: a partial last tile in both directions -- the temporal pass's 20x20 luminance window meets the frame edge inside a tile
+@pytest.mark.parametrize("w,h", [(W, H), (250, 150)])
+def test_denoiser_matches_oracle_over_a_moving_sequence(w, h):
     ctx = api.Context(device=0)
     scene, models, mid, xf = build(ctx)
     sky = P.sky_state()
-    pipe = pipeline(ctx)
-    orc = O.Denoiser(W, H)
+    pipe = pipeline(ctx, w, h)
+    orc = O.Denoiser(w, h)
+    yy, xx = np.mgrid[0:h, 0:w]
+    last_tiles = (xx >= w // 16 * 16) | (yy >= h // 16 * 16)   # the partial tile column and row (none at 256x160)
     prev = xf.copy()
     worst = 0.0
     for f in range(1, 7):
@@ -81,6 +85,15 @@ def test_denoiser_matches_oracle_over_a_moving_sequence():
         rel = float(np.sqrt(((a - b) ** 2).sum() / max(1e-30, (b ** 2).sum())))
         rel_acc = float(np.sqrt(((acc[hit][:, :3].astype(np.float64) - want_acc[hit][:, :3]) ** 2).sum() / max(1e-30, (want_acc[hit][:, :3].astype(np.float64) ** 2).sum())))
         assert rel <= 1e-3 and rel_acc <= 1e-3, (f, rel, rel_acc)
+        edge = hit & last_tiles
+        if last_tiles.any():   # the same bound over the partial tiles alone: an error there cannot hide in the frame-wide sum
+            assert edge.sum() > 500
+            a, b = unpack(g["denoised"])[edge].astype(np.float64), unpack(want_den)[edge].astype(np.float64)
+            rel_edge = float(np.sqrt(((a - b) ** 2).sum() / max(1e-30, (b ** 2).sum())))
+            want_edge = want_acc[edge][:, :3].astype(np.float64)
+            rel_acc_edge = float(np.sqrt(((acc[edge][:, :3].astype(np.float64) - want_edge) ** 2).sum() / max(1e-30, (want_edge ** 2).sum())))
+            assert rel_edge <= 1e-3 and rel_acc_edge <= 1e-3, (f, rel_edge, rel_acc_edge)
+            worst = max(worst, rel_edge, rel_acc_edge)
         assert np.abs(acc[hit][:, 3] - want_acc[hit][:, 3]).max() <= 1e-3  # accumulated frame counts
         assert np.array_equal(g["denoised"][~hit], want_den[~hit])         # the sky stays as miss.rmiss wrote it
         worst = max(worst, rel, rel_acc)
