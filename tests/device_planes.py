@@ -45,3 +45,30 @@ def empty_scene(ctx):
     scene = api.Scene(ctx)
     scene.commit()
     return scene
+
+
+class DeviceMemory:
+    """caller-owned device memory (hipMalloc), filled from `array`: what a test binds a plane to"""
+
+    def __init__(self, array):
+        self._lib = _hip()
+        self._lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        self._lib.hipFree.argtypes = [ctypes.c_void_p]
+        a = np.ascontiguousarray(array)
+        self.dtype, self.shape, self.nbytes = a.dtype, a.shape, a.nbytes
+        p = ctypes.c_void_p()
+        assert self._lib.hipMalloc(ctypes.byref(p), self.nbytes) == 0
+        self.ptr = p.value
+        assert self._lib.hipMemcpy(ctypes.c_void_p(self.ptr), a.ctypes.data_as(ctypes.c_void_p), self.nbytes, 1) == 0
+
+    def read(self, pipe):
+        """the contents, once the pipeline's stream has drained"""
+        out = np.empty(self.shape, self.dtype)
+        pipe.exposure()
+        assert self._lib.hipMemcpy(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.ptr), self.nbytes, 2) == 0
+        return out
+
+    def free(self):
+        if self.ptr:
+            assert self._lib.hipFree(ctypes.c_void_p(self.ptr)) == 0
+            self.ptr = None

@@ -339,3 +339,16 @@ class Denoiser:
         self.have = True
         self.prev_cam = camera_from(cam)
         return den, hout["accum"].copy()
+
+
+def denoise_steps(inp):
+    """The oracle's filter over one case of tests/denoise_witness.py, one step at a time, as tests/test_gpu_denoise_planes.py drives the
+    device: the previous frame's planes through a first frame (which leaves their geometry as the history's), the case's accumulation
+    written over the radiance history, then the current frame. -> (denoised plane, accumulation plane)"""
+    p = inp["params"]
+    h, w = inp["cur"]["depth"].shape
+    orc = Denoiser(w, h, p["max_frames"], p["disocclusion"], p["sigma"], p["power"], p["radius"])
+    if inp["have_history"]:
+        orc.frame(inp["prev"], inp["prev_cam"], inp["frame_index"] - 1)
+        orc.hist[orc.parity]["accum"][:] = inp["hist"]
+    return orc.frame(inp["cur"], inp["cam"], inp["frame_index"])

@@ -85,6 +85,10 @@ def test_denoiser_matches_oracle_over_a_moving_sequence(w, h):
         rel = float(np.sqrt(((a - b) ** 2).sum() / max(1e-30, (b ** 2).sum())))
         rel_acc = float(np.sqrt(((acc[hit][:, :3].astype(np.float64) - want_acc[hit][:, :3]) ** 2).sum() / max(1e-30, (want_acc[hit][:, :3].astype(np.float64) ** 2).sum())))
         assert rel <= 1e-3 and rel_acc <= 1e-3, (f, rel, rel_acc)
+        # ... and value for value: a sum over 20 000 pixels cannot see one wrong pixel, and the two sides are the same float32 operations
+        for name, got, want in (("accumulation", acc, want_acc), ("denoised", g["denoised"].view(np.float16), want_den.view(np.float16))):
+            differs = hit & (got != want).any(axis=-1)
+            assert not differs.any(), (f, name, int(differs.sum()), np.argwhere(differs)[0].tolist(), got[differs][0], want[differs][0])
         edge = hit & last_tiles
         if last_tiles.any():   # the same bound over the partial tiles alone: an error there cannot hide in the frame-wide sum
             assert edge.sum() > 500
