@@ -14,6 +14,7 @@
  *     so for those rows PARITY WITH THE REAL VULKAN OUTPUT IS UNPINNED; parity is defined against
  *     this restatement. The DDA and the codecs, and the sky, the sun, the hash keys and the hash insert, are held to a second,
  *     independent numpy witness (tests/golden/make_shader_fixtures.py, tests/radiance_witness.py): two witnesses, still unpinned.
+ *     So are the camera-ray pass and the sun-shadow + AO pass, per pixel: tests/frame_witness.py, a float64 voxel ray caster.
  *   - sky bake: pinned against fixtures generated in-container from the reference's own
  *     dataset.bin / datasetSolar.bin (tests/golden/make_sky_fixtures.py).
  */

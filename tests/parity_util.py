@@ -98,6 +98,26 @@ def oracle_scene(desc: SceneDesc):
     return s
 
 
+def oracle_scene_with_history(models, palette, instances):
+    """instances: [(model, obj_to_world[12], previous mat4[16] or None)], as tests/frame_witness.py lists them"""
+    s = O.Scene()
+    for b, m in models:
+        s.add_model(b, m, palette)
+    for mid, t, prev in instances:
+        s.add_instance(mid, t, prev)
+    s.commit()
+    return s
+
+
+def hip_scene_with_history(ctx, models, palette, instances):
+    ms = [api.Model(ctx, b, m, palette) for b, m in models]
+    s = api.Scene(ctx)
+    for mid, t, prev in instances:
+        s.add_instance(ms[mid], t, prev)
+    s.commit()
+    return s
+
+
 def render_oracle(oscene, cam, sky, w, h, passes, noise5=None, rand=0, mode=O.ORC_MODE_HIER, rows=None, stats=None,
                   noise0=None, gi=None, frame_index=1, g=None, gi_threads=0):
     """gi_threads > 0: the GI passes on that many host threads (orc_pass_final_gather_mt / orc_pass_surfel_mt: the serial passes' result)"""
