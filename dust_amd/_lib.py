@@ -301,6 +301,23 @@ MESH_WALLS = 1
 MESH_ANY_PALETTE = 2
 
 
+class BoxesQuery(C.Structure):  # DustHipBoxesQuery, 48 bytes: a SurfaceQuery's layout with the stacking axis where its faces stand; flags BOXES_ANY_PALETTE
+    _fields_ = [("struct_size", C.c_uint32), ("axis", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class Box(C.Structure):  # DustHipBox, 8 bytes: the key of the box's lowest corner voxel, its palette index and its extents - 1 along x, y, z
+    _fields_ = [("key", C.c_uint32), ("palette", C.c_uint8), ("dx", C.c_uint8), ("dy", C.c_uint8), ("dz", C.c_uint8)]
+
+
+class BoxesResult(C.Structure):  # DustHipBoxesResult, 64 bytes: boxes, the rects of all slices, the voxels they hold, their bounds
+    _fields_ = [("boxes", C.c_uint32), ("rects", C.c_uint32), ("voxels", C.c_uint32), ("lo", C.c_uint8 * 3), ("pad0", C.c_uint8),
+                ("hi", C.c_uint8 * 3), ("pad1", C.c_uint8), ("reserved", C.c_uint32 * 11)]
+
+
+BOXES_ANY_PALETTE = 1
+
+
 class DeltaQuery(C.Structure):  # DustHipDeltaQuery, 48 bytes: a SurfaceQuery's layout with the kinds that count where its faces stand
     _fields_ = [("struct_size", C.c_uint32), ("kinds", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
                 ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
@@ -516,6 +533,7 @@ SYMBOLS = {
     "dust_hip_model_surface": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_surface_apply": (C.c_int, [_P, _P, C.c_int32, _u32p]),
     "dust_hip_model_mesh": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    "dust_hip_model_boxes": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
     "dust_hip_model_delta": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P]),
     "dust_hip_model_delta_apply": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     "dust_hip_model_columns": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),

@@ -62,6 +62,10 @@ SURFACE_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("faces", "u1"), ("palette", "u1
 # DustHipMeshResult (64 bytes) and DustHipMeshQuad (8 bytes): the result and the list entries of dust_hip_model_mesh
 MESH_RESULT_DTYPE = np.dtype([("quads", "<u4"), ("faces", "<u4"), ("quads_by_face", "<u4", 6), ("faces_by_face", "<u4", 6), ("largest", "<u4"), ("reserved", "<u4")])
 MESH_QUAD_DTYPE = np.dtype([("key", "<u4"), ("face", "u1"), ("palette", "u1"), ("du", "u1"), ("dv", "u1")])
+# DustHipBoxesResult (64 bytes) and DustHipBox (8 bytes): the result and the list entries of dust_hip_model_boxes
+BOXES_RESULT_DTYPE = np.dtype([("boxes", "<u4"), ("rects", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("pad0", "u1"), ("hi", "u1", 3), ("pad1", "u1"),
+                               ("reserved", "<u4", 11)])
+BOX_DTYPE = np.dtype([("key", "<u4"), ("palette", "u1"), ("dx", "u1"), ("dy", "u1"), ("dz", "u1")])
 # DustHipDeltaResult (64 bytes) and DustHipDeltaVoxel (8 bytes): the result and the list entries of dust_hip_model_delta, and the
 # records dust_hip_model_delta_apply takes
 DELTA_RESULT_DTYPE = np.dtype([("voxels", "<u4"), ("added", "<u4"), ("removed", "<u4"), ("repainted", "<u4"), ("solid_before", "<u4"), ("solid_after", "<u4"),
@@ -503,6 +507,28 @@ class Model:
         quads = np.zeros(int(capacity), MESH_QUAD_DTYPE)
         L.check(self._lib.dust_hip_model_mesh(self._h, C.byref(q), _ptr(out), _ptr(quads) if capacity else None, int(capacity)))
         return out[0], quads[: min(int(capacity), int(out[0]["quads"]))]
+
+    def boxes(self, axis=0, palette=-1, region=None, any_palette=False, capacity=None):
+        """The model's solid voxels merged into axis-aligned boxes (dust_hip_model_boxes): the convex pieces of a compound collider, an
+        exact snapshot, a replayable description. `palette` and `region` select the voxels as in Model.surface (nothing outside the
+        region exists for the call). Per slice of `axis` (0 x, 1 y, 2 z) a run is a maximal stretch of voxels of one palette index
+        along u, a rect a maximal stack of identical runs along v (Model.mesh's axes), and a box a maximal stack of identical rects
+        along `axis`; any_palette=True merges across palette indices. A canonical partition, not the minimum-count decomposition.
+        Returns (result, boxes): result a BOXES_RESULT_DTYPE record (boxes, rects, voxels, lo, hi); boxes a BOX_DTYPE array (key
+        x << 16 | y << 8 | z of the lowest corner voxel, palette, dx, dy, dz the extents minus 1) of the first min(result.boxes,
+        capacity) boxes in ascending (slice, v0, u0) -- capacity=None makes two calls, one to count and one to list everything.
+        box_shapes turns the records into Model.edit_shapes records, box_bounds into inclusive bounds. The model is only read."""
+        q = L.BoxesQuery(struct_size=C.sizeof(L.BoxesQuery), axis=int(axis), palette=palette, flags=L.BOXES_ANY_PALETTE if any_palette else 0)
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        out = np.zeros(1, BOXES_RESULT_DTYPE)
+        if capacity is None:
+            L.check(self._lib.dust_hip_model_boxes(self._h, C.byref(q), _ptr(out), None, 0))
+            capacity = int(out[0]["boxes"])
+        boxes = np.zeros(int(capacity), BOX_DTYPE)
+        L.check(self._lib.dust_hip_model_boxes(self._h, C.byref(q), _ptr(out), _ptr(boxes) if capacity else None, int(capacity)))
+        return out[0], boxes[: min(int(capacity), int(out[0]["boxes"]))]
 
     def delta(self, after, kinds=L.DELTA_ALL, palette=-1, region=None, capacity=None, tables=False):
         """The voxels in which `after` differs from this model at the same tree coordinates (dust_hip_model_delta). `kinds` the
@@ -1244,6 +1270,25 @@ def mesh_corners(quads):
     normals = np.zeros((n_quads, 3), np.int8)
     normals[rows, axis] = np.where(face & 1, 1, -1)
     return corners, normals
+
+
+def box_bounds(boxes):
+    """Host only: the inclusive voxel bounds of Model.boxes' records -> (lo, hi) int32 (N, 3)."""
+    boxes = np.asarray(boxes, BOX_DTYPE).reshape(-1)
+    key = boxes["key"].astype(np.int32)
+    lo = np.stack([key >> 16, (key >> 8) & 255, key & 255], axis=1).astype(np.int32)
+    hi = lo + np.stack([boxes["dx"], boxes["dy"], boxes["dz"]], axis=1).astype(np.int32)
+    return lo, hi
+
+
+def box_shapes(boxes, op=L.EDIT_PLACE, palette=None):
+    """Host only: Model.boxes' records as EDIT_SHAPE_DTYPE BOX records for Model.edit_shapes: a the lowest corner, b the lowest corner
+    plus the extents, so that the centres of exactly the box's voxels lie inside; palette the record's own unless one is given.
+    Placing a model's boxes into an empty model of the same palette gives the model's voxels back. A call takes at most
+    L.MAX_EDIT_SHAPES shapes: callers chunk."""
+    boxes = np.asarray(boxes, BOX_DTYPE).reshape(-1)
+    lo, hi = box_bounds(boxes)
+    return edit_shapes(L.SHAPE_BOX, lo, hi + 1, op=op, palette=boxes["palette"].astype(np.int32) if palette is None else palette)
 
 
 def top_level_build(boxes):

@@ -179,6 +179,9 @@ struct DustHipContext : RefCounted {
   // model voxelisation (triangle.hip): the inside bit of every voxel of a dust_hip_model_fill_mesh call, in EditArgs::brick_mask's
   // layout (2 MiB, allocated by the first such call; zeroed by every call)
   DeviceBuffer fill_volume;
+  // model boxes (boxes.hip): a bit plane per slice of a dust_hip_model_boxes call's stacking axis -- the rects that continue the slice
+  // before (2 MiB, allocated by the first such call). Every call writes the planes of the slices it reads: nothing is cached across calls
+  DeviceBuffer boxes_volume;
 };
 // wait for everything enqueued on the context's streams (and remember that we did: scene commits recycle their pinned staging
 // slots by this, without an event per commit)

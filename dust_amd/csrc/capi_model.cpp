@@ -1,6 +1,6 @@
 // capi_model.cpp -- the model handle of the C ABI (include/dust_hip.h): the upload of the device hierarchy, device-side voxel and shape
 // edits (edit.hip), model stamps (stamp.hip), model casts (cast.hip), model islands (island.hip), model floods (flood.hip), model
-// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip), model surfaces (surface.hip), model meshes (mesh.hip), model deltas
+// distances (distance.hip), model reductions (reduce.hip), model censuses (census.hip), model surfaces (surface.hip), model meshes (mesh.hip), model boxes (boxes.hip), model deltas
 // (delta.hip), model columns (column.hip) and model fracture (fracture.hip). What needs no device is in three headers: the hierarchy build itself
 // (root, l2, mid, dense_mask, the per-cell table, bounds) in hierarchy.hpp, the arithmetic on the callers' records (conversion, chunks,
 // cell lists, cast hits, census records, surface, mesh, delta and columns queries, a delta_apply's records) in model_records.hpp, a reduction's vote and the plan of its levels in reduce_rule.hpp.
@@ -1409,6 +1409,62 @@ DustStatus dust_hip_model_mesh(const DustHipModel* m, const DustHipMeshQuery* q,
       }
     }
     if (result) *result = dust::mesh_result(empty ? nullptr : acc);
+    return DUST_OK;
+  });
+}
+
+// ---- model boxes (boxes.hip): the solid voxels merged into boxes under boxes_rule.hpp's rule, counted (k_boxes_count, which also leaves
+// every slice's D plane in the context's D volume) and listed (k_boxes_list) without writing anything to the model. Reads the model
+// as dust_hip_model_mesh does; the per-slice table is the surface list's.
+DustStatus dust_hip_model_boxes(const DustHipModel* m, const DustHipBoxesQuery* q, DustHipBoxesResult* result, DustHipBox* boxes, uint32_t capacity) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);  // (before the query is looked at)
+  if (s != DUST_OK) return s;
+  if (!q) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipBoxesQuery");
+  dust::BoxesArgs a{};
+  bool empty = false;
+  if (const char* why = dust::device_boxes(*q, a, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  if (capacity && !boxes) return fail(DUST_ERR_INVALID_ARGUMENT, "null boxes with capacity > 0");
+  return guarded([&]() -> DustStatus {
+    uint32_t acc[dust::kBoxesAccWords] = {};
+    if (!empty) {
+      DustHipContext* ctx = m->ctx;
+      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_TRY(join_side(ctx));
+      hipStream_t st = ctx->stream;
+      if ((s = cast_source_masks(ctx, m, &a.brick_mask)) != DUST_OK) return s;
+      // the grid only where a byte is needed: for the count pass under a filter or where runs stop at a change of material, for the
+      // list pass (a record's palette) once it is known that something is listed
+      if ((a.byte != 0u || !a.any_palette) && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, dust::kBoxesAccWords * 4)) != DUST_OK) return s;
+      if ((s = lazy_alloc(ctx->boxes_volume, dust::kBoxesVolumeWords * 4, "the boxes' D volume (2 MiB)")) != DUST_OK) return s;
+      const size_t L = dust::kLattice;
+      static_assert(dust::kBoxesSlices <= 1024u && dust::kBoxesSlices <= dust::kLattice, "the boxes list fits the first block of the surface list's table");
+      if (capacity && (s = lazy_alloc(ctx->surface_table, (L + dust::kSurfaceScanWords) * 4, "the surface, mesh and boxes lists' table (1 MiB)")) != DUST_OK) return s;
+      a.acc = static_cast<uint32_t*>(ctx->stage_out.p);
+      a.dvol = static_cast<uint32_t*>(ctx->boxes_volume.p);
+      a.slice_count = capacity ? static_cast<uint32_t*>(ctx->surface_table.p) : nullptr;
+      HIP_TRY(hipMemsetAsync(a.acc, 0, dust::kBoxesAccWords * 4, st));
+      if (capacity) HIP_TRY(hipMemsetAsync(a.slice_count, 0, L * 4, st));
+      HIP_TRY(dust::launch_boxes_count(a, st));
+      HIP_TRY(hipMemcpyAsync(acc, a.acc, sizeof(acc), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      const uint32_t staged = std::min(dust::boxes_result(acc).boxes, capacity);
+      if (staged) {
+        if (!a.grid && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+        if ((s = grow(ctx, ctx->stage_aux, size_t(staged) * sizeof(DustHipBox))) != DUST_OK) return s;
+        uint32_t* scan_tmp = a.slice_count + L;  // 256 block sums, then the total (the boxes again)
+        HIP_TRY(dust::launch_table_scan(dust::TableScan{{a.slice_count, nullptr}, {scan_tmp + 256, nullptr}, scan_tmp}, 1, st));
+        a.scan_tmp = scan_tmp;
+        a.boxes = static_cast<uint64_t*>(ctx->stage_aux.p);
+        a.capacity = staged;
+        HIP_TRY(dust::launch_boxes_list(a, st));
+        HIP_TRY(hipMemcpyAsync(boxes, a.boxes, size_t(staged) * sizeof(DustHipBox), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+    }
+    if (result) *result = dust::boxes_result(empty ? nullptr : acc);
     return DUST_OK;
   });
 }

@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp, resample.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, boxes.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp, resample.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp, tests/cpp/fracture_rule_test.cpp and tests/cpp/resample_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/boxes_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp, tests/cpp/fracture_rule_test.cpp and tests/cpp/resample_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/dust_hip.h"
+#include "boxes.hpp"
 #include "cast.hpp"
 #include "census.hpp"
 #include "column.hpp"
@@ -31,6 +32,7 @@ static_assert(sizeof(DustHipSurfaceQuery) == 48 && sizeof(DustHipSurfaceResult) 
 static_assert(sizeof(DustHipMeshQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipMeshResult) == 64 && sizeof(DustHipMeshQuad) == 8 &&
                   DUST_HIP_MESH_WALLS == DUST_HIP_SURFACE_WALLS,
               "mesh records");
+static_assert(sizeof(DustHipBoxesQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipBoxesResult) == 64 && sizeof(DustHipBox) == 8, "boxes records");
 static_assert(sizeof(DustHipDeltaQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipDeltaResult) == 64 && sizeof(DustHipDeltaVoxel) == 8 &&
                   kDeltaBins == DUST_HIP_DELTA_BINS && kDeltaMaxRecords == DUST_HIP_MAX_DELTA_RECORDS && kDeltaAdded == DUST_HIP_DELTA_ADDED &&
                   kDeltaRemoved == DUST_HIP_DELTA_REMOVED && kDeltaRepainted == DUST_HIP_DELTA_REPAINTED,
@@ -357,6 +359,37 @@ inline DustHipMeshResult mesh_result(const uint32_t* acc) {
     r.faces_by_face[d] = acc[6 + d]; r.faces += acc[6 + d];
   }
   r.largest = acc[12];
+  return r;
+}
+
+// A boxes query as the kernels read it (dust_hip_model_boxes): the stacking axis, the filter's grid byte and the region clipped to the
+// tree. nullptr: the query is fine; otherwise why the call refuses it, in the header's order. `empty` as in device_surface: nothing is
+// looked at and no launch is made -- lo and hi are not set.
+inline const char* device_boxes(const DustHipBoxesQuery& q, BoxesArgs& d, bool& empty) {
+  if (q.axis > 2u) return "axis must be 0..2";
+  if ((q.flags & ~DUST_HIP_BOXES_ANY_PALETTE) != 0u) return "unknown boxes flag";
+  if (q.palette < -1 || q.palette > 254) return "palette must be -1 (every solid voxel) or 0..254";
+  for (int r = 0; r < 3; ++r)
+    if (q.lo[r] >= 256u || q.hi[r] >= 256u) return "region coordinate outside the tree extent";
+  d.axis = q.axis;
+  d.byte = q.palette < 0 ? 0u : uint32_t(q.palette) + 1u;
+  d.any_palette = (q.flags & DUST_HIP_BOXES_ANY_PALETTE) ? 1u : 0u;
+  empty = false;
+  for (int r = 0; r < 3; ++r) empty |= q.lo[r] > q.hi[r];
+  if (empty) return nullptr;
+  for (int r = 0; r < 3; ++r) { d.lo[r] = q.lo[r]; d.hi[r] = q.hi[r]; }
+  return nullptr;
+}
+// What a boxes call's caller gets from the device's kBoxesAccWords accumulator; null: nothing was looked at -- the zero result, bounds
+// 255 / 0 (what a region without a solid voxel has too).
+inline DustHipBoxesResult boxes_result(const uint32_t* acc) {
+  DustHipBoxesResult r{};
+  for (int k = 0; k < 3; ++k) r.lo[k] = 255;
+  if (!acc) return r;
+  r.boxes = acc[0] - acc[1];
+  r.rects = acc[0];
+  r.voxels = acc[2];
+  for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[3 + k]); r.hi[k] = uint8_t(acc[6 + k]); }
   return r;
 }
 

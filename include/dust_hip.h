@@ -783,6 +783,69 @@ typedef struct DustHipMeshResult {     /* 64 bytes */
 } DustHipMeshResult;
 DustStatus dust_hip_model_mesh(const DustHipModel*, const DustHipMeshQuery*, DustHipMeshResult* result /* may be NULL */,
                                DustHipMeshQuad* quads /* capacity; may be NULL when capacity == 0 */, uint32_t capacity);
+/* Model boxes: a solid as a short list of axis-aligned boxes -- the convex pieces of a compound collider for a rigid-body solver (a
+ * detached island, a fractured piece), the smallest exact snapshot of a model the library hands out, a replayable description (every
+ * box is a DUST_HIP_SHAPE_BOX record of dust_hip_model_edit_shapes), and the volume counterpart of dust_hip_model_mesh for editors and
+ * exports. dust_hip_model_boxes merges the solid voxels under one canonical rule: the output is a function of the model and the
+ * query alone, two runs or two implementations give the same bytes.
+ *
+ * Query: DustHipSurfaceQuery's layout with `axis` where `faces` stands: the stacking axis n (0 x, 1 y, 2 z), the last one merged.
+ * Set S: the voxels that are solid, lie inside the clipped inclusive region and pass the palette filter (palette -1: every solid
+ * voxel; 0..254: only voxels of that palette index) -- what dust_hip_model_surface counts in `solid` for the same palette and region.
+ * Nothing outside the region exists for the call: runs, rects and boxes are cut at the region's faces.
+ * Axes: dust_hip_model_mesh's. n = x: u = z, v = y; n = y: u = z, v = x; n = z: u = y, v = x. A slice is one value of the n
+ * coordinate, a row one value of v within a slice.
+ * Run: a maximal set of consecutive u in one row whose voxels are all in S and all hold the same palette index (under
+ * DUST_HIP_BOXES_ANY_PALETTE the palette condition is dropped).
+ * Rect: a maximal set of consecutive rows v0..v1 of one slice that each contain the identical run: the same u0, the same u1 and the
+ * same palette index (unless ANY_PALETTE) -- dust_hip_model_mesh's quad over S instead of the exposed faces.
+ * Box: a maximal set of consecutive slices s0..s1 that each contain the identical rect: the same u0, u1, v0, v1 and palette index
+ * (unless ANY_PALETTE). Slices s0 - 1 and s1 + 1 do not contain that rect; a larger or smaller rect at the same corner does not
+ * merge. The boxes partition S. This is NOT the minimum-count decomposition: in exchange the answer depends on no processing order.
+ * Record: key is x << 16 | y << 8 | z of the box's lowest corner voxel; palette 0..254, under ANY_PALETTE that of the key voxel; dx,
+ * dy, dz the extents along the world axes minus 1 (extents run 1..256). The device writes a record as one 64-bit word.
+ * Order and capacity: the boxes come in ascending (s0, v0, u0); for axis 0 that is ascending key. The first min(result.boxes,
+ * capacity) records are written; the slots past them are left untouched. result.boxes is the full count whatever the capacity;
+ * capacity 0 counts only.
+ * Result: boxes; rects, the rects of all slices (the boxes there would be without stacking); voxels, |S|, which equals the sum of the
+ * boxes' volumes; lo / hi, the inclusive bounds of S (255, 255, 255 / 0, 0, 0 when S is empty); the pad and reserved words are 0.
+ * There is no "largest volume": a count-only call needs the depth of no box and stays one launch.
+ * lo > hi on an axis is legal and gives the zero result (bounds 255 / 0).
+ * The model is only read, with dust_hip_model_surface's guarantees: one that is not editable stays not editable (its blocks' masks
+ * are scattered into the context's 2 MiB scratch, and it is expanded into the 16 MiB scratch grid only when a byte is needed: a
+ * palette filter, runs that stop at a change of material, a list); the generation does not move; the island labelling and all
+ * fields stand.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, every output untouched: a null model or query; a struct_size below the struct's size; an
+ * axis above 2; a flag bit other than DUST_HIP_BOXES_ANY_PALETTE; a palette below -1 or above 254; a region coordinate >= 256; null
+ * boxes with capacity > 0. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material byte
+ * 255), before the query is looked at. The call is synchronous, like every model call. Everything is integer arithmetic: two runs
+ * give the same bytes.
+ * Out of scope: the minimum-count decomposition; boxes across materials other than by ANY_PALETTE; convex pieces other than boxes;
+ * 4096^3 trees; an asynchronous form; boxes across the instances of a scene. */
+#define DUST_HIP_BOXES_ANY_PALETTE 1u  /* flags: runs, rects and boxes merge across palette indices */
+typedef struct DustHipBoxesQuery {     /* 48 bytes, DustHipSurfaceQuery's layout with `axis` where `faces` stands */
+  uint32_t struct_size;
+  uint32_t axis;                 /* 0..2: the stacking axis n, the last one merged */
+  uint32_t flags;                /* DUST_HIP_BOXES_ANY_PALETTE or 0 */
+  int32_t palette;               /* -1: every solid voxel; 0..254: only voxels of this palette index */
+  uint32_t lo[3], hi[3];         /* inclusive region, clipped to the tree */
+  uint32_t reserved[2];          /* 0 */
+} DustHipBoxesQuery;
+typedef struct DustHipBox {            /* 8 bytes */
+  uint32_t key;                  /* x << 16 | y << 8 | z of the box's lowest corner voxel */
+  uint8_t palette;               /* 0..254; under ANY_PALETTE that of the key voxel */
+  uint8_t dx, dy, dz;            /* extents along x, y, z minus 1 */
+} DustHipBox;
+typedef struct DustHipBoxesResult {    /* 64 bytes */
+  uint32_t boxes;                /* number of boxes */
+  uint32_t rects;                /* rects of all slices: the boxes there would be without stacking */
+  uint32_t voxels;               /* |S|: the sum of the boxes' volumes */
+  uint8_t lo[3], pad0;           /* inclusive bounds of S; 255,255,255 when S is empty */
+  uint8_t hi[3], pad1;           /* 0,0,0 when S is empty; pad bytes 0 */
+  uint32_t reserved[11];         /* 0 */
+} DustHipBoxesResult;
+DustStatus dust_hip_model_boxes(const DustHipModel*, const DustHipBoxesQuery*, DustHipBoxesResult* result /* may be NULL */,
+                                DustHipBox* boxes /* capacity; may be NULL when capacity == 0 */, uint32_t capacity);
 /* Model deltas: what changed between two states of a model, as a list -- an edit replicated to clients without sending the model, an
  * undo / redo stack, an incremental save, the voxels a blast removed as particles of the right materials -- and the list handed back:
  * dust_hip_model_delta_apply plays it onto a model in either direction and says how many voxels were not in the state it assumes.

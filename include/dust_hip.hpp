@@ -328,6 +328,18 @@ class VoxGeometry {
     if (result) *result = r;
     return quads;
   }
+  // Model boxes (dust_hip_model_boxes): the solid voxels inside the query's region merged into axis-aligned boxes under the header's
+  // canonical rule (not the minimum-count decomposition) -- every box, in ascending (slice, v0, u0) of query.axis: two calls, one to
+  // count. Only reads.
+  std::vector<DustHipBox> boxes(DustHipBoxesQuery query, DustHipBoxesResult* result = nullptr) const {
+    query.struct_size = sizeof(query);
+    DustHipBoxesResult r{};
+    check(dust_hip_model_boxes(h_, &query, &r, nullptr, 0));
+    std::vector<DustHipBox> boxes(r.boxes);
+    check(dust_hip_model_boxes(h_, &query, &r, boxes.data(), uint32_t(boxes.size())));
+    if (result) *result = r;
+    return boxes;
+  }
   // Model deltas (dust_hip_model_delta / delta_apply): the voxels in which `after` differs from this geometry, of the kinds among
   // query.kinds inside the query's region -- counted into the result, listed (every one of them, in the order of the blocks: two calls,
   // one to count), and per value before and after into `counts` (2 * DUST_HIP_DELTA_BINS), if given. Only reads both. delta_apply plays
