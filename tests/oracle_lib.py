@@ -287,6 +287,13 @@ class GI:
     def pool(self):
         return np.frombuffer(C.string_at(self.l.orc_gi_pool_ptr(self.h), self.pool_size * 16), SURFEL_DTYPE).copy()
 
+    def write(self, hash, pool):
+        """the whole state from arrays as hash() and pool() return them (or the hash as uint32[capacity + 2, 3])"""
+        h, p = np.ascontiguousarray(hash), np.ascontiguousarray(pool, SURFEL_DTYPE)
+        assert h.nbytes == (self.capacity + 2) * 12 and p.nbytes == self.pool_size * 16, (h.nbytes, p.nbytes)
+        C.memmove(self.l.orc_gi_hash_ptr(self.h), h.ctypes.data, h.nbytes)
+        C.memmove(self.l.orc_gi_pool_ptr(self.h), p.ctypes.data, p.nbytes)
+
     def insert(self, pos, direction, value, frame):
         self.l.orc_hash_insert(self.h, (C.c_int32 * 3)(*pos), direction, f3(value), frame)
 
