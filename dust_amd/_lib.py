@@ -451,6 +451,20 @@ NO_CELL = 0xFFFF
 FRACTURE_SEAMS, FRACTURE_LABELLED = 0, 1
 
 
+class BodyQuery(C.Structure):  # DustHipBodyQuery, 48 bytes: a SurfaceQuery's layout with the kind of group where its faces stand
+    _fields_ = [("struct_size", C.c_uint32), ("group", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class Body(C.Structure):  # DustHipBody, 96 bytes: a group's key, counted voxels and bounds; the sums of w, of w x, y, z and of w xx, yy, zz, xy, yz, zx
+    _fields_ = [("key", C.c_uint32), ("voxels", C.c_uint32), ("lo", C.c_uint8 * 3), ("reserved0", C.c_uint8), ("hi", C.c_uint8 * 3),
+                ("reserved1", C.c_uint8), ("mass", C.c_uint64), ("m1", C.c_uint64 * 3), ("m2", C.c_uint64 * 6)]
+
+
+BODIES_ALL, BODIES_MATERIALS, BODIES_ISLANDS, BODIES_CELLS = 0, 1, 2, 3
+BODY_WEIGHTS = 255
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -548,6 +562,7 @@ SYMBOLS = {
     "dust_hip_model_fracture_at": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "dust_hip_model_fracture_detach": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "dust_hip_model_fracture_apply": (C.c_int, [_P, C.c_uint32, C.c_int32, _u32p]),
+    "dust_hip_model_bodies": (C.c_int, [_P, _P, _P, _u32p, _P, C.c_uint32]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

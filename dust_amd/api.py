@@ -102,6 +102,9 @@ FRACTURE_CELL_DTYPE = np.dtype([("voxels", "<u4"), ("cut_faces", "<u4"), ("lo", 
 # DustHipMidNode and DustHipL2Cell, 16 bytes each: the records of dust_hip_model_read_hierarchy
 MID_NODE_DTYPE = np.dtype([("mask_lo", "<u4"), ("mask_hi", "<u4"), ("first_block", "<u4"), ("pad", "<u4")])
 L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8")])
+# DustHipBody (96 bytes): one group of dust_hip_model_bodies -- key, counted voxels, bounds, mass, first and second moments
+BODY_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("reserved0", "u1"), ("hi", "u1", 3), ("reserved1", "u1"), ("mass", "<u8"),
+                       ("m1", "<u8", 3), ("m2", "<u8", 6)])
 ISLAND_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("flags", "u1"), ("hi", "u1", 3), ("reserved", "u1"), ("sum", "<u8", 3)])
 FLT_MAX = float(np.finfo(np.float32).max)
 
@@ -885,6 +888,33 @@ class Model:
         L.check(self._lib.dust_hip_model_fracture_apply(self._h, int(where), int(value), C.byref(changed)))
         return changed.value
 
+    def bodies(self, group=L.BODIES_ALL, weights=None, palette=-1, region=None, capacity=None):
+        """Mass, first and second moments per group of voxels (dust_hip_model_bodies): what a rigid-body solver needs of a piece.
+        `group` L.BODIES_ALL (one record, key 0), L.BODIES_MATERIALS (255 records, key the palette index), L.BODIES_ISLANDS (one per
+        island of the standing find_islands labelling, ascending keys) or L.BODIES_CELLS (one per seed of the standing fracture).
+        `weights` 255 integers 0..65535 by palette index, None: every voxel weighs 1. `palette` and `region` select the voxels as in
+        Model.surface. Returns a BODY_DTYPE array (key, voxels, lo, hi, mass, m1 = sums of w x, w y, w z, m2 = sums of w xx, w yy,
+        w zz, w xy, w yz, w zx over integer voxel coordinates) of the first min(groups, capacity) groups -- capacity=None makes two
+        calls, one to count. body_properties turns the records into mass, centre of mass and inertia tensor. The model is only read."""
+        q = L.BodyQuery(struct_size=C.sizeof(L.BodyQuery), group=int(group), palette=int(palette))
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        w = None
+        if weights is not None:
+            wide = np.asarray(weights).reshape(-1)
+            if wide.shape != (L.BODY_WEIGHTS,) or wide.min() < 0 or wide.max() > 65535:
+                raise ValueError("weights must be 255 integers in 0..65535")
+            w = np.ascontiguousarray(wide, dtype=np.uint16)
+        n = C.c_uint32()
+        if capacity is None:
+            L.check(self._lib.dust_hip_model_bodies(self._h, C.byref(q), _ptr(w) if w is not None else None, C.byref(n), None, 0))
+            capacity = n.value
+        records = np.zeros(int(capacity), BODY_DTYPE)
+        L.check(self._lib.dust_hip_model_bodies(self._h, C.byref(q), _ptr(w) if w is not None else None, C.byref(n),
+                                                _ptr(records) if capacity else None, int(capacity)))
+        return records[: min(int(capacity), n.value)]
+
     def distance(self, target=L.DISTANCE_TO_SOLID, metric=L.DISTANCE_EUCLIDEAN, max_radius=L.DISTANCE_MAX_RADIUS, walls=False, palette=0):
         """The exact distance from every voxel to the nearest target (dust_hip_model_distance): target L.DISTANCE_TO_SOLID (the solid
         voxels), L.DISTANCE_TO_EMPTY (the voxels holding None) or L.DISTANCE_TO_MATERIAL (the solid voxels of palette index `palette`);
@@ -1270,6 +1300,34 @@ def mesh_corners(quads):
     normals = np.zeros((n_quads, 3), np.int8)
     normals[rows, axis] = np.where(face & 1, 1, -1)
     return corners, normals
+
+
+def body_properties(records, voxel_size=1.0):
+    """Host only: Model.bodies' records -> (mass, com, inertia): mass (n,) the sum of the weights; com (n, 3) the centre of mass,
+    (m1 / mass + 0.5) * voxel_size; inertia (n, 3, 3) the tensor about the centre of mass with every voxel a solid cube of side
+    voxel_size: C_ab = m2_ab - m1_a m1_b / mass, I_xx = (C_yy + C_zz + mass / 6) * voxel_size^2, I_xy = -C_xy * voxel_size^2. Computed
+    in exact rational arithmetic and rounded once to float64. A record of mass 0 gives zeros."""
+    from fractions import Fraction
+    records = np.asarray(records, BODY_DTYPE).reshape(-1)
+    n = len(records)
+    mass, com, inertia = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3, 3))
+    size = Fraction(voxel_size)
+    pairs = {(0, 0): 0, (1, 1): 1, (2, 2): 2, (0, 1): 3, (1, 2): 4, (0, 2): 5}   # m2's order: xx, yy, zz, xy, yz, zx
+    for i, r in enumerate(records):
+        m = int(r["mass"])
+        if m == 0:
+            continue
+        m1 = [int(v) for v in r["m1"]]
+        m2 = [int(v) for v in r["m2"]]
+        c = {ab: Fraction(m2[k]) - Fraction(m1[ab[0]] * m1[ab[1]], m) for ab, k in pairs.items()}
+        mass[i] = float(m)
+        for a in range(3):
+            com[i, a] = float((Fraction(m1[a], m) + Fraction(1, 2)) * size)
+            others = [b for b in range(3) if b != a]
+            inertia[i, a, a] = float((c[(others[0], others[0])] + c[(others[1], others[1])] + Fraction(m, 6)) * size * size)
+        for a, b in ((0, 1), (1, 2), (0, 2)):
+            inertia[i, a, b] = inertia[i, b, a] = float(-c[(a, b)] * size * size)
+    return mass, com, inertia
 
 
 def box_bounds(boxes):

@@ -1107,6 +1107,80 @@ DustStatus dust_hip_model_fracture_apply(DustHipModel* m, uint32_t where, int32_
   });
 }
 
+// ---- model bodies (body.hip): mass, first and second moments per group of voxels -- the whole model, a palette index, an island of the
+// standing labelling, a cell of the standing fracture. Nothing is written but the context's scratch; no rebuild
+DustStatus dust_hip_model_bodies(const DustHipModel* m, const DustHipBodyQuery* q, const uint16_t* weights, uint32_t* n_bodies, DustHipBody* bodies,
+                                 uint32_t capacity) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);  // (before the query is looked at)
+  if (s != DUST_OK) return s;
+  if (!q || !n_bodies) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipBodyQuery");
+  dust::BodyArgs a{};
+  bool empty = false;
+  if (const char* why = dust::device_bodies(*q, a, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  if (capacity && !bodies) return fail(DUST_ERR_INVALID_ARGUMENT, "null bodies with capacity > 0");
+  // (a model that is not editable holds neither a labelling nor a cell field)
+  if (a.group == dust::kBodiesIslands && (!m->edit || !m->edit->labels_valid)) return no_labelling();
+  if (a.group == dust::kBodiesCells && (!m->edit || !m->edit->fracture.valid)) return no_cells();
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));
+    hipStream_t st = ctx->stream;
+    uint32_t total = 1;
+    if (a.group == dust::kBodiesMaterials) total = dust::kBodyMaterials;
+    if (a.group == dust::kBodiesCells) total = m->edit->fracture_seeds;
+    if (a.group == dust::kBodiesIslands) {
+      // the roots, their counts and the scan are the context's, shared by its models: found again, as a repeated find_islands does
+      EditState& es = *m->edit;
+      if ((s = grow(ctx, ctx->island_mask, size_t(dust::kIslandRows) * 8)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->island_count, size_t(dust::kIslandRows) * 4)) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->island_tmp, 260 * 4)) != DUST_OK) return s;
+      dust::IslandArgs ia{};
+      ia.grid = static_cast<const uint8_t*>(es.grid.p);
+      ia.label = static_cast<uint32_t*>(es.labels.p);  // flat already: the pass writes no word of it
+      ia.root_mask = static_cast<uint64_t*>(ctx->island_mask.p);
+      ia.root_count = static_cast<uint32_t*>(ctx->island_count.p);
+      ia.scan_tmp = static_cast<uint32_t*>(ctx->island_tmp.p);
+      ia.corners = es.labels_corners;
+      HIP_TRY(dust::launch_island_label(ia, false, st));
+      HIP_TRY(hipMemcpyAsync(&total, ia.scan_tmp + 256, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      a.label = ia.label;
+      a.root_mask = ia.root_mask;
+      a.root_count = ia.root_count;
+      a.scan_tmp = ia.scan_tmp;
+    }
+    a.capacity = std::min(total, capacity);
+    if (a.capacity) {
+      if (!empty) {
+        if ((s = cast_source_masks(ctx, m, &a.brick_mask)) != DUST_OK) return s;
+        // the grid only where a material is needed
+        if ((weights || a.byte != 0u || a.group == dust::kBodiesMaterials) && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+        if (a.group == dust::kBodiesCells) a.field = static_cast<const uint16_t*>(m->edit->fracture.values.p);
+        if (weights) {
+          if ((s = grow(ctx, ctx->stage_in, dust::kBodyMaterials * sizeof(uint16_t))) != DUST_OK) return s;
+          HIP_TRY(hipMemcpyAsync(ctx->stage_in.p, weights, dust::kBodyMaterials * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+          a.weights = static_cast<const uint16_t*>(ctx->stage_in.p);
+        }
+      }
+      if ((s = grow(ctx, ctx->stage_aux, size_t(a.capacity) * sizeof(dust::BodyAcc))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, size_t(a.capacity) * sizeof(dust::BodyRecord))) != DUST_OK) return s;
+      a.acc = static_cast<dust::BodyAcc*>(ctx->stage_aux.p);
+      a.records = static_cast<dust::BodyRecord*>(ctx->stage_out.p);
+      HIP_TRY(hipMemsetAsync(a.acc, 0, size_t(a.capacity) * sizeof(dust::BodyAcc), st));
+      if (a.group == dust::kBodiesIslands) HIP_TRY(dust::launch_body_keys(a, st));
+      if (!empty) HIP_TRY(dust::launch_bodies(a, st));
+      HIP_TRY(dust::launch_bodies_emit(a, st));
+      HIP_TRY(hipMemcpyAsync(bodies, a.records, size_t(a.capacity) * sizeof(dust::BodyRecord), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));  // (the weights have left the caller's array)
+    }
+    *n_bodies = total;
+    return DUST_OK;
+  });
+}
+
 // ---- model distances (distance.hip): the exact distance from every voxel to the nearest target voxel, kept on the device with the model
 static_assert(sizeof(DustHipDistanceQuery) == 32 && sizeof(DustHipDistanceResult) == 32 && sizeof(dust::DistanceAcc) == 16, "distance records");
 DustStatus dust_hip_model_distance(DustHipModel* m, const DustHipDistanceQuery* q, DustHipDistanceResult* out) {

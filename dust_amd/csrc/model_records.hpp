@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, boxes.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp, resample.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, boxes.hpp, body.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp, resample.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/boxes_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp, tests/cpp/fracture_rule_test.cpp and tests/cpp/resample_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/boxes_rule_test.cpp, tests/cpp/body_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp, tests/cpp/fracture_rule_test.cpp and tests/cpp/resample_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/dust_hip.h"
+#include "body.hpp"
 #include "boxes.hpp"
 #include "cast.hpp"
 #include "census.hpp"
@@ -33,6 +34,11 @@ static_assert(sizeof(DustHipMeshQuery) == sizeof(DustHipSurfaceQuery) && sizeof(
                   DUST_HIP_MESH_WALLS == DUST_HIP_SURFACE_WALLS,
               "mesh records");
 static_assert(sizeof(DustHipBoxesQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipBoxesResult) == 64 && sizeof(DustHipBox) == 8, "boxes records");
+static_assert(sizeof(DustHipBodyQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipBody) == 96 && sizeof(DustHipBody) == sizeof(BodyRecord) &&
+                  offsetof(DustHipBody, mass) == offsetof(BodyRecord, mass) && offsetof(DustHipBody, m2) == offsetof(BodyRecord, m2) &&
+                  kBodiesAll == DUST_HIP_BODIES_ALL && kBodiesMaterials == DUST_HIP_BODIES_MATERIALS && kBodiesIslands == DUST_HIP_BODIES_ISLANDS &&
+                  kBodiesCells == DUST_HIP_BODIES_CELLS && kBodyMaterials == DUST_HIP_BODY_WEIGHTS,
+              "body records");
 static_assert(sizeof(DustHipDeltaQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipDeltaResult) == 64 && sizeof(DustHipDeltaVoxel) == 8 &&
                   kDeltaBins == DUST_HIP_DELTA_BINS && kDeltaMaxRecords == DUST_HIP_MAX_DELTA_RECORDS && kDeltaAdded == DUST_HIP_DELTA_ADDED &&
                   kDeltaRemoved == DUST_HIP_DELTA_REMOVED && kDeltaRepainted == DUST_HIP_DELTA_REPAINTED,
@@ -391,6 +397,28 @@ inline DustHipBoxesResult boxes_result(const uint32_t* acc) {
   r.voxels = acc[2];
   for (int k = 0; k < 3; ++k) { r.lo[k] = uint8_t(255u - acc[3 + k]); r.hi[k] = uint8_t(acc[6 + k]); }
   return r;
+}
+
+// A body query as the kernels read it (dust_hip_model_bodies): the group kind, the filter's grid byte, the region and the root cells it
+// reaches. nullptr: the query is fine; otherwise why the call refuses it, in the header's order. `empty` as in device_surface: no voxel
+// is looked at -- lo, hi and box are not set.
+inline const char* device_bodies(const DustHipBodyQuery& q, BodyArgs& d, bool& empty) {
+  if (q.group > DUST_HIP_BODIES_CELLS) return "unknown body group";
+  if (q.flags != 0u) return "unknown bodies flag";
+  if (q.reserved[0] != 0u || q.reserved[1] != 0u) return "reserved word not 0";
+  if (q.palette < -1 || q.palette > 254) return "palette must be -1 (every solid voxel) or 0..254";
+  for (int r = 0; r < 3; ++r)
+    if (q.lo[r] >= 256u || q.hi[r] >= 256u) return "region coordinate outside the tree extent";
+  d.group = q.group;
+  d.byte = q.palette < 0 ? 0u : uint32_t(q.palette) + 1u;
+  empty = false;
+  for (int r = 0; r < 3; ++r) empty |= q.lo[r] > q.hi[r];
+  if (empty) return nullptr;
+  for (int r = 0; r < 3; ++r) {
+    d.lo[r] = q.lo[r]; d.hi[r] = q.hi[r];
+    d.box.lo[r] = q.lo[r] >> 4; d.box.hi[r] = q.hi[r] >> 4;
+  }
+  return nullptr;
 }
 
 // A delta query as the kernels read it (dust_hip_model_delta): the kinds, the filter's grid byte, the region clipped to the tree and the

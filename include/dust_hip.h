@@ -1361,6 +1361,68 @@ DustStatus dust_hip_model_fracture(DustHipModel*, const DustHipFractureQuery*, c
 DustStatus dust_hip_model_fracture_at(DustHipModel*, const uint32_t* xyz, uint16_t* cells, uint32_t n);
 DustStatus dust_hip_model_fracture_detach(DustHipModel*, const uint32_t* cells, uint32_t n, uint32_t flags, DustHipModel** out /* may be NULL */);
 DustStatus dust_hip_model_fracture_apply(DustHipModel*, uint32_t where, int32_t value, uint32_t* changed /* may be NULL */);
+/* Model bodies: WHAT A RIGID-BODY SOLVER NEEDS OF A PIECE. find_islands and fracture say which voxels form a piece, detach lifts pieces
+ * out, boxes and mesh give the colliders; a solver also needs mass, centre of mass and inertia tensor per body. One read-only call sums
+ * them per GROUP of voxels, with a weight per material: a piece that is half stone and half wood has its centre where it belongs.
+ *
+ * Counted: a voxel COUNTS when it is solid, lies inside the inclusive region lo..hi (DustHipSurfaceQuery's rules: a coordinate >= 256
+ * is refused; lo > hi on an axis is the empty region), passes the palette filter (palette -1: every solid voxel; 0..254: only voxels
+ * of that palette index) and belongs to a group of the chosen kind.
+ * Groups: query.group is one of
+ *   DUST_HIP_BODIES_ALL        one record, key 0: every counted voxel;
+ *   DUST_HIP_BODIES_MATERIALS  255 records, record p with key p: the counted voxels of palette index p;
+ *   DUST_HIP_BODIES_ISLANDS    one record per island of the STANDING labelling (dust_hip_model_find_islands), in ascending key order:
+ *                              number and order are exactly what a find_islands on the standing labelling would report now, islands
+ *                              detached earlier excluded. An island without a counted voxel still gets its record: the zero record
+ *                              with its key;
+ *   DUST_HIP_BODIES_CELLS      one record per seed of the STANDING fracture (dust_hip_model_fracture), n_seeds records, key i. Voxels
+ *                              that answer DUST_HIP_NO_CELL belong to no group.
+ * Weights: w = weights[palette index], 255 uint16 entries, 0..65535; weights == NULL: every voxel weighs 1. A weight of 0 is legal: the
+ * voxel still counts in `voxels` and the bounds.
+ * Records: key; voxels, the counted voxels of the group; lo / hi, their inclusive bounds (255, 255, 255 / 0, 0, 0 when there are none);
+ * mass, the sum of w; m1, the sums of w x, w y, w z; m2, the sums of w xx, w yy, w zz, w xy, w yz, w zx -- x, y, z the voxel's integer
+ * coordinates, as `sum` in DustHipIsland (centre of mass = m1 / mass + 0.5). All integer and exact. Overflow bound: a sum is at most
+ * 65535 * 255^2 * 2^24 < 2^56, below 2^63. With weights == NULL, voxels, lo, hi and m1 are byte for byte those of find_islands, of
+ * fracture or of a whole-tree census over the same voxels. The tensor about the centre of mass with every voxel a solid unit cube:
+ * C_ab = m2_ab - m1_a m1_b / mass, I_xx = C_yy + C_zz + mass / 6, I_xy = -C_xy.
+ * Capacity: *n_bodies is the number of groups whatever the capacity; the first min(*n_bodies, capacity) records are written and the
+ * slots past them are left untouched; capacity 0 only counts (the conventions of find_islands).
+ * The model is only read: the generation does not move, the island labelling and all three fields stand. ALL and MATERIALS work on a
+ * model that is not editable and leave it so, under census's guarantees (its blocks' masks are scattered into the context's 2 MiB
+ * scratch, and it is expanded into the 16 MiB scratch grid only when a material is needed: weights, a palette filter, MATERIALS).
+ * Synchronous, like every model call. Everything is integer arithmetic: two runs give the same bytes.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, the outputs untouched: a null model, query or n_bodies; a struct_size below the struct's
+ * size; an unknown group; flags or reserved words not 0; a palette outside -1..254; a region coordinate >= 256; null bodies with
+ * capacity > 0. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it (4096^3 trees, models that hold material byte 255), before the
+ * query is looked at. DUST_ERR_NOT_READY from ISLANDS without a standing labelling and from CELLS without a standing cell field, as
+ * island_of and fracture_at answer -- also on a model that is not editable, which cannot hold either.
+ * Out of scope: world-space bodies over a scene's instances; float densities; groups named by a field's range; an asynchronous form;
+ * 4096^3 trees. */
+#define DUST_HIP_BODIES_ALL       0u
+#define DUST_HIP_BODIES_MATERIALS 1u
+#define DUST_HIP_BODIES_ISLANDS   2u
+#define DUST_HIP_BODIES_CELLS     3u
+#define DUST_HIP_BODY_WEIGHTS     255u   /* entries of a weight table, and records of a MATERIALS call */
+typedef struct DustHipBodyQuery {      /* 48 bytes, DustHipSurfaceQuery's layout with `group` where `faces` stands */
+  uint32_t struct_size;
+  uint32_t group;                      /* DUST_HIP_BODIES_* */
+  uint32_t flags;                      /* 0 */
+  int32_t palette;                     /* -1: every solid voxel; 0..254: only voxels of this palette index */
+  uint32_t lo[3], hi[3];               /* inclusive region; lo > hi: nothing */
+  uint32_t reserved[2];                /* 0 */
+} DustHipBodyQuery;
+typedef struct DustHipBody {           /* 96 bytes */
+  uint32_t key, voxels;                /* the group's key; its counted voxels */
+  uint8_t lo[3], reserved0;            /* inclusive bounds of the counted voxels; 255,255,255 when there are none */
+  uint8_t hi[3], reserved1;            /* 0,0,0 when there are none; reserved bytes 0 */
+  uint64_t mass;                       /* sum of w */
+  uint64_t m1[3];                      /* sums of w x, w y, w z */
+  uint64_t m2[6];                      /* sums of w xx, w yy, w zz, w xy, w yz, w zx */
+} DustHipBody;
+DustStatus dust_hip_model_bodies(const DustHipModel*, const DustHipBodyQuery*,
+                                 const uint16_t* weights /* 255, by palette index; NULL: every voxel weighs 1 */,
+                                 uint32_t* n_bodies, DustHipBody* bodies /* capacity; may be NULL when capacity == 0 */,
+                                 uint32_t capacity);
 /* Model resampling: A STAMP UNDER ANY ROTATION, SCALE OR SHEAR. stamp, cast and delta place a piece under the 48 signed axis
  * permutations: a fallen wall segment lands at 0 or 90 degrees, never at 30; a prefab cannot be pasted at 1.5 times its size. A resample
  * is a stamp whose geometry is a fixed-point affine map from the destination to the source -- the voxels of one model pasted into

@@ -483,6 +483,18 @@ class VoxGeometry {
     check(dust_hip_model_info(h_, &num_blocks, &nm));
     return changed;
   }
+  // Model bodies (dust_hip_model_bodies): mass, first and second moments per group of the query's kind -- the whole geometry, a palette
+  // index, an island of the standing labelling, a cell of the standing fracture -- with a weight per palette index (255 entries;
+  // nullptr: every voxel weighs 1). Every record, in key order: two calls, one to count. Only reads.
+  std::vector<DustHipBody> bodies(DustHipBodyQuery query, const uint16_t* weights = nullptr) const {
+    query.struct_size = sizeof(query);
+    uint32_t n = 0;
+    check(dust_hip_model_bodies(h_, &query, weights, &n, nullptr, 0));
+    std::vector<DustHipBody> out(n);
+    check(dust_hip_model_bodies(h_, &query, weights, &n, out.data(), uint32_t(out.size())));
+    if (n < out.size()) out.resize(n);
+    return out;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
