@@ -465,6 +465,20 @@ BODIES_ALL, BODIES_MATERIALS, BODIES_ISLANDS, BODIES_CELLS = 0, 1, 2, 3
 BODY_WEIGHTS = 255
 
 
+class JointQuery(C.Structure):  # DustHipJointQuery, 48 bytes: a SurfaceQuery's layout with the kind of group where its faces stand
+    _fields_ = [("struct_size", C.c_uint32), ("group", C.c_uint32), ("flags", C.c_uint32), ("palette", C.c_int32),
+                ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class Joint(C.Structure):  # DustHipJoint, 80 bytes: the two groups, the faces they share, by direction from a to b, the bounds and sums of the face centres in half voxels
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("faces", C.c_uint32), ("reserved0", C.c_uint32), ("by_face", C.c_uint32 * 6),
+                ("lo2", C.c_uint16 * 3), ("hi2", C.c_uint16 * 3), ("reserved1", C.c_uint32), ("sum2", C.c_uint64 * 3)]
+
+
+JOINTS_MATERIALS, JOINTS_CELLS = 0, 1
+JOINT_REST = 0xFFFF
+
+
 class HierarchyInfo(C.Structure):  # DustHipHierarchyInfo, 48 bytes: what dust_hip_model_read_hierarchy reports besides the arrays
     _fields_ = [("struct_size", C.c_uint32), ("extent_log2", C.c_uint32), ("n_mid", C.c_uint32), ("n_l2", C.c_uint32),
                 ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
@@ -563,6 +577,7 @@ SYMBOLS = {
     "dust_hip_model_fracture_detach": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "dust_hip_model_fracture_apply": (C.c_int, [_P, C.c_uint32, C.c_int32, _u32p]),
     "dust_hip_model_bodies": (C.c_int, [_P, _P, _P, _u32p, _P, C.c_uint32]),
+    "dust_hip_model_joints": (C.c_int, [_P, _P, _u32p, _P, C.c_uint32]),
     "dust_hip_model_info": (C.c_int, [_P, _u32p, _u64p]),
     "dust_hip_model_read": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64]),
     "dust_hip_model_read_hierarchy": (C.c_int, [_P, C.POINTER(HierarchyInfo), _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64]),

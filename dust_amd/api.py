@@ -105,6 +105,9 @@ L2_CELL_DTYPE = np.dtype([("mid", "<u4"), ("bounds", "<u4"), ("child_mask", "<u8
 # DustHipBody (96 bytes): one group of dust_hip_model_bodies -- key, counted voxels, bounds, mass, first and second moments
 BODY_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("reserved0", "u1"), ("hi", "u1", 3), ("reserved1", "u1"), ("mass", "<u8"),
                        ("m1", "<u8", 3), ("m2", "<u8", 6)])
+# DustHipJoint (80 bytes): one pair of groups of dust_hip_model_joints -- the keys, the shared faces, by direction, bounds and sums of the face centres
+JOINT_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("faces", "<u4"), ("reserved0", "<u4"), ("by_face", "<u4", 6), ("lo2", "<u2", 3), ("hi2", "<u2", 3),
+                        ("reserved1", "<u4"), ("sum2", "<u8", 3)])
 ISLAND_DTYPE = np.dtype([("key", "<u4"), ("voxels", "<u4"), ("lo", "u1", 3), ("flags", "u1"), ("hi", "u1", 3), ("reserved", "u1"), ("sum", "<u8", 3)])
 FLT_MAX = float(np.finfo(np.float32).max)
 
@@ -915,6 +918,26 @@ class Model:
                                                 _ptr(records) if capacity else None, int(capacity)))
         return records[: min(int(capacity), n.value)]
 
+    def joints(self, group, region=None, capacity=None):
+        """The contact faces between neighbouring groups of voxels (dust_hip_model_joints): one JOINT_DTYPE record per pair of distinct
+        groups that share at least one voxel face, in ascending (a, b). `group` L.JOINTS_MATERIALS (a voxel's group is its palette
+        index) or L.JOINTS_CELLS (its cell of the standing fracture; a solid voxel beyond it has group L.JOINT_REST, always b). Only
+        the solid voxels inside `region` (clipped to the tree) exist. A record holds faces, by_face (the direction from the a voxel to
+        the b voxel: -x, +x, -y, +y, -z, +z), lo2 / hi2 and sum2 (bounds and sums of the face centres in half voxels). Returns the
+        first min(pairs, capacity) records -- capacity=None makes two calls, one to count. joint_properties turns the records into
+        area, anchor and normal. The model is only read."""
+        q = L.JointQuery(struct_size=C.sizeof(L.JointQuery), group=int(group), palette=-1)
+        lo, hi = ((0, 0, 0), (255, 255, 255)) if region is None else region
+        q.lo[:] = [int(v) for v in lo]
+        q.hi[:] = [int(v) for v in hi]
+        n = C.c_uint32()
+        if capacity is None:
+            L.check(self._lib.dust_hip_model_joints(self._h, C.byref(q), C.byref(n), None, 0))
+            capacity = n.value
+        records = np.zeros(int(capacity), JOINT_DTYPE)
+        L.check(self._lib.dust_hip_model_joints(self._h, C.byref(q), C.byref(n), _ptr(records) if capacity else None, int(capacity)))
+        return records[: min(int(capacity), n.value)]
+
     def distance(self, target=L.DISTANCE_TO_SOLID, metric=L.DISTANCE_EUCLIDEAN, max_radius=L.DISTANCE_MAX_RADIUS, walls=False, palette=0):
         """The exact distance from every voxel to the nearest target (dust_hip_model_distance): target L.DISTANCE_TO_SOLID (the solid
         voxels), L.DISTANCE_TO_EMPTY (the voxels holding None) or L.DISTANCE_TO_MATERIAL (the solid voxels of palette index `palette`);
@@ -1328,6 +1351,26 @@ def body_properties(records, voxel_size=1.0):
         for a, b in ((0, 1), (1, 2), (0, 2)):
             inertia[i, a, b] = inertia[i, b, a] = float(-c[(a, b)] * size * size)
     return mass, com, inertia
+
+
+def joint_properties(records, voxel_size=1.0):
+    """Host only: Model.joints' records -> (area, anchor, normal): area (n,) faces * voxel_size^2; anchor (n, 3) the centroid of the
+    face centres, sum2 / (2 faces) * voxel_size; normal (n, 3) the unnormalised area vector pointing from a to b, (by_face[+x] -
+    by_face[-x], ...) * voxel_size^2. Computed in exact rational arithmetic and rounded once to float64."""
+    from fractions import Fraction
+    records = np.asarray(records, JOINT_DTYPE).reshape(-1)
+    n = len(records)
+    area, anchor, normal = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3))
+    size = Fraction(voxel_size)
+    for i, r in enumerate(records):
+        faces = int(r["faces"])
+        if faces == 0:
+            continue
+        area[i] = float(faces * size * size)
+        for k in range(3):
+            anchor[i, k] = float(Fraction(int(r["sum2"][k]), 2 * faces) * size)
+            normal[i, k] = float((int(r["by_face"][2 * k + 1]) - int(r["by_face"][2 * k])) * size * size)
+    return area, anchor, normal
 
 
 def box_bounds(boxes):

@@ -1181,6 +1181,69 @@ DustStatus dust_hip_model_bodies(const DustHipModel* m, const DustHipBodyQuery* 
   });
 }
 
+// ---- model joints (joint.hip): one record per pair of groups -- palette indices, or the cells of the standing fracture and REST -- that
+// share a voxel face. Nothing is written but the context's scratch; no rebuild. The pairs are collected in a hash table in stage_aux
+// (counters in front); a table that turns out too small is doubled and the pass repeated on a cleared one
+DustStatus dust_hip_model_joints(const DustHipModel* m, const DustHipJointQuery* q, uint32_t* n_joints, DustHipJoint* joints, uint32_t capacity) {
+  if (!m) return fail(DUST_ERR_INVALID_ARGUMENT, "null model");
+  DustStatus s = editable_kind(m);  // (before the query is looked at)
+  if (s != DUST_OK) return s;
+  if (!q || !n_joints) return fail(DUST_ERR_INVALID_ARGUMENT, "null argument");
+  STRUCT_TRY(q, "DustHipJointQuery");
+  dust::JointArgs a{};
+  bool empty = false;
+  if (const char* why = dust::device_joints(*q, a, empty)) return fail(DUST_ERR_INVALID_ARGUMENT, why);
+  if (capacity && !joints) return fail(DUST_ERR_INVALID_ARGUMENT, "null joints with capacity > 0");
+  // (a model that is not editable holds no cell field)
+  if (a.group == dust::kJointsCells && (!m->edit || !m->edit->fracture.valid)) return no_cells();
+  if (empty) { *n_joints = 0; return DUST_OK; }
+  return guarded([&]() -> DustStatus {
+    DustHipContext* ctx = m->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(join_side(ctx));
+    hipStream_t st = ctx->stream;
+    if ((s = cast_source_masks(ctx, m, &a.brick_mask)) != DUST_OK) return s;
+    if (a.group == dust::kJointsMaterials && (s = source_grid(ctx, nullptr, m, &a.grid)) != DUST_OK) return s;
+    if (a.group == dust::kJointsCells) a.field = static_cast<const uint16_t*>(m->edit->fracture.values.p);
+    constexpr size_t head = 64;  // the counters, then the slots
+    uint32_t counters[dust::kJointCounterWords] = {};
+    for (a.slots_log2 = dust::joint_first_slots_log2(a.box.count());; ++a.slots_log2) {
+      if (a.slots_log2 > dust::kJointMaxSlotsLog2) return fail(DUST_ERR_OUT_OF_MEMORY, "the largest joint table overflowed");  // (it cannot)
+      const size_t bytes = head + (size_t(1) << a.slots_log2) * sizeof(dust::JointSlot);
+      if ((s = grow(ctx, ctx->stage_aux, bytes)) != DUST_OK) return s;
+      a.counters = static_cast<uint32_t*>(ctx->stage_aux.p);
+      a.slots = reinterpret_cast<dust::JointSlot*>(static_cast<uint8_t*>(ctx->stage_aux.p) + head);
+      HIP_TRY(hipMemsetAsync(ctx->stage_aux.p, 0, bytes, st));
+      HIP_TRY(dust::launch_joints(a, st));
+      HIP_TRY(hipMemcpyAsync(counters, a.counters, sizeof(counters), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (counters[dust::kJointOverflow] == 0u) break;
+    }
+    a.n = counters[dust::kJointClaims];
+    a.capacity = std::min(a.n, capacity);
+    if (a.capacity) {
+      // the claimed slots as (key, slot) pairs, sorted by key: four arrays of n words and the sort's scratch in stage_in
+      const size_t words = (size_t(a.n) + 63) & ~size_t(63);
+      if ((s = grow(ctx, ctx->stage_in, words * 16 + dust::radix_sort_scratch_bytes(a.n))) != DUST_OK) return s;
+      if ((s = grow(ctx, ctx->stage_out, size_t(a.capacity) * sizeof(dust::JointRecord))) != DUST_OK) return s;
+      uint32_t* base = static_cast<uint32_t*>(ctx->stage_in.p);
+      uint32_t* keys[2] = {base, base + 2 * words};
+      uint32_t* vals[2] = {base + words, base + 3 * words};
+      a.keys = keys[0]; a.vals = vals[0];
+      a.records = static_cast<dust::JointRecord*>(ctx->stage_out.p);
+      HIP_TRY(dust::launch_joints_compact(a, st));
+      bool in_b = false;
+      HIP_TRY(dust::radix_sort_pairs(base + 4 * words, keys[0], vals[0], keys[1], vals[1], a.n, dust::kJointKeyBits, &in_b, st));
+      a.sorted_keys = keys[in_b ? 1 : 0]; a.sorted_vals = vals[in_b ? 1 : 0];
+      HIP_TRY(dust::launch_joints_emit(a, st));
+      HIP_TRY(hipMemcpyAsync(joints, a.records, size_t(a.capacity) * sizeof(dust::JointRecord), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    *n_joints = a.n;
+    return DUST_OK;
+  });
+}
+
 // ---- model distances (distance.hip): the exact distance from every voxel to the nearest target voxel, kept on the device with the model
 static_assert(sizeof(DustHipDistanceQuery) == 32 && sizeof(DustHipDistanceResult) == 32 && sizeof(dust::DistanceAcc) == 16, "distance records");
 DustStatus dust_hip_model_distance(DustHipModel* m, const DustHipDistanceQuery* q, DustHipDistanceResult* out) {

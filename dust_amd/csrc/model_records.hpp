@@ -1,7 +1,7 @@
 // model_records.hpp -- the device-free half of the model calls (capi_model.cpp): the integer and float arithmetic that turns a caller's
-// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, boxes.hpp, body.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp, resample.hpp), cuts a call into chunks, bins a chunk's records into
+// record (include/dust_hip.h) into the device's (edit.hpp, stamp.hpp, cast.hpp, distance.hpp, census.hpp, surface.hpp, mesh.hpp, boxes.hpp, body.hpp, joint.hpp, delta.hpp, column.hpp, neighbour.hpp, settle.hpp, triangle.hpp, fracture.hpp, resample.hpp), cuts a call into chunks, bins a chunk's records into
 // root cells, decodes a cast's result and turns a census's accumulators into the caller's records. No HIP call, no handle, no error state:
-// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/boxes_rule_test.cpp, tests/cpp/body_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp, tests/cpp/fracture_rule_test.cpp and tests/cpp/resample_rule_test.cpp drive it on a CPU.
+// tests/cpp/model_records_test.cpp, tests/cpp/census_records_test.cpp, tests/cpp/surface_rule_test.cpp, tests/cpp/mesh_rule_test.cpp, tests/cpp/boxes_rule_test.cpp, tests/cpp/body_rule_test.cpp, tests/cpp/joint_rule_test.cpp, tests/cpp/delta_rule_test.cpp, tests/cpp/column_rule_test.cpp, tests/cpp/neighbour_rule_test.cpp, tests/cpp/settle_rule_test.cpp, tests/cpp/triangle_rule_test.cpp, tests/cpp/fracture_rule_test.cpp and tests/cpp/resample_rule_test.cpp drive it on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "distance.hpp"
 #include "edit.hpp"
 #include "fracture.hpp"
+#include "joint.hpp"
 #include "mesh.hpp"
 #include "neighbour.hpp"
 #include "resample.hpp"
@@ -39,6 +40,11 @@ static_assert(sizeof(DustHipBodyQuery) == sizeof(DustHipSurfaceQuery) && sizeof(
                   kBodiesAll == DUST_HIP_BODIES_ALL && kBodiesMaterials == DUST_HIP_BODIES_MATERIALS && kBodiesIslands == DUST_HIP_BODIES_ISLANDS &&
                   kBodiesCells == DUST_HIP_BODIES_CELLS && kBodyMaterials == DUST_HIP_BODY_WEIGHTS,
               "body records");
+static_assert(sizeof(DustHipJointQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipJoint) == 80 && sizeof(DustHipJoint) == sizeof(JointRecord) &&
+                  offsetof(DustHipJoint, by_face) == offsetof(JointRecord, by_face) && offsetof(DustHipJoint, lo2) == offsetof(JointRecord, lo2) &&
+                  offsetof(DustHipJoint, sum2) == offsetof(JointRecord, sum2) && kJointsMaterials == DUST_HIP_JOINTS_MATERIALS &&
+                  kJointsCells == DUST_HIP_JOINTS_CELLS && kJointRest == DUST_HIP_JOINT_REST && kJointRest == DUST_HIP_NO_CELL,
+              "joint records");
 static_assert(sizeof(DustHipDeltaQuery) == sizeof(DustHipSurfaceQuery) && sizeof(DustHipDeltaResult) == 64 && sizeof(DustHipDeltaVoxel) == 8 &&
                   kDeltaBins == DUST_HIP_DELTA_BINS && kDeltaMaxRecords == DUST_HIP_MAX_DELTA_RECORDS && kDeltaAdded == DUST_HIP_DELTA_ADDED &&
                   kDeltaRemoved == DUST_HIP_DELTA_REMOVED && kDeltaRepainted == DUST_HIP_DELTA_REPAINTED,
@@ -417,6 +423,29 @@ inline const char* device_bodies(const DustHipBodyQuery& q, BodyArgs& d, bool& e
   for (int r = 0; r < 3; ++r) {
     d.lo[r] = q.lo[r]; d.hi[r] = q.hi[r];
     d.box.lo[r] = q.lo[r] >> 4; d.box.hi[r] = q.hi[r] >> 4;
+  }
+  return nullptr;
+}
+
+// A joint query as the kernels read it (dust_hip_model_joints): the group kind, the region clipped to the tree as device_columns clips it
+// (a coordinate past 255 is cut back to it; lo past hi is the empty region) and the root cells it reaches. nullptr: the query is fine;
+// otherwise why the call refuses it, in the header's order. `empty`: no voxel is looked at -- lo, hi and box are not set.
+inline const char* device_joints(const DustHipJointQuery& q, JointArgs& d, bool& empty) {
+  if (q.group > DUST_HIP_JOINTS_CELLS) return "unknown joint group";
+  if (q.flags != 0u) return "unknown joints flag";
+  if (q.reserved[0] != 0u || q.reserved[1] != 0u) return "reserved word not 0";
+  if (q.palette != -1) return "palette must be -1 (reserved for a later filter)";
+  d.group = q.group;
+  uint32_t lo[3], hi[3];
+  empty = false;
+  for (int r = 0; r < 3; ++r) {
+    lo[r] = q.lo[r]; hi[r] = std::min(q.hi[r], 255u);
+    empty |= lo[r] > hi[r];
+  }
+  if (empty) return nullptr;
+  for (int r = 0; r < 3; ++r) {
+    d.lo[r] = lo[r]; d.hi[r] = hi[r];
+    d.box.lo[r] = lo[r] >> 4; d.box.hi[r] = hi[r] >> 4;
   }
   return nullptr;
 }

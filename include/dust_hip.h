@@ -1423,6 +1423,69 @@ DustStatus dust_hip_model_bodies(const DustHipModel*, const DustHipBodyQuery*,
                                  const uint16_t* weights /* 255, by palette index; NULL: every voxel weighs 1 */,
                                  uint32_t* n_bodies, DustHipBody* bodies /* capacity; may be NULL when capacity == 0 */,
                                  uint32_t capacity);
+/* Model joints: THE CONTACT FACES BETWEEN NEIGHBOURING PIECES. fracture breaks a solid into cells, fracture_detach lifts pieces out,
+ * boxes gives each piece its colliders, bodies its mass, centre and inertia; what holds the pieces together is missing: fracture's
+ * cut_faces are scalars. One read-only call returns, for every pair of distinct GROUPS that share at least one voxel face, a record of
+ * that contact -- the area stands for strength, the centroid is the anchor, the direction counts give the normal -- in canonical order
+ * and exact. The same call answers it per material: how much stone touches wood, and where.
+ *
+ * Voxels: a voxel EXISTS for the call when it is solid and lies inside the inclusive region lo..hi, clipped to the tree as
+ * dust_hip_model_columns clips it (a coordinate past 255 is cut back to it; lo > hi on an axis is the empty region). Nothing outside the
+ * region exists, as in boxes and columns.
+ * Groups: query.group is one of
+ *   DUST_HIP_JOINTS_MATERIALS  the voxel's group is its palette index, 0..254;
+ *   DUST_HIP_JOINTS_CELLS      the group is the cell index of the STANDING fracture (dust_hip_model_fracture), 0..4095; a solid voxel
+ *                              that answers DUST_HIP_NO_CELL -- beyond max_distance2, outside the fracture's region or filter -- has
+ *                              group DUST_HIP_JOINT_REST: the unbroken rest of the piece.
+ * Island groups are deliberately absent: under the labelling's own connectivity two islands never share a face.
+ * Faces: a face is a pair of voxels p and p + e_r, r one of x, y, z, that both exist and whose groups differ. Each face is counted once
+ * and belongs to the pair (a, b) of its two groups with a < b; REST is always b. There is no neighbour across a face of the tree.
+ * Records: a, b, the two group keys; faces, the faces they share; by_face, the faces by the direction FROM the a voxel TO the b voxel in
+ * the order of the DUST_HIP_FACE_* bits (-x, +x, -y, +y, -z, +z), summing to faces; lo2 / hi2, the inclusive bounds of the face centres
+ * in HALF voxels on the lattice 0..512; sum2, the sums of the face centres in half voxels. The centre of face (p, r) is 2 p + 1 + e_r:
+ * 2 p_r + 2 along r, 2 p + 1 on the other two axes. A sum needs 64 bits: one pair can hold about 5 * 10^7 faces of coordinates up to
+ * 511. A pair without faces has no record. All integer and exact. Area = faces, anchor = sum2 / (2 faces), the unnormalised normal from
+ * a to b = (by_face[+x] - by_face[-x], ...). Under CELLS with the fracture's own region the faces of the records with b != REST sum to
+ * the fracture result's cut_faces, and those of the records that name cell c to that cell's cut_faces.
+ * Capacity: *n_joints is the number of pairs whatever the capacity; the first min(*n_joints, capacity) records in ascending (a, b) are
+ * written and the bytes past them are left untouched; capacity 0 only counts. The empty region: *n_joints = 0, DUST_OK.
+ * The model is only read: the generation does not move, committed scenes keep answering, the island labelling and all three fields
+ * stand. MATERIALS works on a model that is not editable and leaves it so, under census's guarantees (its blocks' masks are scattered
+ * into the context's 2 MiB scratch and it is expanded into the 16 MiB scratch grid). Synchronous, like every model call. Integer adds
+ * and maxima, the output sorted by key: two runs give the same bytes.
+ * Memory: the pairs are collected in a hash table of 80-byte slots in the context's scratch: sixteen slots per root cell of the region,
+ * between 1024 and 65 536 (5 MiB for the whole tree: MATERIALS' 32 385 possible pairs at a load below one half); a table that turns
+ * out too small is doubled and the pass repeated, up to 2^24 slots (1.25 GiB), which the 8 390 656 pairs of 4096 cells and REST cannot
+ * fill. The sort takes 16 bytes per pair more. DUST_ERR_OUT_OF_MEMORY when the device cannot hold them.
+ * Refused with DUST_ERR_INVALID_ARGUMENT, the outputs untouched: a null model, query or n_joints; a struct_size below the struct's
+ * size; an unknown group; flags or reserved words not 0; a palette other than -1 (reserved for a later filter); null joints with
+ * capacity > 0. DUST_ERR_UNSUPPORTED exactly where set_voxels returns it, before the query is looked at. DUST_ERR_NOT_READY from CELLS
+ * without a standing cell field, as fracture_at answers -- also on a model that is not editable, which cannot hold one.
+ * Out of scope: contacts with the tree's faces (find_islands' `anchored` covers the common case); edge and corner contacts; a palette
+ * filter; breaking joints or solving anything on the device -- the host owns the graph. */
+#define DUST_HIP_JOINTS_MATERIALS 0u
+#define DUST_HIP_JOINTS_CELLS     1u
+#define DUST_HIP_JOINT_REST       0xFFFFu /* the group of a solid voxel that answers DUST_HIP_NO_CELL */
+typedef struct DustHipJointQuery {     /* 48 bytes, DustHipSurfaceQuery's layout with `group` where `faces` stands */
+  uint32_t struct_size;
+  uint32_t group;                      /* DUST_HIP_JOINTS_* */
+  uint32_t flags;                      /* 0 */
+  int32_t palette;                     /* -1 (reserved for a later filter) */
+  uint32_t lo[3], hi[3];               /* inclusive region, clipped to the tree; lo > hi: nothing */
+  uint32_t reserved[2];                /* 0 */
+} DustHipJointQuery;
+typedef struct DustHipJoint {          /* 80 bytes */
+  uint32_t a, b;                       /* the two group keys, a < b; b may be DUST_HIP_JOINT_REST */
+  uint32_t faces;                      /* shared faces */
+  uint32_t reserved0;                  /* 0 */
+  uint32_t by_face[6];                 /* by the direction from the a voxel to the b voxel: -x, +x, -y, +y, -z, +z */
+  uint16_t lo2[3], hi2[3];             /* inclusive bounds of the face centres in half voxels */
+  uint32_t reserved1;                  /* 0 */
+  uint64_t sum2[3];                    /* sums of the face centres in half voxels */
+} DustHipJoint;
+DustStatus dust_hip_model_joints(const DustHipModel*, const DustHipJointQuery*,
+                                 uint32_t* n_joints, DustHipJoint* joints /* capacity; may be NULL when capacity == 0 */,
+                                 uint32_t capacity);
 /* Model resampling: A STAMP UNDER ANY ROTATION, SCALE OR SHEAR. stamp, cast and delta place a piece under the 48 signed axis
  * permutations: a fallen wall segment lands at 0 or 90 degrees, never at 30; a prefab cannot be pasted at 1.5 times its size. A resample
  * is a stamp whose geometry is a fixed-point affine map from the destination to the source -- the voxels of one model pasted into

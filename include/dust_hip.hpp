@@ -495,6 +495,18 @@ class VoxGeometry {
     if (n < out.size()) out.resize(n);
     return out;
   }
+  // Model joints (dust_hip_model_joints): one record per pair of groups -- palette indices, or the cells of the standing fracture with
+  // DUST_HIP_JOINT_REST for the solid voxels beyond it -- that share a voxel face: the faces, their directions from a to b, the bounds
+  // and sums of their centres in half voxels. Every record, in ascending (a, b): two calls, one to count. Only reads.
+  std::vector<DustHipJoint> joints(DustHipJointQuery query) const {
+    query.struct_size = sizeof(query);
+    uint32_t n = 0;
+    check(dust_hip_model_joints(h_, &query, &n, nullptr, 0));
+    std::vector<DustHipJoint> out(n);
+    check(dust_hip_model_joints(h_, &query, &n, out.data(), uint32_t(out.size())));
+    if (n < out.size()) out.resize(n);
+    return out;
+  }
   // the obj_to_world of an instance of reduce(levels)'s geometry that stands where an instance of this one with `obj_to_world_3x4`
   // stands: columns 0..2 scaled by 2^levels, the translation unchanged
   static std::array<float, 12> lod_transform(const float obj_to_world_3x4[12], uint32_t levels) {
